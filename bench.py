@@ -2,7 +2,7 @@
 """Headline benchmark: rendered views/s, forward+backward, 200k Gaussians @ 1080p (BASELINE.json
 configs[2]; SURVEY.md 8(d) scene S(200000,1920,1080,3,seed=3)), 1..8 MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process starts N fresh rank processes (one per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set; it has not touched the GPU itself), waits, relays rank 0's JSON line and
@@ -71,6 +71,13 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--min-timed-s", type=float, default=0.0,
+                    help="repeat the timed region (whole regions of --steps steps) until it adds up to this many seconds and report "
+                         "the median region; default 0: ONE region, exactly --steps timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step computed (images, radii, gradients; the train workload: "
+                         "losses and parameter gradients) as DIR/<name>.npy in float32 / float64, 60 MB at most in all: an array "
+                         "larger than its share is written as a fixed, seeded sample of its values (benchkit.common.dump_outputs)")
     ap.add_argument("--gaussians", type=int, default=200000)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
@@ -214,7 +221,7 @@ def secondary_legs(a, ctx, head):
     t0 = time.perf_counter()
     base = copy.copy(a)
     base.light, base.no_secondary, base.copy_gbs = True, True, head.get("hbm_copy_GBs_measured")
-    base.grad_hash = False
+    base.grad_hash, base.dump_outputs = False, None
 
     def variant(**kw):
         v = copy.copy(base)

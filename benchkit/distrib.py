@@ -180,8 +180,11 @@ def timed_repeats(dist, dev, steps, step, min_s=None):
     """The timed region, repeated: whole regions of EXACTLY `steps` steps (each bracketed by barrier + synchronize, MAX over
     ranks) until they add up to MIN_TIMED_S seconds and there are at least two.  The driver's `--steps 20` is 42 ms of work
     for a 2-ms step -- one region of that length moves by +-1.5 % with the box; the line reports the MEDIAN region (and min /
-    max).  Every rank sees the same (reduced) durations, so all ranks take the same number of repetitions."""
+    max).  Every rank sees the same (reduced) durations, so all ranks take the same number of repetitions.  ``min_s`` <= 0: ONE
+    region, i.e. exactly ``steps`` timed steps (bench.py's headline default; --min-timed-s asks for the repetition)."""
     min_s = MIN_TIMED_S if min_s is None else min_s
+    if min_s <= 0:
+        return [timed_region(dist, dev, steps, step)]
     els = []
     while True:
         els.append(timed_region(dist, dev, steps, step))

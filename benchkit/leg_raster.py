@@ -12,7 +12,7 @@ from .distrib import (COMM_KEYS, FORCE_DIST, LIGHT_TIMED_S, MAX_REPEATS, MIN_TIM
 from .roofline import (HBM_COPY_GBS, HBM_PEAK_GBS, ROOT, algorithmic_bytes, algorithmic_bytes_skinned, build_roofline, measure_copy_peak,   # noqa: F401
                        pmc_view_traffic, scaling_model, train_step_roofline)
 from .baseline import PARITY_BORDER, PARITY_RGB_TOL, cpu_baseline    # noqa: F401
-from .common import _release, _tile_list_stats
+from .common import _release, _tile_list_stats, dump_outputs
 
 
 def leg_raster(a, ctx):
@@ -155,9 +155,26 @@ def leg_raster(a, ctx):
             torch.cuda.synchronize(dev); t0 = _t.perf_counter(); step(); t1 = _t.perf_counter(); torch.cuda.synchronize(dev)
             t2 = _t.perf_counter()
             _log(f"host submission {1e3 * (t1 - t0):.3f} ms, step complete after {1e3 * (t2 - t0):.3f} ms")
-    _log(f"timed region ({a.steps} steps, repeated until {MIN_TIMED_S} s)")
-    els = timed_repeats(dist, dev, a.steps, step, min_s=LIGHT_TIMED_S if a.light else None)
+    _log(f"timed region ({a.steps} steps" + (f", repeated until {LIGHT_TIMED_S if a.light else a.min_timed_s} s)"
+                                             if a.light or getattr(a, "min_timed_s", 0.0) > 0 else ")"))
+    els = timed_repeats(dist, dev, a.steps, step, min_s=LIGHT_TIMED_S if a.light else getattr(a, "min_timed_s", 0.0))
     el = _median(els)
+    dumped = None
+    if getattr(a, "dump_outputs", None) and rank == 0:
+        # what the last timed step handed its caller: every view's image and radii, and the gradients summed over the step's
+        # views (and ranks) in the engines' flat layout -- means3D 3, scales 3, rotations 4, opacity 1, sh 3 M floats per Gaussian
+        torch.cuda.synchronize()
+        src = [eng] if graph is not None else engs
+        out_arrays = {"color": torch.cat([e.color.view(-1, 3, H, W) for e in src]),
+                      "radii": torch.cat([e.radii.view(-1, N) for e in src])}
+        if not a.forward_only:
+            g, o = (eng.grad_flat if graph is not None else batch.acc), 0
+            for name, n, shape in (("grad_means3D", 3, (N, 3)), ("grad_scales", 3, (N, 3)), ("grad_rotations", 4, (N, 4)),
+                                   ("grad_opacities", 1, (N, 1)), ("grad_shs", 3 * shs.shape[1], (N, shs.shape[1], 3))):
+                out_arrays[name] = g[o:o + N * n].view(*shape); o += N * n
+        if reg is not None:
+            out_arrays.update(reg_grad_scales=reg_sc.grad, reg_grad_offsets=reg_off.grad)
+        dumped = dump_outputs(a.dump_outputs, out_arrays)
     _log(f"{el / a.steps * 1e3:.3f} ms per step (median of {len(els)} regions); one view per step")
     assert all(0 <= r_ <= e.cap for e in engs for r_ in (e.num_rendered() if getattr(e, "K", 1) > 1 else [e.num_rendered()])), \
         "pair capacity / short-list hint violated"
@@ -260,7 +277,7 @@ def leg_raster(a, ctx):
                                        "(+ the all-reduce with several ranks): SURVEY.md 8(d) Timing" if el_loss is not None else
                                        "forward only (no loss, no backward)",
         "raster_fwd_bwd_ms_one_view": el_one / n_one * 1e3, "views_per_s_one_view_per_step": world * n_one / el_one,
-        "timed_region_s": sum(els), "repeats": len(els), "ms_per_step_min": min(els) / a.steps * 1e3,
+        "timed_region_s": sum(els), "repeats": len(els), "timed_steps": a.steps * len(els), "ms_per_step_min": min(els) / a.steps * 1e3,
         "ms_per_step_max": max(els) / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"S({N},{W},{H},deg={deg},seed={seed}): {N} Gaussians, {W}x{H}, SH deg {deg}, "
@@ -291,6 +308,8 @@ def leg_raster(a, ctx):
                                          comm.get("allreduce_exposed_ms") if comm else None)
     if grad_hash is not None:
         out["grad_sha256"] = grad_hash
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
     if dp_check is not None:
         out.update(dp_check)
     if one_by_algo is not None:

@@ -149,3 +149,41 @@ def test_skinned_byte_split_matches_the_survey_formula():
     extra_read = N * (12 + 4 * J) - N * 28
     assert per["sg_preprocess_fwd_kernel"] == base_per["sg_preprocess_fwd_kernel"] + extra_read
     assert total == base_total + 2 * extra_read + N * 12 - N * 28
+
+
+def test_headline_default_is_exactly_steps_timed_steps(monkeypatch):
+    """bench.py's headline region runs --steps steps ONCE by default (--min-timed-s 0); --min-timed-s S repeats it."""
+    calls = []
+    monkeypatch.setattr(bench._distrib, "timed_region", lambda dist, dev, steps, step: calls.append(steps) or 0.001)
+    assert len(bench.timed_repeats(None, None, 9, None, min_s=0.0)) == 1 and calls == [9]
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "9"])
+    a = bench.parse_args()
+    assert a.steps == 9 and a.min_timed_s == 0.0 and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "9", "--min-timed-s", "0.5", "--dump-outputs", "d"])
+    a = bench.parse_args()
+    assert a.min_timed_s == 0.5 and a.dump_outputs == "d"
+
+
+def test_dump_outputs_fits_the_budget_and_samples_the_same_values_every_time(tmp_path):
+    import numpy as np
+    import torch
+    from benchkit.common import DUMP_BUDGET_BYTES, dump_outputs, dump_plan
+    rng = np.random.default_rng(0)
+    arrays = {"big": torch.from_numpy(rng.standard_normal((40, 1000, 1000)).astype(np.float32)),       # 160 MB
+              "small": torch.arange(12, dtype=torch.int32).view(3, 4),
+              "loss": torch.tensor(0.25, dtype=torch.float64)}
+    m1 = dump_outputs(str(tmp_path / "a"), arrays)
+    m2 = dump_outputs(str(tmp_path / "b"), arrays)
+    assert m1 == m2
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 64 * 2 ** 20 and m1["big"]["written"] == (DUMP_BUDGET_BYTES - 8 - 12 * 4) // 4
+    for name in arrays:
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64 and float(np.load(tmp_path / "a" / "loss.npy")) == 0.25
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), np.arange(12, dtype=np.float32).reshape(3, 4))
+    assert m1["small"]["sampled"] is None and m1["big"]["sampled"] is not None
+    big = np.load(tmp_path / "a" / "big.npy")                   # a sample of the array's own values, in index order
+    assert np.isin(big[:100], arrays["big"].numpy().reshape(-1)).all()
+    # the plan: small arrays whole, the rest shares what is left equally
+    assert dump_plan({"x": (10, 4), "y": (1000, 4), "z": (1000, 4)}, budget=4040) == {"x": 10, "y": 500, "z": 500}

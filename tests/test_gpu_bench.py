@@ -54,10 +54,10 @@ def test_single_gpu_line_carries_the_contract():
 
 @pytest.mark.gpu
 def test_timed_region_is_repeated_and_the_schema_is_one():
-    """--steps 3 of a small scene is a few milliseconds: the region is repeated (whole regions of 3 steps) until it adds up to
-    0.5 s, the line reports the median; the collective keys exist (null) without a collective."""
-    j = _line(_bench("--gpus", "1", "--no-cpu-baseline", *SMALL))
-    assert j["repeats"] >= 2 and j["timed_region_s"] >= 0.5 and j["steps"] == 3
+    """--steps 3 of a small scene is a few milliseconds: with --min-timed-s 0.5 the region is repeated (whole regions of 3 steps)
+    until it adds up to 0.5 s, the line reports the median; the collective keys exist (null) without a collective."""
+    j = _line(_bench("--gpus", "1", "--no-cpu-baseline", "--min-timed-s", "0.5", *SMALL))
+    assert j["repeats"] >= 2 and j["timed_region_s"] >= 0.5 and j["steps"] == 3 and j["timed_steps"] == 3 * j["repeats"]
     assert j["ms_per_step_min"] <= j["ms_per_step"] <= j["ms_per_step_max"]
     for k in ("allreduce_ms", "allreduce_bytes", "allreduce_algorithm", "allreduce_per_link_bound_ms", "allreduce_exposed_ms"):
         assert k in j and j[k] is None
@@ -66,6 +66,29 @@ def test_timed_region_is_repeated_and_the_schema_is_one():
     assert j["roofline"]["bound"] == "hbm" and j["roofline"]["traffic"] is None
     if j["roofline"]["dominant_kernel"] in ("sg_render_bwd_kernel", "sg_render_fwd_kernel"):
         assert j["roofline_valu"]["frac"] is None and "PMC" in j["roofline_valu"]["note"]
+
+
+@pytest.mark.gpu
+def test_steps_sets_the_timed_steps_and_the_outputs_of_the_last_one_are_dumped(tmp_path):
+    """By default the timed region is ONE region of exactly --steps steps; --dump-outputs writes what the last of them computed
+    (every view's image and radii, the summed gradients), the same bytes in two runs with the same arguments, 64 MB at most."""
+    import numpy as np
+    runs = []
+    for d in ("a", "b"):
+        j = _line(_bench("--gpus", "1", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / d), *SMALL))
+        assert j["steps"] == 3 and j["repeats"] == 1 and j["timed_steps"] == 3
+        assert abs(j["ms_per_step"] - j["timed_region_s"] / 3 * 1e3) < 1e-9 * j["ms_per_step"]
+        runs.append(j["dumped_outputs"]["arrays"])
+    assert runs[0] == runs[1]
+    names = {"color", "radii", "grad_means3D", "grad_scales", "grad_rotations", "grad_opacities", "grad_shs"}
+    assert set(runs[0]) == names and runs[0]["color"]["shape"] == [16, 3, 368, 640] and runs[0]["grad_shs"]["shape"] == [20000, 16, 3]
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert x.dtype == np.float32 and np.isfinite(x).all() and np.array_equal(x, y), n
+        total += os.path.getsize(tmp_path / "a" / f"{n}.npy")
+    assert total <= 64 * 2 ** 20
+    assert np.abs(np.load(tmp_path / "a" / "grad_means3D.npy")).max() > 0 and np.load(tmp_path / "a" / "radii.npy").max() > 0
 
 
 @pytest.mark.gpu
@@ -91,7 +114,7 @@ def test_rccl_branches_run_with_one_rank_avatar_and_train():
     """The same for the other two workloads: the avatar step (fused LBS path, 3 + 3 + 1 + 3 * 16 floats per Gaussian all-reduced) and the
     complete training step (parameter gradients written straight into ONE flat buffer -- sings_amd.decode.set_gradient_arena --
     and all-reduced in place)."""
-    small = ["--gaussians", "20000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    small = ["--gaussians", "20000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--min-timed-s", "0.5"]
     env = {"SINGS_BENCH_FORCE_DIST": "1"}
     ref = _line(_bench("--workload", "avatar", "--grad-hash", *small))
     j = _line(_bench("--workload", "avatar", "--grad-hash", *small, env=env))

@@ -19,7 +19,9 @@ def close(a, b, tol=1e-6):
 
 
 def test_g1_rotations():
-    close(lo.matrix_to_quaternion(T(G["g1_mats"])), G["g1_m2q"], 0)          # same ops -> identical
+    # same ops -> identical up to torch's float32 CPU sqrt, whose last bit differs between x86 CPUs (the golden's machine and an
+    # AMD EPYC host part in 1 of 6 square roots here): |q| <= 1, so 2.4e-7 is 2 ulps of 1.0
+    close(lo.matrix_to_quaternion(T(G["g1_mats"])), G["g1_m2q"], 2.4e-7)
     close(lo.rotation_6d_to_matrix(T(G["g1_d6"])), G["g1_d6_to_mat"], 1e-7)
     close(lo.quaternion_multiply(T(G["g1_qa"]), T(G["g1_qb"])), G["g1_qmul"], 0)
     close(lo.quaternion_to_matrix(T(G["g1_qa"])), G["g1_q2m"], 1e-6)

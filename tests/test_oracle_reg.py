@@ -23,7 +23,10 @@ def test_region_laplacian_oracle_matches_reference():
     lh = ro.region_laplacian_hands(x, tv, te, tl)
     lh.backward()
     assert abs(lh.item() - G["lap_hands_loss"]) <= 1e-6 * abs(G["lap_hands_loss"])
-    np.testing.assert_allclose(x.grad.numpy(), G["lap_hands_grad"], rtol=1e-5, atol=1e-9)
+    # the cotangent weights take float32 square roots whose last bit differs between x86 CPUs (tests/test_oracle_lbs.py::
+    # test_g1_rotations); where L x nearly cancels that is 2.3e-7 of a gradient of scale 0.37: atol 1e-6 of the largest entry
+    g = G["lap_hands_grad"]
+    np.testing.assert_allclose(x.grad.numpy(), g, rtol=1e-5, atol=1e-6 * float(np.abs(g).max()))
 
 
 def test_l2norm_and_edge_loss_oracle_match_reference():

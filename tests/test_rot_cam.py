@@ -40,7 +40,8 @@ def test_rotation_conversions_match_reference():
     eq(R.standardize_quaternion(T("q")), "q_std")
     G1 = np.load(os.path.join(os.path.dirname(__file__), "golden", "lbs_golden.npz"))
     t1 = lambda k: torch.from_numpy(G1[k])
-    np.testing.assert_array_equal(R.matrix_to_quaternion(t1("g1_mats")).numpy(), G1["g1_m2q"])
+    # (identical up to torch's float32 CPU sqrt, whose last bit differs between x86 CPUs: tests/test_oracle_lbs.py::test_g1_rotations)
+    np.testing.assert_allclose(R.matrix_to_quaternion(t1("g1_mats")).numpy(), G1["g1_m2q"], rtol=0, atol=2.4e-7)
     np.testing.assert_array_equal(R.quaternion_multiply(t1("g1_qa"), t1("g1_qb")).numpy(), G1["g1_qmul"])
     np.testing.assert_allclose(R.rotation_6d_to_matrix(t1("g1_d6")).numpy(), G1["g1_d6_to_mat"], rtol=1e-6, atol=1e-7)
     np.testing.assert_allclose(R.quaternion_to_matrix(t1("g1_qa")).numpy(), G1["g1_q2m"], rtol=1e-6, atol=1e-7)
