@@ -77,6 +77,10 @@ FLAG_FORWARD_COMPOSITE = 16          # SG_FLAG_FORWARD_COMPOSITE
 FLAG_SH_PLANAR = 32                  # SG_FLAG_SH_PLANAR
 FLAG_LONG_ROWS = 64                  # SG_FLAG_LONG_ROWS
 NUM_RENDERED_LONG_LIST = -2          # SG_NUM_RENDERED_LONG_LIST
+# bits of the binning header's flag word (header word 1, set where sings_amd/csrc/sg_binning.hip writes `header[1] = hflags`,
+# once per scan kernel): what the "async" / "deferred" checks read instead of the count NUM_RENDERED_LONG_LIST stands for
+HDR_FLAG_OVERFLOW = 1               # more pairs than the capacity of the call
+HDR_FLAG_LONG_LIST = 2              # a tile list longer than a flag of the call promised (SG_FLAG_SHORT_LISTS / SG_FLAG_LONG_ROWS)
 
 
 def load():

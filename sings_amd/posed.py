@@ -105,6 +105,14 @@ def forward_chunk(gs_attrs, lbs_weights, A_t2pose, inv_A_t2cano=None, transl=Non
     }
 
 
+def _capacity_floor(cap, P, W, H):                   # the FrameAnimator's engines: 8 pairs per Gaussian + 1 per tile, at least
+    return max(cap, 8 * P + ((W + 15) // 16) * ((H + 15) // 16), 1 << 16)
+
+
+def _grown(need):                                    # ... and what a count of `need` pairs asks for
+    return need + need // 4 + 1024
+
+
 class FrameAnimator:
     """Forward-only rendering of posed frames, ``streams`` frames in flight: one pre-allocated SkinnedEngine (workspaces)
     per stream, nothing allocated or synchronised per frame except one read of the pair counts per round (a frame whose
@@ -133,6 +141,22 @@ class FrameAnimator:
             self.shape, self.cap = (P, J, W, H, M), cap
         return self.engs
 
+    def _settle(self, counts, cap, flags=0):
+        """Frames rendered with capacity ``cap`` have reported their pair counts (``num_rendered()``, or the header's count and
+        flag word of a frame whose count was not read): drops the long-rows hint for good if a list outgrew its row.  Returns None
+        if the frames stand, else the capacity to render them again with: ``cap`` after a NUM_RENDERED_LONG_LIST count (it hides
+        the frame's R: the plain path counts it), ``_grown(R)`` if R exceeded ``cap``."""
+        if self.long_rows and min(counts) == _lib.NUM_RENDERED_LONG_LIST:
+            self.long_rows = False
+            return cap
+        long_list = bool(flags & _lib.HDR_FLAG_LONG_LIST)        # (the header's R is the frame's: it may also have overflowed)
+        if long_list:
+            self.long_rows = False
+        need = max(counts)
+        if need > cap:
+            return _grown(need)
+        return cap if long_list else None
+
     def render_round(self, jobs, bg_color, scaling_modifier=1.0):
         """jobs: up to ``streams`` tuples (camera dict, A_cano2pose [J,4,4], transl | None, smpl_scale | None,
         ext_tfs | None) -> list of clamped images [3,H,W] (the keys 'render' of get_render_pkg_fused)."""
@@ -141,7 +165,7 @@ class FrameAnimator:
         J = int(jobs[0][1].reshape(-1, 16).shape[0])
         W, H = int(jobs[0][0]['image_width']), int(jobs[0][0]['image_height'])
         P = int(c['xyz_canon'].shape[0])
-        cap = max(self.cap, 8 * P + ((W + 15) // 16) * ((H + 15) // 16), 1 << 16)
+        cap = _capacity_floor(self.cap, P, W, H)
         cur = torch.cuda.current_stream(self.dev)
         while True:
             engs = self._engines(J, W, H, cap)
@@ -158,14 +182,9 @@ class FrameAnimator:
                     outs[-1].record_stream(cur)
             for st in self.streams[:len(jobs)]:
                 cur.wait_stream(st)
-            counts = [e.num_rendered() for e in engs[:len(jobs)]]
-            if self.long_rows and min(counts) == _lib.NUM_RENDERED_LONG_LIST:
-                self.long_rows = False                           # a list outgrew its row: these frames again, on the plain path
-                continue
-            need = max(counts)
-            if need <= self.cap:
+            cap = self._settle([e.num_rendered() for e in engs[:len(jobs)]], self.cap)
+            if cap is None:
                 return outs
-            cap = need + need // 4 + 1024
 
 
     def render_frames(self, jobs, bg_color, scaling_modifier=1.0, depth=None):
@@ -185,7 +204,7 @@ class FrameAnimator:
             cam, A, transl, smpl_scale, ext = job
             J = int(A.reshape(-1, 16).shape[0])
             W, H = int(cam['image_width']), int(cam['image_height'])
-            cap = max(self.cap, 8 * P + ((W + 15) // 16) * ((H + 15) // 16), 1 << 16)
+            cap = _capacity_floor(self.cap, P, W, H)
             if self.shape != (P, J, W, H, int(c['shs'].shape[1])) or cap > self.cap:
                 torch.cuda.synchronize(self.dev)                 # (engines in flight are about to be replaced)
             e, st = self._engines(J, W, H, cap)[i % self.n], self.streams[i % self.n]
@@ -208,13 +227,11 @@ class FrameAnimator:
             ev.synchronize()
             # compared with the capacity of the engine that rendered it: an earlier pop may have grown self.cap while this
             # frame was still queued, and a count between the two capacities means a background-only image
-            if int(slot[0]) > cap_used or (int(slot[1]) & 2):    # rare: grow the workspaces / drop the hint, render this frame again
+            cap = self._settle([int(slot[0])], cap_used, int(slot[1]))
+            if cap is not None:                                  # rare: grow the workspaces / drop the hint, render this frame again
                 torch.cuda.synchronize(self.dev)
-                if int(slot[1]) & 2:
-                    self.long_rows = False
-                if int(slot[0]) > cap_used:
-                    need = int(slot[0])
-                    self._engines(self.shape[1], self.shape[2], self.shape[3], need + need // 4 + 1024)
+                if cap > cap_used:
+                    self._engines(self.shape[1], self.shape[2], self.shape[3], cap)
                 img = self.render_round([job], bg_color, scaling_modifier)[0]
                 torch.cuda.synchronize(self.dev)
             return i, img
@@ -288,7 +305,7 @@ class FrameAnimator:
                     raise ValueError("render_frames_batched: one smpl_scale per batch of frames")
             J = int(batch[0][1].reshape(-1, 16).shape[0])
             W, H = int(batch[0][0]['image_width']), int(batch[0][0]['image_height'])
-            cap = max(getattr(self, "_fcap", 0), 8 * P + ((W + 15) // 16) * ((H + 15) // 16), 1 << 16)
+            cap = _capacity_floor(getattr(self, "_fcap", 0), P, W, H)
             engs = self._frame_engines(J, W, H, K, cap)
             e, st = engs[state['b'] % self.n], self.streams[state['b'] % self.n]
             state['b'] += 1
@@ -300,21 +317,18 @@ class FrameAnimator:
             ev.synchronize()
             with torch.cuda.stream(st):
                 Rs = e.num_rendered()                            # (this engine has nothing else queued: one launch per engine)
-            long_list = self.long_rows and min(Rs[:len(batch)]) == _lib.NUM_RENDERED_LONG_LIST
-            if max(Rs[:len(batch)]) > e.cap or long_list:        # rare: grow the workspaces / drop the hint, render this batch again
+            if self._settle(Rs[:len(batch)], e.cap) is not None:    # rare: grow the workspaces / drop the hint, render this batch again
                 torch.cuda.synchronize(self.dev)
-                if long_list:
-                    self.long_rows = False
                 # (a NEW set of engines either way: the queued batches keep theirs, whose counts are still to be read)
                 need = max(max(Rs[:len(batch)]), self._fcap - self._fcap // 5)
                 J, W, H = self._fshape[1], self._fshape[2], self._fshape[3]
-                e2 = self._frame_engines(J, W, H, K, need + need // 4 + 1024)[0]
+                e2 = self._frame_engines(J, W, H, K, _grown(need))[0]
                 img, ev = launch(i0, batch, e2, self.streams[0])
                 torch.cuda.synchronize(self.dev)
                 Rs2 = e2.num_rendered()
                 if max(Rs2[:len(batch)]) > e2.cap:               # (both at once: the plain path has now counted the batch)
                     need = max(Rs2[:len(batch)])
-                    e2 = self._frame_engines(J, W, H, K, need + need // 4 + 1024)[0]
+                    e2 = self._frame_engines(J, W, H, K, _grown(need))[0]
                     img, ev = launch(i0, batch, e2, self.streams[0])
                     torch.cuda.synchronize(self.dev)
             for k in range(len(batch)):

@@ -6,13 +6,15 @@ canonical means / rotations / scales, the skinning weights and the cano->pose jo
 ``A_cano2pose = A_t2pose @ inv_A_t2cano`` (:398-399); posed means, rotation quaternions and the
 blended T[N,4,4] never reach HBM.  Gradients flow to xyz_canon, rotmat_canon, scales, opacity, shs,
 ``A`` (hence body_pose / global_orient through the SMPL chain in torch) and ``transl``.
+
+Pair capacity, overflow check and the learned long-rows hint: ``sings_amd.overflow`` (``run_forward``), the same policy as the
+drop-in rasterizer's, with the per-op differences spelled out at the two calls below.
 """
 import ctypes as C
 
 import torch
 
-from . import _lib
-from . import rasterizer as _rz
+from . import _lib, overflow
 from .rasterizer import _f32, _ptr, _settings_struct
 
 
@@ -68,36 +70,29 @@ class _RasterizeSkinnedGaussians(torch.autograd.Function):
         radii = torch.empty((P,), dtype=torch.int32, device=dev)
         e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
         pxyz, pq, psc = (e(P, 3), e(P, 4), e(P, 3)) if return_posed else (None, None, None)
-        cap, sync, sig = _rz._forward_plan(dev, P, W, H)     # see rasterizer.set_overflow_check
-        hint_key = (dev.index,) + sig
-        rows = not rs.debug and _rz._rows_ok.get(hint_key, False)    # learned by a "sync" forward of this shape (rasterizer.py)
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            if sync and not rs.debug:
-                _rz._arm_early_count(s, dev)
-            while True:
-                s.flags = _lib.FLAG_LONG_ROWS if rows else 0
-                L = _lib.layout(P, W, H, cap)
-                geom = torch.empty(L.geom_bytes, dtype=torch.uint8, device=dev)
-                binning = torch.empty(L.bin_bytes, dtype=torch.uint8, device=dev)
-                img = torch.empty(L.img_bytes, dtype=torch.uint8, device=dev)
-                nr = C.c_int64(0)
-                _lib.check(lib.sg_skinned_forward(C.byref(s), P, C.byref(k), _ptr(shs), _ptr(opacities), _ptr(scales),
-                                                  _ptr(geom), _ptr(binning), cap, _ptr(img), _ptr(color), _ptr(radii),
-                                                  _ptr(pxyz), _ptr(pq), _ptr(psc), C.byref(nr) if sync else None, stream),
-                           "skinned forward")
-                R = int(nr.value) if sync else None
-                if sync and rows and R == _lib.NUM_RENDERED_LONG_LIST:       # a list outgrew its row: this frame again, without the hint
-                    _rz._rows_ok[hint_key] = rows = False
-                    continue
-                if not sync or R <= cap:
-                    break
-                cap = int(R * _rz._HEADROOM) + 1024
-            if sync:
-                _rz._forward_done_sync(dev, R, sig)
-                _rz._learn_hints(s, hint_key)
-            else:
-                _rz._after_forward(dev, binning, cap)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        geom = binning = img = None
+
+        def launch(cap, flags, sync):
+            nonlocal geom, binning, img
+            s.flags = flags
+            L = _lib.layout(P, W, H, cap)
+            geom = torch.empty(L.geom_bytes, dtype=torch.uint8, device=dev)
+            binning = torch.empty(L.bin_bytes, dtype=torch.uint8, device=dev)
+            img = torch.empty(L.img_bytes, dtype=torch.uint8, device=dev)
+            nr = C.c_int64(0)
+            _lib.check(lib.sg_skinned_forward(C.byref(s), P, C.byref(k), _ptr(shs), _ptr(opacities), _ptr(scales),
+                                              _ptr(geom), _ptr(binning), cap, _ptr(img), _ptr(color), _ptr(radii),
+                                              _ptr(pxyz), _ptr(pq), _ptr(psc), C.byref(nr) if sync else None, stream),
+                       "skinned forward")
+            return (int(nr.value),) if sync else None
+
+        cap, counts = overflow.run_forward(
+            dev, P, W, H, s, launch, lambda: binning[:8].view(torch.int32), debug=rs.debug,
+            hints=(_lib.FLAG_LONG_ROWS,),     # avatar frames are images of few tiles: only the long-rows hint applies
+            hints_need_sync=False,            # in every mode / under capture: a violated hint is reported like an overflow there
+            early_count=True)                 # "sync" forwards read R from the early-count word and learn the hints from it
+        R = None if counts is None else counts[0]
         ctx.rs, ctx.cap, ctx.M, ctx.num_rendered = rs, cap, M, R
         ctx.has_rot = rotmat_canon is not None
         ctx.has_ext = ext_tfs is not None
@@ -214,7 +209,6 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
         P = int(xyz_canon.shape[0]); H, W = int(rs.image_height), int(rs.image_width); M = int(shs.shape[1])
         keep = []
         s = _settings_struct(rs, dev, M, keep)
-        s.flags = _lib.FLAG_THROUGHPUT
         k = _skin_struct(dev, xyz_canon, rotmat_canon, lbs_weights, A16[0], smpl_scale,
                          None if transl is None else transl.reshape(-1)[:3], None, keep)
         k.A = A16.data_ptr()
@@ -222,45 +216,32 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
         fb = _frame_batch(K, cam_stride, tstride)
         color = torch.empty((K, 3, H, W), dtype=torch.float32, device=dev)
         radii = torch.empty((K, P), dtype=torch.int32, device=dev)
-        T = ((W + 15) // 16) * ((H + 15) // 16)
-        # the same plan as the single-frame op (rasterizer.set_overflow_check): "sync" reads the K pair counts before returning,
-        # "async" does so for the first call of a shape only and afterwards copies the K headers' (worst R, OR of the flags) to the
-        # pinned ring without waiting, "deferred" / a graph capture folds them into the device-side accumulator
-        cap, sync, sig = _rz._forward_plan(dev, P, W, H)
-        hint_key = (dev.index,) + sig
-        rows = not rs.debug and _rz._rows_ok.get(hint_key, False)    # learned by a "sync" single-frame forward of this shape
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            while True:
-                s.flags = _lib.FLAG_THROUGHPUT | (_lib.FLAG_LONG_ROWS if rows else 0)
-                L = _lib.SgLayout(); sizes = [C.c_size_t() for _ in range(4)]
-                _lib.check(lib.sg_frames_layout(P, W, H, cap, K, C.byref(L), *[C.byref(x) for x in sizes]), "sg_frames_layout")
-                geom = torch.empty(sizes[0].value, dtype=torch.uint8, device=dev)
-                binning = torch.empty(sizes[1].value, dtype=torch.uint8, device=dev)
-                img = torch.empty(sizes[2].value, dtype=torch.uint8, device=dev)
-                nr = (C.c_int64 * K)()
-                _lib.check(lib.sg_skinned_forward_frames(C.byref(s), C.byref(fb), P, C.byref(k), _ptr(shs), _ptr(opacities), _ptr(scales),
-                                                         _ptr(geom), _ptr(binning), cap, _ptr(img), _ptr(color), _ptr(radii), None, None,
-                                                         None, nr if sync else None, stream), "skinned forward (frames)")
-                if not sync:
-                    break
-                if rows and min(int(v) for v in nr) == _lib.NUM_RENDERED_LONG_LIST:
-                    _rz._rows_ok[hint_key] = rows = False
-                    continue
-                R = max(int(v) for v in nr)
-                if R <= cap:
-                    break
-                cap = int(R * _rz._HEADROOM) + 1024
-            if sync:
-                _rz._forward_done_sync(dev, R, sig)
-            else:
-                # largest pair count and the OR of the K frames' flag words (a frame's "long list" bit must not hide another
-                # frame's "overflow" bit: ADVICE r4) -> the asynchronous / deferred check of the single-frame op
-                h = binning.view(K, L.bin_bytes)[:, :8].view(torch.int32)
-                flags = (h[:, 1:2] & _rz._flag_bits(dev)).amax(0).sum().to(torch.int32)
-                hdr = torch.stack([h[:, 0].amax(), flags]).contiguous()
-                _rz._after_forward(dev, hdr.view(torch.uint8), cap)
-                nr = [0] * K
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        L = geom = binning = img = sizes = None
+
+        def launch(cap, flags, sync):
+            nonlocal L, geom, binning, img, sizes
+            s.flags = flags
+            L = _lib.SgLayout(); sizes = [C.c_size_t() for _ in range(4)]
+            _lib.check(lib.sg_frames_layout(P, W, H, cap, K, C.byref(L), *[C.byref(x) for x in sizes]), "sg_frames_layout")
+            geom = torch.empty(sizes[0].value, dtype=torch.uint8, device=dev)
+            binning = torch.empty(sizes[1].value, dtype=torch.uint8, device=dev)
+            img = torch.empty(sizes[2].value, dtype=torch.uint8, device=dev)
+            nr = (C.c_int64 * K)()
+            _lib.check(lib.sg_skinned_forward_frames(C.byref(s), C.byref(fb), P, C.byref(k), _ptr(shs), _ptr(opacities), _ptr(scales),
+                                                     _ptr(geom), _ptr(binning), cap, _ptr(img), _ptr(color), _ptr(radii), None, None,
+                                                     None, nr if sync else None, stream), "skinned forward (frames)")
+            return [int(v) for v in nr] if sync else None
+
+        # (unread: the largest pair count and the OR of the K frames' flag words go to the check of the single-frame op)
+        cap, nr = overflow.run_forward(
+            dev, P, W, H, s, launch, lambda: overflow.frames_header(binning, K, L.bin_bytes), debug=rs.debug,
+            base_flags=_lib.FLAG_THROUGHPUT,  # K frames share the GPU: long tile lists are not split over workgroups
+            hints=(_lib.FLAG_LONG_ROWS,),     # avatar frames are images of few tiles: only the long-rows hint applies
+            hints_need_sync=False,            # in every mode / under capture: a violated hint is reported like an overflow there
+            early_count=False)                # one early-count word holds one frame's count: the K counts are read after the call
+        if nr is None:
+            nr = [0] * K
         ctx.rs, ctx.cap, ctx.M, ctx.K, ctx.fb = rs, cap, M, K, (cam_stride, tstride)
         ctx.num_rendered = [int(v) for v in nr]
         ctx.has_rot = rotmat_canon is not None

@@ -26,7 +26,7 @@ of an old version refuses.
 import torch
 
 from . import decode as _dec
-from . import rasterizer as _rz
+from . import overflow
 from .train_step import capture_step
 
 
@@ -104,8 +104,8 @@ class AvatarTrainer:
             self.flat = torch.zeros(n, dtype=torch.float32, device=self.dev)
             self.views = _dec.set_gradient_arena(self.params, self.flat)
         if self.dev.type == "cuda":
-            _rz.set_overflow_check("sync")                       # the next steps size the pair capacity for the new set
-            _rz.reset_overflow_state()
+            overflow.set_overflow_check("sync")                  # the next steps size the pair capacity for the new set
+            overflow.reset_overflow_state()
         self._sizing = 2 if self.use_graph else 0
 
     def _body(self):
@@ -129,13 +129,13 @@ class AvatarTrainer:
             s["A"].copy_(A); s["gt"].copy_(gt_rgb); s["mask"].copy_(mask)
         if self.use_graph and self._sizing == 0:
             if self.captured is None:
-                _rz.set_deferred_overflow_check(True, capacity_pairs=_rz._capacity_hint.get(self.dev.index))
+                overflow.set_deferred_overflow_check(True, capacity_pairs=overflow.capacity_pairs(self.dev))
                 # (the capture's warm-up runs execute the body -- statistics included -- without being steps: put the statistics back)
                 keep = [x.clone() for x in (self.m.xyz_gradient_accum, self.m.denom, self.m.max_radii2D)]
                 self.captured = CapturedStep(self.m, self._body, warmup=2, device=self.dev)
                 for dst, src in zip((self.m.xyz_gradient_accum, self.m.denom, self.m.max_radii2D), keep):
                     dst.copy_(src)
-                _rz.check_deferred_overflow(self.dev)
+                overflow.check_deferred_overflow(self.dev)
             ld = self.captured.replay()
         else:
             ld = self._body()                                    # eager (and the synchronous sizing steps in front of a capture)

@@ -162,6 +162,33 @@ def test_direct_binning_of_few_tile_frames_leaves_the_bits_of_the_scatter_path(K
         assert fa.long_rows is False and torch.equal(img, torch.clamp(c_plain, 0.0, 1.0))
 
 
+def test_frame_animator_pipelines_fall_back_from_the_long_rows_hint():
+    """The pipelined FrameAnimator paths pass SG_FLAG_LONG_ROWS optimistically as ``render_round`` does: on the scene of the test
+    above whose list outgrows its row (refused on the device), ``render_frames`` (counts read from the copied headers) and
+    ``render_frames_batched`` (K frames per dispatch) drop the hint for good and hand out what ``render_round`` renders."""
+    from sings_amd.posed import FrameAnimator
+    dev = _dev()
+    N, J, W, H, F = 100000, 52, 160, 288, 4
+    s, ins, A, transl, one, stacked, dL = _avatar(N, J, W, H, 5, F, False, True)
+    canon = dict(xyz_canon=ins["xyz"] * 0.02, rotmat_canon=None, scales=ins["sc"], opacity=ins["op"], shs=ins["sh"],
+                 lbs_weights=ins["w"], active_sh_degree=0)
+    camd = {k_: (torch.from_numpy(np.ascontiguousarray(v)).to(dev) if isinstance(v, np.ndarray) else v) for k_, v in s["cam"].items()}
+    bg = torch.from_numpy(s["bg"]).to(dev)
+    jobs = [(camd, A[f].reshape(J, 4, 4), transl[f], ins["smpl_scale"], None) for f in range(F)]
+    ref = FrameAnimator(canon, streams=1)
+    want = [ref.render_round([job], bg)[0].clone() for job in jobs]
+    assert ref.long_rows is False
+    bgv = torch.clamp(bg, 0.0, 1.0)[:, None, None].expand(3, H, W)
+    assert not any(torch.equal(w, bgv) for w in want)
+    for run in (lambda fa: fa.render_frames(iter(jobs), bg), lambda fa: fa.render_frames_batched(iter(jobs), bg, frames_per_launch=4)):
+        fa = FrameAnimator(canon, streams=2)
+        got = dict(run(fa))
+        torch.cuda.synchronize()
+        assert fa.long_rows is False and sorted(got) == list(range(F))
+        for f in range(F):
+            assert torch.equal(got[f], want[f]), f
+
+
 def test_a_frame_that_overflows_its_workspace_is_background_with_zero_gradient_and_harms_no_other_frame():
     """The pair capacity lies between the smallest and the largest R of the batch: frames that fit render and differentiate as
     ever, frames that do not render the background, report their (too large) R, and contribute ZERO to the summed gradient --

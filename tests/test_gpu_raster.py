@@ -649,7 +649,7 @@ def test_drop_in_surface_learns_the_short_list_hint_and_never_returns_a_wrong_fr
     NEXT frame of that (device, P, W, H) runs with SG_FLAG_SHORT_LISTS (direct binning at this image size) and gives the same bits.  When
     the scene then grows a long list under the hint, the frame is rendered again without it before the call returns."""
     from diff_gaussian_rasterization import GaussianRasterizer
-    from sings_amd import rasterizer as rz
+    from sings_amd import overflow as ov, rasterizer as rz
     dev = _dev()
     N, W, H = 30000, 1280, 1040
     rz.reset_overflow_state(dev)
@@ -665,13 +665,13 @@ def test_drop_in_surface_learns_the_short_list_hint_and_never_returns_a_wrong_fr
 
     s = synthetic_scene(N, W, H, 3, 41)
     c0, g0 = frame(s)                                            # plain path; learns the hint
-    assert rz._short_ok.get(key) is True
+    assert ov._short_ok.get(key) is True
     c1, g1 = frame(s)                                            # with the hint
     assert torch.equal(c1, c0) and all(torch.equal(a, b) for a, b in zip(g1, g0))
     s2 = synthetic_scene(N, W, H, 3, 41)
     s2["means3D"][:, :2] *= 0.02                                 # lists of more than 1024 entries
     c2, g2 = frame(s2)                                           # under the hint: refused on the device, rendered again without it
-    assert rz._short_ok.get(key) is False
+    assert ov._short_ok.get(key) is False
     rz.reset_overflow_state(dev)
     c3, g3 = frame(s2)                                           # never hinted
     assert torch.equal(c2, c3) and all(torch.equal(a, b) for a, b in zip(g2, g3))
@@ -832,7 +832,7 @@ def test_deferred_overflow_check():
     """Deferred mode: the forward never reads the pair count (no host synchronisation inside a step).  A call whose count
     exceeds the capacity renders the background; check_deferred_overflow() reports it once, grows the capacity, and the
     next call is complete and equal to the synchronous result."""
-    from sings_amd import rasterizer as rz
+    from sings_amd import overflow as ov, rasterizer as rz
     from sings_amd.rasterizer import GaussianRasterizer
     dev = _dev()
     s = synthetic_scene(4000, 160, 128, 1, 29)
@@ -841,10 +841,10 @@ def test_deferred_overflow_check():
     args = dict(means3D=t(s["means3D"]), means2D=torch.zeros(4000, 3, device=dev), opacities=t(s["opacities"]), shs=t(s["shs"]),
                 scales=t(s["scales"]), rotations=t(s["rotations"]))
     ref, _ = GaussianRasterizer(rs)(**args)                      # synchronous mode (default)
-    hint = dict(rz._capacity_hint)
+    hint = dict(ov._capacity_hint)
     try:
         rz.set_deferred_overflow_check(True, capacity_pairs=1, device=dev)
-        rz._capacity_hint[dev.index] = 1
+        ov._capacity_hint[dev.index] = 1
         # (the wrapper never goes below max(hint, 4 P + tiles, 2^16) pairs: make the scene exceed that floor instead)
         big = synthetic_scene(30000, 160, 128, 1, 31)
         big["scales"] = big["scales"] * 6.0
@@ -867,7 +867,7 @@ def test_deferred_overflow_check():
     finally:
         rz.set_deferred_overflow_check(False)
         rz.reset_overflow_state()
-        rz._capacity_hint.update(hint)
+        ov._capacity_hint.update(hint)
 
 
 def test_default_overflow_mode_never_returns_a_wrong_frame():
@@ -876,10 +876,10 @@ def test_default_overflow_mode_never_returns_a_wrong_frame():
     gradients.  The count comes back through the early-count word (SgRasterSettings.count_signal), i.e. without a stream
     synchronisation: the composite kernel may still be running when the call returns; results are complete once the
     stream is."""
-    from sings_amd import rasterizer as rz
+    from sings_amd import overflow as ov, rasterizer as rz
     from sings_amd.rasterizer import GaussianRasterizer
     dev = _dev()
-    assert rz._mode == {"mode": "sync", "on_overflow": "raise"}
+    assert ov._mode == {"mode": "sync", "on_overflow": "raise"}
     rz.reset_overflow_state()
     big = synthetic_scene(30000, 160, 128, 1, 31)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
@@ -890,11 +890,11 @@ def test_default_overflow_mode_never_returns_a_wrong_frame():
     bgv = t(big["bg"])[:, None, None].expand(3, big["H"], big["W"])
     try:
         small, _ = GaussianRasterizer(brs)(**args(0.3))
-        cap0 = rz._capacity_hint[dev.index]
-        assert rz._signal.get(dev.index) is not None and not rz._pending.get(dev.index)   # early-count words in use, nothing async
+        cap0 = ov._capacity_hint[dev.index]
+        assert ov._signal.get(dev.index) is not None and not ov._pending.get(dev.index)   # early-count words in use, nothing async
         a8 = args(8.0)
         huge, _ = GaussianRasterizer(brs)(**a8)                     # > 2x the pairs of the frame before
-        assert rz._capacity_hint[dev.index] > cap0
+        assert ov._capacity_hint[dev.index] > cap0
         assert not torch.equal(huge, bgv)
         huge.sum().backward()
         assert float(a8["scales"].grad.abs().sum()) > 0
@@ -919,7 +919,7 @@ def test_async_overflow_check_is_opt_in_and_raises_late():
     renders the background, and the NEXT call RAISES (on_overflow="raise" is the default; "warn" downgrades it to a
     RuntimeWarning) with a capacity that fits from then on."""
     import warnings
-    from sings_amd import rasterizer as rz
+    from sings_amd import overflow as ov, rasterizer as rz
     from sings_amd.rasterizer import GaussianRasterizer
     dev = _dev()
     rz.reset_overflow_state()
@@ -932,18 +932,18 @@ def test_async_overflow_check_is_opt_in_and_raises_late():
     bgv = t(big["bg"])[:, None, None].expand(3, big["H"], big["W"])
     try:
         rz.set_overflow_check("async")
-        assert rz._mode["on_overflow"] == "raise"
+        assert ov._mode["on_overflow"] == "raise"
         small, _ = GaussianRasterizer(brs)(**args(0.3))              # first call of this signature: synchronous
-        assert not rz._pending.get(dev.index)
-        cap0 = rz._capacity_hint[dev.index]
+        assert not ov._pending.get(dev.index)
+        cap0 = ov._capacity_hint[dev.index]
         small2, _ = GaussianRasterizer(brs)(**args(0.3))             # asynchronous from now on
-        assert len(rz._pending[dev.index]) == 1 and torch.equal(small, small2)
+        assert len(ov._pending[dev.index]) == 1 and torch.equal(small, small2)
         huge, _ = GaussianRasterizer(brs)(**args(8.0))               # > 2x the pairs: overflows the capacity, not yet known
         assert torch.equal(huge, bgv)
         torch.cuda.synchronize()
         with pytest.raises(RuntimeError, match="rendered the background"):     # late, but loud
             GaussianRasterizer(brs)(**args(0.3))
-        assert rz._capacity_hint[dev.index] > cap0
+        assert ov._capacity_hint[dev.index] > cap0
         redo, _ = GaussianRasterizer(brs)(**args(8.0))               # capacity grown by now
         assert not torch.equal(redo, bgv)
         # "warn": the same event as a RuntimeWarning

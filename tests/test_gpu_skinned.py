@@ -167,7 +167,7 @@ def test_fused_op_learns_the_long_rows_hint_and_reports_a_violation():
     """rasterize_skinned_gaussians in "sync" mode reads the count word's SG_COUNT_FLAG_HALF_LONG_ROWS bit; the next call of that
     (device, P, W, H) -- in any overflow mode -- passes SG_FLAG_LONG_ROWS (direct binning of the few-tile frame) and returns the same
     bits.  A violated hint: "sync" renders the frame again without it; "deferred" reports it from check_deferred_overflow()."""
-    from sings_amd import rasterizer as rz
+    from sings_amd import overflow as ov, rasterizer as rz
     from sings_amd.skinned import rasterize_skinned_gaussians
     dev = torch.device("cuda:0")
     s = _scene(5000, 24, 11, isotropic=False)
@@ -183,7 +183,7 @@ def test_fused_op_learns_the_long_rows_hint_and_reports_a_violation():
         color.backward(t(s["dL"]))
         return color.detach().clone(), [x.grad.clone() for x in (xyz, Rc, sc, op, sh)]
     c0, g0 = frame()
-    assert rz._rows_ok.get(key) is True
+    assert ov._rows_ok.get(key) is True
     c1, g1 = frame()                                            # hinted
     assert torch.equal(c0, c1) and all(torch.equal(a, b) for a, b in zip(g0, g1))
     rz.set_deferred_overflow_check(True, device=dev)

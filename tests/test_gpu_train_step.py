@@ -109,7 +109,7 @@ def test_full_step_replays_from_a_hip_graph(defer_join):
     query behind the raster forward, the backward pass staged by hand in `AvatarStep.backward` (photometric gradients, the
     regularisers' gradients on their stream, one addition, the decoders' backward from the sums: round 5) -- against a reference
     computed with the early join and one plain autograd pass."""
-    from sings_amd import rasterizer as rz
+    from sings_amd import overflow as ov, rasterizer as rz
     from sings_amd.decode import AppearanceDecoder, GeometryDecoder, HexPlaneField
     from sings_amd.rasterizer import GaussianRasterizationSettings
     from sings_amd.regularizers import GaussiansEdgeLoss, L2Norm
@@ -151,7 +151,7 @@ def test_full_step_replays_from_a_hip_graph(defer_join):
         return loss.detach().clone()     # (nothing of the autograd graph may stay alive across the end of the capture:
                                          #  returning `loss` itself crashed hipStreamEndCapture in this test)
 
-    hint = dict(rz._capacity_hint)
+    hint = dict(ov._capacity_hint)
     try:
         ref = []
         for f in frames:                                          # eager references (synchronous mode)
@@ -166,7 +166,7 @@ def test_full_step_replays_from_a_hip_graph(defer_join):
                 assert abs(float(l) - ref[k][0]) <= 1e-6 * abs(ref[k][0]), (k, float(l), ref[k][0])
                 for p, r in zip(params, ref[k][1]):
                     assert (p.grad - r).abs().max().item() <= 1e-5 * r.abs().max().item() + 1e-12, k
-        rz.set_deferred_overflow_check(True, capacity_pairs=int(max(rz._capacity_hint.values()) * 1.5))
+        rz.set_deferred_overflow_check(True, capacity_pairs=int(max(ov._capacity_hint.values()) * 1.5))
         A_static.copy_(frames[0])
         side = torch.cuda.Stream(dev); side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -185,7 +185,7 @@ def test_full_step_replays_from_a_hip_graph(defer_join):
                 assert d <= 1e-5 * r.abs().max().item() + 1e-12, (k, d)      # (tri-plane sums: atomics order)
     finally:
         rz.set_deferred_overflow_check(False)
-        rz.reset_overflow_state(); rz._capacity_hint.update(hint)
+        rz.reset_overflow_state(); ov._capacity_hint.update(hint)
 
 
 _CAPTURE_GUARD_SCRIPT = r"""
