@@ -5,5 +5,6 @@ from sings_amd.rasterizer import (  # noqa: F401
     GaussianRasterizationSettings,
     GaussianRasterizer,
     rasterize_gaussians,
+    rasterize_gaussians_aux,
     _RasterizeGaussians,
 )

@@ -90,8 +90,9 @@ typedef struct SgLayout {
  * as a multiple computed by the caller.
  * History: 5 = round 5's first tree; 6 = SgTriplane gained `feature_minor` (+ `reserved`) at its end, sg_weight_grad_ws_bytes grew
  * (two partial slabs per workgroup for <= 64 outputs); entry points added since 5: sg_linear_backward_fan, sg_rows_laplacian,
- * sg_scales_head_forward / _backward. */
-#define SG_ABI_VERSION 7
+ * sg_scales_head_forward / _backward.  8 = depth and alpha maps:
+ * sg_aux_layout, sg_rasterize_forward_aux / _backward_aux, sg_skinned_forward_aux / _backward_aux added (nothing else changed). */
+#define SG_ABI_VERSION 8
 int sg_abi_version(void);
 const char *sg_version(void);
 const char *sg_last_error(void);
@@ -536,6 +537,50 @@ int sg_linear_backward_fan(int N, int Cin, int Cout, int act, const float *aux, 
 size_t sg_weight_grad_ws_bytes(int N, int Cout, int Cin);
 int sg_weight_grad(int N, int Cout, int Cin, const float *dz, const float *x, void *ws, float *dW, float *db,
                    void *stream);
+
+/* ---- depth and alpha maps (ABI 8) ------------------------------------------------------------------------------------------------
+ * For pixel p and the entries i the forward composites there (front to back, the colour's alpha_i, T_i and termination):
+ *   depth[p] = sum_i z_i alpha_i T_i      (accumulated view-space depth, not normalised: 0 where nothing is composited;
+ *                                           expected depth = depth / alpha)
+ *   alpha[p] = 1 - T_final[p]             (so colour = sum_i c_i alpha_i T_i + (1 - alpha) bg exactly)
+ * Both maps are [H,W] fp32, fully written.  z_i is the Gaussian's view-space z (the value the preprocess keys the depth sort on).
+ * The backward adds dL/ddepth and dL/dalpha to the colour's adjoints: dL/dalpha_i gains the terms of the colour recursion with
+ * colour (z, 1) and background 0, and dL/dz_i = sum_p dL/ddepth_p alpha_i T_i reaches means3D through the view transform (the
+ * posed mean, then LBS, in the skinned op).  Thresholds are decided as for the colour alone; dL_dmeans2D includes the new terms.
+ *
+ * Each call takes the parameters of its plain counterpart plus aux_ws: one view's aux workspace of sg_aux_layout's size, written
+ * by the forward and read and written by the backward (kept between them like image_ws).  The calls are single-frame and accept
+ * SG_FLAG_SHORT_LISTS, SG_FLAG_LONG_ROWS and SG_FLAG_WS_CLEAN; the other flags are refused (status 1, sg_last_error) before
+ * anything is launched.  Capacity overflow and hint violations are reported exactly as by the plain calls.  dL_ddepth / dL_dalpha
+ * [H,W] may each be NULL (zero). */
+int sg_aux_layout(int P, int width, int height, size_t capacity_pairs, size_t *aux_bytes);
+int sg_rasterize_forward_aux(const SgRasterSettings *s, int P, const float *means3D, const float *shs,
+                             const float *colors_precomp, const float *opacities, const float *scales,
+                             const float *rotations, const float *cov3D_precomp, void *geom_ws,
+                             void *binning_ws, size_t capacity_pairs, void *image_ws, float *out_color,
+                             int32_t *radii, int write_point_keys, int64_t *num_rendered_host, void *aux_ws,
+                             float *out_depth, float *out_alpha, void *stream);
+int sg_rasterize_backward_aux(const SgRasterSettings *s, int P, const float *means3D, const float *shs,
+                              const float *colors_precomp, const float *opacities, const float *scales,
+                              const float *rotations, const float *cov3D_precomp, const int32_t *radii,
+                              const void *geom_ws, const void *binning_ws, size_t capacity_pairs,
+                              const void *image_ws, void *bwd_ws, const float *dL_dout_color,
+                              float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dsh, float *dL_dcolors,
+                              float *dL_dopacity, float *dL_dscales, float *dL_drotations,
+                              float *dL_dcov3D, void *aux_ws, const float *dL_ddepth, const float *dL_dalpha, void *stream);
+int sg_skinned_forward_aux(const SgRasterSettings *s, int P, const SgSkinInputs *skin, const float *shs,
+                           const float *opacities, const float *scales, void *geom_ws, void *binning_ws,
+                           size_t capacity_pairs, void *image_ws, float *out_color, int32_t *radii,
+                           float *posed_xyz, float *posed_rotq, float *posed_scales,
+                           int64_t *num_rendered_host, void *aux_ws, float *out_depth, float *out_alpha, void *stream);
+int sg_skinned_backward_aux(const SgRasterSettings *s, int P, const SgSkinInputs *skin, const float *shs,
+                            const float *opacities, const float *scales, const int32_t *radii,
+                            const void *geom_ws, const void *binning_ws, size_t capacity_pairs,
+                            const void *image_ws, void *bwd_ws, float *skin_ws, const float *dL_dout_color,
+                            const float *dL_dposed_xyz_in, const float *dL_dposed_rotq_in,
+                            float *dL_dxyz_canon, float *dL_drot_canon, float *dL_dscales,
+                            float *dL_dopacity, float *dL_dsh, float *dL_dmeans2D, float *dL_dA,
+                            float *dL_dtransl, void *aux_ws, const float *dL_ddepth, const float *dL_dalpha, void *stream);
 
 /* ---- optional per-kernel timing (bench / profiling only; process-global, not thread-safe).
  * When enabled, every kernel launch of forward/backward is bracketed by hipEvents on the

@@ -64,9 +64,10 @@ EXPORTS = ("sg_abi_version", "sg_version", "sg_last_error", "sg_layout", "sg_ras
            "sg_weight_grad_ws_bytes", "sg_weight_grad", "sg_linear_forward", "sg_linear_backward", "sg_linear_backward_accumulate", "sg_linear_backward_fan", "sg_copy_probe",
            "sg_frames_layout", "sg_rasterize_forward_frames", "sg_skinned_forward_frames", "sg_read_num_rendered_frames", "sg_photo_loss_backward_frames",
            "sg_rasterize_backward_records_frames", "sg_rasterize_backward_gaussians_frames", "sg_skin_ws_floats_frames",
-           "sg_skinned_backward_gaussians_frames", "sg_photo_loss_frames")
+           "sg_skinned_backward_gaussians_frames", "sg_photo_loss_frames",
+           "sg_aux_layout", "sg_rasterize_forward_aux", "sg_rasterize_backward_aux", "sg_skinned_forward_aux", "sg_skinned_backward_aux")
 NUM_KERNELS = 8
-ABI_VERSION = 7                      # SG_ABI_VERSION
+ABI_VERSION = 8                      # SG_ABI_VERSION
 FLAG_SHORT_LISTS = 1                 # SG_FLAG_SHORT_LISTS
 COUNT_FLAG_HALF_ROWS = 4             # SG_COUNT_FLAG_HALF_ROWS
 COUNT_FLAG_HALF_LONG_ROWS = 8        # SG_COUNT_FLAG_HALF_LONG_ROWS
@@ -194,6 +195,14 @@ def load():
     for f in ("sg_region_laplacian", "sg_rows_laplacian", "sg_mesh_edge_loss", "sg_l2norm_reg", "sg_gaussian_edge_loss", "sg_gaussian_edge_prepare",
               "sg_gaussian_edge_finish"):
         getattr(lib, f).restype = C.c_int
+    # depth and alpha maps (ABI 8): the plain calls' parameters + the aux workspace (+ the two maps / their gradients) before the stream
+    lib.sg_aux_layout.argtypes = [i32, i32, i32, sz, C.POINTER(sz)]
+    lib.sg_rasterize_forward_aux.argtypes = lib.sg_rasterize_forward.argtypes[:-1] + [vp, vp, vp, vp]
+    lib.sg_rasterize_backward_aux.argtypes = lib.sg_rasterize_backward.argtypes[:-1] + [vp, vp, vp, vp]
+    lib.sg_skinned_forward_aux.argtypes = lib.sg_skinned_forward.argtypes[:-1] + [vp, vp, vp, vp]
+    lib.sg_skinned_backward_aux.argtypes = lib.sg_skinned_backward.argtypes[:-1] + [vp, vp, vp, vp]
+    for f in ("sg_aux_layout", "sg_rasterize_forward_aux", "sg_rasterize_backward_aux", "sg_skinned_forward_aux", "sg_skinned_backward_aux"):
+        getattr(lib, f).restype = C.c_int
     for f in ("sg_layout", "sg_rasterize_forward", "sg_rasterize_backward", "sg_mark_visible",
               "sg_read_num_rendered", "sg_skinned_forward", "sg_skinned_backward"):
         getattr(lib, f).restype = C.c_int
@@ -210,3 +219,10 @@ def layout(P, W, H, cap):
     L = SgLayout()
     check(load().sg_layout(P, W, H, cap, C.byref(L)), "sg_layout")
     return L
+
+
+def aux_layout(P, W, H, cap):
+    """Bytes of one view's aux workspace (depth / alpha maps: sg_aux_layout)."""
+    n = C.c_size_t(0)
+    check(load().sg_aux_layout(P, W, H, cap, C.byref(n)), "sg_aux_layout")
+    return int(n.value)

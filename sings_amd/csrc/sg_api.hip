@@ -28,7 +28,7 @@ static int sg_fail(const char *what, hipError_t e)
         }                                                                    \
     } while (0)
 
-extern "C" const char *sg_version(void) { return "sings_hip 0.7 (gfx950, abi 7)"; }
+extern "C" const char *sg_version(void) { return "sings_hip 0.8 (gfx950, abi 8)"; }
 extern "C" int sg_abi_version(void) { return SG_ABI_VERSION; }
 extern "C" const char *sg_last_error(void) { return g_err; }
 
@@ -213,16 +213,48 @@ static int sg_read_counts(const void *binning_ws, size_t bin_stride, int K, int6
     return 0;
 }
 
+// The flags the depth / alpha entry points accept: the learned list hints and the clean-workspace promise.  THROUGHPUT, the
+// FORWARD_BINNING / FORWARD_COMPOSITE split and SH_PLANAR select kernels or layouts that have no AUX variant.
+static int sg_aux_flags(const char *who, int flags)
+{
+    static const struct { int bit; const char *name; } refused[] = {
+        { SG_FLAG_THROUGHPUT, "SG_FLAG_THROUGHPUT" }, { SG_FLAG_FORWARD_BINNING, "SG_FLAG_FORWARD_BINNING" },
+        { SG_FLAG_FORWARD_COMPOSITE, "SG_FLAG_FORWARD_COMPOSITE" }, { SG_FLAG_SH_PLANAR, "SG_FLAG_SH_PLANAR" } };
+    char msg[200];
+    for (const auto &r : refused)
+        if (flags & r.bit) {
+            snprintf(msg, sizeof msg, "%s: %s is not supported with depth / alpha maps", who, r.name);
+            return sg_fail(msg, hipSuccess);
+        }
+    const int known = SG_FLAG_SHORT_LISTS | SG_FLAG_LONG_ROWS | SG_FLAG_WS_CLEAN;
+    if (flags & ~known) { snprintf(msg, sizeof msg, "%s: unknown flags 0x%x", who, flags & ~known); return sg_fail(msg, hipSuccess); }
+    return 0;
+}
+
+extern "C" int sg_aux_layout(int P, int width, int height, size_t cap, size_t *aux_bytes)
+{
+    SgLayout L;
+    if (!aux_bytes) return sg_fail("sg_aux_layout", hipSuccess);
+    if (sg_layout(P, width, height, cap, &L)) return 1;          // (the same size checks)
+    *aux_bytes = sg_aux_bytes(cap);
+    return 0;
+}
+
 static int sg_forward_impl(const char *who, const SgRasterSettings *s, const SgFrameBatch *fb, int P, const SgSkinInputs *skin,
                            const float *means3D, const float *shs, const float *colors_precomp, const float *opacities,
                            const float *scales, const float *rotations, const float *cov3D_precomp, void *geom_ws, void *binning_ws,
                            size_t cap, void *image_ws, float *out_color, int32_t *radii, float *posed_xyz, float *posed_rotq,
-                           float *posed_scales, int write_point_keys, int64_t *num_rendered_host, void *stream)
+                           float *posed_scales, int write_point_keys, int64_t *num_rendered_host, void *stream,
+                           void *aux_ws = nullptr, float *out_depth = nullptr, float *out_alpha = nullptr)
 {
     hipStream_t st = (hipStream_t)stream;
     SgCam c;
     char msg[160];
     if (sg_make_cam(s, &c)) { snprintf(msg, sizeof msg, "%s: bad settings", who); return sg_fail(msg, hipSuccess); }
+    if (aux_ws) {
+        if (sg_aux_flags(who, c.flags)) return 1;
+        if (!out_depth || !out_alpha) { snprintf(msg, sizeof msg, "%s: null pointer (out_depth / out_alpha)", who); return sg_fail(msg, hipSuccess); }
+    }
     if (skin) {
         if (sg_check_skin(skin, P, true)) { snprintf(msg, sizeof msg, "%s: bad skin inputs (J in 1..64, ext_tfs all or none)", who); return sg_fail(msg, hipSuccess); }
         if (P < 0 || !geom_ws || !binning_ws || !image_ws || !out_color || (P > 0 && (!shs || !opacities || !scales || !radii))) {
@@ -263,7 +295,8 @@ static int sg_forward_impl(const char *who, const SgRasterSettings *s, const SgF
         SG_CHECK_LAST("binning", s, st);
     }
     if (do_comp) {
-        sg_launch_render_fwd(c, bt, g, b, cap, im, out_color, write_point_keys, st);
+        const SgAuxFwd ax = sg_aux_fwd_view(aux_ws, g, out_depth, out_alpha);
+        sg_launch_render_fwd(c, bt, g, b, cap, im, out_color, write_point_keys, st, aux_ws ? &ax : nullptr);
         SG_CHECK_LAST("render_fwd", s, st);
     }
     if (!do_bin) return 0;
@@ -492,6 +525,120 @@ extern "C" int sg_skinned_backward_gaussians(const SgRasterSettings *s, int P, c
     return sg_skinned_backward_gaussians_frames(s, &SG_ONE_FRAME, P, skin, shs, opacities, scales, radii, geom_ws, binning_ws, cap,
                                                 bwd_ws, skin_ws, accumulate, dL_dposed_xyz_in, dL_dposed_rotq_in, dL_dxyz_canon,
                                                 dL_drot_canon, dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA, dL_dtransl, stream);
+}
+
+// ---- depth and alpha maps (ABI 8) ----------------------------------------------------------------------------------------------
+extern "C" int sg_rasterize_forward_aux(const SgRasterSettings *s, int P, const float *means3D, const float *shs,
+                                        const float *colors_precomp, const float *opacities, const float *scales,
+                                        const float *rotations, const float *cov3D_precomp, void *geom_ws,
+                                        void *binning_ws, size_t cap, void *image_ws, float *out_color,
+                                        int32_t *radii, int write_point_keys, int64_t *num_rendered_host, void *aux_ws,
+                                        float *out_depth, float *out_alpha, void *stream)
+{
+    if (!aux_ws) return sg_fail("sg_rasterize_forward_aux: null pointer (aux_ws)", hipSuccess);
+    return sg_forward_impl("sg_rasterize_forward_aux", s, &SG_ONE_FRAME, P, nullptr, means3D, shs, colors_precomp, opacities, scales,
+                           rotations, cov3D_precomp, geom_ws, binning_ws, cap, image_ws, out_color, radii, nullptr, nullptr, nullptr,
+                           write_point_keys, num_rendered_host, stream, aux_ws, out_depth, out_alpha);
+}
+
+extern "C" int sg_skinned_forward_aux(const SgRasterSettings *s, int P, const SgSkinInputs *skin, const float *shs,
+                                      const float *opacities, const float *scales, void *geom_ws, void *binning_ws,
+                                      size_t cap, void *image_ws, float *out_color, int32_t *radii, float *posed_xyz,
+                                      float *posed_rotq, float *posed_scales, int64_t *num_rendered_host, void *aux_ws,
+                                      float *out_depth, float *out_alpha, void *stream)
+{
+    if (!aux_ws) return sg_fail("sg_skinned_forward_aux: null pointer (aux_ws)", hipSuccess);
+    return sg_forward_impl("sg_skinned_forward_aux", s, &SG_ONE_FRAME, P, skin, nullptr, shs, nullptr, opacities, scales, nullptr, nullptr,
+                           geom_ws, binning_ws, cap, image_ws, out_color, radii, posed_xyz, posed_rotq, posed_scales, 0,
+                           num_rendered_host, stream, aux_ws, out_depth, out_alpha);
+}
+
+// backward composite with the depth / alpha adjoints: gradient records + the dL/dz plane of aux_ws
+static int sg_records_aux(const char *who, const SgRasterSettings *s, const SgCam &c, int P, const void *geom_ws, const void *binning_ws,
+                          size_t cap, const void *image_ws, void *bwd_ws, const float *dL_dout_color, void *aux_ws,
+                          const float *dL_ddepth, const float *dL_dalpha, hipStream_t st)
+{
+    SgLayout L;
+    sg_layout(P, c.W, c.H, cap, &L);
+    SgBatch bt = sg_batch_one(P);
+    SgGeom g = sg_geom_view((void *)geom_ws, L);
+    SgBin b = sg_bin_view((void *)binning_ws, L);
+    SgImg im = sg_img_view((void *)image_ws, L);
+    const SgAuxBwd ax = sg_aux_bwd_view(aux_ws, cap, g, dL_ddepth, dL_dalpha);
+    sg_launch_render_bwd(c, bt, g, b, cap, im, dL_dout_color, sg_rec_view(bwd_ws, cap), st, &ax);
+    SG_CHECK_LAST(who, s, st);
+    return 0;
+}
+
+extern "C" int sg_rasterize_backward_aux(const SgRasterSettings *s, int P, const float *means3D, const float *shs,
+                                         const float *colors_precomp, const float *opacities, const float *scales,
+                                         const float *rotations, const float *cov3D_precomp, const int32_t *radii,
+                                         const void *geom_ws, const void *binning_ws, size_t cap, const void *image_ws,
+                                         void *bwd_ws, const float *dL_dout_color, float *dL_dmeans3D,
+                                         float *dL_dmeans2D, float *dL_dsh, float *dL_dcolors, float *dL_dopacity,
+                                         float *dL_dscales, float *dL_drotations, float *dL_dcov3D, void *aux_ws,
+                                         const float *dL_ddepth, const float *dL_dalpha, void *stream)
+{
+    (void)opacities;
+    hipStream_t st = (hipStream_t)stream;
+    SgCam c;
+    if (sg_make_cam(s, &c)) return sg_fail("sg_rasterize_backward_aux: bad settings", hipSuccess);
+    if (sg_aux_flags("sg_rasterize_backward_aux", c.flags)) return 1;
+    if (P <= 0) return 0;
+    if (!means3D || !radii || !geom_ws || !binning_ws || !image_ws || !bwd_ws || !dL_dout_color || !dL_dmeans3D ||
+        !dL_dmeans2D || !dL_dopacity || !aux_ws)
+        return sg_fail("sg_rasterize_backward_aux: null pointer", hipSuccess);
+    if (shs && !dL_dsh) return sg_fail("sg_rasterize_backward_aux: dL_dsh missing", hipSuccess);
+    int rc = sg_records_aux("render_bwd_aux", s, c, P, geom_ws, binning_ws, cap, image_ws, bwd_ws, dL_dout_color, aux_ws, dL_ddepth,
+                            dL_dalpha, st);
+    if (rc) return rc;
+    SgLayout L;
+    sg_layout(P, c.W, c.H, cap, &L);
+    SgGeom g = sg_geom_view((void *)geom_ws, L);
+    SgBin b = sg_bin_view((void *)binning_ws, L);
+    const SgAuxBwd ax = sg_aux_bwd_view(aux_ws, cap, g, dL_ddepth, dL_dalpha);
+    sg_launch_preprocess_bwd(c, sg_batch_one(P), P, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, g,
+                             sg_rec_view(bwd_ws, cap), cap, b.header, sg_lds_hist(c.gx, c.gy) ? b.rec_valid : nullptr, nullptr,
+                             dL_dmeans3D, dL_dmeans2D, shs ? dL_dsh : nullptr,
+                             dL_dcolors, dL_dopacity, cov3D_precomp ? nullptr : dL_dscales,
+                             cov3D_precomp ? nullptr : dL_drotations, dL_dcov3D, 0, st, ax.dz);
+    SG_CHECK_LAST("preprocess_bwd_aux", s, st);
+    return 0;
+}
+
+extern "C" int sg_skinned_backward_aux(const SgRasterSettings *s, int P, const SgSkinInputs *skin, const float *shs,
+                                       const float *opacities, const float *scales, const int32_t *radii,
+                                       const void *geom_ws, const void *binning_ws, size_t cap, const void *image_ws,
+                                       void *bwd_ws, float *skin_ws, const float *dL_dout_color,
+                                       const float *dL_dposed_xyz_in, const float *dL_dposed_rotq_in, float *dL_dxyz_canon,
+                                       float *dL_drot_canon, float *dL_dscales, float *dL_dopacity, float *dL_dsh,
+                                       float *dL_dmeans2D, float *dL_dA, float *dL_dtransl, void *aux_ws, const float *dL_ddepth,
+                                       const float *dL_dalpha, void *stream)
+{
+    (void)opacities;
+    hipStream_t st = (hipStream_t)stream;
+    SgCam c;
+    if (sg_make_cam(s, &c)) return sg_fail("sg_skinned_backward_aux: bad settings", hipSuccess);
+    if (sg_aux_flags("sg_skinned_backward_aux", c.flags)) return 1;
+    if (sg_check_skin(skin, P, false)) return sg_fail("sg_skinned_backward_aux: bad skin inputs (ext_tfs are forward-only)", hipSuccess);
+    if (P <= 0) return 0;
+    if (!shs || !scales || !radii || !geom_ws || !binning_ws || !image_ws || !bwd_ws || !skin_ws || !dL_dout_color ||
+        !dL_dxyz_canon || !dL_dscales || !dL_dopacity || !dL_dsh || !dL_dmeans2D || !dL_dA || !aux_ws)
+        return sg_fail("sg_skinned_backward_aux: null pointer", hipSuccess);
+    int rc = sg_records_aux("render_bwd_aux", s, c, P, geom_ws, binning_ws, cap, image_ws, bwd_ws, dL_dout_color, aux_ws, dL_ddepth,
+                            dL_dalpha, st);
+    if (rc) return rc;
+    SgLayout L;
+    sg_layout(P, c.W, c.H, cap, &L);
+    SgGeom g = sg_geom_view((void *)geom_ws, L);
+    SgBin b = sg_bin_view((void *)binning_ws, L);
+    const SgAuxBwd ax = sg_aux_bwd_view(aux_ws, cap, g, dL_ddepth, dL_dalpha);
+    sg_launch_skin_bwd(c, sg_batch_one(P), P, skin, shs, scales, radii, g, sg_rec_view(bwd_ws, cap), cap, b.header,
+                       sg_lds_hist(c.gx, c.gy) ? b.rec_valid : nullptr, dL_dposed_xyz_in, dL_dposed_rotq_in,
+                       skin_ws, dL_dxyz_canon, dL_drot_canon, dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA,
+                       dL_dtransl, 0, st, ax.dz);
+    SG_CHECK_LAST("skin_bwd_aux", s, st);
+    return 0;
 }
 
 __global__ void sg_mark_visible_kernel(int P, const float *__restrict__ means3D, const float *__restrict__ view,

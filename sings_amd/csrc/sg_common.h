@@ -132,6 +132,37 @@ static inline SgRec sg_rec_view(const void *bwd_ws, size_t cap)
     return r;
 }
 
+// ---- depth and alpha maps (sg_aux_layout, the *_aux entry points) -------------------------------------------------------------
+// One view's aux workspace: the accumulated depth D at every checkpoint of the forward ([sg_ckpt_cap slots][256 pixels], the slots
+// of SgImg::ckpt, beside its (T, colour) float4s), then dL/dz of every (tile, Gaussian) pair ([cap], the Gaussian-major slot of
+// that pair's 36-byte gradient record).
+static inline size_t sg_aux_ckd_bytes(size_t cap) { return sg_align((size_t)sg_ckpt_cap(cap) * 256 * 4); }
+static inline size_t sg_aux_bytes(size_t cap) { return sg_aux_ckd_bytes(cap) + sg_align((cap + 1) * 4); }
+struct SgAuxFwd {          // forward composite: z per Gaussian (SgGeom::depth), the two [H,W] maps, the D checkpoints
+    const float *depth;
+    float *out_depth, *out_alpha;
+    float *ckD;
+};
+struct SgAuxBwd {          // backward composite: z per Gaussian, the D checkpoints, dL/ddepth and dL/dalpha per pixel (either may be null),
+    const float *depth;    // dL/dz per pair
+    const float *ckD;
+    const float *dL_ddepth, *dL_dalpha;
+    float *dz;
+};
+static inline SgAuxFwd sg_aux_fwd_view(void *aux_ws, const SgGeom &g, float *out_depth, float *out_alpha)
+{
+    SgAuxFwd a;
+    a.depth = g.depth; a.out_depth = out_depth; a.out_alpha = out_alpha; a.ckD = (float *)aux_ws;
+    return a;
+}
+static inline SgAuxBwd sg_aux_bwd_view(void *aux_ws, size_t cap, const SgGeom &g, const float *dL_ddepth, const float *dL_dalpha)
+{
+    SgAuxBwd a;
+    a.depth = g.depth; a.ckD = (const float *)aux_ws; a.dL_ddepth = dL_ddepth; a.dL_dalpha = dL_dalpha;
+    a.dz = (float *)((char *)aux_ws + sg_aux_ckd_bytes(cap));
+    return a;
+}
+
 static inline SgGeom sg_geom_view(void *ws, const SgLayout &L)
 {
     char *b = (char *)ws;
@@ -248,10 +279,11 @@ void sg_launch_preprocess_fwd(const SgCam &c, const SgBatch &bt, int P, const fl
 void sg_launch_binning(const SgCam &c, const SgBatch &bt, int P, const int32_t *radii, SgGeom g, SgBin b, size_t cap,
                        int write_keys, hipStream_t st);
 static inline uint32_t sg_cap32(size_t cap) { return cap > 0xffffffffull ? 0xffffffffu : (uint32_t)cap; }
+// ax != null (single frame only): the AUX composite kernels, which also produce the depth / alpha maps / dL/dz per pair
 void sg_launch_render_fwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, size_t cap, SgImg im, float *out_color,
-                          int write_keys, hipStream_t st);
+                          int write_keys, hipStream_t st, const SgAuxFwd *ax = nullptr);
 void sg_launch_render_bwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, size_t cap, SgImg im,
-                          const float *dL_dpix, SgRec grec, hipStream_t st);
+                          const float *dL_dpix, SgRec grec, hipStream_t st, const SgAuxBwd *ax = nullptr);
 // a9out [K][P][12]: the per-Gaussian sums of frame f's gradient records (sg_skin.hip::sg_record_sums_kernel), for the K-frame
 // per-Gaussian backward kernels
 void sg_launch_record_sums(const SgBatch &bt, int P, const int32_t *radii, SgGeom g, SgRec grec, size_t cap, const uint32_t *header,
@@ -264,7 +296,7 @@ void sg_launch_preprocess_bwd(const SgCam &c, const SgBatch &bt, int P, const fl
                               const int32_t *radii, SgGeom g, SgRec grec, size_t cap, const uint32_t *header, const uint8_t *rec_valid,
                               float4 *a9buf, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dsh,
                               float *dL_dcolors, float *dL_dopacity, float *dL_dscales,
-                              float *dL_drots, float *dL_dcov3D, int accumulate, hipStream_t st);
+                              float *dL_drots, float *dL_dcov3D, int accumulate, hipStream_t st, const float *dz = nullptr);
 
 // per-kernel event timing (sg_api.hip)
 // Zero `bytes` (a multiple of 4) at the 4-byte aligned address p with a KERNEL.  Not hipMemsetAsync: a step replayed from
@@ -333,4 +365,4 @@ void sg_launch_skin_bwd(const SgCam &c, const SgBatch &bt, int P, const SgSkinIn
                         const int32_t *radii, SgGeom g, SgRec grec, size_t cap, const uint32_t *header, const uint8_t *rec_valid,
                         const float *dposed_xyz_in, const float *dposed_rotq_in, float *slab, float *dL_dxyz_canon, float *dL_drot_canon,
                         float *dL_dscales, float *dL_dopacity, float *dL_dsh, float *dL_dmeans2D, float *dL_dA,
-                        float *dL_dtransl, int accumulate, hipStream_t st);
+                        float *dL_dtransl, int accumulate, hipStream_t st, const float *dz = nullptr);

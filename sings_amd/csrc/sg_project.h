@@ -457,6 +457,22 @@ __device__ __forceinline__ void sg_sum_records_coop(SgRec grec, size_t cap, bool
     }
 }
 
+// (AUX) dL/dz of a Gaussian: the sum of its dz plane entries (sg_aux_bytes), one per record slot, added in the order
+// sg_sum_records_coop adds the records -- slot by slot, records whose `valid` byte is 0 entering as zeros
+__device__ __forceinline__ float sg_sum_dz(const float *__restrict__ dz, size_t cap, bool vis, float4 recC,
+                                           const uint8_t *__restrict__ valid)
+{
+    const uint32_t goff = __float_as_uint(recC.y), wh = __float_as_uint(recC.w);
+    const uint32_t tt = vis ? (wh & 0xffffu) * (wh >> 16) : 0u;
+    float a = 0.0f;
+    for (uint32_t k = 0; k < tt; k++) {
+        const size_t r = (size_t)goff + k;
+        if (r >= cap) break;
+        a += (!valid || valid[r]) ? dz[r] : 0.0f;
+    }
+    return a;
+}
+
 // Backward of sg_project_fwd for one VISIBLE Gaussian.  a9 = summed record
 // (mean2D.x, mean2D.y, conic.x, conic.y, conic.w, opacity, colour r,g,b).
 // dsh_out: (D+1)^2 x 3 gradient rows of this Gaussian (written iff want_sh; pass a local array); `first` false: ADDED to what the

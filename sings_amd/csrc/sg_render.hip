@@ -169,10 +169,11 @@ __device__ __forceinline__ int sg_compact_quadrant(const uint32_t *__restrict__ 
 #define SG_FWD_ARGS W, H, gx, T, nblocks, ranges, pair_keys, point_list, point_keys, recA, recB, recC, bg, out_color, final_T, \
                     n_contrib, ck_start, ckpt, ck_cap, header, pair_mask, tile_count, long_items, mask_plane, plan, item_w, w_plane, key_pitch
 // WEIGHTS: leave the backward's work-item weights (few-tile frames: item_w, first_item); always with PIPE
-template <bool PIPE, bool WEIGHTS>
-__device__ __forceinline__ void sg_render_fwd_body(SG_FWD_PARAMS)
+// AUX: also accumulate D = sum z alpha T per pixel and write the depth / alpha maps (`ax`); AUX = false ignores `ax`
+template <bool PIPE, bool WEIGHTS, bool AUX = false>
+__device__ __forceinline__ void sg_render_fwd_body(SG_FWD_PARAMS, SgAuxFwd ax = SgAuxFwd{})
 {
-    __shared__ float4 sR[SG_FB][3];            // staged entry: (mean x, mean y, A', B') (C', opacity, colour 0, 1) (colour 2, -, -, -)
+    __shared__ float4 sR[SG_FB][3];            // staged entry: (mean x, mean y, A', B') (C', opacity, colour 0, 1) (colour 2, z [AUX], -, -)
     __shared__ uint32_t sM[SG_FB];
     __shared__ uint16_t sList[4][SG_FB];       // byte offsets into sR (index * 48)
     __shared__ float4 sBox[4];
@@ -219,13 +220,14 @@ __device__ __forceinline__ void sg_render_fwd_body(SG_FWD_PARAMS)
     const uint32_t cks = n > SG_SEG ? ck_start[tile] : 0xffffffffu;   // segmented list: checkpoint slots cks + segment
     const uint32_t first_item = (PIPE || WEIGHTS) ? plan[tile].x : 0u;   // first backward work item of this tile
     float Tr = 1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
+    float Dz = 0.0f;                                   // (AUX) accumulated depth
     uint32_t last = 0;
     bool done = !inside;
     const unsigned long long lt = (1ull << lane) - 1ull;
     // software pipeline over batches: the gathers of batch k+1 are in flight while batch k is composited (a tile
     // whose list is thousands of entries long runs alone on its CU -- nothing else hides the two dependent loads)
     float4 pa = make_float4(0, 0, 0, 0), pb = pa;
-    float pc = 0.0f;
+    float pc = 0.0f, pz = 0.0f;
     static_assert((SG_WSORT_MAX + SG_RANKSORT_MAX) * 8 <= SG_FB * 48, "sort buffers alias sR");
     if (n > 0 && n <= SG_WSORT_MAX) {
         // Short list (<= 1024 entries: every list at cfg3, most of an avatar's): this workgroup sorts the tile's keys itself, in LDS, and hands the order to
@@ -239,11 +241,15 @@ __device__ __forceinline__ void sg_render_fwd_body(SG_FWD_PARAMS)
             const uint32_t gid = (uint32_t)key;
             point_list[range.x + i] = gid;
             if (point_keys) point_keys[range.x + i] = ((uint64_t)tile << 32) | (key >> 32);
-            if (i == tid) { pa = recA[SG_REC_STRIDE * (size_t)gid]; pb = recB[SG_REC_STRIDE * (size_t)gid]; pc = recC[SG_REC_STRIDE * (size_t)gid].x; }
+            if (i == tid) {
+                pa = recA[SG_REC_STRIDE * (size_t)gid]; pb = recB[SG_REC_STRIDE * (size_t)gid]; pc = recC[SG_REC_STRIDE * (size_t)gid].x;
+                if (AUX) pz = ax.depth[gid];
+            }
         }
     } else if (tid < n) {                                   // long list: sorted by sg_tile_sort_kernel / sg_tile_rank_kernel
         const uint32_t gid = point_list[range.x + tid];
         pa = recA[SG_REC_STRIDE * (size_t)gid]; pb = recB[SG_REC_STRIDE * (size_t)gid]; pc = recC[SG_REC_STRIDE * (size_t)gid].x;
+        if (AUX) pz = ax.depth[gid];
     }
     for (int base = 0; base < n; base += SG_FB) {
         {   // this quadrant's pixels that are still being composited
@@ -257,6 +263,7 @@ __device__ __forceinline__ void sg_render_fwd_body(SG_FWD_PARAMS)
             sR[tid][0] = make_float4(pa.x, pa.y, SG_KA * pa.z, SG_KB * pa.w);
             sR[tid][1] = make_float4(SG_KA * pb.x, pb.y, pb.z, pb.w);
             sR[tid][2].x = pc;
+            if (AUX) sR[tid][2].y = pz;
             const uint32_t mk = sg_quad_mask(pa, pb, (float)X0, (float)Y0, sBox);
             sM[tid] = mk;
             staged = mk != 0u;
@@ -265,6 +272,7 @@ __device__ __forceinline__ void sg_render_fwd_body(SG_FWD_PARAMS)
         if (e + SG_FB < n) {
             const uint32_t gid = point_list[range.x + e + SG_FB];
             pa = recA[SG_REC_STRIDE * (size_t)gid]; pb = recB[SG_REC_STRIDE * (size_t)gid]; pc = recC[SG_REC_STRIDE * (size_t)gid].x;
+            if (AUX) pz = ax.depth[gid];
         }
         if (PIPE || WEIGHTS) {
             // few-tile frames: the weight of the backward work item (tile, this segment) = entries composited somewhere; the
@@ -279,15 +287,17 @@ __device__ __forceinline__ void sg_render_fwd_body(SG_FWD_PARAMS)
         __syncthreads();
         if (__ballot(done) == ~0ull) continue;             // this quadrant is finished (wave-uniform)
         // state in front of entry `base`, for the backward pass of the segments behind it (SG_FB == SG_SEG)
-        if (base > 0 && ckok && cks != 0xffffffffu && cks + (uint32_t)(base / SG_SEG) < ck_cap)
+        if (base > 0 && ckok && cks != 0xffffffffu && cks + (uint32_t)(base / SG_SEG) < ck_cap) {
             ckpt[(size_t)(cks + (uint32_t)(base / SG_SEG)) * 256 + ckidx] = make_float4(Tr, C0, C1, C2);
+            if (AUX) ax.ckD[(size_t)(cks + (uint32_t)(base / SG_SEG)) * 256 + ckidx] = Dz;
+        }
         const int cnt = n - base < SG_FB ? n - base : SG_FB;
         uint16_t *list = sList[wave];
         const int nl = sg_compact_quadrant<48>(sM, cnt, wave, lane, lt, list, SG_FB);
         uint32_t lastk = 0xffffffffu;                      // record offset of the last entry blended in this batch
         // one (entry, quadrant) pass -- straight-line, predicated: no exec-mask branches.  (A macro, not a lambda: captured by
         // reference, `done` lived in a byte register and every pass paid three extra vector instructions for it.)
-#define SG_FWD_PASS(ga, gb, gc, ko)                                                                        \
+#define SG_FWD_PASS(ga, gb, gc, gz, ko)                                                                    \
         do {                                                                                               \
             const float dx = (ga).x - pxf, dy = (ga).y - pyf;                                              \
             const float power = sg_power2((ga).z, (ga).w, (gb).x, dx, dy);                                 \
@@ -298,6 +308,7 @@ __device__ __forceinline__ void sg_render_fwd_body(SG_FWD_PARAMS)
             const bool blend = valid & !term;                                                              \
             const float w = blend ? alpha * Tr : 0.0f;                                                     \
             C0 = fmaf((gb).z, w, C0); C1 = fmaf((gb).w, w, C1); C2 = fmaf((gc), w, C2);                    \
+            if (AUX) Dz = fmaf((gz), w, Dz);                                                               \
             Tr = blend ? test_T : Tr;                                                                      \
             lastk = blend ? (ko) : lastk;                                                                  \
             done = done | term;                                                                            \
@@ -307,7 +318,7 @@ __device__ __forceinline__ void sg_render_fwd_body(SG_FWD_PARAMS)
         // VCC / scalar registers.  With one wave per SIMD (the regime this walk exists for) every vector -> scalar -> vector hop
         // is exposed latency: the all-vector form is 10 us faster on the avatar frame (106 vs 116 us); with eight busy waves the
         // extra vector instructions cost 4 us at cfg3 (74.7 vs 70.7), hence the macro for the plain loop.  Same-box A/B both ways.
-        auto pass = [&](const float4 ga, const float4 gb, const float gc, const uint32_t ko) { SG_FWD_PASS(ga, gb, gc, ko); };
+        auto pass = [&](const float4 ga, const float4 gb, const float gc, const float gz, const uint32_t ko) { SG_FWD_PASS(ga, gb, gc, gz, ko); };
         if (PIPE) {
             // Software pipeline over the quadrant's list: the record of entry i + 1 and the list word of entry i + 2 are
             // requested BEFORE the arithmetic of entry i (two register sets, A and B, alternate: no copies).  As a plain loop
@@ -319,17 +330,20 @@ __device__ __forceinline__ void sg_render_fwd_body(SG_FWD_PARAMS)
             uint32_t kA = nl > 0 ? list[0] : 0u, kB = nl > 1 ? list[1] : kA;
             float4 aA = rec_of(kA)[0], bA = rec_of(kA)[1];
             float cA = rec_of(kA)[2].x;
+            float zA = AUX ? rec_of(kA)[2].y : 0.0f;
             for (int i = 0; i < nl; i += 2) {
                 const float4 aB = rec_of(kB)[0], bB = rec_of(kB)[1];
                 const float cB = rec_of(kB)[2].x;
+                const float zB = AUX ? rec_of(kB)[2].y : 0.0f;
                 const uint32_t kA2 = list[i + 2 < nl ? i + 2 : nl - 1];
                 __builtin_amdgcn_sched_barrier(0);          // (hipcc otherwise sinks the requests to just in front of their use)
-                pass(aA, bA, cA, kA);
+                pass(aA, bA, cA, zA, kA);
                 if (i + 1 >= nl) break;
                 aA = rec_of(kA2)[0]; bA = rec_of(kA2)[1]; cA = rec_of(kA2)[2].x;
+                if (AUX) zA = rec_of(kA2)[2].y;
                 const uint32_t kB2 = list[i + 3 < nl ? i + 3 : nl - 1];
                 __builtin_amdgcn_sched_barrier(0);
-                pass(aB, bB, cB, kB);
+                pass(aB, bB, cB, zB, kB);
                 kA = kA2; kB = kB2;
             }
         } else {
@@ -338,13 +352,17 @@ __device__ __forceinline__ void sg_render_fwd_body(SG_FWD_PARAMS)
                 const float4 *rec = (const float4 *)((const char *)&sR[0][0] + ko);
                 const float4 ga = rec[0], gb = rec[1];
                 const float gc = rec[2].x;
-                SG_FWD_PASS(ga, gb, gc, ko);
+                const float gz = AUX ? rec[2].y : 0.0f;
+                SG_FWD_PASS(ga, gb, gc, gz, ko);
             }
         }
 #undef SG_FWD_PASS
         if (lastk != 0xffffffffu) last = (uint32_t)base + lastk / 48u + 1u;
     }
-    if (cks < ck_cap && ckok) ckpt[(size_t)cks * 256 + ckidx] = make_float4(Tr, C0, C1, C2);   // slot 0: final state
+    if (cks < ck_cap && ckok) {
+        ckpt[(size_t)cks * 256 + ckidx] = make_float4(Tr, C0, C1, C2);   // slot 0: final state
+        if (AUX) ax.ckD[(size_t)cks * 256 + ckidx] = Dz;
+    }
     if (inside) {
         const size_t pid = (size_t)py * W + px, hw = (size_t)H * W;
         final_T[pid] = Tr;
@@ -352,6 +370,7 @@ __device__ __forceinline__ void sg_render_fwd_body(SG_FWD_PARAMS)
         out_color[pid] = fmaf(Tr, bg[0], C0);
         out_color[hw + pid] = fmaf(Tr, bg[1], C1);
         out_color[2 * hw + pid] = fmaf(Tr, bg[2], C2);
+        if (AUX) { ax.out_depth[pid] = Dz; ax.out_alpha[pid] = 1.0f - Tr; }
     }
 }
 
@@ -362,6 +381,13 @@ sg_render_fwd_kernel(SG_FWD_PARAMS) { sg_render_fwd_body<false, false>(SG_FWD_AR
 // regime of the LDS histogram in the preprocess), where the kernel ends in a handful of deep tiles, one wave per SIMD.
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7)))
 sg_render_fwd_deep_kernel(SG_FWD_PARAMS) { sg_render_fwd_body<true, true>(SG_FWD_ARGS); }
+// The two kernels above with the depth / alpha maps (SgAuxFwd): single-frame calls of sg_rasterize_forward_aux /
+// sg_skinned_forward_aux.  Separate symbols, so that profiles and sg_kernel_name keep the plain kernels apart.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+sg_render_fwd_aux_kernel(SG_FWD_PARAMS, SgAuxFwd ax) { sg_render_fwd_body<false, false, true>(SG_FWD_ARGS, ax); }
+// (six waves per SIMD: at seven the extra accumulator and z spilled 8 bytes per lane)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6)))
+sg_render_fwd_deep_aux_kernel(SG_FWD_PARAMS, SgAuxFwd ax) { sg_render_fwd_body<true, true, true>(SG_FWD_ARGS, ax); }
 // Frame blockIdx.y of a launch of K frames (sg_common.h, SgBatch): the frame's workspaces at base + frame x stride, its image at
 // + frame x 3 H W.  Also the kernel of few-tile frames that share the chip with other views (SG_FLAG_THROUGHPUT), K = 1 included:
 // every SIMD has other waves to run there, the pipelined walk's extra vector instructions only cost issue slots (344 -> 319 us for
@@ -386,7 +412,7 @@ sg_render_fwd_frames_kernel(SgBatch bt, SG_FWD_PARAMS)
 static inline int sg_render_blocks(int T) { return ((T + 8 * SG_XCD_RUN - 1) / (8 * SG_XCD_RUN)) * (8 * SG_XCD_RUN); }
 
 void sg_launch_render_fwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, size_t cap, SgImg im, float *out_color,
-                          int write_keys, hipStream_t st)
+                          int write_keys, hipStream_t st, const SgAuxFwd *ax)
 {
     static_assert(SG_FB == SG_SEG, "forward batches are the checkpoint granularity");
     const int T = c.gx * c.gy;
@@ -400,7 +426,14 @@ void sg_launch_render_fwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, 
                        im.final_T, im.n_contrib, b.ck_start, im.ckpt, sg_ckpt_cap(cap), b.header, b.pair_mask, b.tile_count,       \
                        (const uint4 *)b.sort_items, sg_mask_plane(cap), b.plan, b.item_w, sg_items_cap((size_t)T, cap), key_pitch
     sg_prof_begin(SG_K_RENDER_FWD, st);
-    if (K > 1 || (few && (c.flags & SG_FLAG_THROUGHPUT))) {
+    if (ax) {
+        // depth / alpha maps: one frame, the single-frame kernels' regimes (the entry points refuse K > 1 and SG_FLAG_THROUGHPUT)
+        if (few) {
+            const int extra = sg_split_long(c.gx, c.gy, c.flags) ? 3 * (int)sg_sort_items_cap(T, cap) : 0;
+            hipLaunchKernelGGL(sg_render_fwd_deep_aux_kernel, dim3(extra + grid), dim3(256), 0, st, SG_RF_ARGS(extra), *ax);
+        } else
+            hipLaunchKernelGGL(sg_render_fwd_aux_kernel, dim3(grid), dim3(256), 0, st, SG_RF_ARGS(grid), *ax);
+    } else if (K > 1 || (few && (c.flags & SG_FLAG_THROUGHPUT))) {
         // K frames per launch, or a few-tile frame that shares the chip with other views: the plain loop (see the kernel)
         if (few) hipLaunchKernelGGL(sg_render_fwd_frames_kernel<true>, dim3(grid, K), dim3(256), 0, st, bt, SG_RF_ARGS(grid));
         else hipLaunchKernelGGL(sg_render_fwd_frames_kernel<false>, dim3(grid, K), dim3(256), 0, st, bt, SG_RF_ARGS(grid));
@@ -450,6 +483,14 @@ __device__ __forceinline__ float sg_reduce9(const float v[9], int lane, float *v
     *v8tot = x;
     return z;
 }
+// (AUX) the tenth partial, dL/dz: summed over the 64 lanes into lane 63 in the fixed order sg_reduce9 sums v[8]
+__device__ __forceinline__ float sg_reduce_to63(float x)
+{
+    x += SG_DPP(x, 0xB1); x += SG_DPP(x, 0x4E); x += SG_DPP(x, 0x141); x += SG_DPP(x, 0x140);
+    asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa\n\ts_nop 1\n\t"
+                 "v_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc" : "+v"(x));
+    return x;
+}
 // value index held by 8-lane group g = lane >> 3 after sg_reduce9: rows (v0|v4, v2|v6, v1|v5, v3|v7)
 __device__ __forceinline__ int sg_red_idx(int lane)
 {
@@ -461,6 +502,9 @@ __device__ __forceinline__ int sg_red_idx(int lane)
 // One (entry, quadrant) pass of the backward composite: `ga, gb, gc` the staged record, KPOS the entry's position in the batch
 // (compared with the pixel's contributor count inside the batch, `ncq_b`), KSLOT its row in sG.  `continue` skips entries that
 // touch no pixel of the quadrant.  Shared by sg_render_bwd_kernel and sg_render_bwd_sparse_kernel.
+// AUX (the depth / alpha maps): the entry's colour gains a fourth channel z with upstream gradient dD = dL/ddepth (so `Sd` carries
+// <colour, dL/dpixel> + D_behind dD), dL/dalpha enters through `tb` (T_final (<bg, dL/dpixel> - dL/dalpha)), and the tenth
+// partial dchan dD = dL/dz goes to slot 9 (lane 63).
 #define SG_BWD_PASS(KPOS, KSLOT)                                                                                      \
     /* straight-line, predicated (alpha_eff = 0 makes every update an exact no-op) */                                 \
     const float dx = ga.x - pxf, dy = ga.y - pyf;                                                                     \
@@ -474,7 +518,7 @@ __device__ __forceinline__ int sg_red_idx(int lane)
     Tr = Tr * rinv;                                  /* T in front of this entry */                                   \
     const float dchan = ae * Tr;                                                                                      \
     /* <colour - colour behind, dL/dpixel>, and the colour behind moves in front of this entry */                     \
-    const float e = fmaf(gc, d2, fmaf(gb.w, d1, gb.z * d0)) - Sd;                                                     \
+    const float e = (AUX ? fmaf(gz, dD, fmaf(gc, d2, fmaf(gb.w, d1, gb.z * d0))) : fmaf(gc, d2, fmaf(gb.w, d1, gb.z * d0))) - Sd; \
     Sd = fmaf(ae, e, Sd);                                                                                             \
     const float dLa = fmaf(-tb, rinv, e * Tr);      /* + (-T_final / (1 - alpha)) <bg, dL/dpixel> */                  \
     const float w = valid ? G * dLa : 0.0f;          /* = dL/dopacity contribution; dL/dG = o * dLa */                \
@@ -488,9 +532,12 @@ __device__ __forceinline__ int sg_red_idx(int lane)
     v[6] = dchan * d0; v[7] = dchan * d1; v[8] = dchan * d2;                                                          \
     float v8;                                                                                                         \
     const float z = sg_reduce9(v, lane, &v8);                                                                         \
+    float v9 = 0.0f;                                                                                                  \
+    if (AUX) v9 = sg_reduce_to63(dchan * dD);                                                                         \
     float *slot = &sG[wave][KSLOT][cslot];               /* lanes 0, 8, .., 56: their value's slot; lane 63: slot 8 */\
     if ((lane & 7) == 0) *slot = z;                                                                                   \
     if (lane == 63) *slot = v8;                                                                                       \
+    if (AUX && lane == 63) sG[wave][KSLOT][9] = v9;                                                                   \
     do { } while (0)
 
 // frame blockIdx.y of a launch of K frames (see SG_FWD_FRAME_OFFSETS)
@@ -526,149 +573,15 @@ struct SgStampScope {
 #else
 #define SG_STAMP_SCOPE
 #endif
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
-sg_render_bwd_kernel(SgBatch bt, int W, int H, int gx, int T, int nblocks, const uint2 *__restrict__ ranges,
-                     const uint32_t *__restrict__ point_list, const float4 *__restrict__ recA,
-                     const float4 *__restrict__ recB, const float4 *__restrict__ recC,
-                     const float *__restrict__ bg, const float *__restrict__ final_T,
-                     const uint32_t *__restrict__ n_contrib, const float *__restrict__ dL_dpix,
-                     float4 *__restrict__ grec_a, float *__restrict__ grec_b, uint32_t cap, const uint32_t *__restrict__ header,
-                     const uint32_t *__restrict__ items, const uint32_t *__restrict__ ck_start,
-                     const float4 *__restrict__ ckpt, uint32_t ck_cap, const uint8_t *__restrict__ pair_mask, uint32_t mask_plane,
-                     int split_long)
-{
-    __shared__ float4 sR[SG_BCH][3];           // staged entry: (mean x, mean y, A', B') (C', opacity, colour 0, 1) (colour 2, -, -, -)
-    __shared__ uint32_t sM[SG_BCH];
-    __shared__ uint16_t sList[4][SG_BB];
-    __shared__ float sG[4][SG_BB][9];          // per-quadrant reduced partials of the batch; [8] = SG_UNSET: quadrant w wrote nothing
-    __shared__ uint32_t smax[4];
-    SG_STAMP_SCOPE
-    SG_BWD_FRAME_OFFSETS;
-    // one workgroup per work item (tile, depth segment); the item list is in tile order, so the XCD-aware map
-    // over the ACTUAL item count keeps neighbouring tiles on one L2.  The grid is an upper bound.
-    (void)T; (void)nblocks;
-    const int nitems = header[1] ? 0 : (int)header[5];             // nothing to do after a capacity overflow
-    const int it = sg_tile_of_block(blockIdx.x);
-    if (it >= nitems) return;
-    const uint32_t item = items[it];
-    const int tile = (int)(item & 0xfffffu), seg = (int)(item >> 20);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int tx = tile % gx, ty = tile / gx;
-    const int X0 = tx * 16, Y0 = ty * 16;
-    const int px = X0 + 8 * (wave & 1) + (lane & 7), py = Y0 + 8 * (wave >> 1) + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float pxf = (float)px, pyf = (float)py;
-    const uint2 range = ranges[tile];
-    const int n = (int)(range.y - range.x);
-    const uint32_t cks = ck_start[tile];
-    const int lo = seg * SG_SEG;                                   // this item: entries [lo, hi)
-    const int hi = cks != 0xffffffffu && lo + SG_SEG < n ? lo + SG_SEG : n;
-    if (lo >= n) return;
-    const size_t pid = (size_t)py * W + px, hw = (size_t)H * W;
-    // per-pixel state: running T, colour accumulated BEHIND the current entry, dL/dpixel, T_final <bg, dL/dpixel>
-    const float Tfin = inside ? final_T[pid] : 0.0f;
-    const uint32_t ncq = inside ? n_contrib[pid] : 0u;
-    const float d0 = inside ? dL_dpix[pid] : 0.0f, d1 = inside ? dL_dpix[hw + pid] : 0.0f, d2 = inside ? dL_dpix[2 * hw + pid] : 0.0f;
-    const float tb = Tfin * (bg[0] * d0 + bg[1] * d1 + bg[2] * d2);
-    // (the colour behind enters the gradient only through <S, dL/dpixel>: ONE running scalar Sd instead of three channels)
-    float Tr = Tfin, Sd = 0.0f;
-    // Not the last segment, and this pixel has contributors behind it: start from the forward checkpoint at `hi`.
-    // T in front of entry hi; S = colour composited behind it, normalised by that T.  (A pixel with ncq <= hi has
-    // nothing behind: final state.  ncq > hi implies the forward reached that boundary with this pixel live.)
-    if (hi < n && ncq > (uint32_t)hi && cks + (uint32_t)(hi / SG_SEG) < ck_cap) {
-        const float4 cb = ckpt[(size_t)(cks + (uint32_t)(hi / SG_SEG)) * 256 + tid];
-        const float4 cf = ckpt[(size_t)cks * 256 + tid];
-        const float rT = 1.0f / cb.x;
-        Tr = cb.x;
-        Sd = fmaf((cf.w - cb.w) * rT, d2, fmaf((cf.z - cb.z) * rT, d1, (cf.y - cb.y) * rT * d0));
-    }
-    uint32_t m = ncq;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { uint32_t u = __shfl_xor(m, o, 64); m = u > m ? u : m; }
-    const int maxq = (int)__builtin_amdgcn_readfirstlane(m);          // this quadrant's deepest contributor
-    if (lane == 0) smax[wave] = m;
-    if (tid < SG_BB) {
-#pragma unroll
-        for (int w = 0; w < 4; w++) sG[w][tid][8] = __uint_as_float(SG_UNSET);
-    }
-    __syncthreads();
-    const int max_contrib = (int)max(max(smax[0], smax[1]), max(smax[2], smax[3]));
-    const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    const int cslot = lane == 63 ? 8 : sg_red_idx(lane);
-    for (int ch = (hi - 1) / SG_BCH; ch >= lo / SG_BCH; ch--) {
-        const int cbase = ch * SG_BCH;
-        const int ccnt = hi - cbase < SG_BCH ? hi - cbase : SG_BCH;
-        // ---- stage the chunk (threads 0..SG_BCH-1): records, quadrant mask, gradient-record slot
-        uint32_t rslot = 0xffffffffu;
-        float opac = 0.0f, cA = 0.0f, cB = 0.0f, cC = 0.0f;
-        if (tid < ccnt) {
-            const int e = cbase + tid;
-            const uint32_t gid = point_list[range.x + e];
-            // quadrants the forward composited this entry in: nothing else can carry a gradient, so neither the
-            // rectangle tests nor the two record gathers are repeated for the rest
-            // (a long tile of a few-tile frame was composited by four workgroups, one mask plane each: sg_render_fwd_body)
-            uint32_t mk = 0u;
-            if (e < max_contrib) {
-                mk = pair_mask[range.x + e];
-                if (split_long && n > SG_WSORT_MAX)
-                    mk = (mk & 1u) | (pair_mask[(size_t)mask_plane + range.x + e] & 2u) | (pair_mask[2 * (size_t)mask_plane + range.x + e] & 4u) |
-                         (pair_mask[3 * (size_t)mask_plane + range.x + e] & 8u);
-            }
-            const float4 c4 = recC[SG_REC_STRIDE * (size_t)gid];
-            if (mk) {
-                const float4 a = recA[SG_REC_STRIDE * (size_t)gid], b = recB[SG_REC_STRIDE * (size_t)gid];
-                opac = b.y; cA = a.z; cB = a.w; cC = b.x;
-                sR[tid][0] = make_float4(a.x, a.y, SG_KA * a.z, SG_KB * a.w);
-                sR[tid][1] = make_float4(SG_KA * b.x, b.y, b.z, b.w);
-                sR[tid][2].x = c4.x;
-            }
-            const uint32_t goff = __float_as_uint(c4.y), mn = __float_as_uint(c4.z), wh = __float_as_uint(c4.w);
-            const int x0 = mn & 0xffff, y0 = mn >> 16, rw = wh & 0xffff;
-            rslot = goff + (uint32_t)((ty - y0) * rw + (tx - x0));
-            sM[tid] = mk;
-        }
-        __syncthreads();
-        for (int kb = (ccnt - 1) / SG_BB; kb >= 0; kb--) {
-            const int b0 = kb * SG_BB, base = cbase + b0;                  // the batch inside the chunk / inside the list
-            const int cnt = ccnt - b0 < SG_BB ? ccnt - b0 : SG_BB;
-            // ---- each wave: the entries that can reach its quadrant, back to front
-            if (base < maxq) {
-                uint16_t *list = sList[wave];
-                const int lim = maxq - base < cnt ? maxq - base : cnt;         // entries >= maxq touch no pixel here
-                const int nl = sg_compact_quadrant<1>(sM + b0, lim, wave, lane, lt, list, SG_BB);
-                const uint32_t ncq_b = ncq > (uint32_t)base ? ncq - (uint32_t)base : 0u;   // contributors of this pixel inside the batch
-                for (int i = nl - 1; i >= 0; i--) {
-                    const uint32_t k = list[i];
-                    const float4 ga = sR[b0 + k][0], gb = sR[b0 + k][1];
-                    const float gc = sR[b0 + k][2].x;
-                    SG_BWD_PASS(k, k);
-                }
-            }
-            __syncthreads();
-            // ---- combine the quadrants in a fixed order, store the record, re-arm the slots (the thread that staged the entry)
-            if (tid >= b0 && tid < b0 + cnt) {
-                const int q0 = tid - b0;
-                float s[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-#pragma unroll
-                for (int w = 0; w < 4; w++)
-                    if (__float_as_uint(sG[w][q0][8]) != SG_UNSET) {
-#pragma unroll
-                        for (int q = 0; q < 9; q++) s[q] += sG[w][q0][q];
-                        sG[w][q0][8] = __uint_as_float(SG_UNSET);
-                    }
-                if (rslot < cap) {
-                    const float no = -opac, nh = 0.5f * no;              // -opacity, -opacity / 2
-                    const float m0 = fmaf(cA, s[0], cB * s[1]), m1 = fmaf(cB, s[0], cC * s[1]);   // conic . first moments
-                    grec_a[2 * (size_t)rslot] = make_float4(no * ddelx_dx * m0, no * ddely_dy * m1, nh * s[2], nh * s[3]);
-                    grec_a[2 * (size_t)rslot + 1] = make_float4(nh * s[4], s[5], s[6], s[7]);
-                    grec_b[rslot] = s[8];
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
+#define SG_BWD_PARAMS SgBatch bt, int W, int H, int gx, int T, int nblocks, const uint2 *__restrict__ ranges,                 \
+                      const uint32_t *__restrict__ point_list, const float4 *__restrict__ recA,                          \
+                      const float4 *__restrict__ recB, const float4 *__restrict__ recC,                                   \
+                      const float *__restrict__ bg, const float *__restrict__ final_T,                                    \
+                      const uint32_t *__restrict__ n_contrib, const float *__restrict__ dL_dpix,                          \
+                      float4 *__restrict__ grec_a, float *__restrict__ grec_b, uint32_t cap, const uint32_t *__restrict__ header, \
+                      const uint32_t *__restrict__ items, const uint32_t *__restrict__ ck_start,                          \
+                      const float4 *__restrict__ ckpt, uint32_t ck_cap, const uint8_t *__restrict__ pair_mask, uint32_t mask_plane, \
+                      int split_long
 
 // ------------------------------------------------------------------------------------------
 // Backward composite for frames of FEW tiles with long lists (an avatar; the regime of sg_lds_hist).
@@ -734,142 +647,19 @@ sg_order_items_kernel(SgBatch bt, const uint32_t *__restrict__ header, const uin
     }
 }
 
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6)))
-sg_render_bwd_sparse_kernel(SgBatch bt, int W, int H, int gx, int T, int nblocks, const uint2 *__restrict__ ranges,
-                            const uint32_t *__restrict__ point_list, const float4 *__restrict__ recA,
-                            const float4 *__restrict__ recB, const float4 *__restrict__ recC,
-                            const float *__restrict__ bg, const float *__restrict__ final_T,
-                            const uint32_t *__restrict__ n_contrib, const float *__restrict__ dL_dpix,
-                            float4 *__restrict__ grec_a, float *__restrict__ grec_b, uint32_t cap, const uint32_t *__restrict__ header,
-                            const uint32_t *__restrict__ items, const uint32_t *__restrict__ ck_start,
-                            const float4 *__restrict__ ckpt, uint32_t ck_cap, const uint8_t *__restrict__ pair_mask, uint32_t mask_plane,
-                            int split_long, const uint32_t *__restrict__ perm, uint8_t *__restrict__ rec_valid)
-{
-    __shared__ float4 sR[SG_BS][3];            // staged entry: (mean x, mean y, A', B') (C', opacity, colour 0, 1) (colour 2, -, -, -)
-    __shared__ uint32_t sM[SG_BS];
-    __shared__ uint16_t sList[4][SG_BB];
-    __shared__ float sG[4][SG_BB][9];          // per-quadrant reduced partials of the sub-batch; [8] = SG_UNSET: quadrant w wrote nothing
-    __shared__ uint32_t smax[4];
-    (void)T; (void)nblocks;
-    SG_BWD_FRAME_OFFSETS;
-    perm = sg_at(perm, (size_t)blockIdx.y * bt.bin); rec_valid = sg_at(rec_valid, (size_t)blockIdx.y * bt.bin);
-    const int nitems = header[1] ? 0 : (int)header[5];
-    if ((int)blockIdx.x >= nitems) return;
-    const uint32_t pit = perm[blockIdx.x];
-    const uint32_t item = items[pit];                               // dispatch order = heaviest first
-    const int tile = (int)(item & 0xfffffu), seg = (int)(item >> 20);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int tx = tile % gx, ty = tile / gx;
-    const int X0 = tx * 16, Y0 = ty * 16;
-    const int px = X0 + 8 * (wave & 1) + (lane & 7), py = Y0 + 8 * (wave >> 1) + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float pxf = (float)px, pyf = (float)py;
-    const uint2 range = ranges[tile];
-    const int n = (int)(range.y - range.x);
-    const uint32_t cks = ck_start[tile];
-    const int lo = seg * SG_SEG;                                   // this item: entries [lo, hi)
-    const int hi = cks != 0xffffffffu && lo + SG_SEG < n ? lo + SG_SEG : n;
-    if (lo >= n) return;
-    const size_t pid = (size_t)py * W + px, hw = (size_t)H * W;
-    const uint32_t ncq = inside ? n_contrib[pid] : 0u;
-    uint32_t m = ncq;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { uint32_t u = __shfl_xor(m, o, 64); m = u > m ? u : m; }
-    const int maxq = (int)__builtin_amdgcn_readfirstlane(m);          // this quadrant's deepest contributor
-    if (lane == 0) smax[wave] = m;
-    __syncthreads();
-    const int max_contrib = (int)max(max(smax[0], smax[1]), max(smax[2], smax[3]));
-    if (lo >= max_contrib) return;                                     // nothing of this segment reached a pixel: its records stay zero
-    // ---- stage the segment: one entry per thread
-    const int cnt = hi - lo;                                           // <= SG_BS
-    uint32_t rslot = 0xffffffffu;
-    float opac = 0.0f, cA = 0.0f, cB = 0.0f, cC = 0.0f;
-    {
-        uint32_t mk = 0u, gid = 0u;
-        const int e = lo + tid;
-        if (tid < cnt && e < max_contrib) {
-            gid = point_list[range.x + e];
-            mk = pair_mask[range.x + e];
-            if (split_long && n > SG_WSORT_MAX)
-                mk = (mk & 1u) | (pair_mask[(size_t)mask_plane + range.x + e] & 2u) | (pair_mask[2 * (size_t)mask_plane + range.x + e] & 4u) |
-                     (pair_mask[3 * (size_t)mask_plane + range.x + e] & 8u);
-            mk &= 15u;
-        }
-        if (mk) {
-            const float4 c4 = recC[SG_REC_STRIDE * (size_t)gid], a = recA[SG_REC_STRIDE * (size_t)gid], b = recB[SG_REC_STRIDE * (size_t)gid];
-            const uint32_t goff = __float_as_uint(c4.y), mn = __float_as_uint(c4.z), wh = __float_as_uint(c4.w);
-            const int x0 = mn & 0xffff, y0 = mn >> 16, rw = wh & 0xffff;
-            rslot = goff + (uint32_t)((ty - y0) * rw + (tx - x0));
-            opac = b.y; cA = a.z; cB = a.w; cC = b.x;
-            sR[tid][0] = make_float4(a.x, a.y, SG_KA * a.z, SG_KB * a.w);
-            sR[tid][1] = make_float4(SG_KA * b.x, b.y, b.z, b.w);
-            sR[tid][2].x = c4.x;
-        }
-        sM[tid] = mk;
-    }
-    // per-pixel state (requested while the gathers above are in flight)
-    const float Tfin = inside ? final_T[pid] : 0.0f;
-    const float d0 = inside ? dL_dpix[pid] : 0.0f, d1 = inside ? dL_dpix[hw + pid] : 0.0f, d2 = inside ? dL_dpix[2 * hw + pid] : 0.0f;
-    const float tb = Tfin * (bg[0] * d0 + bg[1] * d1 + bg[2] * d2);
-    float Tr = Tfin, Sd = 0.0f;
-    if (hi < n && ncq > (uint32_t)hi && cks + (uint32_t)(hi / SG_SEG) < ck_cap) {       // (see sg_render_bwd_kernel)
-        const float4 cb = ckpt[(size_t)(cks + (uint32_t)(hi / SG_SEG)) * 256 + tid];
-        const float4 cf = ckpt[(size_t)cks * 256 + tid];
-        const float rT = 1.0f / cb.x;
-        Tr = cb.x;
-        Sd = fmaf((cf.w - cb.w) * rT, d2, fmaf((cf.z - cb.z) * rT, d1, (cf.y - cb.y) * rT * d0));
-    }
-    const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    const int cslot = lane == 63 ? 8 : sg_red_idx(lane);
-    if (tid < SG_BB) {                                                  // armed once; the combine step re-arms what it consumed (round 5:
-#pragma unroll                                                          //  one barrier per sub-batch less)
-        for (int w = 0; w < 4; w++) sG[w][tid][8] = __uint_as_float(SG_UNSET);
-    }
-    __syncthreads();
-    // ---- the sub-batches, back to front, out of LDS
-    for (int sb = (cnt - 1) / SG_BB; sb >= 0; sb--) {
-        const int b0 = sb * SG_BB, base = lo + b0;                      // staged index / list position of the sub-batch's first entry
-        const int bc = cnt - b0 < SG_BB ? cnt - b0 : SG_BB;
-        if (base < maxq) {
-            uint16_t *list = sList[wave];
-            const int lim = maxq - base < bc ? maxq - base : bc;          // entries >= maxq touch no pixel here
-            const int nl = sg_compact_quadrant<1>(sM + b0, lim, wave, lane, lt, list, SG_BB);
-            const uint32_t ncq_b = ncq > (uint32_t)base ? ncq - (uint32_t)base : 0u;   // contributors of this pixel inside the sub-batch
-            for (int i = nl - 1; i >= 0; i--) {
-                const uint32_t k = list[i];
-                const float4 ga = sR[b0 + k][0], gb = sR[b0 + k][1];
-                const float gc = sR[b0 + k][2].x;
-                SG_BWD_PASS(k, k);
-            }
-        }
-        __syncthreads();
-        // ---- combine the quadrants in a fixed order and store the record (the thread that staged the entry)
-        if (tid >= b0 && tid < b0 + bc) {
-            const int q0 = tid - b0;
-            float s9[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-#pragma unroll
-            for (int w = 0; w < 4; w++)
-                if (__float_as_uint(sG[w][q0][8]) != SG_UNSET) {
-#pragma unroll
-                    for (int q = 0; q < 9; q++) s9[q] += sG[w][q0][q];
-                    sG[w][q0][8] = __uint_as_float(SG_UNSET);
-                }
-            if (rslot < cap) {
-            const float no = -opac, nh = 0.5f * no;
-            const float m0 = fmaf(cA, s9[0], cB * s9[1]), m1 = fmaf(cB, s9[0], cC * s9[1]);
-            grec_a[2 * (size_t)rslot] = make_float4(no * ddelx_dx * m0, no * ddely_dy * m1, nh * s9[2], nh * s9[3]);
-            grec_a[2 * (size_t)rslot + 1] = make_float4(nh * s9[4], s9[5], s9[6], s9[7]);
-            grec_b[rslot] = s9[8];
-            rec_valid[rslot] = 1;                                  // (every other record of the frame is never read: sg_sum_records_coop)
-            }
-        }
-        __syncthreads();
-    }
-}
+// The two backward composite kernels, and (SG_BWD_AUX 1) their variants with the depth / alpha adjoints (sg_rasterize_backward_aux,
+// sg_skinned_backward_aux: one frame).  One source, included twice, so that the plain kernels stay the round-5 kernels
+// instruction for instruction (as inlined bodies the compiler allocated them differently) and the aux kernels are separate
+// symbols for the profiles.
+#define SG_BWD_AUX 0
+#include "sg_render_bwd.inc"
+#undef SG_BWD_AUX
+#define SG_BWD_AUX 1
+#include "sg_render_bwd.inc"
+#undef SG_BWD_AUX
 
 void sg_launch_render_bwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, size_t cap, SgImg im,
-                          const float *dL_dpix, SgRec grec, hipStream_t st)
+                          const float *dL_dpix, SgRec grec, hipStream_t st, const SgAuxBwd *ax)
 {
     static_assert(SG_SEG % SG_BB == 0, "segments are whole backward batches");
     const int T = c.gx * c.gy;
@@ -881,11 +671,22 @@ void sg_launch_render_bwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, 
         // few tiles, long lists: order the work items (heaviest first), then only the entries the forward composited are touched --
         // and only their records are marked valid (rec_valid: cleared by the forward's scatter) and ever read
         hipLaunchKernelGGL(sg_order_items_kernel, dim3(1, K), dim3(256), 0, st, bt, b.header, b.item_w, b.item_perm);
+        if (ax)
+        hipLaunchKernelGGL(sg_render_bwd_sparse_aux_kernel, dim3(grid, K), dim3(256), 0, st, bt, c.W, c.H, c.gx, T, grid, b.ranges,
+                           b.point_list, g.recA, g.recB, g.recC, c.bg, im.final_T, im.n_contrib, dL_dpix,
+                           grec.a, grec.b, cap32, b.header, b.items, b.ck_start, im.ckpt, sg_ckpt_cap(cap), b.pair_mask, sg_mask_plane(cap),
+                           sg_split_long(c.gx, c.gy, c.flags) ? 1 : 0, b.item_perm, b.rec_valid, *ax);
+        else
         hipLaunchKernelGGL(sg_render_bwd_sparse_kernel, dim3(grid, K), dim3(256), 0, st, bt, c.W, c.H, c.gx, T, grid, b.ranges,
                            b.point_list, g.recA, g.recB, g.recC, c.bg, im.final_T, im.n_contrib, dL_dpix,
                            grec.a, grec.b, cap32, b.header, b.items, b.ck_start, im.ckpt, sg_ckpt_cap(cap), b.pair_mask, sg_mask_plane(cap),
                            sg_split_long(c.gx, c.gy, c.flags) ? 1 : 0, b.item_perm, b.rec_valid);
-    } else
+    } else if (ax)
+    hipLaunchKernelGGL(sg_render_bwd_aux_kernel, dim3(grid, K), dim3(256), 0, st, bt, c.W, c.H, c.gx, T, grid, b.ranges,
+                       b.point_list, g.recA, g.recB, g.recC, c.bg, im.final_T, im.n_contrib, dL_dpix,
+                       grec.a, grec.b, cap32, b.header, b.items, b.ck_start, im.ckpt, sg_ckpt_cap(cap), b.pair_mask, sg_mask_plane(cap),
+                       sg_split_long(c.gx, c.gy, c.flags) ? 1 : 0, *ax);
+    else
     hipLaunchKernelGGL(sg_render_bwd_kernel, dim3(grid, K), dim3(256), 0, st, bt, c.W, c.H, c.gx, T, grid, b.ranges,
                        b.point_list, g.recA, g.recB, g.recC, c.bg, im.final_T, im.n_contrib, dL_dpix,
                        grec.a, grec.b, cap32, b.header, b.items, b.ck_start, im.ckpt, sg_ckpt_cap(cap), b.pair_mask, sg_mask_plane(cap),

@@ -304,201 +304,20 @@ sg_skin_fwd_kernel(SgCam c, SgBatch bt, int P, SgSkin k, const float *__restrict
 // Backward: LBS^T.  Per Gaussian: dL/dxyz_canon, dL/dR_canon, dL/dscales, dL/dopacity, dL/dsh;
 // per workgroup: partial dL/dA [Jp x 16] (matrix cores) and dL/dtransl [3] written to a slab
 // (reduced by sg_skin_reduce_kernel -- no atomics, deterministic).
-template <int D, bool ACC>
-// D = 0 (what SinGS trains at): three waves per SIMD.  Unconstrained hipcc takes 196 registers = two waves per SIMD = 2 048 resident
-// waves, and an avatar of 150 k Gaussians is 2 344 waves: a second, 14 %-full round (the kernel is latency-bound: a round costs what
-// a wave costs).  With the hint it fits 168 registers without scratch.  D >= 1 would spill (36-52 B at D = 1): left alone.
-__global__ void __launch_bounds__(SG_SKIN_THREADS) __attribute__((amdgpu_waves_per_eu(D == 0 ? 3 : 1, D == 0 ? 3 : 10)))
-sg_skin_bwd_kernel(SgCam c, int P, SgSkin k, const float *__restrict__ shs, const float *__restrict__ scales,
-                   const int32_t *__restrict__ radii, SgGeom g, SgRec grec, size_t cap,
-                   const uint32_t *__restrict__ header, const uint8_t *__restrict__ rec_valid, const float *__restrict__ dposed_xyz_in, const float *__restrict__ dposed_rotq_in,
-                   float *__restrict__ dL_dxyz_canon, float *__restrict__ dL_drot_canon,
-                   float *__restrict__ dL_dscales, float *__restrict__ dL_dopacity, float *__restrict__ dL_dsh,
-                   float *__restrict__ dL_dmeans2D, float *__restrict__ slab, int slab_stride)
-{
-    constexpr bool accumulate = ACC;                            // (compile-time: see sg_preprocess_bwd_kernel)
-    __shared__ float sA[SG_JMAX * 16];
-    // per wave: [weights tile | T transpose scratch, later the dT tile]; between the two uses the whole 2 x 4.3 KB is
-    // the staging buffer of the record sums and of the dL/dsh rows
-    __shared__ float sWT[SG_SKIN_WAVES][2 * 64 * SG_WSTRIDE];
-    static_assert(2 * 64 * SG_WSTRIDE >= SG_REC_CHUNK * 12 && 2 * 64 * SG_WSTRIDE >= 32 * SG_ROW_LDS, "staging buffer size");
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    float *const sWw = sWT[wave], *const sTw = sWT[wave] + 64 * SG_WSTRIDE;
-    const int g0 = (blockIdx.x * SG_SKIN_WAVES + wave) * 64;
-    const int idx = g0 + lane;
-    sg_load_A(k, sA);
-    __syncthreads();
-    float T[12];
-    sg_skin_T(k.lbs_w, k.J, P, g0, lane, sA, sWw, sTw, T);
-    const bool live = idx < P;
-    float dT[12];
-#pragma unroll
-    for (int i = 0; i < 12; i++) dT[i] = 0.0f;
-    float dtr[3] = { 0, 0, 0 };
-    const int Mrows = c.M;
-    constexpr int nc = (D + 1) * (D + 1);
-    // this Gaussian's gradient records: wave-cooperative, coalesced (as in sg_preprocess_bwd_kernel)
-    const bool vis = live && radii[idx] > 0 && header[1] == 0u;     // forward overflowed: zero gradients (see sg_preprocess.hip)
-    float4 rc = make_float4(0, 0, 0, 0);
-    if (vis) { const uint2 sl = g.slot[idx]; rc.y = __uint_as_float(sl.x); rc.w = __uint_as_float(sl.y); }
-    float a9[9];
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
-    sg_sum_records_coop(grec, cap, vis, rc, lane, sWw, a9, rec_valid);
-    float dsh[nc * 3];
-#pragma unroll
-    for (int i = 0; i < nc * 3; i++) dsh[i] = 0.0f;
-    if (live) {
-        float dxc[3] = { 0, 0, 0 }, dRc[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, dsc[3] = { 0, 0, 0 }, dop = 0, g2[2] = { 0, 0 };
-        const bool have_in = dposed_xyz_in != nullptr || dposed_rotq_in != nullptr;
-        if (vis || have_in) {
-            SgPosed ps;
-            sg_pose_gaussian(k, idx, T, scales, ps);
-            SgGaussGrad G;
-#pragma unroll
-            for (int i = 0; i < 3; i++) { G.dmean[i] = 0; G.dsc[i] = 0; G.dcol[i] = 0; }
-#pragma unroll
-            for (int i = 0; i < 4; i++) G.drot[i] = 0;
-            G.g2[0] = G.g2[1] = 0; G.dop = 0;
-            if (vis)
-                sg_project_bwd<D>(c, ps.p, ps.s3, ps.q, nullptr, shs + (size_t)idx * Mrows * 3, g.flags[idx], a9, true, dsh, G);
-            if (dposed_xyz_in) {
-#pragma unroll
-                for (int i = 0; i < 3; i++) G.dmean[i] += dposed_xyz_in[3 * idx + i];
-            }
-            if (dposed_rotq_in) {
-#pragma unroll
-                for (int i = 0; i < 4; i++) G.drot[i] += dposed_rotq_in[4 * idx + i];
-            }
-            g2[0] = G.g2[0]; g2[1] = G.g2[1]; dop = G.dop;
-            // scales_posed = scales * s ; p = (T33 x + t) * s + transl
-#pragma unroll
-            for (int i = 0; i < 3; i++) { dsc[i] = G.dsc[i] * ps.sc; dtr[i] = G.dmean[i]; }
-            float dps[3] = { G.dmean[0] * ps.sc, G.dmean[1] * ps.sc, G.dmean[2] * ps.sc };
-            float dRd[9];
-            sg_m2q_bwd(ps.q, ps.best, ps.qab, G.drot, dRd);
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-#pragma unroll
-                for (int kx = 0; kx < 3; kx++) {
-                    // dT33 = dp x^T + dRdef Rc^T
-                    dT[4 * i + kx] = dps[i] * ps.x[kx] + dRd[3 * i] * ps.Rc[3 * kx] + dRd[3 * i + 1] * ps.Rc[3 * kx + 1] + dRd[3 * i + 2] * ps.Rc[3 * kx + 2];
-                }
-                dT[4 * i + 3] = dps[i];
-            }
-#pragma unroll
-            for (int kx = 0; kx < 3; kx++) {
-                dxc[kx] = T[kx] * dps[0] + T[4 + kx] * dps[1] + T[8 + kx] * dps[2];
-#pragma unroll
-                for (int j = 0; j < 3; j++)      // dRc = T33^T dRdef
-                    dRc[3 * kx + j] = T[kx] * dRd[j] + T[4 + kx] * dRd[3 + j] + T[8 + kx] * dRd[6 + j];
-            }
-        }
-        // accumulate: the frames of one optimisation step share ONE canonical-gradient buffer (sg_skinned_backward_gaussians)
-        if (accumulate) {
-#pragma unroll
-            for (int i = 0; i < 3; i++) { dxc[i] += dL_dxyz_canon[3 * idx + i]; dsc[i] += dL_dscales[3 * idx + i]; }
-            dop += dL_dopacity[idx];
-        }
-        dL_dxyz_canon[3 * idx] = dxc[0]; dL_dxyz_canon[3 * idx + 1] = dxc[1]; dL_dxyz_canon[3 * idx + 2] = dxc[2];
-        if (dL_drot_canon) {
-            if (k.rot6d) {
-                float d6[6], dd[6];
-#pragma unroll
-                for (int i = 0; i < 6; i++) d6[i] = k.rot_canon[6 * (size_t)idx + i];
-                sg_r6d2m_bwd(d6, dRc, dd);
-#pragma unroll
-                for (int i = 0; i < 6; i++) dL_drot_canon[6 * (size_t)idx + i] = dd[i] + (accumulate ? dL_drot_canon[6 * (size_t)idx + i] : 0.0f);
-            } else {
-#pragma unroll
-                for (int i = 0; i < 9; i++) dL_drot_canon[9 * (size_t)idx + i] = dRc[i] + (accumulate ? dL_drot_canon[9 * (size_t)idx + i] : 0.0f);
-            }
-        }
-        dL_dscales[3 * idx] = dsc[0]; dL_dscales[3 * idx + 1] = dsc[1]; dL_dscales[3 * idx + 2] = dsc[2];
-        dL_dopacity[idx] = dop;
-        dL_dmeans2D[3 * idx] = g2[0]; dL_dmeans2D[3 * idx + 1] = g2[1]; dL_dmeans2D[3 * idx + 2] = 0.0f;
-    }
-    // dL/dsh: coefficient-major planes [M][P][3], only the (D+1)^2 in use (SG_FLAG_SH_PLANAR: 12-byte stores, coalesced across
-    // the lanes); or the reference's rows (every one of the M rows is written): through LDS as 16-B-per-lane coalesced stores when
-    // M == 16
-    if (c.flags & SG_FLAG_SH_PLANAR) {
-        if (live) {
-#pragma unroll
-            for (int kq = 0; kq < nc; kq++)
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++) {
-                    float *d = dL_dsh + ((size_t)kq * P + idx) * 3 + ch;
-                    *d = accumulate ? dsh[3 * kq + ch] + *d : dsh[3 * kq + ch];
-                }
-        }
-    } else if (Mrows == 16) {
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            if ((lane >> 5) == h) {
-                float *row = sWw + (lane & 31) * SG_ROW_LDS;
-#pragma unroll
-                for (int i = 0; i < 48; i++) row[i] = i < nc * 3 ? dsh[i < nc * 3 ? i : 0] : 0.0f;
-            }
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            __builtin_amdgcn_wave_barrier();
-            sg_rows48_store(dL_dsh, g0 + 32 * h, P, lane, sWw, 32, accumulate != 0);
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            __builtin_amdgcn_wave_barrier();
-        }
-    } else if (live) {
-        float *dsh_row = dL_dsh + (size_t)idx * Mrows * 3;
-        if (accumulate) {
-#pragma unroll
-            for (int i = 0; i < nc * 3; i++) dsh_row[i] += dsh[i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < nc * 3; i++) dsh_row[i] = dsh[i];
-            for (int i = nc * 3; i < Mrows * 3; i++) dsh_row[i] = 0.0f;
-        }
-    }
-    // ---- dA[J x 16] += W^T[J x 64] . dT[64 x 16] on the matrix cores
-    float *sdT = sTw;
-#pragma unroll
-    for (int i = 0; i < 12; i++) sdT[lane * SG_WSTRIDE + i] = dT[i];
-#pragma unroll
-    for (int i = 12; i < 16; i++) sdT[lane * SG_WSTRIDE + i] = 0.0f;
-    const int nchunk = (k.J + 15) >> 4;
-    // every wave owns one slab row (no cross-wave stage): [Jp x 16] dA partials + 3 dtransl partials
-    float *out = slab + ((size_t)blockIdx.x * SG_SKIN_WAVES + wave) * slab_stride;
-    const bool vec = (k.J & 3) == 0;
-    float4 wv[4];
-    if (vec) sg_w_fetch(k.lbs_w, k.J, P, g0, 0, lane, wv);
-    for (int cch = 0; cch < nchunk; cch++) {
-        if (vec) {
-            sg_w_stash(wv, lane, sWw);
-            if (cch + 1 < nchunk) sg_w_fetch(k.lbs_w, k.J, P, g0, cch + 1, lane, wv);
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-        } else {
-            sg_stage_w_chunk(k.lbs_w, k.J, P, g0, cch, lane, sWw);
-            __builtin_amdgcn_s_waitcnt(0);
-        }
-        __builtin_amdgcn_wave_barrier();
-        f32x4 acc = (f32x4){ 0.0f, 0.0f, 0.0f, 0.0f };
-#pragma unroll
-        for (int kk = 0; kk < 16; kk++) {
-            float av = sWw[(4 * kk + (lane >> 4)) * SG_WSTRIDE + (lane & 15)];     // W^T[joint lane&15][gaussian]
-            float bv = sdT[(4 * kk + (lane >> 4)) * SG_WSTRIDE + (lane & 15)];          // dT[gaussian][entry lane&15]
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
-        }
-        // acc[r] = dA[joint 16c + 4(lane>>4) + r][entry lane&15]
-#pragma unroll
-        for (int r = 0; r < 4; r++) out[(16 * cch + 4 * (lane >> 4) + r) * 16 + (lane & 15)] = acc[r];
-        __builtin_amdgcn_wave_barrier();
-    }
-    // dtransl: wave sum
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        float v = dtr[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) out[SG_JMAX * 16 + i] = v;
-    }
-}
+#define SG_SKBWD_PARAMS SgCam c, int P, SgSkin k, const float *__restrict__ shs, const float *__restrict__ scales,                      \
+                   const int32_t *__restrict__ radii, SgGeom g, SgRec grec, size_t cap,                                              \
+                   const uint32_t *__restrict__ header, const uint8_t *__restrict__ rec_valid, const float *__restrict__ dposed_xyz_in, const float *__restrict__ dposed_rotq_in, \
+                   float *__restrict__ dL_dxyz_canon, float *__restrict__ dL_drot_canon,                                             \
+                   float *__restrict__ dL_dscales, float *__restrict__ dL_dopacity, float *__restrict__ dL_dsh,                      \
+                   float *__restrict__ dL_dmeans2D, float *__restrict__ slab, int slab_stride
+// The single-frame kernel and (SG_SKBWD_AUX 1) its variant for the depth / alpha maps (sg_skinned_backward_aux).  One source,
+// included twice: as an inlined body the plain kernel compiled to different code.
+#define SG_SKBWD_AUX 0
+#include "sg_skin_bwd.inc"
+#undef SG_SKBWD_AUX
+#define SG_SKBWD_AUX 1
+#include "sg_skin_bwd.inc"
+#undef SG_SKBWD_AUX
 
 // ---- K frames per launch (round 4) -----------------------------------------------------------------------------------------
 // bt.K frames of the SAME canonical Gaussians: the wave walks the frames -- blend T with frame f's joint transforms, sum frame f's
@@ -1393,7 +1212,7 @@ void sg_launch_skin_bwd(const SgCam &c, const SgBatch &bt, int P, const SgSkinIn
                         const int32_t *radii, SgGeom g, SgRec grec, size_t cap, const uint32_t *header, const uint8_t *rec_valid,
                         const float *dposed_xyz_in, const float *dposed_rotq_in, float *slab, float *dL_dxyz_canon, float *dL_drot_canon,
                         float *dL_dscales, float *dL_dopacity, float *dL_dsh, float *dL_dmeans2D, float *dL_dA,
-                        float *dL_dtransl, int accumulate, hipStream_t st)
+                        float *dL_dtransl, int accumulate, hipStream_t st, const float *dz)
 {
     if (P <= 0) return;
     SgSkin k = { in->J, in->rot_format == SG_ROT_CANON_6D, in->xyz_canon, in->rot_canon, in->lbs_weights, in->A, in->smpl_scale,
@@ -1416,7 +1235,14 @@ void sg_launch_skin_bwd(const SgCam &c, const SgBatch &bt, int P, const SgSkinIn
     const float4 *a9buf = (const float4 *)(slab + (slab_frame + (size_t)SG_RED_GROUPS * stride) * bt.K);
     if (bt.K > 1)
         sg_launch_record_sums(bt, P, radii, g, grec, cap, header, rec_valid, (float4 *)a9buf, st);
+#define SG_SBA(DD) hipLaunchKernelGGL((sg_skin_bwd_aux_kernel<DD>), grid, block, 0, st, c, P, k, shs, scales, radii, g,       \
+                                     grec, cap, header, rec_valid, dposed_xyz_in, dposed_rotq_in, dL_dxyz_canon,  \
+                                     dL_drot_canon, dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, slab, stride, dz)
+    if (dz)       // (the aux entry point: K = 1, accumulate = 0)
+        switch (c.D) { case 0: SG_SBA(0); break; case 1: SG_SBA(1); break; case 2: SG_SBA(2); break; default: SG_SBA(3); break; }
+    else
     switch (c.D) { case 0: SG_SB(0); break; case 1: SG_SB(1); break; case 2: SG_SB(2); break; default: SG_SB(3); break; }
+#undef SG_SBA
     float *part = slab + slab_frame * bt.K;
     hipLaunchKernelGGL(sg_skin_reduce1_kernel, dim3((stride + 63) / 64, SG_RED_GROUPS / 4, bt.K), dim3(256), 0, st, slab,
                        nblocks * SG_SKIN_WAVES, stride, part, slab_frame);

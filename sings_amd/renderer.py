@@ -50,7 +50,9 @@ def _settings(data, bg_color, scaling_modifier, active_sh_degree):
         prefiltered=False, debug=False)
 
 
-def render(means3D, feats, opacity, scales, rotations, data, scaling_modifier=1.0, bg_color=None, active_sh_degree=0):
+def render(means3D, feats, opacity, scales, rotations, data, scaling_modifier=1.0, bg_color=None, active_sh_degree=0,
+           return_aux=False):
+    """``return_aux``: the package also carries 'depth' and 'alpha' ([1,H,W], differentiable; GaussianRasterizer.forward_aux)."""
     dev = means3D.device
     if bg_color is None:
         bg_color = torch.zeros(3, dtype=torch.float32, device=dev)
@@ -61,18 +63,27 @@ def render(means3D, feats, opacity, scales, rotations, data, scaling_modifier=1.
         pass
     shs, rgb = (None, feats) if feats.dim() == 2 else (feats, None)
     rasterizer = GaussianRasterizer(raster_settings=_settings(data, bg_color, scaling_modifier, active_sh_degree))
-    rendered_image, radii = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs, opacities=opacity,
-                                       scales=scales, rotations=rotations, colors_precomp=rgb)
+    if return_aux:
+        rendered_image, radii, depth, alpha = rasterizer.forward_aux(
+            means3D=means3D, means2D=screenspace_points, shs=shs, opacities=opacity, scales=scales, rotations=rotations,
+            colors_precomp=rgb)
+    else:
+        rendered_image, radii = rasterizer(means3D=means3D, means2D=screenspace_points, shs=shs, opacities=opacity,
+                                           scales=scales, rotations=rotations, colors_precomp=rgb)
     raw = rendered_image
     rendered_image = torch.clamp(rendered_image, 0.0, 1.0)
     # 'render_raw' (not in the reference's dict): the unclamped image, input of the fused loss (photo_loss.py)
-    return {"render": rendered_image, "render_raw": raw, "viewspace_points": screenspace_points,
-            "visibility_filter": radii > 0, "radii": radii}
+    pkg = {"render": rendered_image, "render_raw": raw, "viewspace_points": screenspace_points,
+           "visibility_filter": radii > 0, "radii": radii}
+    if return_aux:
+        pkg.update(depth=depth, alpha=alpha)
+    return pkg
 
 
 def get_render_pkg_fused(data, canon, A_cano2pose, bg_color, smpl_scale=None, transl=None, ext_tfs=None,
-                         scaling_modifier=1.0, return_posed=False):
-    """canon: dict(xyz_canon, rotmat_canon|None, scales, opacity, shs, lbs_weights, active_sh_degree)."""
+                         scaling_modifier=1.0, return_posed=False, return_aux=False):
+    """canon: dict(xyz_canon, rotmat_canon|None, scales, opacity, shs, lbs_weights, active_sh_degree).  ``return_aux``: the
+    package also carries 'depth' (sum_i z_i alpha_i T_i) and 'alpha' (1 - T_final), [1,H,W] and differentiable."""
     rs = _settings(data, bg_color, scaling_modifier, canon['active_sh_degree'])
     # per-call holder of the screen-space gradient, exactly the reference's idiom (gs_renderer_single.py:50-56)
     xyz = canon['xyz_canon']
@@ -83,13 +94,15 @@ def get_render_pkg_fused(data, canon, A_cano2pose, bg_color, smpl_scale=None, tr
     out = rasterize_skinned_gaussians(xyz, canon.get('rotmat_canon'), canon['scales'], canon['opacity'],
                                       canon['shs'], canon['lbs_weights'], A_cano2pose, rs, smpl_scale=smpl_scale,
                                       transl=transl, ext_tfs=ext_tfs, return_posed=return_posed,
-                                      means2D=screenspace_points)
+                                      means2D=screenspace_points, return_aux=return_aux)
     radii = out[1]
     pkg = {"render": torch.clamp(out[0], 0.0, 1.0), "render_raw": out[0], "viewspace_points": screenspace_points,
            "visibility_filter": radii > 0,
            "radii": radii, "human_visibility_filter": radii > 0, "human_radii": radii}
     if return_posed:
         pkg.update(xyz=out[2], rotq=out[3], scales=out[4])
+    if return_aux:
+        pkg.update(depth=out[-2], alpha=out[-1])
     return pkg
 
 

@@ -47,11 +47,13 @@ def _skin_struct(dev, xyz_canon, rotmat_canon, lbs_weights, A, smpl_scale, trans
 class _RasterizeSkinnedGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz_canon, rotmat_canon, scales, opacities, shs, A, transl, lbs_weights, smpl_scale, ext_tfs,
-                raster_settings, return_posed, means2D=None):
+                raster_settings, return_posed, means2D=None, return_aux=False):
         lib = _lib.load()
         dev = xyz_canon.device
         if dev.type != "cuda":
             raise RuntimeError("sings_amd fused LBS+raster runs on the MI355X only; there is no CPU fallback")
+        if return_aux:
+            ctx.set_materialize_grads(False)
         rs = raster_settings
         xyz_canon = _f32(xyz_canon, "xyz_canon", dev)
         rot_shape = None if rotmat_canon is None else tuple(rotmat_canon.shape)
@@ -70,21 +72,26 @@ class _RasterizeSkinnedGaussians(torch.autograd.Function):
         radii = torch.empty((P,), dtype=torch.int32, device=dev)
         e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
         pxyz, pq, psc = (e(P, 3), e(P, 4), e(P, 3)) if return_posed else (None, None, None)
+        depth, alpha = (e(1, H, W), e(1, H, W)) if return_aux else (None, None)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        geom = binning = img = None
+        geom = binning = img = aux = None
 
         def launch(cap, flags, sync):
-            nonlocal geom, binning, img
+            nonlocal geom, binning, img, aux
             s.flags = flags
             L = _lib.layout(P, W, H, cap)
             geom = torch.empty(L.geom_bytes, dtype=torch.uint8, device=dev)
             binning = torch.empty(L.bin_bytes, dtype=torch.uint8, device=dev)
             img = torch.empty(L.img_bytes, dtype=torch.uint8, device=dev)
             nr = C.c_int64(0)
-            _lib.check(lib.sg_skinned_forward(C.byref(s), P, C.byref(k), _ptr(shs), _ptr(opacities), _ptr(scales),
-                                              _ptr(geom), _ptr(binning), cap, _ptr(img), _ptr(color), _ptr(radii),
-                                              _ptr(pxyz), _ptr(pq), _ptr(psc), C.byref(nr) if sync else None, stream),
-                       "skinned forward")
+            args = (C.byref(s), P, C.byref(k), _ptr(shs), _ptr(opacities), _ptr(scales), _ptr(geom), _ptr(binning), cap, _ptr(img),
+                    _ptr(color), _ptr(radii), _ptr(pxyz), _ptr(pq), _ptr(psc), C.byref(nr) if sync else None)
+            if return_aux:
+                aux = torch.empty(_lib.aux_layout(P, W, H, cap), dtype=torch.uint8, device=dev)
+                _lib.check(lib.sg_skinned_forward_aux(*args, _ptr(aux), _ptr(depth), _ptr(alpha), stream),
+                           "skinned forward (depth / alpha maps)")
+            else:
+                _lib.check(lib.sg_skinned_forward(*args, stream), "skinned forward")
             return (int(nr.value),) if sync else None
 
         cap, counts = overflow.run_forward(
@@ -99,18 +106,28 @@ class _RasterizeSkinnedGaussians(torch.autograd.Function):
         ctx.rot_shape = rot_shape
         ctx.has_m2d = means2D is not None
         ctx.return_posed = return_posed
+        ctx.return_aux = return_aux
+        ctx.aux_ws = aux
         ctx.aux = (lbs_weights, smpl_scale, A.shape, None if transl is None else transl.shape)
         z = torch.empty(0, device=dev)
         ctx.save_for_backward(xyz_canon, rotmat_canon if ctx.has_rot else z, scales, opacities, shs,
                               _f32(A, "A", dev), transl if transl is not None else z, radii, geom, binning, img)
         ctx.mark_non_differentiable(radii)
+        out = (color, radii)
         if return_posed:
             ctx.mark_non_differentiable(psc)
-            return color, radii, pxyz, pq, psc
-        return color, radii
+            out += (pxyz, pq, psc)
+        if return_aux:
+            out += (depth, alpha)
+        return out
 
     @staticmethod
-    def backward(ctx, g_color, _g_radii=None, g_pxyz=None, g_pq=None, _g_psc=None):
+    def backward(ctx, g_color, _g_radii=None, *g_rest):
+        g_rest = g_rest + (None,) * 5
+        g_pxyz, g_pq = g_rest[:2] if ctx.return_posed else (None, None)
+        g_depth, g_alpha = g_rest[3:5] if ctx.return_posed else g_rest[:2]
+        if not ctx.return_aux:
+            g_depth = g_alpha = None
         lib = _lib.load()
         if ctx.has_ext:
             raise RuntimeError("ext_tfs are forward-only (the reference applies them under no_grad: anim_avatar.py:27)")
@@ -127,7 +144,10 @@ class _RasterizeSkinnedGaussians(torch.autograd.Function):
         d_xyz, d_scales, d_op, d_sh, d_m2d = e(P, 3), e(P, 3), e(P, 1), e(P, ctx.M, 3), e(P, 3)
         d_rot = e(P, int(rotmat_canon.shape[1])) if ctx.has_rot else None
         d_A = e(k.J, 16); d_tr = e(3)
-        g_color = _f32(g_color, "grad_out_color", dev)
+        g_color = (torch.zeros((3, H, W), dtype=torch.float32, device=dev) if g_color is None
+                   else _f32(g_color, "grad_out_color", dev))
+        g_depth = None if g_depth is None else _f32(g_depth, "grad_depth", dev)
+        g_alpha = None if g_alpha is None else _f32(g_alpha, "grad_alpha", dev)
         g_pxyz = None if g_pxyz is None else _f32(g_pxyz, "grad posed xyz", dev)
         g_pq = None if g_pq is None else _f32(g_pq, "grad posed rotq", dev)
         with torch.cuda.device(dev):
@@ -135,20 +155,23 @@ class _RasterizeSkinnedGaussians(torch.autograd.Function):
             bwd_ws = torch.empty(L.bwd_bytes, dtype=torch.uint8, device=dev)
             skin_ws = e(int(lib.sg_skin_ws_floats(P)))
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.sg_skinned_backward(
-                C.byref(s), P, C.byref(k), _ptr(shs), _ptr(opacities), _ptr(scales), _ptr(radii), _ptr(geom),
-                _ptr(binning), ctx.cap, _ptr(img), _ptr(bwd_ws), _ptr(skin_ws), _ptr(g_color), _ptr(g_pxyz), _ptr(g_pq),
-                _ptr(d_xyz), _ptr(d_rot), _ptr(d_scales), _ptr(d_op), _ptr(d_sh), _ptr(d_m2d), _ptr(d_A), _ptr(d_tr),
-                stream), "skinned backward")
+            args = (C.byref(s), P, C.byref(k), _ptr(shs), _ptr(opacities), _ptr(scales), _ptr(radii), _ptr(geom),
+                    _ptr(binning), ctx.cap, _ptr(img), _ptr(bwd_ws), _ptr(skin_ws), _ptr(g_color), _ptr(g_pxyz), _ptr(g_pq),
+                    _ptr(d_xyz), _ptr(d_rot), _ptr(d_scales), _ptr(d_op), _ptr(d_sh), _ptr(d_m2d), _ptr(d_A), _ptr(d_tr))
+            if g_depth is None and g_alpha is None:     # neither map carries a gradient: the plain backward, bit for bit
+                _lib.check(lib.sg_skinned_backward(*args, stream), "skinned backward")
+            else:
+                _lib.check(lib.sg_skinned_backward_aux(*args, _ptr(ctx.aux_ws), _ptr(g_depth), _ptr(g_alpha), stream),
+                           "skinned backward (depth / alpha maps)")
         return (d_xyz, None if d_rot is None else d_rot.view(ctx.rot_shape), d_scales, d_op.view_as(opacities), d_sh,
                 d_A.view(A_shape), None if transl_shape is None else d_tr.view(transl_shape), None, None, None, None, None,
-                d_m2d if ctx.has_m2d else None)
+                d_m2d if ctx.has_m2d else None, None)
 
 
 def rasterize_skinned_gaussians(xyz_canon, rotmat_canon, scales, opacities, shs, lbs_weights, A_cano2pose,
                                 raster_settings, smpl_scale=None, transl=None, ext_tfs=None, return_posed=False,
-                                means2D=None):
-    """color, radii[, posed_xyz, posed_rotq, posed_scales] = fused LBS + rasterization of one posed frame.
+                                means2D=None, return_aux=False):
+    """color, radii[, posed_xyz, posed_rotq, posed_scales][, depth, alpha] = fused LBS + rasterization of one posed frame.
 
     ``rotmat_canon=None`` means isotropic Gaussians (identity canonical rotation, sings_hybrid.py:358-361); a ``[N,6]``
     tensor is the geometry decoder's 6-D output: ``rotation_6d_to_matrix`` (sings_hybrid.py:356-357) is then evaluated
@@ -157,9 +180,12 @@ def rasterize_skinned_gaussians(xyz_canon, rotmat_canon, scales, opacities, shs,
     gradient the densifier reads as ITS gradient -- the reference's ``viewspace_points`` idiom
     (gs_renderer_single.py:50-56, consumer sings_hybrid.py:1013-1015), one holder per call, so several views of a
     step keep their own statistics.
+    ``return_aux``: also the accumulated depth sum_i z_i alpha_i T_i and the alpha map 1 - T_final, both [1,H,W] and
+    differentiable (expected depth = depth / alpha), appended at the end of the outputs.
     """
     return _RasterizeSkinnedGaussians.apply(xyz_canon, rotmat_canon, scales, opacities, shs, A_cano2pose, transl,
-                                            lbs_weights, smpl_scale, ext_tfs, raster_settings, return_posed, means2D)
+                                            lbs_weights, smpl_scale, ext_tfs, raster_settings, return_posed, means2D,
+                                            return_aux)
 
 
 class _RasterizeSkinnedFrames(torch.autograd.Function):
