@@ -91,7 +91,9 @@ typedef struct SgLayout {
  * History: 5 = round 5's first tree; 6 = SgTriplane gained `feature_minor` (+ `reserved`) at its end, sg_weight_grad_ws_bytes grew
  * (two partial slabs per workgroup for <= 64 outputs); entry points added since 5: sg_linear_backward_fan, sg_rows_laplacian,
  * sg_scales_head_forward / _backward.  8 = depth and alpha maps:
- * sg_aux_layout, sg_rasterize_forward_aux / _backward_aux, sg_skinned_forward_aux / _backward_aux added (nothing else changed). */
+ * sg_aux_layout, sg_rasterize_forward_aux / _backward_aux, sg_skinned_forward_aux / _backward_aux added (nothing else changed);
+ * entry points added since 8: sg_frames_aux_layout, sg_skinned_forward_frames_aux, sg_rasterize_backward_records_frames_aux,
+ * sg_skinned_backward_gaussians_frames_aux (depth and alpha maps of K frames). */
 #define SG_ABI_VERSION 8
 int sg_abi_version(void);
 const char *sg_version(void);
@@ -549,7 +551,7 @@ int sg_weight_grad(int N, int Cout, int Cin, const float *dz, const float *x, vo
  * posed mean, then LBS, in the skinned op).  Thresholds are decided as for the colour alone; dL_dmeans2D includes the new terms.
  *
  * Each call takes the parameters of its plain counterpart plus aux_ws: one view's aux workspace of sg_aux_layout's size, written
- * by the forward and read and written by the backward (kept between them like image_ws).  The calls are single-frame and accept
+ * by the forward and read and written by the backward (kept between them like image_ws).  These calls are single-frame and accept
  * SG_FLAG_SHORT_LISTS, SG_FLAG_LONG_ROWS and SG_FLAG_WS_CLEAN; the other flags are refused (status 1, sg_last_error) before
  * anything is launched.  Capacity overflow and hint violations are reported exactly as by the plain calls.  dL_ddepth / dL_dalpha
  * [H,W] may each be NULL (zero). */
@@ -581,6 +583,32 @@ int sg_skinned_backward_aux(const SgRasterSettings *s, int P, const SgSkinInputs
                             float *dL_dxyz_canon, float *dL_drot_canon, float *dL_dscales,
                             float *dL_dopacity, float *dL_dsh, float *dL_dmeans2D, float *dL_dA,
                             float *dL_dtransl, void *aux_ws, const float *dL_ddepth, const float *dL_dalpha, void *stream);
+
+/* Depth and alpha maps of K frames (the *_frames layout above, entry points added to ABI 8).  aux_ws holds K consecutive single-view
+ * aux workspaces (sg_frames_aux_layout: K x sg_aux_layout's size, K in 1..SG_MAX_FRAMES); out_depth / out_alpha and dL_ddepth /
+ * dL_dalpha are [K,H,W] (either adjoint may be NULL: zero).  Each call takes the parameters of its plain K-frame counterpart plus
+ * those below, and accepts SG_FLAG_THROUGHPUT, SG_FLAG_LONG_ROWS, SG_FLAG_SHORT_LISTS and SG_FLAG_WS_CLEAN; the other flags, a bad
+ * SgFrameBatch, NULL aux_ws / maps and (backward) accumulate != 0 are refused (status 1, sg_last_error) before anything is launched.
+ * The K frames' maps and gradients are bit for bit those of K single-frame *_aux calls; a frame whose pairs overflow the capacity (or
+ * violate a list hint: reported per frame as by the plain calls) renders the background with depth = alpha = 0 and adds nothing to
+ * any gradient.  sg_rasterize_backward_records_frames_aux serves whichever op produced the frames. */
+int sg_frames_aux_layout(int P, int width, int height, size_t capacity_pairs, int K, size_t *aux_bytes);
+int sg_skinned_forward_frames_aux(const SgRasterSettings *s, const SgFrameBatch *fb, int P, const SgSkinInputs *skin, const float *shs,
+                                  const float *opacities, const float *scales, void *geom_ws, void *binning_ws, size_t capacity_pairs,
+                                  void *image_ws, float *out_color, int32_t *radii, float *posed_xyz, float *posed_rotq,
+                                  float *posed_scales, int64_t *num_rendered_host, void *aux_ws, float *out_depth, float *out_alpha,
+                                  void *stream);
+int sg_rasterize_backward_records_frames_aux(const SgRasterSettings *s, const SgFrameBatch *fb, int P, const void *geom_ws,
+                                             const void *binning_ws, size_t capacity_pairs, const void *image_ws, void *bwd_ws,
+                                             const float *dL_dout_color, void *aux_ws, const float *dL_ddepth, const float *dL_dalpha,
+                                             void *stream);
+int sg_skinned_backward_gaussians_frames_aux(const SgRasterSettings *s, const SgFrameBatch *fb, int P, const SgSkinInputs *skin,
+                                             const float *shs, const float *opacities, const float *scales, const int32_t *radii,
+                                             const void *geom_ws, const void *binning_ws, size_t capacity_pairs, const void *bwd_ws,
+                                             float *skin_ws, int accumulate, const float *dL_dposed_xyz_in,
+                                             const float *dL_dposed_rotq_in, float *dL_dxyz_canon, float *dL_drot_canon,
+                                             float *dL_dscales, float *dL_dopacity, float *dL_dsh, float *dL_dmeans2D, float *dL_dA,
+                                             float *dL_dtransl, void *aux_ws, void *stream);
 
 /* ---- optional per-kernel timing (bench / profiling only; process-global, not thread-safe).
  * When enabled, every kernel launch of forward/backward is bracketed by hipEvents on the

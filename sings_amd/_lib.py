@@ -65,7 +65,9 @@ EXPORTS = ("sg_abi_version", "sg_version", "sg_last_error", "sg_layout", "sg_ras
            "sg_frames_layout", "sg_rasterize_forward_frames", "sg_skinned_forward_frames", "sg_read_num_rendered_frames", "sg_photo_loss_backward_frames",
            "sg_rasterize_backward_records_frames", "sg_rasterize_backward_gaussians_frames", "sg_skin_ws_floats_frames",
            "sg_skinned_backward_gaussians_frames", "sg_photo_loss_frames",
-           "sg_aux_layout", "sg_rasterize_forward_aux", "sg_rasterize_backward_aux", "sg_skinned_forward_aux", "sg_skinned_backward_aux")
+           "sg_aux_layout", "sg_rasterize_forward_aux", "sg_rasterize_backward_aux", "sg_skinned_forward_aux", "sg_skinned_backward_aux",
+           "sg_frames_aux_layout", "sg_skinned_forward_frames_aux", "sg_rasterize_backward_records_frames_aux",
+           "sg_skinned_backward_gaussians_frames_aux")
 NUM_KERNELS = 8
 ABI_VERSION = 8                      # SG_ABI_VERSION
 FLAG_SHORT_LISTS = 1                 # SG_FLAG_SHORT_LISTS
@@ -201,7 +203,14 @@ def load():
     lib.sg_rasterize_backward_aux.argtypes = lib.sg_rasterize_backward.argtypes[:-1] + [vp, vp, vp, vp]
     lib.sg_skinned_forward_aux.argtypes = lib.sg_skinned_forward.argtypes[:-1] + [vp, vp, vp, vp]
     lib.sg_skinned_backward_aux.argtypes = lib.sg_skinned_backward.argtypes[:-1] + [vp, vp, vp, vp]
-    for f in ("sg_aux_layout", "sg_rasterize_forward_aux", "sg_rasterize_backward_aux", "sg_skinned_forward_aux", "sg_skinned_backward_aux"):
+    # ... of K frames (entry points added to ABI 8): the plain K-frame calls' parameters + the same additions
+    lib.sg_frames_aux_layout.argtypes = [i32, i32, i32, sz, i32, C.POINTER(sz)]
+    lib.sg_skinned_forward_frames_aux.argtypes = lib.sg_skinned_forward_frames.argtypes[:-1] + [vp, vp, vp, vp]
+    lib.sg_rasterize_backward_records_frames_aux.argtypes = lib.sg_rasterize_backward_records_frames.argtypes[:-1] + [vp, vp, vp, vp]
+    lib.sg_skinned_backward_gaussians_frames_aux.argtypes = lib.sg_skinned_backward_gaussians_frames.argtypes[:-1] + [vp, vp]
+    for f in ("sg_aux_layout", "sg_rasterize_forward_aux", "sg_rasterize_backward_aux", "sg_skinned_forward_aux", "sg_skinned_backward_aux",
+              "sg_frames_aux_layout", "sg_skinned_forward_frames_aux", "sg_rasterize_backward_records_frames_aux",
+              "sg_skinned_backward_gaussians_frames_aux"):
         getattr(lib, f).restype = C.c_int
     for f in ("sg_layout", "sg_rasterize_forward", "sg_rasterize_backward", "sg_mark_visible",
               "sg_read_num_rendered", "sg_skinned_forward", "sg_skinned_backward"):
@@ -225,4 +234,11 @@ def aux_layout(P, W, H, cap):
     """Bytes of one view's aux workspace (depth / alpha maps: sg_aux_layout)."""
     n = C.c_size_t(0)
     check(load().sg_aux_layout(P, W, H, cap, C.byref(n)), "sg_aux_layout")
+    return int(n.value)
+
+
+def frames_aux_layout(P, W, H, cap, K):
+    """Bytes of the aux workspace of K frames (K consecutive single-view aux workspaces: sg_frames_aux_layout)."""
+    n = C.c_size_t(0)
+    check(load().sg_frames_aux_layout(P, W, H, cap, K, C.byref(n)), "sg_frames_aux_layout")
     return int(n.value)

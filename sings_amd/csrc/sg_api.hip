@@ -215,18 +215,19 @@ static int sg_read_counts(const void *binning_ws, size_t bin_stride, int K, int6
 
 // The flags the depth / alpha entry points accept: the learned list hints and the clean-workspace promise.  THROUGHPUT, the
 // FORWARD_BINNING / FORWARD_COMPOSITE split and SH_PLANAR select kernels or layouts that have no AUX variant.
-static int sg_aux_flags(const char *who, int flags)
+// The K-frame entry points (`frames`) also accept THROUGHPUT: their composites are the frames kernels, which have AUX variants.
+static int sg_aux_flags(const char *who, int flags, bool frames = false)
 {
     static const struct { int bit; const char *name; } refused[] = {
         { SG_FLAG_THROUGHPUT, "SG_FLAG_THROUGHPUT" }, { SG_FLAG_FORWARD_BINNING, "SG_FLAG_FORWARD_BINNING" },
         { SG_FLAG_FORWARD_COMPOSITE, "SG_FLAG_FORWARD_COMPOSITE" }, { SG_FLAG_SH_PLANAR, "SG_FLAG_SH_PLANAR" } };
     char msg[200];
     for (const auto &r : refused)
-        if (flags & r.bit) {
+        if ((flags & r.bit) && !(frames && r.bit == SG_FLAG_THROUGHPUT)) {
             snprintf(msg, sizeof msg, "%s: %s is not supported with depth / alpha maps", who, r.name);
             return sg_fail(msg, hipSuccess);
         }
-    const int known = SG_FLAG_SHORT_LISTS | SG_FLAG_LONG_ROWS | SG_FLAG_WS_CLEAN;
+    const int known = SG_FLAG_SHORT_LISTS | SG_FLAG_LONG_ROWS | SG_FLAG_WS_CLEAN | (frames ? SG_FLAG_THROUGHPUT : 0);
     if (flags & ~known) { snprintf(msg, sizeof msg, "%s: unknown flags 0x%x", who, flags & ~known); return sg_fail(msg, hipSuccess); }
     return 0;
 }
@@ -240,19 +241,30 @@ extern "C" int sg_aux_layout(int P, int width, int height, size_t cap, size_t *a
     return 0;
 }
 
+// K consecutive single-view aux workspaces (frame f's at + f sg_aux_bytes)
+extern "C" int sg_frames_aux_layout(int P, int width, int height, size_t cap, int K, size_t *aux_bytes)
+{
+    SgLayout L;
+    if (K < 1 || K > SG_MAX_FRAMES) return sg_fail("sg_frames_aux_layout: K must be 1..16", hipSuccess);
+    if (!aux_bytes) return sg_fail("sg_frames_aux_layout: null pointer", hipSuccess);
+    if (sg_layout(P, width, height, cap, &L)) return 1;
+    *aux_bytes = sg_aux_bytes(cap) * (size_t)K;
+    return 0;
+}
+
 static int sg_forward_impl(const char *who, const SgRasterSettings *s, const SgFrameBatch *fb, int P, const SgSkinInputs *skin,
                            const float *means3D, const float *shs, const float *colors_precomp, const float *opacities,
                            const float *scales, const float *rotations, const float *cov3D_precomp, void *geom_ws, void *binning_ws,
                            size_t cap, void *image_ws, float *out_color, int32_t *radii, float *posed_xyz, float *posed_rotq,
                            float *posed_scales, int write_point_keys, int64_t *num_rendered_host, void *stream,
-                           void *aux_ws = nullptr, float *out_depth = nullptr, float *out_alpha = nullptr)
+                           void *aux_ws = nullptr, float *out_depth = nullptr, float *out_alpha = nullptr, bool aux_frames = false)
 {
     hipStream_t st = (hipStream_t)stream;
     SgCam c;
     char msg[160];
     if (sg_make_cam(s, &c)) { snprintf(msg, sizeof msg, "%s: bad settings", who); return sg_fail(msg, hipSuccess); }
     if (aux_ws) {
-        if (sg_aux_flags(who, c.flags)) return 1;
+        if (sg_aux_flags(who, c.flags, aux_frames)) return 1;
         if (!out_depth || !out_alpha) { snprintf(msg, sizeof msg, "%s: null pointer (out_depth / out_alpha)", who); return sg_fail(msg, hipSuccess); }
     }
     if (skin) {
@@ -295,7 +307,8 @@ static int sg_forward_impl(const char *who, const SgRasterSettings *s, const SgF
         SG_CHECK_LAST("binning", s, st);
     }
     if (do_comp) {
-        const SgAuxFwd ax = sg_aux_fwd_view(aux_ws, g, out_depth, out_alpha);
+        SgAuxFwd ax = sg_aux_fwd_view(aux_ws, g, out_depth, out_alpha);
+        ax.ws = sg_aux_bytes(cap); ax.map = (size_t)c.W * (size_t)c.H;       // (frame f of a K-frame call; unused by one frame)
         sg_launch_render_fwd(c, bt, g, b, cap, im, out_color, write_point_keys, st, aux_ws ? &ax : nullptr);
         SG_CHECK_LAST("render_fwd", s, st);
     }
@@ -637,6 +650,86 @@ extern "C" int sg_skinned_backward_aux(const SgRasterSettings *s, int P, const S
                        sg_lds_hist(c.gx, c.gy) ? b.rec_valid : nullptr, dL_dposed_xyz_in, dL_dposed_rotq_in,
                        skin_ws, dL_dxyz_canon, dL_drot_canon, dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA,
                        dL_dtransl, 0, st, ax.dz);
+    SG_CHECK_LAST("skin_bwd_aux", s, st);
+    return 0;
+}
+
+// ---- depth and alpha maps of K frames (ABI 8, entry points added) ----------------------------------------------------------------
+extern "C" int sg_skinned_forward_frames_aux(const SgRasterSettings *s, const SgFrameBatch *fb, int P, const SgSkinInputs *skin,
+                                             const float *shs, const float *opacities, const float *scales, void *geom_ws,
+                                             void *binning_ws, size_t cap, void *image_ws, float *out_color, int32_t *radii,
+                                             float *posed_xyz, float *posed_rotq, float *posed_scales, int64_t *num_rendered_host,
+                                             void *aux_ws, float *out_depth, float *out_alpha, void *stream)
+{
+    if (!aux_ws) return sg_fail("sg_skinned_forward_frames_aux: null pointer (aux_ws)", hipSuccess);
+    return sg_forward_impl("sg_skinned_forward_frames_aux", s, fb, P, skin, nullptr, shs, nullptr, opacities, scales, nullptr, nullptr,
+                           geom_ws, binning_ws, cap, image_ws, out_color, radii, posed_xyz, posed_rotq, posed_scales, 0,
+                           num_rendered_host, stream, aux_ws, out_depth, out_alpha, true);
+}
+
+// the K frames' backward composites with the depth / alpha adjoints (whichever op produced the frames): gradient records + the
+// dL/dz plane of every frame's aux workspace
+extern "C" int sg_rasterize_backward_records_frames_aux(const SgRasterSettings *s, const SgFrameBatch *fb, int P, const void *geom_ws,
+                                                        const void *binning_ws, size_t cap, const void *image_ws, void *bwd_ws,
+                                                        const float *dL_dout_color, void *aux_ws, const float *dL_ddepth,
+                                                        const float *dL_dalpha, void *stream)
+{
+    static const char *who = "sg_rasterize_backward_records_frames_aux";
+    hipStream_t st = (hipStream_t)stream;
+    SgCam c;
+    char msg[160];
+    if (sg_make_cam(s, &c)) { snprintf(msg, sizeof msg, "%s: bad settings", who); return sg_fail(msg, hipSuccess); }
+    if (sg_aux_flags(who, c.flags, true)) return 1;
+    if (!aux_ws) { snprintf(msg, sizeof msg, "%s: null pointer (aux_ws)", who); return sg_fail(msg, hipSuccess); }
+    if (P <= 0) return 0;
+    if (!geom_ws || !binning_ws || !image_ws || !bwd_ws || !dL_dout_color) { snprintf(msg, sizeof msg, "%s: null pointer", who); return sg_fail(msg, hipSuccess); }
+    SgLayout L;
+    sg_layout(P, c.W, c.H, cap, &L);
+    SgBatch bt;
+    if (sg_make_batch(fb, P, c, L, cap, &bt)) { snprintf(msg, sizeof msg, "%s: bad frame batch", who); return sg_fail(msg, hipSuccess); }
+    SgGeom g = sg_geom_view((void *)geom_ws, L);
+    SgBin b = sg_bin_view((void *)binning_ws, L);
+    SgImg im = sg_img_view((void *)image_ws, L);
+    SgAuxBwd ax = sg_aux_bwd_view(aux_ws, cap, g, dL_ddepth, dL_dalpha);
+    ax.ws = sg_aux_bytes(cap); ax.map = (size_t)c.W * (size_t)c.H;
+    sg_launch_render_bwd(c, bt, g, b, cap, im, dL_dout_color, sg_rec_view(bwd_ws, cap), st, &ax);
+    SG_CHECK_LAST("render_bwd_aux", s, st);
+    return 0;
+}
+
+extern "C" int sg_skinned_backward_gaussians_frames_aux(const SgRasterSettings *s, const SgFrameBatch *fb, int P, const SgSkinInputs *skin,
+                                                        const float *shs, const float *opacities, const float *scales,
+                                                        const int32_t *radii, const void *geom_ws, const void *binning_ws, size_t cap,
+                                                        const void *bwd_ws, float *skin_ws, int accumulate,
+                                                        const float *dL_dposed_xyz_in, const float *dL_dposed_rotq_in,
+                                                        float *dL_dxyz_canon, float *dL_drot_canon, float *dL_dscales,
+                                                        float *dL_dopacity, float *dL_dsh, float *dL_dmeans2D, float *dL_dA,
+                                                        float *dL_dtransl, void *aux_ws, void *stream)
+{
+    static const char *who = "sg_skinned_backward_gaussians_frames_aux";
+    (void)opacities;
+    hipStream_t st = (hipStream_t)stream;
+    SgCam c;
+    char msg[160];
+    if (sg_make_cam(s, &c)) { snprintf(msg, sizeof msg, "%s: bad settings", who); return sg_fail(msg, hipSuccess); }
+    if (sg_aux_flags(who, c.flags, true)) return 1;
+    if (accumulate) { snprintf(msg, sizeof msg, "%s: accumulate != 0 is not supported with depth / alpha maps", who); return sg_fail(msg, hipSuccess); }
+    if (sg_check_skin(skin, P, false)) { snprintf(msg, sizeof msg, "%s: bad skin inputs (ext_tfs are forward-only)", who); return sg_fail(msg, hipSuccess); }
+    if (!aux_ws) { snprintf(msg, sizeof msg, "%s: null pointer (aux_ws)", who); return sg_fail(msg, hipSuccess); }
+    if (P <= 0) return 0;
+    if (!shs || !scales || !radii || !geom_ws || !binning_ws || !bwd_ws || !skin_ws || !dL_dxyz_canon || !dL_dscales ||
+        !dL_dopacity || !dL_dsh || !dL_dmeans2D || !dL_dA) { snprintf(msg, sizeof msg, "%s: null pointer", who); return sg_fail(msg, hipSuccess); }
+    SgLayout L;
+    sg_layout(P, c.W, c.H, cap, &L);
+    SgBatch bt;
+    if (sg_make_batch(fb, P, c, L, cap, &bt)) { snprintf(msg, sizeof msg, "%s: bad frame batch", who); return sg_fail(msg, hipSuccess); }
+    SgGeom g = sg_geom_view((void *)geom_ws, L);
+    SgBin b = sg_bin_view((void *)binning_ws, L);
+    const SgAuxBwd ax = sg_aux_bwd_view(aux_ws, cap, g, nullptr, nullptr);
+    sg_launch_skin_bwd(c, bt, P, skin, shs, scales, radii, g, sg_rec_view(bwd_ws, cap), cap, b.header, sg_lds_hist(c.gx, c.gy) ? b.rec_valid : nullptr,
+                       dL_dposed_xyz_in, dL_dposed_rotq_in,
+                       skin_ws, dL_dxyz_canon, dL_drot_canon, dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA,
+                       dL_dtransl, 0, st, ax.dz, sg_aux_bytes(cap));
     SG_CHECK_LAST("skin_bwd_aux", s, st);
     return 0;
 }

@@ -138,21 +138,26 @@ static inline SgRec sg_rec_view(const void *bwd_ws, size_t cap)
 // that pair's 36-byte gradient record).
 static inline size_t sg_aux_ckd_bytes(size_t cap) { return sg_align((size_t)sg_ckpt_cap(cap) * 256 * 4); }
 static inline size_t sg_aux_bytes(size_t cap) { return sg_aux_ckd_bytes(cap) + sg_align((cap + 1) * 4); }
+// K-frame calls (the *_frames_aux entry points): frame f's aux workspace at + f ws bytes, its maps / map adjoints at + f map floats,
+// its z at + f SgBatch::geom bytes (SgGeom::depth lies in the geometry workspace); the single-frame kernels ignore both strides.
 struct SgAuxFwd {          // forward composite: z per Gaussian (SgGeom::depth), the two [H,W] maps, the D checkpoints
     const float *depth;
     float *out_depth, *out_alpha;
     float *ckD;
+    size_t ws, map;        // (K frames) bytes between the frames' aux workspaces, floats between their maps
 };
 struct SgAuxBwd {          // backward composite: z per Gaussian, the D checkpoints, dL/ddepth and dL/dalpha per pixel (either may be null),
     const float *depth;    // dL/dz per pair
     const float *ckD;
     const float *dL_ddepth, *dL_dalpha;
     float *dz;
+    size_t ws, map;        // (K frames) as in SgAuxFwd
 };
 static inline SgAuxFwd sg_aux_fwd_view(void *aux_ws, const SgGeom &g, float *out_depth, float *out_alpha)
 {
     SgAuxFwd a;
     a.depth = g.depth; a.out_depth = out_depth; a.out_alpha = out_alpha; a.ckD = (float *)aux_ws;
+    a.ws = 0; a.map = 0;
     return a;
 }
 static inline SgAuxBwd sg_aux_bwd_view(void *aux_ws, size_t cap, const SgGeom &g, const float *dL_ddepth, const float *dL_dalpha)
@@ -160,6 +165,7 @@ static inline SgAuxBwd sg_aux_bwd_view(void *aux_ws, size_t cap, const SgGeom &g
     SgAuxBwd a;
     a.depth = g.depth; a.ckD = (const float *)aux_ws; a.dL_ddepth = dL_ddepth; a.dL_dalpha = dL_dalpha;
     a.dz = (float *)((char *)aux_ws + sg_aux_ckd_bytes(cap));
+    a.ws = 0; a.map = 0;
     return a;
 }
 
@@ -279,15 +285,16 @@ void sg_launch_preprocess_fwd(const SgCam &c, const SgBatch &bt, int P, const fl
 void sg_launch_binning(const SgCam &c, const SgBatch &bt, int P, const int32_t *radii, SgGeom g, SgBin b, size_t cap,
                        int write_keys, hipStream_t st);
 static inline uint32_t sg_cap32(size_t cap) { return cap > 0xffffffffull ? 0xffffffffu : (uint32_t)cap; }
-// ax != null (single frame only): the AUX composite kernels, which also produce the depth / alpha maps / dL/dz per pair
+// ax != null: the AUX composite kernels, which also produce the depth / alpha maps / dL/dz per pair (K frames: the strides of `ax`)
 void sg_launch_render_fwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, size_t cap, SgImg im, float *out_color,
                           int write_keys, hipStream_t st, const SgAuxFwd *ax = nullptr);
 void sg_launch_render_bwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, size_t cap, SgImg im,
                           const float *dL_dpix, SgRec grec, hipStream_t st, const SgAuxBwd *ax = nullptr);
 // a9out [K][P][12]: the per-Gaussian sums of frame f's gradient records (sg_skin.hip::sg_record_sums_kernel), for the K-frame
-// per-Gaussian backward kernels
+// per-Gaussian backward kernels.  dz != null (depth / alpha maps): frame f's dL/dz plane at dz + f dz_stride bytes, its per-Gaussian
+// sum into the spare float of the 48-byte block (float 9)
 void sg_launch_record_sums(const SgBatch &bt, int P, const int32_t *radii, SgGeom g, SgRec grec, size_t cap, const uint32_t *header,
-                           const uint8_t *rec_valid, float4 *a9out, hipStream_t st);
+                           const uint8_t *rec_valid, float4 *a9out, hipStream_t st, const float *dz = nullptr, size_t dz_stride = 0);
 // bytes behind the K record buffers of a K-frame backward workspace: the a9 block of the K-camera per-Gaussian backward (K > 1)
 static inline size_t sg_a9_bytes(int P, int K) { return K > 1 ? sg_align((size_t)K * (size_t)P * 48 + 256) : 0; }
 void sg_launch_preprocess_bwd(const SgCam &c, const SgBatch &bt, int P, const float *means3D, const float *shs,
@@ -365,4 +372,4 @@ void sg_launch_skin_bwd(const SgCam &c, const SgBatch &bt, int P, const SgSkinIn
                         const int32_t *radii, SgGeom g, SgRec grec, size_t cap, const uint32_t *header, const uint8_t *rec_valid,
                         const float *dposed_xyz_in, const float *dposed_rotq_in, float *slab, float *dL_dxyz_canon, float *dL_drot_canon,
                         float *dL_dscales, float *dL_dopacity, float *dL_dsh, float *dL_dmeans2D, float *dL_dA,
-                        float *dL_dtransl, int accumulate, hipStream_t st, const float *dz = nullptr);
+                        float *dL_dtransl, int accumulate, hipStream_t st, const float *dz = nullptr, size_t dz_stride = 0);

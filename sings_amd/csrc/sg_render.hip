@@ -408,6 +408,26 @@ sg_render_fwd_frames_kernel(SgBatch bt, SG_FWD_PARAMS)
     out_color += (size_t)blockIdx.y * bt.image;
     sg_render_fwd_body<false, WEIGHTS>(SG_FWD_ARGS);
 }
+// The kernel above with the depth / alpha maps: K-frame calls of sg_skinned_forward_frames_aux (and its THROUGHPUT frames, K = 1
+// included).  A separate symbol, so that the plain frames kernel keeps its instructions; the frame's z is in its geometry workspace,
+// its D checkpoints in its aux workspace (+ frame x ax.ws), its maps at + frame x H W.
+template <bool WEIGHTS>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+sg_render_fwd_frames_aux_kernel(SgBatch bt, SG_FWD_PARAMS, SgAuxFwd ax)
+{
+    const size_t fb = (size_t)blockIdx.y * bt.bin, fg = (size_t)blockIdx.y * bt.geom, fi = (size_t)blockIdx.y * bt.img;
+    ranges = sg_at(ranges, fb); pair_keys = sg_at(pair_keys, fb); point_list = sg_at(point_list, fb);
+    point_keys = sg_at(point_keys, fb); ck_start = sg_at(ck_start, fb); header = sg_at(header, fb);
+    pair_mask = sg_at(pair_mask, fb); tile_count = sg_at(tile_count, fb); long_items = sg_at(long_items, fb);
+    plan = sg_at(plan, fb); item_w = sg_at(item_w, fb);
+    recA = sg_at(recA, fg); recB = sg_at(recB, fg); recC = sg_at(recC, fg);
+    final_T = sg_at(final_T, fi); n_contrib = sg_at(n_contrib, fi); ckpt = sg_at(ckpt, fi);
+    out_color += (size_t)blockIdx.y * bt.image;
+    const size_t fm = (size_t)blockIdx.y * ax.map;
+    ax.depth = sg_at(ax.depth, fg); ax.ckD = sg_at(ax.ckD, (size_t)blockIdx.y * ax.ws);
+    ax.out_depth += fm; ax.out_alpha += fm;
+    sg_render_fwd_body<false, WEIGHTS, true>(SG_FWD_ARGS, ax);
+}
 
 static inline int sg_render_blocks(int T) { return ((T + 8 * SG_XCD_RUN - 1) / (8 * SG_XCD_RUN)) * (8 * SG_XCD_RUN); }
 
@@ -426,8 +446,12 @@ void sg_launch_render_fwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, 
                        im.final_T, im.n_contrib, b.ck_start, im.ckpt, sg_ckpt_cap(cap), b.header, b.pair_mask, b.tile_count,       \
                        (const uint4 *)b.sort_items, sg_mask_plane(cap), b.plan, b.item_w, sg_items_cap((size_t)T, cap), key_pitch
     sg_prof_begin(SG_K_RENDER_FWD, st);
-    if (ax) {
-        // depth / alpha maps: one frame, the single-frame kernels' regimes (the entry points refuse K > 1 and SG_FLAG_THROUGHPUT)
+    if (ax && (K > 1 || (few && (c.flags & SG_FLAG_THROUGHPUT)))) {
+        // depth / alpha maps of K frames, or of a few-tile frame that shares the chip: the frames kernel's regime, as below
+        if (few) hipLaunchKernelGGL(sg_render_fwd_frames_aux_kernel<true>, dim3(grid, K), dim3(256), 0, st, bt, SG_RF_ARGS(grid), *ax);
+        else hipLaunchKernelGGL(sg_render_fwd_frames_aux_kernel<false>, dim3(grid, K), dim3(256), 0, st, bt, SG_RF_ARGS(grid), *ax);
+    } else if (ax) {
+        // depth / alpha maps of one frame: the single-frame kernels' regimes (the single-frame entry points refuse SG_FLAG_THROUGHPUT)
         if (few) {
             const int extra = sg_split_long(c.gx, c.gy, c.flags) ? 3 * (int)sg_sort_items_cap(T, cap) : 0;
             hipLaunchKernelGGL(sg_render_fwd_deep_aux_kernel, dim3(extra + grid), dim3(256), 0, st, SG_RF_ARGS(extra), *ax);
@@ -552,6 +576,14 @@ __device__ __forceinline__ int sg_red_idx(int lane)
         grec_a = sg_at(grec_a, fr); grec_b = sg_at(grec_b, fr);                                                          \
         dL_dpix += (size_t)blockIdx.y * bt.image;                                                                        \
     }
+// (AUX kernels) frame blockIdx.y's z (geometry workspace), D checkpoints and dL/dz plane (aux workspace: + frame x ax.ws bytes) and
+// map adjoints (+ frame x ax.map floats; either may be null).  One frame: every stride is 0.
+#define SG_BWD_AUX_FRAME_OFFSETS                                                                                        \
+    {                                                                                                                   \
+        const size_t fa = (size_t)blockIdx.y * ax.ws, fm = (size_t)blockIdx.y * ax.map * sizeof(float);               \
+        ax.depth = sg_at(ax.depth, (size_t)blockIdx.y * bt.geom); ax.ckD = sg_at(ax.ckD, fa); ax.dz = sg_at(ax.dz, fa);  \
+        ax.dL_ddepth = sg_at(ax.dL_ddepth, fm); ax.dL_dalpha = sg_at(ax.dL_dalpha, fm);                                  \
+    }
 // Round 5: the dependent gathers of an item (list id -> record slot -> records) are done in ONE round per chunk of SG_BCH entries, one
 // entry per thread, and the 64-entry batches then run out of LDS -- at cfg3 (lists of ~96 entries) one round per tile instead of one
 // per batch; the quadrant-sum slots are re-armed by the combine step itself (one barrier per batch less).  148.4 -> 145.8 us per
@@ -648,7 +680,7 @@ sg_order_items_kernel(SgBatch bt, const uint32_t *__restrict__ header, const uin
 }
 
 // The two backward composite kernels, and (SG_BWD_AUX 1) their variants with the depth / alpha adjoints (sg_rasterize_backward_aux,
-// sg_skinned_backward_aux: one frame).  One source, included twice, so that the plain kernels stay the round-5 kernels
+// sg_skinned_backward_aux: one frame; sg_rasterize_backward_records_frames_aux: K frames).  One source, included twice, so that the plain kernels stay the round-5 kernels
 // instruction for instruction (as inlined bodies the compiler allocated them differently) and the aux kernels are separate
 // symbols for the profiles.
 #define SG_BWD_AUX 0

@@ -1,6 +1,7 @@
 // Backward composite kernels of sg_render.hip, included there twice: SG_BWD_AUX 0 defines sg_render_bwd_kernel and
 // sg_render_bwd_sparse_kernel, SG_BWD_AUX 1 sg_render_bwd_aux_kernel and sg_render_bwd_sparse_aux_kernel, which also take the
-// depth / alpha adjoints (`ax`: SG_BWD_PASS) and write the dL/dz plane.  In the plain kernels every AUX branch is dead.
+// depth / alpha adjoints (`ax`: SG_BWD_PASS) and write the dL/dz plane, frame blockIdx.y's (SG_BWD_AUX_FRAME_OFFSETS).  In the plain
+// kernels every AUX branch is dead.
 // (no include guard: included once per variant)
 
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
@@ -21,6 +22,9 @@ sg_render_bwd_kernel(SG_BWD_PARAMS)
     __shared__ uint32_t smax[4];
     SG_STAMP_SCOPE
     SG_BWD_FRAME_OFFSETS;
+#if SG_BWD_AUX
+    SG_BWD_AUX_FRAME_OFFSETS;
+#endif
     // one workgroup per work item (tile, depth segment); the item list is in tile order, so the XCD-aware map
     // over the ACTUAL item count keeps neighbouring tiles on one L2.  The grid is an upper bound.
     (void)T; (void)nblocks;
@@ -173,6 +177,9 @@ sg_render_bwd_sparse_kernel(SG_BWD_PARAMS, const uint32_t *__restrict__ perm, ui
     __shared__ uint32_t smax[4];
     (void)T; (void)nblocks;
     SG_BWD_FRAME_OFFSETS;
+#if SG_BWD_AUX
+    SG_BWD_AUX_FRAME_OFFSETS;
+#endif
     perm = sg_at(perm, (size_t)blockIdx.y * bt.bin); rec_valid = sg_at(rec_valid, (size_t)blockIdx.y * bt.bin);
     const int nitems = header[1] ? 0 : (int)header[5];
     if ((int)blockIdx.x >= nitems) return;

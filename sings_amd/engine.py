@@ -455,14 +455,24 @@ class _FramesBase:
 class SkinnedFramesEngine(_FramesBase):
     """LBS-fused path, K posed frames of the same canonical Gaussians per call.  Flat gradient layout as ``SkinnedEngine``
     (xyz_canon 3P, scales 3P, opacity P, sh 3MP, [rot_canon]); per frame: ``color`` [K,3,H,W], ``radii`` [K,P], ``d_means2D``
-    [K,P,3], ``d_A`` [K,J,16], ``d_transl`` [K,3]."""
+    [K,P,3], ``d_A`` [K,J,16], ``d_transl`` [K,3].  ``aux``: the forward also writes ``depth`` and ``alpha`` [K,1,H,W] (the
+    ``*_frames_aux`` entry points: no ``phase`` split, no ``sh_planar``, the backward writes the gradients)."""
 
-    def __init__(self, P, J, W, H, sh_coeffs, K, device, capacity_pairs, with_rot=False, grad_flat=None, rot_width=9, sh_planar=False):
+    def __init__(self, P, J, W, H, sh_coeffs, K, device, capacity_pairs, with_rot=False, grad_flat=None, rot_width=9, sh_planar=False,
+                 aux=False):
         self.dev = torch.device(device)
         self.J, self.M = int(J), int(sh_coeffs)
         self.sh_planar = bool(sh_planar)
+        self.aux = bool(aux)
+        if self.aux and self.sh_planar:
+            raise ValueError("SkinnedFramesEngine: the depth / alpha maps (aux=True) do not support sh_planar")
         self._alloc(P, W, H, K, capacity_pairs)
         f32 = dict(dtype=torch.float32, device=self.dev)
+        self.aux_ws = self.depth = self.alpha = None
+        if self.aux:
+            self.aux_ws = torch.empty(_lib.frames_aux_layout(self.P, self.W, self.H, self.cap, self.K), dtype=torch.uint8, device=self.dev)
+            self.depth = torch.empty((self.K, 1, self.H, self.W), **f32)
+            self.alpha = torch.empty((self.K, 1, self.H, self.W), **f32)
         self.skin_ws = torch.empty(int(self.lib.sg_skin_ws_floats_frames(self.P, self.K)), **f32)
         rot_width = int(rot_width)
         per = 3 + 3 + 1 + 3 * self.M + (rot_width if with_rot else 0)
@@ -523,9 +533,12 @@ class SkinnedFramesEngine(_FramesBase):
         """``phase``: None = the whole forward; "binning" / "composite" = its two halves as separate calls on the same workspaces
         (SG_FLAG_FORWARD_BINNING / _COMPOSITE), for a caller that runs them on different streams and orders them with events.
         ``posed_out``: optional (xyz [K,P,3], quaternions [K,P,4], scales [K,P,3]) fp32 tensors the posed values of the K frames are
-        also written to (what forward_chunk returns, sings_hybrid.py:512-553; the render itself never reads them back)."""
+        also written to (what forward_chunk returns, sings_hybrid.py:512-553; the render itself never reads them back).
+        ``aux`` engines also write ``depth`` / ``alpha`` and take no ``phase``."""
         if self._s is None or self._fb is None or self._k is None:
             raise RuntimeError("SkinnedFramesEngine: set_camera() and set_frames() first")
+        if self.aux and phase is not None:
+            raise ValueError("SkinnedFramesEngine: the depth / alpha maps (aux=True) have no phase split")
         if posed_out is not None:
             for x, wdt in zip(posed_out, (3, 4, 3)):
                 if (tuple(x.shape) != (self.K, self.P, wdt) or x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.dev):
@@ -537,33 +550,52 @@ class SkinnedFramesEngine(_FramesBase):
         if phase == "composite":
             self._s.flags &= ~_lib.FLAG_WS_CLEAN
         self._clean = False
-        _lib.check(self.lib.sg_skinned_forward_frames(
-            C.byref(self._s), C.byref(self._fb), self.P, C.byref(self._k), _ptr(shs), _ptr(opacities), _ptr(scales),
-            _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.img), _ptr(self.color), _ptr(self.radii), _ptr(pxyz), _ptr(pq),
-            _ptr(psc), nr if sync_num_rendered and phase != "composite" else None, self._stream()), "skinned forward (frames)")
+        args = (C.byref(self._s), C.byref(self._fb), self.P, C.byref(self._k), _ptr(shs), _ptr(opacities), _ptr(scales),
+                _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.img), _ptr(self.color), _ptr(self.radii), _ptr(pxyz), _ptr(pq),
+                _ptr(psc), nr if sync_num_rendered and phase != "composite" else None)
+        if self.aux:
+            _lib.check(self.lib.sg_skinned_forward_frames_aux(*args, _ptr(self.aux_ws), _ptr(self.depth), _ptr(self.alpha),
+                                                              self._stream()), "skinned forward (frames, depth / alpha maps)")
+        else:
+            _lib.check(self.lib.sg_skinned_forward_frames(*args, self._stream()), "skinned forward (frames)")
         self._clean = phase != "binning"                      # (the COMPOSITE leaves the counters zeroed for the next forward)
         return [int(v) for v in nr] if sync_num_rendered and phase != "composite" else None
 
-    def backward(self, shs, opacities, scales, dL_dcolor, accumulate=False):
-        """``dL_dcolor`` [K,3,H,W].  ``accumulate``: the K frames' sum is ADDED to the gradient buffer (a later batch of the step)."""
-        self.backward_records(dL_dcolor)
+    def backward(self, shs, opacities, scales, dL_dcolor, accumulate=False, dL_ddepth=None, dL_dalpha=None):
+        """``dL_dcolor`` [K,3,H,W].  ``accumulate``: the K frames' sum is ADDED to the gradient buffer (a later batch of the step).
+        ``dL_ddepth`` / ``dL_dalpha``: [K,1,H,W] adjoints of the maps (``aux`` engines; None: zero)."""
+        self.backward_records(dL_dcolor, dL_ddepth, dL_dalpha)
         self.backward_gaussians(shs, opacities, scales, accumulate)
 
-    def backward_records(self, dL_dcolor):
-        """First half of ``backward``: the per-tile composite backward of the K frames (VALU-bound)."""
-        _lib.check(self.lib.sg_rasterize_backward_records_frames(
-            C.byref(self._s), C.byref(self._fb), self.P, _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.img),
-            _ptr(self.bwd_ws), _ptr(dL_dcolor), self._stream()), "skinned backward (records, frames)")
+    def backward_records(self, dL_dcolor, dL_ddepth=None, dL_dalpha=None):
+        """First half of ``backward``: the per-tile composite backward of the K frames (VALU-bound).  ``aux`` engines also take the
+        maps' adjoints (and write every frame's dL/dz plane into ``aux_ws``)."""
+        if not self.aux and (dL_ddepth is not None or dL_dalpha is not None):
+            raise ValueError("SkinnedFramesEngine: dL_ddepth / dL_dalpha need an engine built with aux=True")
+        args = (C.byref(self._s), C.byref(self._fb), self.P, _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.img),
+                _ptr(self.bwd_ws), _ptr(dL_dcolor))
+        if self.aux:
+            _lib.check(self.lib.sg_rasterize_backward_records_frames_aux(*args, _ptr(self.aux_ws), _ptr(dL_ddepth), _ptr(dL_dalpha),
+                                                                         self._stream()),
+                       "skinned backward (records, frames, depth / alpha maps)")
+        else:
+            _lib.check(self.lib.sg_rasterize_backward_records_frames(*args, self._stream()), "skinned backward (records, frames)")
 
     def backward_gaussians(self, shs, opacities, scales, accumulate=False):
-        """Second half: record sums + the per-Gaussian chain rule summed over the K frames (latency-bound)."""
+        """Second half: record sums + the per-Gaussian chain rule summed over the K frames (latency-bound).  ``aux`` engines add
+        every frame's dL/dz to its posed means and write the gradients (no ``accumulate``)."""
         accumulate, done = self._chain_state(accumulate)
-        _lib.check(self.lib.sg_skinned_backward_gaussians_frames(
-            C.byref(self._s), C.byref(self._fb), self.P, C.byref(self._k), _ptr(shs), _ptr(opacities), _ptr(scales),
-            _ptr(self.radii), _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.bwd_ws), _ptr(self.skin_ws),
-            int(bool(accumulate)), None, None, _ptr(self.d_xyz), _ptr(self.d_rot), _ptr(self.d_scales), _ptr(self.d_opacity),
-            _ptr(self.d_sh), _ptr(self.d_means2D), _ptr(self.d_A), _ptr(self.d_transl), self._stream()),
-            "skinned backward (gaussians, frames)")
+        if self.aux and accumulate:
+            raise ValueError("SkinnedFramesEngine: the depth / alpha maps (aux=True) write the gradients (no accumulate)")
+        args = (C.byref(self._s), C.byref(self._fb), self.P, C.byref(self._k), _ptr(shs), _ptr(opacities), _ptr(scales),
+                _ptr(self.radii), _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.bwd_ws), _ptr(self.skin_ws),
+                int(bool(accumulate)), None, None, _ptr(self.d_xyz), _ptr(self.d_rot), _ptr(self.d_scales), _ptr(self.d_opacity),
+                _ptr(self.d_sh), _ptr(self.d_means2D), _ptr(self.d_A), _ptr(self.d_transl))
+        if self.aux:
+            _lib.check(self.lib.sg_skinned_backward_gaussians_frames_aux(*args, _ptr(self.aux_ws), self._stream()),
+                       "skinned backward (gaussians, frames, depth / alpha maps)")
+        else:
+            _lib.check(self.lib.sg_skinned_backward_gaussians_frames(*args, self._stream()), "skinned backward (gaussians, frames)")
         if done is not None:
             done.record(torch.cuda.current_stream(self.dev))
 

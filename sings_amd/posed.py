@@ -245,26 +245,27 @@ class FrameAnimator:
 
 
     # ---- K frames of the same Gaussians per dispatch (round 4: sings_amd.engine.SkinnedFramesEngine) -------------------------
-    def _frame_engines(self, J, W, H, K, cap):
+    def _frame_engines(self, J, W, H, K, cap, aux=False):
         from .engine import SkinnedFramesEngine
         c = self.canon
         P, M = int(c['xyz_canon'].shape[0]), int(c['shs'].shape[1])
         rot = c.get('rotmat_canon')
-        key = (P, J, W, H, M, K, None if rot is None else int(rot.reshape(P, -1).shape[1]))
+        key = (P, J, W, H, M, K, None if rot is None else int(rot.reshape(P, -1).shape[1]), bool(aux))
         if getattr(self, "_fshape", None) != key or cap > getattr(self, "_fcap", 0):
             self._fengs = []
             self._fengs = [SkinnedFramesEngine(P, J, W, H, M, K, self.dev, capacity_pairs=cap, with_rot=rot is not None,
-                                               rot_width=9 if rot is None else key[6]) for _ in range(self.n)]
+                                               rot_width=9 if rot is None else key[6], aux=aux) for _ in range(self.n)]
             self._fshape, self._fcap = key, cap
         return self._fengs
 
-    def render_frames_batched(self, jobs, bg_color, frames_per_launch=8, scaling_modifier=1.0):
+    def render_frames_batched(self, jobs, bg_color, frames_per_launch=8, scaling_modifier=1.0, return_aux=False):
         """``render_frames`` with K = ``frames_per_launch`` consecutive frames per DISPATCH: the reference's chunk
         (``SinGS.forward_chunk``, sings_hybrid.py:474-569, rendered one frame at a time at gs_trainer.py:684-714) goes through
         every kernel of the forward once -- canonical inputs read once for the K poses, K frames' worth of workgroups for the
         latency-bound kernels.  One launch per stream in flight.  Jobs as in ``render_round`` but WITHOUT ``ext_tfs`` (the K-frame
         entry points take none) and with one ``smpl_scale`` for the batch; the cameras of a batch may differ.  Yields
-        (index, clamped image) in order; images are bit-identical to the per-frame path's."""
+        (index, clamped image) in order; images are bit-identical to the per-frame path's.  ``return_aux``: yields (index, image,
+        depth [1,H,W], alpha [1,H,W]) -- the maps of ``get_render_pkg_fused(return_aux=True)``, re-rendered fallbacks included."""
         from collections import deque
         c = self.canon
         K = max(1, min(int(frames_per_launch), 16))
@@ -292,9 +293,13 @@ class FrameAnimator:
                 e.set_frames(c['xyz_canon'], c.get('rotmat_canon'), c['lbs_weights'], A, batch[0][3], tr)
                 e.forward(c['shs'], c['opacity'], c['scales'])
                 img = torch.clamp(e.color, 0.0, 1.0)             # [K,3,H,W]: a new tensor, the engine's image buffer is reused
+                maps = (e.depth.clone(), e.alpha.clone()) if return_aux else None      # (so are its map buffers)
                 ev = torch.cuda.Event(); ev.record(st)
             img.record_stream(cur)
-            return img, ev
+            if maps is not None:
+                for m in maps:
+                    m.record_stream(cur)
+            return (img, maps), ev
 
         def submit(i0, batch):
             for j in batch:
@@ -306,7 +311,7 @@ class FrameAnimator:
             J = int(batch[0][1].reshape(-1, 16).shape[0])
             W, H = int(batch[0][0]['image_width']), int(batch[0][0]['image_height'])
             cap = _capacity_floor(getattr(self, "_fcap", 0), P, W, H)
-            engs = self._frame_engines(J, W, H, K, cap)
+            engs = self._frame_engines(J, W, H, K, cap, return_aux)
             e, st = engs[state['b'] % self.n], self.streams[state['b'] % self.n]
             state['b'] += 1
             img, ev = launch(i0, batch, e, st)
@@ -322,17 +327,21 @@ class FrameAnimator:
                 # (a NEW set of engines either way: the queued batches keep theirs, whose counts are still to be read)
                 need = max(max(Rs[:len(batch)]), self._fcap - self._fcap // 5)
                 J, W, H = self._fshape[1], self._fshape[2], self._fshape[3]
-                e2 = self._frame_engines(J, W, H, K, _grown(need))[0]
+                e2 = self._frame_engines(J, W, H, K, _grown(need), return_aux)[0]
                 img, ev = launch(i0, batch, e2, self.streams[0])
                 torch.cuda.synchronize(self.dev)
                 Rs2 = e2.num_rendered()
                 if max(Rs2[:len(batch)]) > e2.cap:               # (both at once: the plain path has now counted the batch)
                     need = max(Rs2[:len(batch)])
-                    e2 = self._frame_engines(J, W, H, K, _grown(need))[0]
+                    e2 = self._frame_engines(J, W, H, K, _grown(need), return_aux)[0]
                     img, ev = launch(i0, batch, e2, self.streams[0])
                     torch.cuda.synchronize(self.dev)
+            img, maps = img
             for k in range(len(batch)):
-                yield i0 + k, img[k]
+                if maps is not None:
+                    yield i0 + k, img[k], maps[0][k], maps[1][k]
+                else:
+                    yield i0 + k, img[k]
 
         batch, i0, i = [], 0, 0
         for i, job in enumerate(jobs):
@@ -354,14 +363,16 @@ class FrameAnimator:
 
 @torch.no_grad()
 def animate_chunk(canon, poses, joints_rest, A_t2cano, cameras, bg_color, transl=None, smpl_scale=None, ext_tfs=None,
-                  parents=SMPL_PARENTS, chunk_size=16, streams=1, animator=None, frames_per_launch=1):
+                  parents=SMPL_PARENTS, chunk_size=16, streams=1, animator=None, frames_per_launch=1, return_aux=False):
     """Renders frames ``poses[f]`` with camera dict ``cameras[f]`` (or one shared dict); yields (f, image[3,H,W]).
 
     canon: dict(xyz_canon, rotmat_canon|None, scales, opacity, shs, lbs_weights, active_sh_degree);
     transl [F,3] or None; ext_tfs: per-frame tuple (trans[F,3], rotmat[F,3,3], scale[F,1]) or None.
     streams > 1 (or an existing ``animator``): that many frames in flight (FrameAnimator); same images.
     frames_per_launch = K > 1 (without ext_tfs): K consecutive frames per DISPATCH (FrameAnimator.render_frames_batched), one such
-    launch per stream in flight; same images."""
+    launch per stream in flight; same images.
+    return_aux: yields (f, image, depth [1,H,W], alpha [1,H,W]) -- the maps of get_render_pkg_fused(return_aux=True) -- on the
+    K-frame path and on the plain per-frame loop; the ``streams`` > 1 per-frame path (render_frames) has no maps: ValueError."""
     F = poses.shape[0]
     inv_cano = torch.inverse(A_t2cano)
     batched = int(frames_per_launch) > 1 and ext_tfs is None
@@ -382,7 +393,11 @@ def animate_chunk(canon, poses, joints_rest, A_t2cano, cameras, bg_color, transl
                            None if transl is None else transl[f], smpl_scale,
                            None if ext_tfs is None else (ext_tfs[0][f], ext_tfs[1][f], ext_tfs[2][f]))
         if batched:
-            yield from animator.render_frames_batched(jobs(), bg_color, frames_per_launch=int(frames_per_launch))
+            yield from animator.render_frames_batched(jobs(), bg_color, frames_per_launch=int(frames_per_launch),
+                                                      return_aux=return_aux)
+        elif return_aux:
+            raise ValueError("animate_chunk: return_aux needs frames_per_launch > 1 or the per-frame loop (streams=1, no animator); "
+                             "FrameAnimator.render_frames has no depth / alpha maps")
         else:
             yield from animator.render_frames(jobs(), bg_color)
         return
@@ -393,5 +408,8 @@ def animate_chunk(canon, poses, joints_rest, A_t2cano, cameras, bg_color, transl
             cam = cameras[f] if isinstance(cameras, (list, tuple)) else cameras
             ext = None if ext_tfs is None else (ext_tfs[0][f], ext_tfs[1][f], ext_tfs[2][f])
             pkg = get_render_pkg_fused(cam, canon, A[i], bg_color, smpl_scale=smpl_scale,
-                                       transl=None if transl is None else transl[f], ext_tfs=ext)
-            yield f, pkg["render"]
+                                       transl=None if transl is None else transl[f], ext_tfs=ext, return_aux=return_aux)
+            if return_aux:
+                yield f, pkg["render"], pkg["depth"], pkg["alpha"]
+            else:
+                yield f, pkg["render"]

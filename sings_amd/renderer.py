@@ -106,13 +106,14 @@ def get_render_pkg_fused(data, canon, A_cano2pose, bg_color, smpl_scale=None, tr
     return pkg
 
 
-def get_render_pkgs_fused(data, canon, A_cano2pose, bg_color, smpl_scale=None, transl=None, scaling_modifier=1.0):
+def get_render_pkgs_fused(data, canon, A_cano2pose, bg_color, smpl_scale=None, transl=None, scaling_modifier=1.0, return_aux=False):
     """The chunk form of ``get_render_pkg_fused``: K posed frames of the same canonical Gaussians in ONE fused call (K <= 16).
 
     ``data``: one camera dict for all frames or a list of K dicts (same image size and field of view); ``A_cano2pose`` [K,J,4,4];
     ``transl`` [K,3] / [3] / None.  Returns the keys of ``get_render_pkg`` with a leading frame axis: 'render' [K,3,H,W],
     'radii' [K,N], 'visibility_filter' [K,N], 'viewspace_points' [K,N,3] (its ``.grad`` receives every frame's screen-space
-    gradient: the densifier's statistics stay per frame)."""
+    gradient: the densifier's statistics stay per frame).  ``return_aux``: the package also carries 'depth' and 'alpha'
+    ([K,1,H,W], differentiable: ``get_render_pkg_fused``'s maps of every frame)."""
     from .skinned import rasterize_skinned_frames
     datas = list(data) if isinstance(data, (list, tuple)) else None
     d0 = datas[0] if datas is not None else data
@@ -129,8 +130,12 @@ def get_render_pkgs_fused(data, canon, A_cano2pose, bg_color, smpl_scale=None, t
     if torch.is_grad_enabled():
         screenspace_points = torch.zeros((K,) + tuple(xyz.shape), dtype=xyz.dtype, device=xyz.device, requires_grad=True) + 0
         screenspace_points.retain_grad()
-    color, radii = rasterize_skinned_frames(xyz, canon.get('rotmat_canon'), canon['scales'], canon['opacity'], canon['shs'],
-                                            canon['lbs_weights'], A_cano2pose, rs, smpl_scale=smpl_scale, transl=transl,
-                                            means2D=screenspace_points)
-    return {"render": torch.clamp(color, 0.0, 1.0), "render_raw": color, "viewspace_points": screenspace_points,
-            "visibility_filter": radii > 0, "radii": radii, "human_visibility_filter": radii > 0, "human_radii": radii}
+    out = rasterize_skinned_frames(xyz, canon.get('rotmat_canon'), canon['scales'], canon['opacity'], canon['shs'],
+                                   canon['lbs_weights'], A_cano2pose, rs, smpl_scale=smpl_scale, transl=transl,
+                                   means2D=screenspace_points, return_aux=return_aux)
+    color, radii = out[0], out[1]
+    pkg = {"render": torch.clamp(color, 0.0, 1.0), "render_raw": color, "viewspace_points": screenspace_points,
+           "visibility_filter": radii > 0, "radii": radii, "human_visibility_filter": radii > 0, "human_radii": radii}
+    if return_aux:
+        pkg.update(depth=out[2], alpha=out[3])
+    return pkg

@@ -196,16 +196,19 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
     before the call returns (one strided copy + stream synchronisation): a frame that would overflow is never returned, the
     workspaces grow and the call is repeated.  With ``set_overflow_check("deferred")`` or inside a HIP-graph capture nothing is
     read on the host: the largest (pair count, overflow flag) of the K frames is folded into the device-side accumulator that
-    ``check_deferred_overflow()`` polls, exactly as the single-frame operator does."""
+    ``check_deferred_overflow()`` polls, exactly as the single-frame operator does.  ``return_aux``: also the K frames' depth and
+    alpha maps (the ``*_frames_aux`` entry points), bit for bit those of K single-frame ``return_aux`` calls."""
 
     @staticmethod
     def forward(ctx, xyz_canon, rotmat_canon, scales, opacities, shs, A, transl, lbs_weights, smpl_scale, raster_settings,
-                means2D=None):
+                means2D=None, return_aux=False):
         from .engine import _frame_batch
         lib = _lib.load()
         dev = xyz_canon.device
         if dev.type != "cuda":
             raise RuntimeError("sings_amd fused LBS+raster runs on the MI355X only; there is no CPU fallback")
+        if return_aux:
+            ctx.set_materialize_grads(False)
         rs = raster_settings
         xyz_canon = _f32(xyz_canon, "xyz_canon", dev)
         rot_shape = None if rotmat_canon is None else tuple(rotmat_canon.shape)
@@ -242,11 +245,13 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
         fb = _frame_batch(K, cam_stride, tstride)
         color = torch.empty((K, 3, H, W), dtype=torch.float32, device=dev)
         radii = torch.empty((K, P), dtype=torch.int32, device=dev)
+        depth, alpha = ((torch.empty((K, 1, H, W), dtype=torch.float32, device=dev),
+                         torch.empty((K, 1, H, W), dtype=torch.float32, device=dev)) if return_aux else (None, None))
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        L = geom = binning = img = sizes = None
+        L = geom = binning = img = sizes = aux = None
 
         def launch(cap, flags, sync):
-            nonlocal L, geom, binning, img, sizes
+            nonlocal L, geom, binning, img, sizes, aux
             s.flags = flags
             L = _lib.SgLayout(); sizes = [C.c_size_t() for _ in range(4)]
             _lib.check(lib.sg_frames_layout(P, W, H, cap, K, C.byref(L), *[C.byref(x) for x in sizes]), "sg_frames_layout")
@@ -254,9 +259,14 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
             binning = torch.empty(sizes[1].value, dtype=torch.uint8, device=dev)
             img = torch.empty(sizes[2].value, dtype=torch.uint8, device=dev)
             nr = (C.c_int64 * K)()
-            _lib.check(lib.sg_skinned_forward_frames(C.byref(s), C.byref(fb), P, C.byref(k), _ptr(shs), _ptr(opacities), _ptr(scales),
-                                                     _ptr(geom), _ptr(binning), cap, _ptr(img), _ptr(color), _ptr(radii), None, None,
-                                                     None, nr if sync else None, stream), "skinned forward (frames)")
+            args = (C.byref(s), C.byref(fb), P, C.byref(k), _ptr(shs), _ptr(opacities), _ptr(scales), _ptr(geom), _ptr(binning), cap,
+                    _ptr(img), _ptr(color), _ptr(radii), None, None, None, nr if sync else None)
+            if return_aux:
+                aux = torch.empty(_lib.frames_aux_layout(P, W, H, cap, K), dtype=torch.uint8, device=dev)
+                _lib.check(lib.sg_skinned_forward_frames_aux(*args, _ptr(aux), _ptr(depth), _ptr(alpha), stream),
+                           "skinned forward (frames, depth / alpha maps)")
+            else:
+                _lib.check(lib.sg_skinned_forward_frames(*args, stream), "skinned forward (frames)")
             return [int(v) for v in nr] if sync else None
 
         # (unread: the largest pair count and the OR of the K frames' flag words go to the check of the single-frame op)
@@ -273,15 +283,19 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
         ctx.has_rot = rotmat_canon is not None
         ctx.rot_shape = rot_shape
         ctx.has_m2d = means2D is not None
+        ctx.return_aux = return_aux
+        ctx.aux_ws = aux
         ctx.aux = (lbs_weights, smpl_scale, A.shape, None if transl is None else transl.shape, sizes[3].value)
         z = torch.empty(0, device=dev)
         ctx.save_for_backward(xyz_canon, rotmat_canon if ctx.has_rot else z, scales, opacities, shs, A16,
                               transl if transl is not None else z, radii, geom, binning, img)
         ctx.mark_non_differentiable(radii)
+        if return_aux:
+            return color, radii, depth, alpha
         return color, radii
 
     @staticmethod
-    def backward(ctx, g_color, _g_radii=None):
+    def backward(ctx, g_color, _g_radii=None, g_depth=None, g_alpha=None):
         from .engine import _frame_batch
         lib = _lib.load()
         xyz_canon, rotmat_canon, scales, opacities, shs, A16, transl, radii, geom, binning, img = ctx.saved_tensors
@@ -301,17 +315,29 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
         d_xyz, d_scales, d_op, d_sh, d_m2d = e(P, 3), e(P, 3), e(P, 1), e(P, ctx.M, 3), e(K, P, 3)
         d_rot = e(P, int(rotmat_canon.shape[1])) if ctx.has_rot else None
         d_A = e(K, k.J, 16); d_tr = e(K, 3)
-        g_color = _f32(g_color, "grad_out_color", dev)
+        g_color = (torch.zeros((K, 3, H, W), dtype=torch.float32, device=dev) if g_color is None
+                   else _f32(g_color, "grad_out_color", dev))
+        if not ctx.return_aux:
+            g_depth = g_alpha = None
+        g_depth = None if g_depth is None else _f32(g_depth, "grad_depth", dev)
+        g_alpha = None if g_alpha is None else _f32(g_alpha, "grad_alpha", dev)
+        aux = g_depth is not None or g_alpha is not None     # neither map carries a gradient: the plain backward, bit for bit
         with torch.cuda.device(dev):
             bwd_ws = torch.empty(bwd_bytes, dtype=torch.uint8, device=dev)
             skin_ws = e(int(lib.sg_skin_ws_floats_frames(P, K)))
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.sg_rasterize_backward_records_frames(C.byref(s), C.byref(fb), P, _ptr(geom), _ptr(binning), ctx.cap, _ptr(img),
-                                                                _ptr(bwd_ws), _ptr(g_color), stream), "skinned backward (records, frames)")
-            _lib.check(lib.sg_skinned_backward_gaussians_frames(
-                C.byref(s), C.byref(fb), P, C.byref(k), _ptr(shs), _ptr(opacities), _ptr(scales), _ptr(radii), _ptr(geom), _ptr(binning),
-                ctx.cap, _ptr(bwd_ws), _ptr(skin_ws), 0, None, None, _ptr(d_xyz), _ptr(d_rot), _ptr(d_scales), _ptr(d_op), _ptr(d_sh),
-                _ptr(d_m2d), _ptr(d_A), _ptr(d_tr), stream), "skinned backward (gaussians, frames)")
+            rec = (C.byref(s), C.byref(fb), P, _ptr(geom), _ptr(binning), ctx.cap, _ptr(img), _ptr(bwd_ws), _ptr(g_color))
+            gau = (C.byref(s), C.byref(fb), P, C.byref(k), _ptr(shs), _ptr(opacities), _ptr(scales), _ptr(radii), _ptr(geom), _ptr(binning),
+                   ctx.cap, _ptr(bwd_ws), _ptr(skin_ws), 0, None, None, _ptr(d_xyz), _ptr(d_rot), _ptr(d_scales), _ptr(d_op), _ptr(d_sh),
+                   _ptr(d_m2d), _ptr(d_A), _ptr(d_tr))
+            if aux:
+                _lib.check(lib.sg_rasterize_backward_records_frames_aux(*rec, _ptr(ctx.aux_ws), _ptr(g_depth), _ptr(g_alpha), stream),
+                           "skinned backward (records, frames, depth / alpha maps)")
+                _lib.check(lib.sg_skinned_backward_gaussians_frames_aux(*gau, _ptr(ctx.aux_ws), stream),
+                           "skinned backward (gaussians, frames, depth / alpha maps)")
+            else:
+                _lib.check(lib.sg_rasterize_backward_records_frames(*rec, stream), "skinned backward (records, frames)")
+                _lib.check(lib.sg_skinned_backward_gaussians_frames(*gau, stream), "skinned backward (gaussians, frames)")
         if transl_shape is None:
             g_tr = None
         elif ctx.fb[1] == 3:
@@ -319,15 +345,17 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
         else:
             g_tr = d_tr.sum(0).view(transl_shape)                 # one translation shared by the K frames
         return (d_xyz, None if d_rot is None else d_rot.view(ctx.rot_shape), d_scales, d_op.view_as(opacities), d_sh,
-                d_A.view(A_shape), g_tr, None, None, None, d_m2d if ctx.has_m2d else None)
+                d_A.view(A_shape), g_tr, None, None, None, d_m2d if ctx.has_m2d else None, None)
 
 
 def rasterize_skinned_frames(xyz_canon, rotmat_canon, scales, opacities, shs, lbs_weights, A_cano2pose, raster_settings,
-                             smpl_scale=None, transl=None, means2D=None):
+                             smpl_scale=None, transl=None, means2D=None, return_aux=False):
     """color [K,3,H,W], radii [K,P] = fused LBS + rasterization of K posed frames of the same canonical Gaussians in one call.
 
     ``A_cano2pose`` [K,J,4,4]; ``transl`` [K,3] (per frame), [3] (shared) or None; ``raster_settings``: one camera, or
     ``viewmatrix`` / ``projmatrix`` [K,4,4] and ``campos`` [K,3] for a camera per frame.  ``means2D``: optional [K,N,3] holder
-    (``requires_grad``) of the per-frame screen-space gradients.  Backward: canonical-Gaussian gradients summed over the K frames."""
+    (``requires_grad``) of the per-frame screen-space gradients.  Backward: canonical-Gaussian gradients summed over the K frames.
+    ``return_aux``: color, radii, depth [K,1,H,W], alpha [K,1,H,W] -- every frame's accumulated depth sum_i z_i alpha_i T_i and alpha
+    map 1 - T_final, differentiable (``rasterize_skinned_gaussians(return_aux=True)`` per frame)."""
     return _RasterizeSkinnedFrames.apply(xyz_canon, rotmat_canon, scales, opacities, shs, A_cano2pose, transl, lbs_weights,
-                                         smpl_scale, raster_settings, means2D)
+                                         smpl_scale, raster_settings, means2D, return_aux)
