@@ -98,7 +98,9 @@ def rasterize(means3D, opacities, view, proj, campos, W, H, tanfovx, tanfovy, bg
     """Forward of the whole rasterizer as ONE autograd graph.  Inputs: numpy arrays or tensors (leaf tensors with
     requires_grad keep their identity so that ``.grad`` is filled by ``out['color'].backward(...)``).
     Returns a dict: color [3,H,W], final_T, n_contrib, radii, rect, tiles_touched, depths, keys, point_list, ranges, R, and
-    ``ndc`` -- the retained [P,2] NDC means whose gradient is the op's ``means2D.grad[:, :2]`` (App. A.4)."""
+    ``ndc`` -- the retained [P,2] NDC means whose gradient is the op's ``means2D.grad[:, :2]`` (App. A.4) -- and the two
+    differentiable maps of the AUX ops: ``depth`` [H,W] = sum over the blended entries of z alpha T, with z the view-space
+    t.z of the graph (not the detached ``depths``), and ``alpha`` [H,W] = 1 - T_final."""
     T = lambda a: a.to(dtype) if torch.is_tensor(a) else torch.as_tensor(np.asarray(a), dtype=dtype)
     p, op, s, q, sh = T(means3D), T(opacities).reshape(-1), T(scales), T(rotations), T(shs)
     Vm, Pm, cam, bgc = T(view).reshape(4, 4), T(proj).reshape(4, 4), T(campos).reshape(3), T(bg).reshape(3)
@@ -182,6 +184,9 @@ def rasterize(means3D, opacities, view, proj, campos, W, H, tanfovx, tanfovy, bg
     # ---- A.3 compositing, one tile at a time, vectorised over (entry, pixel)
     color = torch.zeros((3, H, W), dtype=dtype) + bgc[:, None, None]
     final_T = torch.ones((H, W), dtype=dtype)
+    depth = torch.zeros((H, W), dtype=dtype)
+    alpha_map = torch.zeros((H, W), dtype=dtype)
+    tz = t[:, 2]
     n_contrib = np.zeros((H, W), np.uint32)
     conic = torch.stack([cx, cy, cz], 1)
     planes = []
@@ -209,29 +214,36 @@ def rasterize(means3D, opacities, view, proj, campos, W, H, tanfovx, tanfovy, bg
         blended = valid & (idx < first_term[None])
         wgt = torch.where(blended, alpha * T_before, torch.zeros_like(alpha))
         C = (rgb[ids].t()[:, :, None] * wgt[None]).sum(1)                                   # [3, npix]
+        D = (tz[ids][:, None] * wgt).sum(0)                                                 # [npix]
         Tfin = torch.where(blended, keep, torch.ones_like(keep)).prod(0)
         last = torch.where(blended, idx + 1, torch.zeros_like(idx)).max(0).values
         h, w_ = ys.shape
-        planes.append((Y0, X0, h, w_, C + Tfin[None] * bgc[:, None], Tfin, last))
-    for Y0, X0, h, w_, col, Tf, last in planes:
+        planes.append((Y0, X0, h, w_, C + Tfin[None] * bgc[:, None], Tfin, last, D))
+    for Y0, X0, h, w_, col, Tf, last, D in planes:
         color[:, Y0:Y0 + h, X0:X0 + w_] = col.reshape(3, h, w_)
         final_T[Y0:Y0 + h, X0:X0 + w_] = Tf.reshape(h, w_)
+        depth[Y0:Y0 + h, X0:X0 + w_] = D.reshape(h, w_)
+        alpha_map[Y0:Y0 + h, X0:X0 + w_] = 1.0 - Tf.reshape(h, w_)
         n_contrib[Y0:Y0 + h, X0:X0 + w_] = last.reshape(h, w_).numpy().astype(np.uint32)
-    return dict(color=color, final_T=final_T.detach(), n_contrib=n_contrib, radii=radii.numpy().astype(np.int32),
+    return dict(color=color, depth=depth, alpha=alpha_map, final_T=final_T.detach(), n_contrib=n_contrib, radii=radii.numpy().astype(np.int32),
                 rect=torch.stack([x0, y0, x1, y1], 1).numpy().astype(np.int32), tiles_touched=tiles.numpy().astype(np.uint32),
                 depths=t[:, 2].detach(), keys=keys, point_list=vals.astype(np.uint32), ranges=ranges, R=int(len(keys)),
                 ndc=ndc, xy=pix.detach(), rgb=rgb.detach(), conic=conic.detach(), visible=ok.numpy())
 
 
-def forward_backward(s, dL_dimage, dtype=torch.float64, scale_modifier=1.0):
-    """Scene dict of sings_amd.scene.synthetic_scene -> (forward dict, gradients dict with the C oracle's key names)."""
+def forward_backward(s, dL_dimage, dtype=torch.float64, scale_modifier=1.0, dL_ddepth=None, dL_dalpha=None):
+    """Scene dict of sings_amd.scene.synthetic_scene -> (forward dict, gradients dict with the C oracle's key names).
+    ``dL_dimage`` may be None; ``dL_ddepth`` / ``dL_dalpha`` [H,W] seed the maps -- autograd then carries dL/dz into the means
+    through t.z itself (the term the two-pass composition of oracle/raster_aux.py adds by hand)."""
     leaf = lambda a: torch.as_tensor(np.asarray(a), dtype=dtype).clone().requires_grad_(True)
     m, o, sc, rt, sh = leaf(s["means3D"]), leaf(s["opacities"]), leaf(s["scales"]), leaf(s["rotations"]), leaf(s["shs"])
     out = rasterize(m, o, s["viewmatrix"], s["projmatrix"], s["campos"], s["W"], s["H"], s["tanfovx"], s["tanfovy"], s["bg"],
                     sc, rt, sh, s["sh_degree"], scale_modifier=scale_modifier, dtype=dtype)
-    out["color"].backward(torch.as_tensor(np.asarray(dL_dimage), dtype=dtype))
+    seeds = [(out[k], g) for k, g in (("color", dL_dimage), ("depth", dL_ddepth), ("alpha", dL_dalpha)) if g is not None]
+    torch.autograd.backward([o for o, _ in seeds], [torch.as_tensor(np.asarray(g), dtype=dtype) for _, g in seeds])
     z = lambda t: torch.zeros_like(t) if t.grad is None else t.grad
     g = dict(dL_dmeans3D=z(m).numpy(), dL_dopacity=z(o).numpy().reshape(-1, 1), dL_dscales=z(sc).numpy(), dL_drots=z(rt).numpy(),
              dL_dsh=z(sh).numpy(), dL_dmean2D=(torch.zeros_like(out["ndc"]) if out["ndc"].grad is None else out["ndc"].grad).numpy())
-    out["color"] = out["color"].detach().numpy()
+    for k in ("color", "depth", "alpha"):
+        out[k] = out[k].detach().numpy()
     return out, g

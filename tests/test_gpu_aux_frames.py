@@ -274,3 +274,71 @@ def test_render_frames_batched_maps_equal_get_render_pkgs_fused(long_list):
         img, d, a = got[f]
         assert torch.equal(img, pkg["render"][f]), f
         assert torch.equal(d, pkg["depth"][f]) and torch.equal(a, pkg["alpha"][f]), f
+
+
+# ---- frames in different regimes ---------------------------------------------------------------------------------------------
+# transl z factors of the avatar (W 160 x H 288, N 20 000): 0.5 -> the body fills the frame, lists <= ~140 entries and thousands of
+# pixels saturate (over-saturated); 1.0 -> short lists (< 256); 2.0 -> ~600; 4.0 -> lists past 1024 (several depth segments with
+# D checkpoints, the bucket sort).  Frame 0 is not the longest, so a frame-0 base for the checkpoints, the z values or the dL/dz
+# plane of a later frame reads another frame's data.
+REGIMES = {4: [1.0, 4.0, 0.5, 2.0], 16: [0.5, 2.0, 1.0, 4.0, 4.0, 1.0, 0.5, 2.0, 1.0, 0.5, 4.0, 2.0, 0.5, 4.0, 1.0, 2.0]}
+
+
+@pytest.mark.parametrize("K,with_rot", [(4, True), (16, False)])
+def test_frames_in_different_regimes_equal_single_frame_calls_and_the_oracle(K, with_rot):
+    from sings_amd.skinned import rasterize_skinned_gaussians
+    dev = _dev()
+    N, J, W, H = 20000, 52, 160, 288
+    s, ins, A, transl, one, stacked, dL = _avatar(N, J, W, H, 7, K, True, with_rot)
+    zf = torch.tensor(REGIMES[K], device=dev)
+    transl = transl.clone()
+    transl[:, 2] = transl[:, 2] * zf
+    gD, gA = _map_losses(K, H, W, 23, dev)
+    # the oracle's view of every frame (posed by the single-frame op): the regimes hold, and one long-list frame's seeds avoid its
+    # borderline pixels so that it can be held against the oracle below
+    posed, lists = [], []
+    for f in range(K):
+        with torch.no_grad():
+            out = rasterize_skinned_gaussians(ins["xyz"], ins["rot"], ins["sc"], ins["op"], ins["sh"], ins["w"], A[f], one[f],
+                                              smpl_scale=ins["smpl_scale"], transl=transl[f], return_posed=True)
+        c = s["cam"]
+        vm, pm, cp = (one[f].viewmatrix.cpu().numpy(), one[f].projmatrix.cpu().numpy(), one[f].campos.cpu().numpy())
+        o, oa = _oracle_pair(out[2].cpu().numpy(), s["opacities"], vm, pm, cp, W, H, math.tan(c["fovx"] * 0.5),
+                             math.tan(c["fovy"] * 0.5), s["bg"], out[4].cpu().numpy(), out[3].cpu().numpy(), s["shs"], 0)
+        posed.append((o, oa, vm))
+        lists.append(int((o["ranges"][:, 1].astype(int) - o["ranges"][:, 0]).max()))
+    saturated = [int((p[0]["final_T"] < 1.5e-4).sum()) for p in posed]
+    assert min(lists) < 256 and max(lists) > 1024 and lists[0] < max(lists), lists
+    assert max(saturated) > 1000, saturated
+    fl = int(np.argmax(lists))
+    o, oa, vm = posed[fl]
+    strict = torch.from_numpy(o["margin"] >= 2e-5).to(dev)
+    dL = dL.clone(); dL[fl][:, ~strict] = 0
+    gD[fl, 0][~strict] = 0; gA[fl, 0][~strict] = 0
+
+    (color, radii, depth, alpha), g, dA, dtr, dm2 = _frames_call(ins, A, transl, stacked, with_rot, dL, gD, gA)
+    acc = {}
+    for f in range(K):
+        lv = _leaves(ins, with_rot)
+        A1, tr1 = A[f].clone().requires_grad_(True), transl[f].clone().requires_grad_(True)
+        m1 = torch.zeros(N, 3, device=dev, requires_grad=True)
+        c1, r1, d1, a1 = rasterize_skinned_gaussians(lv["xyz"], lv["rot"], lv["sc"], lv["op"], lv["sh"], ins["w"], A1, one[f],
+                                                     smpl_scale=ins["smpl_scale"], transl=tr1, means2D=m1, return_aux=True)
+        ((c1 * dL[f]).sum() + (d1 * gD[f]).sum() + (a1 * gA[f]).sum()).backward()
+        torch.cuda.synchronize()
+        for name, a, b in (("color", color[f], c1.detach()), ("radii", radii[f], r1), ("depth", depth[f], d1.detach()),
+                           ("alpha", alpha[f], a1.detach()), ("dA", dA[f], A1.grad), ("dtransl", dtr[f], tr1.grad),
+                           ("means2D", dm2[f], m1.grad)):
+            assert torch.equal(a, b), (f, REGIMES[K][f], name)
+        for k, v in lv.items():
+            if v is not None:
+                acc[k] = v.grad.clone() if f == 0 else acc[k] + v.grad
+    for k in acc:
+        assert torch.equal(g[k], acc[k]), k
+    # the long-list frame against the oracle: maps, its screen-space gradient and dL/dtransl (= the sum of the posed-mean
+    # gradients, the dz x view-row term included)
+    np.testing.assert_array_equal(radii[fl].cpu().numpy(), o["radii"])
+    _check_maps(o, oa, depth[fl], alpha[fl])
+    ref = _reference_grads(o, oa, dL[fl].cpu().numpy(), gD[fl, 0].cpu().numpy(), gA[fl, 0].cpu().numpy(), vm)
+    _grad_close("viewspace", dm2[fl].cpu().numpy(), ref["means2D"])
+    _grad_close("transl", dtr[fl].cpu().numpy(), ref["means3D"].sum(0), rtol=2e-3, atol=2e-4)

@@ -1,6 +1,6 @@
 """GPU parity of the depth and alpha maps (rasterize_gaussians_aux, rasterize_skinned_gaussians(return_aux=True)).
 
-The reference is a composition of the existing raster oracle, two passes over the same Gaussians:
+The reference is oracle/raster_aux.py: a composition of the existing raster oracle, two passes over the same Gaussians:
  * the colour pass with the scene's colours and background;
  * the aux pass with colors_precomp = (z, 1, 0) and background 0, whose channels 0 and 1 are depth and alpha.
 Reference gradients: the colour pass's backward + the aux pass's backward seeded with (dL/ddepth, dL/dalpha, 0) + the aux pass's
@@ -15,7 +15,7 @@ import pytest
 import torch
 
 from oracle import lbs_oracle as lo
-from oracle import raster_oracle as ro
+from oracle.raster_aux import oracle_pair as _oracle_pair, reference_grads as _reference_grads
 from sings_amd.camera import make_camera
 from sings_amd.scene import synthetic_scene
 
@@ -39,37 +39,6 @@ def _settings(s, dev):
         image_height=s["H"], image_width=s["W"], tanfovx=s["tanfovx"], tanfovy=s["tanfovy"], bg=t(s["bg"]),
         scale_modifier=1.0, viewmatrix=t(s["viewmatrix"]), projmatrix=t(s["projmatrix"]), sh_degree=s["sh_degree"],
         campos=t(s["campos"]), prefiltered=False, debug=False)
-
-
-def _view_row(view):
-    """d z / d mean: z = view[2] x + view[6] y + view[10] z + view[14] (column-major 4x4, as the preprocess reads it)."""
-    v = np.asarray(view, np.float64).reshape(-1)
-    return v[[2, 6, 10]]
-
-
-def _oracle_pair(means3D, opac, view, proj, campos, W, H, tx, ty, bg, scales, rots, shs, deg):
-    """(colour pass, aux pass) of the raster oracle."""
-    o = ro.forward(means3D, opac, view, proj, campos, W, H, tx, ty, bg, scales=scales, rotations=rots, shs=shs, sh_degree=deg)
-    P = means3D.shape[0]
-    zc = np.stack([o["depths"].astype(np.float32), np.ones(P, np.float32), np.zeros(P, np.float32)], 1)
-    oa = ro.forward(means3D, opac, view, proj, campos, W, H, tx, ty, np.zeros(3, np.float32), scales=scales, rotations=rots,
-                    colors_precomp=np.ascontiguousarray(zc), sh_degree=deg)
-    return o, oa
-
-
-def _reference_grads(o, oa, dLc, gD, gA, view):
-    """Per input: colour pass + aux pass + dL/dz through the view row."""
-    gc = ro.backward(o, dLc)
-    ga = ro.backward(oa, np.stack([gD, gA, np.zeros_like(gD)]).astype(np.float32))
-    dz = ga["dL_dcolor"][:, 0].astype(np.float64)
-    return {
-        "means3D": gc["dL_dmeans3D"] + ga["dL_dmeans3D"] + dz[:, None] * _view_row(view)[None, :],
-        "means2D": gc["dL_dmean2D"] + ga["dL_dmean2D"],
-        "opacities": gc["dL_dopacity"] + ga["dL_dopacity"],
-        "scales": gc["dL_dscales"] + ga["dL_dscales"],
-        "rotations": gc["dL_drots"] + ga["dL_drots"],
-        "shs": gc["dL_dsh"],
-    }
 
 
 def _grad_close(name, a, b, rtol=1e-3, atol=6e-6):
