@@ -2,7 +2,7 @@
 """Headline benchmark: rendered views/s, forward+backward, 200k Gaussians @ 1080p (BASELINE.json
 configs[2]; SURVEY.md 8(d) scene S(200000,1920,1080,3,seed=3)), 1..8 MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process starts N fresh rank processes (one per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set; it has not touched the GPU itself), waits, relays rank 0's JSON line and
@@ -18,13 +18,15 @@ Gaussians (default 8: ONE dispatch per kernel for the 8 cameras -- the *_frames 
 `--streams` HIP streams (default 2) and their gradient rows are folded in one pass once they have joined
 (sings_amd.dp.GradientPipeline).  `--views-per-step 8 --frames-per-launch 1 --streams 3` is the round-3 schedule (one engine per
 view).
-`--views-per-step 1 --streams 1` is the reference's one frame per step (gs_trainer.py:207-215); the default run times
+`--views-per-step 1 --streams 1` is the reference's one frame per step (gs_trainer.py:207-215); a `--full` run times
 that too, after the batched region, and reports it as `train_step_ms_one_view`.  With N > 1 every (rank, view) pair
 renders a DIFFERENT camera of the same Gaussians (frame-parallel) and the ranks sum the canonical-Gaussian gradients of
 the batch with ONE RCCL all-reduce per step (in chunks, each behind its part of the fold), i.e. the 47 MB all-reduce is paid
 once per step of 16 views ("scaling": "weak": the batch per rank is fixed).
 
-Prints ONE JSON line (rank 0).  Besides the driver's contract it carries
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the --steps steps, writes --dump-outputs and prints the line:
+`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the configuration it measured, nothing more.  With `--full`,
+after that timed region and in the same process, it also measures and checks everything else and the line carries
   roofline      - SURVEY.md 8(d): bound "hbm", the WHOLE pass of a view -- algorithmic bytes per view / seconds per view against
                   the float4-copy bandwidth MEASURED in this run (sg_copy_probe over 1 GiB, best of 3; `peak_spec` 8 TB/s rides
                   along), `traffic` = PMC bytes per view; the dominant kernel's own figure (its algorithmic bytes / its live
@@ -36,6 +38,8 @@ Prints ONE JSON line (rank 0).  Besides the driver's contract it carries
   cpu_baseline  - PyTorch-CPU "LBS + project" (oracle/lbs_project_torch.py) on all host cores, median of 10 at
                   N = 6 890 / 50 k / 200 k; the scalar C raster oracle (1 core, full views) rides along as an extra key
   allreduce_*   - stand-alone collective time, the part of it the step cannot hide, bytes, per-link bound
+  kernel_ms, train_step_ms_one_view, scaling_model, dp_parity / ranks_agree (N > 1), and, on one GPU at the default
+  configuration, `secondary`: the other BASELINE configurations (cfg2, cfg4, cfg5, both training steps, the drop-in surface)
 """
 import argparse
 import ctypes as C
@@ -84,9 +88,14 @@ def parse_args():
     ap.add_argument("--sh-degree", type=int, default=3)
     ap.add_argument("--scene-seed", type=int, default=3,
                     help="seed of the synthetic scene S(N,W,H,deg,seed) (SURVEY.md 8(d): cfg2 = 2, cfg3 = 3, cfg5 = 5; what tests/test_gpu_raster.py checks)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed region, also measure and check everything else: the one-view-per-step legs, "
+                         "per-kernel times, rooflines, the collective probe, the CPU baseline and parity views, the N > 1 "
+                         "self-checks and (default single-GPU configuration) the `secondary` block.  Off: the line carries the "
+                         "headline figure and its configuration only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="default single-GPU run only: skip the `secondary` block (the other BASELINE configurations, each a timed "
+                    help="--full default single-GPU run only: skip the `secondary` block (the other BASELINE configurations, each a timed "
                          "region of >= 0.3 s in this same process: cfg2 forward, cfg4 avatar, cfg5 + regularisers, the full training "
                          "step at K = 1 and K = 16, the drop-in autograd surface)")
     ap.add_argument("--light", action="store_true",
@@ -169,10 +178,12 @@ def main():
         ctx[3].destroy_process_group()
     if out is not None:
         _log("done")
+        out["full"] = bool(a.full)
         out["wall_s"] = time.perf_counter() - t_wall
         _emit(out)
         # a multi-GPU run is short and decisive or it is an error: one rank per device over RCCL (dist_setup refuses anything else on a
-        # box with enough GPUs), the reduced bytes equal on all ranks and equal to the re-rendered sum, the whole run inside MULTI_GPU_WALL_S
+        # box with enough GPUs), with --full the reduced bytes equal on all ranks and equal to the re-rendered sum, the whole run inside
+        # MULTI_GPU_WALL_S
         if ctx[1] > 1 and not ctx[4].get("ranks_per_device", 1) > 1:
             if ctx[4].get("rccl_world") != ctx[1] or out.get("ranks_agree") is False or out["wall_s"] > MULTI_GPU_WALL_S:
                 raise SystemExit(f"bench.py: the {ctx[1]}-GPU run is not decisive: rccl_world={ctx[4].get('rccl_world')}, "
@@ -183,8 +194,8 @@ MULTI_GPU_WALL_S = 120               # --gpus N > 1: the whole run (all ranks up
 
 
 def wants_secondary(a, ctx):
-    """The default single-GPU headline run (what the driver launches) also measures every other BASELINE configuration."""
-    return (ctx[1] == 1 and not a.no_secondary and not a.no_cpu_baseline and not a.light and a.workload == "raster" and not a.forward_only
+    """A --full single-GPU run at the headline configuration also measures every other BASELINE configuration."""
+    return (a.full and ctx[1] == 1 and not a.no_secondary and not a.no_cpu_baseline and not a.light and a.workload == "raster" and not a.forward_only
             and not a.graph and (a.gaussians, a.width, a.height, a.sh_degree) == (200000, 1920, 1080, 3) and not a.regularisers)
 
 

@@ -172,7 +172,7 @@ def leg_avatar(a, ctx):
         dumped = dump_outputs(a.dump_outputs, {"color": torch.cat([e.color.view(-1, 3, H, W) for e in engs]),
                                                "radii": torch.cat([e.radii.view(-1, N) for e in engs]),
                                                "grad_flat": batch.acc[:active]})
-    comm = allreduce_probe(fp, batch.acc[:active])
+    comm = allreduce_probe(fp, batch.acc[:active]) if a.full else None
     assert all((0 <= min(e.num_rendered()) and max(e.num_rendered()) <= e.cap) if Kf > 1 else 0 <= e.num_rendered() <= e.cap for e in engs), \
         "pair capacity / long-rows hint violated"
     grad_hash = None
@@ -180,6 +180,11 @@ def leg_avatar(a, ctx):
         step(0)
         torch.cuda.synchronize()
         grad_hash = _grad_sha256(batch.acc)
+    if not a.full:
+        return _avatar_line(a, world, N, J, W, H, F, Rmax, tile_mean, tile_max, k_views, Kf, n_batches, n_streams, pipelined, els,
+                            dinfo, grad_hash, dumped) if rank == 0 else None
+
+    # --full from here on: the other measurements and checks of this configuration, after the headline's timed region
     # the reference's unit of work: ONE frame per optimisation step on the current stream (gs_trainer.py:207-215)
     def step_one_frame(i):
         one_view(0, shard.frame(i), eng, loss1)
@@ -208,22 +213,10 @@ def leg_avatar(a, ctx):
         dp_check.update(algo_info)
         dp_check.update(densification_stats_check(ctx, fp, engs))
     if rank == 0:
-        out = {"metric": "train-step views/sec (LBS-fused fwd + L1/SSIM loss + bwd), avatar ~150k Gaussians x 120 AMASS frames",
-               "value": world * a.steps * k_views / el, "unit": "views/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-               "ms_per_step": el / a.steps * 1e3, "ms_per_view": el / a.steps * 1e3 / k_views,
-               "train_step_ms_one_view": el_one / n_one * 1e3, "timed_region_s": sum(els), "repeats": len(els),
-               "timed_steps": a.steps * len(els), "ms_per_step_min": min(els) / a.steps * 1e3, "ms_per_step_max": max(els) / a.steps * 1e3, "higher_is_better": True,
-               "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-               "config": {"workload": f"avatar_scene(N={N}, J={J}) {W}x{H} fx=fy=5000, {F} AMASS frames, SH deg 0, fused LBS+raster "
-                                      f"fwd + L1/SSIM loss + bwd, R<={Rmax}, frame-parallel dp{world}", "gaussians": N, "joints": J,
-                          "width": W, "height": H, "max_num_rendered": Rmax, "tile_list_mean": tile_mean, "tile_list_max": tile_max,
-                          "views_per_step": k_views, "frames_per_launch": Kf, "launch_batches_per_step": n_batches,
-                          "streams": 2 if pipelined else n_streams,
-                          "schedule": "pipeline: composite kernels on one stream, binning / loss / per-Gaussian backward of the "
-                                      "other batches beside them on a high-priority stream" if pipelined else
-                                      "every batch runs its whole chain on one of the streams",
-                          "parallelism": f"dp{world}"},
-               "kernel_ms": kern}
+        out = _avatar_line(a, world, N, J, W, H, F, Rmax, tile_mean, tile_max, k_views, Kf, n_batches, n_streams, pipelined, els,
+                           dinfo, grad_hash, dumped)
+        out["train_step_ms_one_view"] = el_one / n_one * 1e3
+        out["kernel_ms"] = kern
         per, total_bytes = algorithmic_bytes_skinned(N, H, W, Rmax, 0, J)
         fps = out["value"] / world
         copy_gbs = a.copy_gbs if getattr(a, "copy_gbs", None) else measure_copy_peak(dev)
@@ -233,7 +226,6 @@ def leg_avatar(a, ctx):
         out["roofline"]["note"] = ("raster + fused LBS bytes at the largest R of the sequence; the L1 + SSIM loss inside the timed "
                                    "step (HW 40 B algorithmic) is not counted")
         out["hbm_copy_GBs_measured"] = copy_gbs
-        out.update(dinfo)
         out.update({k: None for k in COMM_KEYS})
         if comm is not None:
             out.update(comm)
@@ -242,10 +234,6 @@ def leg_avatar(a, ctx):
         out["gradient_floats_per_gaussian"] = {"buffer": per_view // N, "carrying_gradient": active // N,
                                                "note": "SH gradients coefficient-major (SG_FLAG_SH_PLANAR): only the (sh_degree+1)^2 "
                                                        "planes in use are written, folded and all-reduced"}
-        if grad_hash is not None:
-            out["grad_sha256"] = grad_hash
-        if dumped is not None:
-            out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
         if world == 1 and not a.no_cpu_baseline:
             _log("avatar: parity of one full-size frame against the composed oracle" + ("" if a.light else " + CPU baseline"))
             out["parity"] = avatar_parity(s, eng, rs, A_all[shard.frame(0)], (xyz, w, sc, op, sh, smpl_scale, transl), t)
@@ -254,6 +242,33 @@ def leg_avatar(a, ctx):
         if dp_check is not None:
             out.update(dp_check)
     return out if rank == 0 else None
+
+
+def _avatar_line(a, world, N, J, W, H, F, Rmax, tile_mean, tile_max, k_views, Kf, n_batches, n_streams, pipelined, els, dinfo, grad_hash,
+                 dumped):
+    """The line of a plain run: what the timed region measured and how it was set up."""
+    el = _median(els)
+    out = {"metric": "train-step views/sec (LBS-fused fwd + L1/SSIM loss + bwd), avatar ~150k Gaussians x 120 AMASS frames",
+           "value": world * a.steps * k_views / el, "unit": "views/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+           "ms_per_step": el / a.steps * 1e3, "ms_per_view": el / a.steps * 1e3 / k_views,
+           "timed_region_s": sum(els), "repeats": len(els),
+           "timed_steps": a.steps * len(els), "ms_per_step_min": min(els) / a.steps * 1e3, "ms_per_step_max": max(els) / a.steps * 1e3, "higher_is_better": True,
+           "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": f"avatar_scene(N={N}, J={J}) {W}x{H} fx=fy=5000, {F} AMASS frames, SH deg 0, fused LBS+raster "
+                                  f"fwd + L1/SSIM loss + bwd, R<={Rmax}, frame-parallel dp{world}", "gaussians": N, "joints": J,
+                      "width": W, "height": H, "max_num_rendered": Rmax, "tile_list_mean": tile_mean, "tile_list_max": tile_max,
+                      "views_per_step": k_views, "frames_per_launch": Kf, "launch_batches_per_step": n_batches,
+                      "streams": 2 if pipelined else n_streams,
+                      "schedule": "pipeline: composite kernels on one stream, binning / loss / per-Gaussian backward of the "
+                                  "other batches beside them on a high-priority stream" if pipelined else
+                                  "every batch runs its whole chain on one of the streams",
+                      "parallelism": f"dp{world}"}}
+    out.update(dinfo)
+    if grad_hash is not None:
+        out["grad_sha256"] = grad_hash
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
+    return out
 
 
 def avatar_parity(s, eng, rs, A, ins, t):

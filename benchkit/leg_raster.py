@@ -101,9 +101,11 @@ def leg_raster(a, ctx):
         engs.append(e)
     if Kf == 1:
         eng = engs[0]
-    else:                                                        # the one-view-per-step leg and the parity views: a plain engine
+    elif a.full:                                                 # the one-view-per-step leg and the parity views: a plain engine
         eng = RasterEngine(N, W, H, shs.shape[1], dev, capacity_pairs=int(R * 1.1) + 4096)
         eng.set_camera(camera(rank * k_views)[3], short_lists=short, long_rows=short)
+    else:                                                        # (a plain run renders no view outside the batch)
+        eng = None
     dL_k = dL if Kf == 1 else dL[None].expand(Kf, -1, -1, -1).contiguous()
     batch = ViewBatch(engs, grads, n_streams, frame_parallel=fp, chunks=a.reduce_chunks)
 
@@ -186,6 +188,39 @@ def leg_raster(a, ctx):
         torch.cuda.synchronize()
         grad_hash = _grad_sha256(eng.grad_flat if graph is not None else batch.acc)
 
+    def headline():
+        """The line of a plain run: what the timed region measured and how it was set up."""
+        out = {
+            "metric": "rendered views/sec fwd+bwd, 200k Gaussians @1080p" if not a.forward_only and (N, W, H) == (200000, 1920, 1080)
+                      else f"rendered views/sec {'forward only' if a.forward_only else 'fwd+bwd'}, {N} Gaussians @{W}x{H}",
+            "value": views_s, "unit": "views/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": ms_per_step, "ms_per_view": ms_per_step / k_views,
+            "timed_region_s": sum(els), "repeats": len(els), "timed_steps": a.steps * len(els), "ms_per_step_min": min(els) / a.steps * 1e3,
+            "ms_per_step_max": max(els) / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"S({N},{W},{H},deg={deg},seed={seed}): {N} Gaussians, {W}x{H}, SH deg {deg}, "
+                                   f"{'forward only' if a.forward_only else 'fwd+bwd'}, "
+                                   f"R={R} (tile,Gaussian) pairs, every view of a step within 0.1 % of that (cameras a few cm apart), "
+                                   f"frame-parallel dp{world}",
+                       "gaussians": N, "width": W, "height": H, "sh_degree": deg, "num_rendered": R, "tile_list_mean": tile_mean,
+                       "tile_list_max": tile_max, "views_per_step": k_views, "frames_per_launch": Kf, "launch_batches_per_step": n_batches,
+                       "streams": n_streams, "regularisers": bool(a.regularisers),
+                       "forward_only": bool(a.forward_only), "hip_graph": bool(a.graph),
+                       "reduction": "one_shot" if a.one_shot_reduce or graph is not None else
+                                    f"fold of {rows} gradient row(s) for {k_views} views + collective in {len(batch.pipe.bounds)} chunk(s)",
+                       "gradient_rows": rows,
+                       "parallelism": f"dp{world}"},
+        }
+        out.update(dinfo)
+        if grad_hash is not None:
+            out["grad_sha256"] = grad_hash
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
+        return out
+    if not a.full:
+        return headline() if rank == 0 else None
+
+    # --full from here on: the other measurements and checks of this configuration, after the headline's timed region
     # the reference's unit of work, one frame per optimisation step (gs_trainer.py:207-215): view 0 alone on the current
     # stream, (+ the all-reduce of its gradients with several ranks), same number of views as the batched region
     def step_one_view(_i=0):
@@ -267,31 +302,13 @@ def leg_raster(a, ctx):
     copy_gbs = a.copy_gbs if getattr(a, "copy_gbs", None) else measure_copy_peak(dev)
     roofline, roofline_valu = build_roofline(kern, per, {"workload": "raster", "gaussians": N, "width": W, "height": H, "sh_degree": deg},
                                              total_bytes, world / views_s, copy_gbs, frames=Kf)
-    out = {
-        "metric": "rendered views/sec fwd+bwd, 200k Gaussians @1080p" if not a.forward_only and (N, W, H) == (200000, 1920, 1080)
-                  else f"rendered views/sec {'forward only' if a.forward_only else 'fwd+bwd'}, {N} Gaussians @{W}x{H}",
-        "value": views_s, "unit": "views/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": ms_per_step, "ms_per_view": ms_per_step / k_views,
+    out = headline()
+    out.update({
         "train_step_ms_one_view": (el_loss if el_loss is not None else el_one) / n_one * 1e3,
         "train_step_ms_one_view_note": "one view per step: forward + clamp / 0.8 L1 + 0.2 SSIM loss against a random target + backward "
                                        "(+ the all-reduce with several ranks): SURVEY.md 8(d) Timing" if el_loss is not None else
                                        "forward only (no loss, no backward)",
         "raster_fwd_bwd_ms_one_view": el_one / n_one * 1e3, "views_per_s_one_view_per_step": world * n_one / el_one,
-        "timed_region_s": sum(els), "repeats": len(els), "timed_steps": a.steps * len(els), "ms_per_step_min": min(els) / a.steps * 1e3,
-        "ms_per_step_max": max(els) / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"S({N},{W},{H},deg={deg},seed={seed}): {N} Gaussians, {W}x{H}, SH deg {deg}, "
-                               f"{'forward only' if a.forward_only else 'fwd+bwd'}, "
-                               f"R={R} (tile,Gaussian) pairs, every view of a step within 0.1 % of that (cameras a few cm apart), "
-                               f"frame-parallel dp{world}",
-                   "gaussians": N, "width": W, "height": H, "sh_degree": deg, "num_rendered": R, "tile_list_mean": tile_mean,
-                   "tile_list_max": tile_max, "views_per_step": k_views, "frames_per_launch": Kf, "launch_batches_per_step": n_batches,
-                   "streams": n_streams, "regularisers": bool(a.regularisers),
-                   "forward_only": bool(a.forward_only), "hip_graph": bool(a.graph),
-                   "reduction": "one_shot" if a.one_shot_reduce or graph is not None else
-                                f"fold of {rows} gradient row(s) for {k_views} views + collective in {len(batch.pipe.bounds)} chunk(s)",
-                   "gradient_rows": rows,
-                   "parallelism": f"dp{world}"},
         "roofline": roofline, "roofline_valu": roofline_valu,
         "roofline_one_view_per_step": {"achieved": total_bytes / (el_one / n_one) / 1e9, "unit": "GB/s",
                                        "frac": total_bytes / (el_one / n_one) / 1e9 / copy_gbs,
@@ -299,17 +316,12 @@ def leg_raster(a, ctx):
                                        "note": "the same whole-pass figure at the reference's one frame per step"},
         "hbm_copy_GBs_measured": copy_gbs,
         "kernel_ms": kern,
-    }
-    out.update(dinfo)
+    })
     out.update({k: None for k in COMM_KEYS})
     if comm is not None:
         out.update(comm)
     out["scaling_model"] = scaling_model(batch.acc.numel() * 4, ms_per_step, el_one / n_one * 1e3,
                                          comm.get("allreduce_exposed_ms") if comm else None)
-    if grad_hash is not None:
-        out["grad_sha256"] = grad_hash
-    if dumped is not None:
-        out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
     if dp_check is not None:
         out.update(dp_check)
     if one_by_algo is not None:

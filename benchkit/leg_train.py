@@ -170,7 +170,7 @@ def leg_train(a, ctx):
         arrays.update({"grad_" + n.replace(".", "_"): p.grad for n, p in step_mod.named_parameters()
                        if p.requires_grad and p.grad is not None})
         dumped = dump_outputs(a.dump_outputs, arrays)
-    comm = allreduce_probe(fp, flat) if fp is not None else None
+    comm = allreduce_probe(fp, flat) if fp is not None and a.full else None
     inplace = (sum(p.grad.numel() * 4 for p, v in zip(params, grad_views) if p.grad is not None and p.grad.data_ptr() == v.data_ptr())
                if fp is not None else None)
     R_last = _rz.check_deferred_overflow(dev)                    # raises if a timed step overflowed the pair capacity
@@ -190,7 +190,8 @@ def leg_train(a, ctx):
                        "parallelism": f"dp{world}"},
             "losses": {k: float(v.detach()) for k, v in ld.items()}})
         out.update(dinfo)
-        out.update({k: None for k in COMM_KEYS})
+        if a.full:
+            out.update({k: None for k in COMM_KEYS})
         if comm is not None:
             out.update(comm)
         if fp is not None:
@@ -201,6 +202,8 @@ def leg_train(a, ctx):
                                 "(config.py:27, gs_trainer.py:209-254); at K > 1 ONE optimiser step consumes a chunk of K frames -- "
                                 "K times fewer parameter updates per frame, a different optimisation trajectory, quoted per frame "
                                 "for throughput only")
+    if rank == 0 and a.full:
+        # --full: the step's roofline against the copy rate of this run, and its parity with the oracle chain
         copy_gbs = a.copy_gbs if getattr(a, "copy_gbs", None) else measure_copy_peak(dev)
         out["hbm_copy_GBs_measured"] = copy_gbs
         out["roofline"] = train_step_roofline(N, Kt, (tri, geo, app), W, H, int(R_last), J, el / a.steps * 1e3, copy_gbs)

@@ -164,6 +164,19 @@ def test_headline_default_is_exactly_steps_timed_steps(monkeypatch):
     assert a.min_timed_s == 0.5 and a.dump_outputs == "d"
 
 
+def test_full_is_off_by_default_and_the_secondary_legs_need_it(monkeypatch):
+    """A plain run measures the headline alone; the other BASELINE configurations ride only on a --full run."""
+    ctx = (0, 1, None, None, {})
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse_args()
+    assert a.full is False and not bench.wants_secondary(a, ctx)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    a = bench.parse_args()
+    assert a.full is True and bench.wants_secondary(a, ctx)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-secondary"])
+    assert not bench.wants_secondary(bench.parse_args(), ctx)
+
+
 def test_dump_outputs_fits_the_budget_and_samples_the_same_values_every_time(tmp_path):
     import numpy as np
     import torch

@@ -27,7 +27,7 @@ def _line(p):
 
 @pytest.mark.gpu
 def test_single_gpu_line_carries_the_contract():
-    j = _line(_bench("--gpus", "1", *SMALL))
+    j = _line(_bench("--gpus", "1", "--full", *SMALL))
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "roofline_valu", "cpu_baseline", "parity",
                 "train_step_ms_one_view"):
@@ -53,10 +53,29 @@ def test_single_gpu_line_carries_the_contract():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("workload", ["raster", "avatar", "train"])
+def test_plain_line_is_the_headline_alone(workload):
+    """Without --full a run sets up, warms up, times its --steps steps and prints the headline: the driver's keys and the
+    configuration, none of the measurements and checks that --full adds after the timed region."""
+    size = SMALL if workload == "raster" else ["--gaussians", "20000", "--steps", "3", "--warmup", "1"]
+    j = _line(_bench("--gpus", "1", "--workload", workload, *size))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "ms_per_view", "n_gpus", "steps", "warmup",
+                "timed_steps", "config"):
+        assert key in j, key
+    assert j["full"] is False and j["value"] > 0 and j["unit"] == "views/s" and j["dtype"] == "f32" and j["higher_is_better"] is True
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["repeats"] == 1 and j["timed_steps"] == 3
+    views = j["config"]["frames_per_step" if workload == "train" else "views_per_step"]
+    assert abs(j["value"] - 1e3 * views / j["ms_per_step"]) <= 1e-9 * j["value"]
+    for key in ("secondary", "roofline", "roofline_valu", "kernel_ms", "cpu_baseline", "parity", "train_step_ms_one_view",
+                "hbm_copy_GBs_measured", "scaling_model", "allreduce_ms"):
+        assert key not in j, key
+
+
+@pytest.mark.gpu
 def test_timed_region_is_repeated_and_the_schema_is_one():
     """--steps 3 of a small scene is a few milliseconds: with --min-timed-s 0.5 the region is repeated (whole regions of 3 steps)
     until it adds up to 0.5 s, the line reports the median; the collective keys exist (null) without a collective."""
-    j = _line(_bench("--gpus", "1", "--no-cpu-baseline", "--min-timed-s", "0.5", *SMALL))
+    j = _line(_bench("--gpus", "1", "--full", "--no-cpu-baseline", "--min-timed-s", "0.5", *SMALL))
     assert j["repeats"] >= 2 and j["timed_region_s"] >= 0.5 and j["steps"] == 3 and j["timed_steps"] == 3 * j["repeats"]
     assert j["ms_per_step_min"] <= j["ms_per_step"] <= j["ms_per_step_max"]
     for k in ("allreduce_ms", "allreduce_bytes", "allreduce_algorithm", "allreduce_per_link_bound_ms", "allreduce_exposed_ms"):
@@ -98,8 +117,8 @@ def test_rccl_branches_run_with_one_rank(algo):
     reduce-scatter + all-gather on device views, GradientPipeline's chunked fold + collective with RCCL work handles and the
     device-side MAX of the timed region all EXECUTE, on a one-rank communicator -- and leave the gradients bit-identical to
     the run without a process group (a one-rank sum is the identity; the backward is bitwise reproducible)."""
-    ref = _line(_bench("--gpus", "1", "--no-cpu-baseline", "--grad-hash", *SMALL))
-    j = _line(_bench("--gpus", "1", "--no-cpu-baseline", "--grad-hash", *SMALL,
+    ref = _line(_bench("--gpus", "1", "--full", "--no-cpu-baseline", "--grad-hash", *SMALL))
+    j = _line(_bench("--gpus", "1", "--full", "--no-cpu-baseline", "--grad-hash", *SMALL,
                      env={"SINGS_BENCH_FORCE_DIST": "1", "SINGS_DP_ALGO": algo}))
     assert j["dist_backend"] == "nccl" and j["rccl_world"] == 1 and j["dist_world"] == 1
     assert j["allreduce_algorithm"] == algo and j["allreduce_ms"] > 0 and j["allreduce_exposed_ms"] > 0
@@ -114,7 +133,7 @@ def test_rccl_branches_run_with_one_rank_avatar_and_train():
     """The same for the other two workloads: the avatar step (fused LBS path, 3 + 3 + 1 + 3 * 16 floats per Gaussian all-reduced) and the
     complete training step (parameter gradients written straight into ONE flat buffer -- sings_amd.decode.set_gradient_arena --
     and all-reduced in place)."""
-    small = ["--gaussians", "20000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--min-timed-s", "0.5"]
+    small = ["--gaussians", "20000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--min-timed-s", "0.5"]
     env = {"SINGS_BENCH_FORCE_DIST": "1"}
     ref = _line(_bench("--workload", "avatar", "--grad-hash", *small))
     j = _line(_bench("--workload", "avatar", "--grad-hash", *small, env=env))
@@ -142,7 +161,7 @@ def test_gpus_2_starts_two_ranks_and_the_collective_layer_sees_them():
     both ranks share the device and the collectives are host-staged gloo (RCCL refuses two ranks on one device); on a
     box with >= 2 GPUs the same command runs over RCCL and `rccl_world` is 2."""
     import torch
-    j = _line(_bench("--gpus", "2", "--no-cpu-baseline", *SMALL))
+    j = _line(_bench("--gpus", "2", "--full", "--no-cpu-baseline", *SMALL))
     assert j["n_gpus"] == 2 and j["dist_world"] == 2
     assert j["config"]["parallelism"] == "dp2"
     if torch.cuda.device_count() >= 2:
@@ -174,7 +193,7 @@ def test_gpus_2_starts_two_ranks_and_the_collective_layer_sees_them():
 def test_gpus_2_avatar_reduces_the_densification_statistics_and_the_ranks_agree():
     """The avatar workload at world 2: gradient sum checked as above, and the densification statistics (sum of |viewspace gradient|,
     visibility count, max radius: sings_hybrid.py:1013-1015, gs_trainer.py:486-492) reduced and equal on both ranks."""
-    j = _line(_bench("--gpus", "2", "--workload", "avatar", "--gaussians", "20000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    j = _line(_bench("--gpus", "2", "--full", "--workload", "avatar", "--gaussians", "20000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
                      "--views-per-step", "8", "--frames-per-launch", "4"))
     assert j["n_gpus"] == 2 and j["dist_world"] == 2 and j["ranks_agree"] is True
     assert j["dp_parity"]["ok"] and j["dp_parity"]["views"] == 16
@@ -185,10 +204,10 @@ def test_gpus_2_avatar_reduces_the_densification_statistics_and_the_ranks_agree(
 
 @pytest.mark.gpu
 def test_default_line_carries_every_baseline_configuration():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` (the driver's command): cfg3 stays `value`; `secondary` holds the other
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full`: cfg3 stays `value`; `secondary` holds the other
     BASELINE configurations, each from a timed region of >= 0.3 s in the same process, with its own roofline against the copy rate
     of the run and a parity block from a full-size oracle view."""
-    j = _line(_bench("--gpus", "1", "--steps", "20", "--warmup", "5", timeout=1500))
+    j = _line(_bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--full", timeout=1500))
     assert j["config"]["gaussians"] == 200000 and j["parity"]["ok"] and j["parity"]["views"] == 3
     assert j["train_step_ms_one_view"] > j["raster_fwd_bwd_ms_one_view"] > 0            # (the loss is inside the one-view train step)
     sec = j["secondary"]

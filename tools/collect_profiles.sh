@@ -19,21 +19,21 @@ cd /tmp && export TMPDIR=/tmp
 K1="--views-per-step 1 --streams 1"
 K8="--views-per-step 8 --frames-per-launch 8 --streams 1"       # 8 frames / cameras per dispatch, one stream: a kernel's duration is its own
 TO="timeout 300"
-$TO python3 $ROOT/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-$TO python3 $ROOT/bench.py --steps 100 --warmup 10 $K1 --no-cpu-baseline > $OUT/bench_cfg3_k1.json 2> $OUT/bench_cfg3_k1.err
-$TO python3 $ROOT/bench.py --workload avatar --steps 100 --warmup 10 > $OUT/bench_avatar.json 2> $OUT/bench_avatar.err
-$TO python3 $ROOT/bench.py --workload avatar --steps 100 --warmup 10 $K1 --no-cpu-baseline > $OUT/bench_avatar_k1.json 2> $OUT/bench_avatar_k1.err
-$TO python3 $ROOT/bench.py --workload train --steps 30 --warmup 5 > $OUT/bench_train.json 2> $OUT/bench_train.err
-$TO python3 $ROOT/bench.py --workload train --views-per-step 16 --steps 30 --warmup 5 --no-cpu-baseline > $OUT/bench_train_k16.json 2> $OUT/bench_train_k16.err
-$TO python3 $ROOT/bench.py --gaussians 50000 --width 512 --height 512 --sh-degree 0 --forward-only --steps 200 --no-cpu-baseline > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
-$TO python3 $ROOT/bench.py --gaussians 500000 --width 2048 --height 2048 --regularisers --steps 40 --no-cpu-baseline > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
-SINGS_BENCH_FORCE_DIST=1 $TO python3 $ROOT/bench.py --steps 100 --warmup 10 --no-cpu-baseline > $OUT/bench_rccl_world1.json 2> $OUT/bench_rccl_world1.err
-SINGS_BENCH_FORCE_DIST=1 SINGS_DP_ALGO=rs_ag $TO python3 $ROOT/bench.py --steps 100 --warmup 10 --no-cpu-baseline > $OUT/bench_rccl_world1_rs_ag.json 2> $OUT/bench_rccl_world1_rs_ag.err
+$TO python3 $ROOT/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+$TO python3 $ROOT/bench.py --full --steps 100 --warmup 10 $K1 --no-cpu-baseline > $OUT/bench_cfg3_k1.json 2> $OUT/bench_cfg3_k1.err
+$TO python3 $ROOT/bench.py --full --workload avatar --steps 100 --warmup 10 > $OUT/bench_avatar.json 2> $OUT/bench_avatar.err
+$TO python3 $ROOT/bench.py --full --workload avatar --steps 100 --warmup 10 $K1 --no-cpu-baseline > $OUT/bench_avatar_k1.json 2> $OUT/bench_avatar_k1.err
+$TO python3 $ROOT/bench.py --full --workload train --steps 30 --warmup 5 > $OUT/bench_train.json 2> $OUT/bench_train.err
+$TO python3 $ROOT/bench.py --full --workload train --views-per-step 16 --steps 30 --warmup 5 --no-cpu-baseline > $OUT/bench_train_k16.json 2> $OUT/bench_train_k16.err
+$TO python3 $ROOT/bench.py --full --gaussians 50000 --width 512 --height 512 --sh-degree 0 --forward-only --steps 200 --no-cpu-baseline > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
+$TO python3 $ROOT/bench.py --full --gaussians 500000 --width 2048 --height 2048 --regularisers --steps 40 --no-cpu-baseline > $OUT/bench_cfg5.json 2> $OUT/bench_cfg5.err
+SINGS_BENCH_FORCE_DIST=1 $TO python3 $ROOT/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline > $OUT/bench_rccl_world1.json 2> $OUT/bench_rccl_world1.err
+SINGS_BENCH_FORCE_DIST=1 SINGS_DP_ALGO=rs_ag $TO python3 $ROOT/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline > $OUT/bench_rccl_world1_rs_ag.json 2> $OUT/bench_rccl_world1_rs_ag.err
 $TO python3 $ROOT/tools/wrapper_time.py > $OUT/wrapper_time.log 2>&1
 # kernel traces (durations + gaps)
 for w in cfg3 avatar; do
   extra=""; [ $w = avatar ] && extra="--workload avatar"
-  $TO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$w -o $w -- python3 $ROOT/bench.py --steps 40 --warmup 5 $K1 --no-cpu-baseline $extra > $OUT/$w.log 2>&1
+  $TO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$w -o $w -- python3 $ROOT/bench.py --full --steps 40 --warmup 5 $K1 --no-cpu-baseline $extra > $OUT/$w.log 2>&1
   f=$(find $OUT/$w -name "*kernel_trace.csv" | head -1)
   python3 $ROOT/tools/timeline.py $f $OUT/${w}_k1_timeline.csv > /dev/null 2>&1
   find $OUT/$w -name "*kernel_stats.csv" -exec cp {} $OUT/${w}_k1_kernel_stats.csv \;
@@ -41,37 +41,37 @@ done
 # K frames / cameras per launch on ONE stream: the K-frame kernels' own durations (the default bench overlaps two such batches)
 for w in cfg3 avatar; do
   extra=""; [ $w = avatar ] && extra="--workload avatar"
-  $TO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${w}_k8t -o $w -- python3 $ROOT/bench.py --steps 20 --warmup 5 $K8 --no-cpu-baseline $extra > $OUT/${w}_k8.log 2>&1
+  $TO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${w}_k8t -o $w -- python3 $ROOT/bench.py --full --steps 20 --warmup 5 $K8 --no-cpu-baseline $extra > $OUT/${w}_k8.log 2>&1
   f=$(find $OUT/${w}_k8t -name "*kernel_trace.csv" | head -1)
   python3 $ROOT/tools/timeline.py $f $OUT/${w}_k8_timeline.csv must=sg_record_sums_kernel > /dev/null 2>&1
   find $OUT/${w}_k8t -name "*kernel_stats.csv" -exec cp {} $OUT/${w}_k8_kernel_stats.csv \;
 done
-$TO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/avd -o avd -- python3 $ROOT/bench.py --workload avatar --steps 30 --warmup 5 --no-cpu-baseline > $OUT/avd.log 2>&1
+$TO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/avd -o avd -- python3 $ROOT/bench.py --full --workload avatar --steps 30 --warmup 5 --no-cpu-baseline > $OUT/avd.log 2>&1
 find $OUT/avd -name "*kernel_stats.csv" -exec cp {} $OUT/avatar_default_kernel_stats.csv \;
-$TO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c3d -o c3d -- python3 $ROOT/bench.py --steps 30 --warmup 5 --no-cpu-baseline > $OUT/c3d.log 2>&1
+$TO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c3d -o c3d -- python3 $ROOT/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline > $OUT/c3d.log 2>&1
 find $OUT/c3d -name "*kernel_stats.csv" -exec cp {} $OUT/cfg3_default_kernel_stats.csv \;
-$TO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/tr -o tr -- python3 $ROOT/bench.py --workload train --steps 30 --warmup 5 --eager > $OUT/tr.log 2>&1
+$TO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/tr -o tr -- python3 $ROOT/bench.py --full --workload train --steps 30 --warmup 5 --eager > $OUT/tr.log 2>&1
 find $OUT/tr -name "*kernel_stats.csv" -exec cp {} $OUT/train_kernel_stats.csv \;
 # one graph-replayed training step as a timeline (which kernels overlap, who waits for whom)
-$TO rocprofv3 --kernel-trace --output-format csv -d $OUT/train_trace -o tt -- python3 $ROOT/bench.py --workload train --steps 10 --warmup 3 > $OUT/train_trace.log 2>&1
+$TO rocprofv3 --kernel-trace --output-format csv -d $OUT/train_trace -o tt -- python3 $ROOT/bench.py --full --workload train --steps 10 --warmup 3 > $OUT/train_trace.log 2>&1
 python3 $ROOT/tools/step_trace.py $(find $OUT/train_trace -name "*kernel_trace.csv" | head -1) > $OUT/train_step_trace.log 2>&1
 # counters: separate passes
 for ctr in FETCH_SIZE WRITE_SIZE; do
-  $TO rocprofv3 --pmc $ctr --output-format csv -d $OUT/pmc_$ctr -o c3 -- python3 $ROOT/bench.py --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/pmc_$ctr.log 2>&1
-  $TO rocprofv3 --pmc $ctr --output-format csv -d $OUT/avatar/pmc_$ctr -o c3 -- python3 $ROOT/bench.py --workload avatar --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/avatar/pmc_$ctr.log 2>&1
+  $TO rocprofv3 --pmc $ctr --output-format csv -d $OUT/pmc_$ctr -o c3 -- python3 $ROOT/bench.py --full --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/pmc_$ctr.log 2>&1
+  $TO rocprofv3 --pmc $ctr --output-format csv -d $OUT/avatar/pmc_$ctr -o c3 -- python3 $ROOT/bench.py --full --workload avatar --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/avatar/pmc_$ctr.log 2>&1
 done
 # the same two counters with 8 frames / cameras per dispatch (per-view traffic of the batched step: tools/pmc_summary.py ... frames_per_launch=8)
 for ctr in FETCH_SIZE WRITE_SIZE; do
-  $TO rocprofv3 --pmc $ctr --output-format csv -d $OUT/k8/pmc_$ctr -o c3 -- python3 $ROOT/bench.py --steps 5 --warmup 2 $K8 --no-cpu-baseline > $OUT/k8/pmc_$ctr.log 2>&1
-  $TO rocprofv3 --pmc $ctr --output-format csv -d $OUT/avatar_k8/pmc_$ctr -o c3 -- python3 $ROOT/bench.py --workload avatar --steps 5 --warmup 2 $K8 --no-cpu-baseline > $OUT/avatar_k8/pmc_$ctr.log 2>&1
+  $TO rocprofv3 --pmc $ctr --output-format csv -d $OUT/k8/pmc_$ctr -o c3 -- python3 $ROOT/bench.py --full --steps 5 --warmup 2 $K8 --no-cpu-baseline > $OUT/k8/pmc_$ctr.log 2>&1
+  $TO rocprofv3 --pmc $ctr --output-format csv -d $OUT/avatar_k8/pmc_$ctr -o c3 -- python3 $ROOT/bench.py --full --workload avatar --steps 5 --warmup 2 $K8 --no-cpu-baseline > $OUT/avatar_k8/pmc_$ctr.log 2>&1
 done
 SQ="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES SQ_BUSY_CYCLES"
-$TO rocprofv3 --pmc $SQ --output-format csv -d $OUT/pmc_SQ -o c3 -- python3 $ROOT/bench.py --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/pmc_SQ.log 2>&1
-$TO rocprofv3 --pmc $SQ --output-format csv -d $OUT/avatar/pmc_SQ -o c3 -- python3 $ROOT/bench.py --workload avatar --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/avatar/pmc_SQ.log 2>&1
+$TO rocprofv3 --pmc $SQ --output-format csv -d $OUT/pmc_SQ -o c3 -- python3 $ROOT/bench.py --full --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/pmc_SQ.log 2>&1
+$TO rocprofv3 --pmc $SQ --output-format csv -d $OUT/avatar/pmc_SQ -o c3 -- python3 $ROOT/bench.py --full --workload avatar --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/avatar/pmc_SQ.log 2>&1
 # how busy the vector ALUs are (quad-cycles with a VALU instruction executing, against wave and wait cycles)
 SQ2="SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_WAIT_INST_ANY"
-$TO rocprofv3 --pmc $SQ2 --output-format csv -d $OUT/pmc_SQ2 -o c3 -- python3 $ROOT/bench.py --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/pmc_SQ2.log 2>&1
-$TO rocprofv3 --pmc $SQ2 --output-format csv -d $OUT/avatar/pmc_SQ2 -o c3 -- python3 $ROOT/bench.py --workload avatar --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/avatar/pmc_SQ2.log 2>&1
+$TO rocprofv3 --pmc $SQ2 --output-format csv -d $OUT/pmc_SQ2 -o c3 -- python3 $ROOT/bench.py --full --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/pmc_SQ2.log 2>&1
+$TO rocprofv3 --pmc $SQ2 --output-format csv -d $OUT/avatar/pmc_SQ2 -o c3 -- python3 $ROOT/bench.py --full --workload avatar --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/avatar/pmc_SQ2.log 2>&1
 # the other raster configurations the bench is run on: instruction counts and HBM traffic for their rooflines
 #   python tools/pmc_summary.py gpurun_out/prof_r03/cfg2 r03_cfg2 gaussians=50000 width=512 height=512 sh_degree=0
 #   python tools/pmc_summary.py gpurun_out/prof_r03/cfg5 r03_cfg5 gaussians=500000 width=2048 height=2048
@@ -80,8 +80,8 @@ CFG5="--gaussians 500000 --width 2048 --height 2048"
 for ctr in FETCH_SIZE WRITE_SIZE SQ; do
   set=$ctr; [ $ctr = SQ ] && set="$SQ"
   mkdir -p $OUT/cfg2 $OUT/cfg5
-  $TO rocprofv3 --pmc $set --output-format csv -d $OUT/cfg2/pmc_$ctr -o c3 -- python3 $ROOT/bench.py $CFG2 --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/cfg2/pmc_$ctr.log 2>&1
-  $TO rocprofv3 --pmc $set --output-format csv -d $OUT/cfg5/pmc_$ctr -o c3 -- python3 $ROOT/bench.py $CFG5 --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/cfg5/pmc_$ctr.log 2>&1
+  $TO rocprofv3 --pmc $set --output-format csv -d $OUT/cfg2/pmc_$ctr -o c3 -- python3 $ROOT/bench.py --full $CFG2 --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/cfg2/pmc_$ctr.log 2>&1
+  $TO rocprofv3 --pmc $set --output-format csv -d $OUT/cfg5/pmc_$ctr -o c3 -- python3 $ROOT/bench.py --full $CFG5 --steps 5 --warmup 2 $K1 --no-cpu-baseline > $OUT/cfg5/pmc_$ctr.log 2>&1
 done
 # the photometric-loss kernels on their own (1080p noise image, and the avatar frame size with 8 frames per launch): kernel stats + counters
 ( cd $ROOT && bash tools/prof_loss.sh ${TAG}_loss 1920x1080 > $OUT/loss_prof.log 2>&1; bash tools/pmc_loss.sh ${TAG}_loss 1920x1080 > $OUT/loss_pmc.log 2>&1;

@@ -8,8 +8,8 @@ i=0
 for CTRS in "SQ_INSTS_VALU SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_LDS" \
             "TCC_HIT_sum TCC_MISS_sum" "GRBM_GUI_ACTIVE SQ_ACTIVE_INST_ANY SQ_INST_CYCLES_VMEM_RD SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"; do
   i=$((i+1))
-  rocprofv3 --pmc $CTRS --output-format csv -d $OUT/k1_$i -o c -- python3 $ROOT/bench.py --steps 5 --warmup 2 $K1 --no-cpu-baseline --no-secondary > $OUT/k1_$i.log 2>&1
-  rocprofv3 --pmc $CTRS --output-format csv -d $OUT/k8_$i -o c -- python3 $ROOT/bench.py --steps 5 --warmup 2 $K8 --no-cpu-baseline --no-secondary > $OUT/k8_$i.log 2>&1
+  rocprofv3 --pmc $CTRS --output-format csv -d $OUT/k1_$i -o c -- python3 $ROOT/bench.py --full --steps 5 --warmup 2 $K1 --no-cpu-baseline --no-secondary > $OUT/k1_$i.log 2>&1
+  rocprofv3 --pmc $CTRS --output-format csv -d $OUT/k8_$i -o c -- python3 $ROOT/bench.py --full --steps 5 --warmup 2 $K8 --no-cpu-baseline --no-secondary > $OUT/k8_$i.log 2>&1
 done
 python3 - <<PY
 import csv, re, glob

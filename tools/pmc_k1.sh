@@ -4,7 +4,7 @@ TAG=$1; shift
 CTRS=${@:-SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_INST_LDS}
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/pmc_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc $CTRS --output-format csv -d $OUT -o c3 -- python3 $ROOT/bench.py --steps 5 --warmup 2 --views-per-step 1 --streams 1 --no-cpu-baseline > $OUT/log.txt 2>&1
+rocprofv3 --pmc $CTRS --output-format csv -d $OUT -o c3 -- python3 $ROOT/bench.py --full --steps 5 --warmup 2 --views-per-step 1 --streams 1 --no-cpu-baseline > $OUT/log.txt 2>&1
 python3 - <<PY
 import csv, re, glob
 from collections import defaultdict

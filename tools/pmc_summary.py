@@ -21,7 +21,7 @@ for kv in sys.argv[3:]:
 frames = int(config.get("frames_per_launch", 1))
 sched = f"--views-per-step {frames} --frames-per-launch {frames} --streams 1" if frames > 1 else "--views-per-step 1 --streams 1"
 meta = {"config": config, "sources": bench.source_hashes(root),
-        "command": f"rocprofv3 --pmc <set> -- python3 bench.py --steps 5 --warmup 2 {sched} --no-cpu-baseline"
+        "command": f"rocprofv3 --pmc <set> -- python3 bench.py --full --steps 5 --warmup 2 {sched} --no-cpu-baseline"
                    + ("" if config["workload"] == "raster" else f" --workload {config['workload']}")}
 
 

@@ -30,6 +30,6 @@ if len(sys.argv) > 1:                                                   # child:
     sys.exit(0)
 for name, args in (("one view per launch", ["--views-per-step", "1", "--streams", "1"]),
                    ("8 cameras per launch", ["--views-per-step", "8", "--frames-per-launch", "8", "--streams", "1"])):
-    p = subprocess.run([sys.executable, __file__, "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-secondary"] + args,
+    p = subprocess.run([sys.executable, __file__, "--full", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-secondary"] + args,
                        capture_output=True, text=True)
     print(name, p.stdout.strip().splitlines()[-1] if p.stdout.strip() else p.stderr[-400:])

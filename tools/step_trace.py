@@ -1,5 +1,5 @@
 """One graph-replayed training step as a timeline: start, duration, hardware queue and name of every kernel, and the idle gaps.
-    rocprofv3 --kernel-trace --output-format csv -d <dir> -o tt -- python3 bench.py --workload train --steps 10 --warmup 3
+    rocprofv3 --kernel-trace --output-format csv -d <dir> -o tt -- python3 bench.py --full --workload train --steps 10 --warmup 3
     python3 tools/step_trace.py <dir>/.../tt_kernel_trace.csv > profiles/<tag>_train_step_trace.log
 (kernels of different streams overlap: the durations do not add up to the step)"""
 import csv, sys
