@@ -93,7 +93,8 @@ typedef struct SgLayout {
  * sg_scales_head_forward / _backward.  8 = depth and alpha maps:
  * sg_aux_layout, sg_rasterize_forward_aux / _backward_aux, sg_skinned_forward_aux / _backward_aux added (nothing else changed);
  * entry points added since 8: sg_frames_aux_layout, sg_skinned_forward_frames_aux, sg_rasterize_backward_records_frames_aux,
- * sg_skinned_backward_gaussians_frames_aux (depth and alpha maps of K frames). */
+ * sg_skinned_backward_gaussians_frames_aux (depth and alpha maps of K frames); sg_lpips_weights_layout, sg_lpips_ws_bytes,
+ * sg_lpips_forward, sg_lpips_backward, sg_lpips_patch_gather, sg_lpips_patch_scatter (the LPIPS-VGG patch loss). */
 #define SG_ABI_VERSION 8
 int sg_abi_version(void);
 const char *sg_version(void);
@@ -609,6 +610,44 @@ int sg_skinned_backward_gaussians_frames_aux(const SgRasterSettings *s, const Sg
                                              const float *dL_dposed_rotq_in, float *dL_dxyz_canon, float *dL_drot_canon,
                                              float *dL_dscales, float *dL_dopacity, float *dL_dsh, float *dL_dmeans2D, float *dL_dA,
                                              float *dL_dtransl, void *aux_ws, void *stream);
+
+/* ---- LPIPS-VGG (the `lpips` 0.1 package: net='vgg', version='0.1', eval mode) and the patch glue of the reference's LPIPS term
+ * (sings/rec/losses/loss.py:71-80; entry points added to ABI 8).  Replaces `lpips.LPIPS(net='vgg')(in0, in1)` -> [B,1,1,1] and
+ * its gradient w.r.t. in0 (the network is frozen: no weight gradients).
+ *
+ * Weights: ONE device buffer of sg_lpips_weights_layout()'s total floats, filled by the caller at the offsets it reports
+ * (offsets[i], in floats, each a multiple of 4):
+ *   i = 3 l      conv l (l = 0..12, features order) forward weights: l = 0 as torch [64][3][3][3]; l >= 1 [Cout][9][Cin], element
+ *                (co, 3 ky + kx, ci) = W[co][ci][ky][kx]
+ *   i = 3 l + 1  conv l bias [Cout]
+ *   i = 3 l + 2  conv l input-gradient weights (l >= 1): [Cin][9][Cout], element (ci, 3 ky + kx, co) = W[co][ci][2-ky][2-kx]
+ *                (W.transpose(0,1).flip(2,3)); l = 0: none (empty)
+ *   i = 39 + k   lin k (k = 0..4) [C_k] (the 1x1 conv's weight, no bias)
+ *   i = 44, 45   scaling layer shift [3], scale [3]
+ * Images: in0, in1 [B][3][H][W] fp32 (H, W >= SG_LPIPS_MIN_SIZE); normalize != 0 maps them to 2x - 1 first (lpips' `normalize`).
+ * sg_lpips_forward writes out[B] (the per-image distance) and keeps in `ws` what sg_lpips_backward reads: the backward must be
+ * given the same sizes, weights and workspace, and nothing may write the workspace in between.  dL_dout [B] (device),
+ * dL_din0 [B][3][H][W].  Bit-reproducible; a tile never spans two images, so an image's value and gradient do not depend on the
+ * rest of the batch.  No host synchronisation.
+ * Patches: raw [K][3][H][W] (the UNCLAMPED render), gt_rgb [K][3][H][W], mask [K][H][W], bg [3], bg_rand [K][3][H][W], origins
+ * [K][n][2] int32 (row, col) of each patch's top-left corner -- device data, clamped into [0, H - patch] x [0, W - patch].
+ * pred_patches / gt_patches [K n][3][patch][patch]:
+ *   pred = min(clamp(raw, 0, 1) mask + bg_rand (1 - mask), 1),  gt = ((gt_rgb mask + bg (1 - mask)) mask + bg_rand (1 - mask))
+ * sg_lpips_patch_scatter writes dL_draw [K][3][H][W] from dL_dpred_patches (every pixel: overlapping patches summed in patch order,
+ * zero outside all patches, the clip's and the clamp's inclusive pass bands applied). */
+#define SG_LPIPS_NUM_OFFSETS 46
+#define SG_LPIPS_MIN_SIZE 16
+int sg_lpips_weights_layout(size_t *offsets, size_t *total_floats);
+int sg_lpips_ws_bytes(int B, int height, int width, size_t *bytes);
+int sg_lpips_forward(int B, int height, int width, int normalize, const float *weights, const float *in0, const float *in1, void *ws,
+                     float *out, void *stream);
+int sg_lpips_backward(int B, int height, int width, int normalize, const float *weights, const void *ws, const float *dL_dout,
+                      float *dL_din0, void *stream);
+int sg_lpips_patch_gather(int K, int n, int patch, int height, int width, const float *raw, const float *gt_rgb, const float *mask,
+                          const float *bg, const float *bg_rand, const int32_t *origins, float *pred_patches, float *gt_patches,
+                          void *stream);
+int sg_lpips_patch_scatter(int K, int n, int patch, int height, int width, const float *raw, const float *mask, const float *bg_rand,
+                           const int32_t *origins, const float *dL_dpred_patches, float *dL_draw, void *stream);
 
 /* ---- optional per-kernel timing (bench / profiling only; process-global, not thread-safe).
  * When enabled, every kernel launch of forward/backward is bracketed by hipEvents on the

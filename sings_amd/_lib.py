@@ -67,7 +67,10 @@ EXPORTS = ("sg_abi_version", "sg_version", "sg_last_error", "sg_layout", "sg_ras
            "sg_skinned_backward_gaussians_frames", "sg_photo_loss_frames",
            "sg_aux_layout", "sg_rasterize_forward_aux", "sg_rasterize_backward_aux", "sg_skinned_forward_aux", "sg_skinned_backward_aux",
            "sg_frames_aux_layout", "sg_skinned_forward_frames_aux", "sg_rasterize_backward_records_frames_aux",
-           "sg_skinned_backward_gaussians_frames_aux")
+           "sg_skinned_backward_gaussians_frames_aux", "sg_lpips_weights_layout", "sg_lpips_ws_bytes", "sg_lpips_forward",
+           "sg_lpips_backward", "sg_lpips_patch_gather", "sg_lpips_patch_scatter")
+LPIPS_NUM_OFFSETS = 46               # SG_LPIPS_NUM_OFFSETS
+LPIPS_MIN_SIZE = 16                  # SG_LPIPS_MIN_SIZE
 NUM_KERNELS = 8
 ABI_VERSION = 8                      # SG_ABI_VERSION
 FLAG_SHORT_LISTS = 1                 # SG_FLAG_SHORT_LISTS
@@ -211,6 +214,16 @@ def load():
     for f in ("sg_aux_layout", "sg_rasterize_forward_aux", "sg_rasterize_backward_aux", "sg_skinned_forward_aux", "sg_skinned_backward_aux",
               "sg_frames_aux_layout", "sg_skinned_forward_frames_aux", "sg_rasterize_backward_records_frames_aux",
               "sg_skinned_backward_gaussians_frames_aux"):
+        getattr(lib, f).restype = C.c_int
+    # LPIPS-VGG (entry points added to ABI 8)
+    lib.sg_lpips_weights_layout.argtypes = [C.POINTER(sz), C.POINTER(sz)]
+    lib.sg_lpips_ws_bytes.argtypes = [i32, i32, i32, C.POINTER(sz)]
+    lib.sg_lpips_forward.argtypes = [i32, i32, i32, i32] + [vp] * 6
+    lib.sg_lpips_backward.argtypes = [i32, i32, i32, i32] + [vp] * 5
+    lib.sg_lpips_patch_gather.argtypes = [i32] * 5 + [vp] * 9
+    lib.sg_lpips_patch_scatter.argtypes = [i32] * 5 + [vp] * 7
+    for f in ("sg_lpips_weights_layout", "sg_lpips_ws_bytes", "sg_lpips_forward", "sg_lpips_backward", "sg_lpips_patch_gather",
+              "sg_lpips_patch_scatter"):
         getattr(lib, f).restype = C.c_int
     for f in ("sg_layout", "sg_rasterize_forward", "sg_rasterize_backward", "sg_mark_visible",
               "sg_read_num_rendered", "sg_skinned_forward", "sg_skinned_backward"):

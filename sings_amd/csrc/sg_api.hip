@@ -31,6 +31,7 @@ static int sg_fail(const char *what, hipError_t e)
 extern "C" const char *sg_version(void) { return "sings_hip 0.8 (gfx950, abi 8)"; }
 extern "C" int sg_abi_version(void) { return SG_ABI_VERSION; }
 extern "C" const char *sg_last_error(void) { return g_err; }
+int sg_set_error(const char *what, hipError_t e) { return sg_fail(what, e); }
 
 extern "C" int sg_layout(int P, int width, int height, size_t cap, SgLayout *L)
 {

@@ -7,6 +7,8 @@
 #include "../../include/sings_hip.h"
 
 #define SG_WAVE 64
+// the thread-local error of sg_last_error() (sg_api.hip), for entry points defined in other translation units; returns 1
+int sg_set_error(const char *what, hipError_t e = hipSuccess);
 // (The compile-time experiment switches of rounds 1-2 -- SG_EXP bits that compiled phases of a kernel out for timing -- are no
 // longer in the product sources; the measurements they produced are in LAB.md, the variants in the git history.)
 #ifdef SG_EXP

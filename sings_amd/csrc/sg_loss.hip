@@ -5,7 +5,7 @@
 //   gt = rgb * mask + bg * (1 - mask)                             loss.py:58
 //   l1_w * |pred - gt|.sum() / mask.sum()                         losses/utils.py:16-20
 //   ssim_w * (1 - ssim(pred, gt)) * mask.sum() / (H W)            losses/utils.py:28-70, loss.py:65-67
-// and their autograd backward down to dL/d(rasterizer output).  (The LPIPS term is a VGG network: out of scope.)
+// and their autograd backward down to dL/d(rasterizer output).  (The LPIPS term: sg_lpips.hip.)
 //
 // The reference runs ~25 elementwise / conv2d kernels each way.  Rounds 3-5 ran two tiled kernels with three fp32 derivative
 // maps per channel between them (36 B/pixel written, 62 B/pixel read back with the halo: 121 us per 1080p view, 5 x its HBM

@@ -12,7 +12,7 @@ renderer's final clamp (gs_renderer_single.py:96):
 (csrc/sg_loss.hip): a forward whose input requires grad computes the gradient for unit upstream weights in the same march and the
 backward multiplies it by the upstream scalar when both terms share it (the usual ``l1 + ssim`` under one sum); with different
 weights for the two terms the gradient kernel runs again with them as device scalars (sg_photo_loss_backward).  No host
-synchronisation anywhere.  LPIPS (a VGG network) is not provided.
+synchronisation anywhere.  The LPIPS patch term: sings_amd/lpips.py.
 No CPU fallback: the HIP library must be present.
 """
 import ctypes as C

@@ -112,7 +112,8 @@ class AvatarTrainer:
         for p in self.params:
             p.grad = None
         s = self._static
-        loss, ld, ex = self.m(s["A"], self.rs, s["gt"], s["mask"], self.bg, smpl_scale=self.smpl_scale, transl=self.transl)
+        loss, ld, ex = self.m(s["A"], self.rs, s["gt"], s["mask"], self.bg, smpl_scale=self.smpl_scale, transl=self.transl,
+                              lpips_origins=s.get("lp_origins"), lpips_bg=s.get("lp_bg"))
         if loss is None:
             self.m.backward(ld, ex)
         else:
@@ -120,13 +121,24 @@ class AvatarTrainer:
         self.m.add_densification_stats(ex)
         return {k: v.detach().reshape(()).clone() for k, v in ld.items()}
 
-    def step(self, A, gt_rgb, mask):
+    def step(self, A, gt_rgb, mask, lpips_origins=None, lpips_bg=None):
+        """``lpips_origins`` / ``lpips_bg``: the step's LPIPS patch corners and random background (``AvatarStep.forward``), copied
+        in like the frame's inputs, so that a replayed graph reads this step's patches."""
         s = self._static
-        if not s or s["A"].shape != A.shape:
+        lp = {"lp_origins": lpips_origins, "lp_bg": lpips_bg}
+        lp = {k: (None if v is None else torch.as_tensor(v).to(self.dev)) for k, v in lp.items()}
+        if lp["lp_origins"] is not None:
+            lp["lp_origins"] = lp["lp_origins"].to(torch.int32)
+        shapes = lambda d: tuple(None if d.get(k) is None else tuple(d[k].shape) for k in ("lp_origins", "lp_bg"))
+        if not s or s["A"].shape != A.shape or shapes(s) != shapes(lp):
             s.update(A=A.clone(), gt=gt_rgb.clone(), mask=mask.clone())
+            s.update({k: (None if v is None else v.clone()) for k, v in lp.items()})
             self.captured = None
         else:
             s["A"].copy_(A); s["gt"].copy_(gt_rgb); s["mask"].copy_(mask)
+            for k, v in lp.items():
+                if v is not None:
+                    s[k].copy_(v)
         if self.use_graph and self._sizing == 0:
             if self.captured is None:
                 overflow.set_deferred_overflow_check(True, capacity_pairs=overflow.capacity_pairs(self.dev))

@@ -4,6 +4,7 @@
     decode_attributes (tri-plane + decoders)          sings_hybrid.py:249-313      sings_amd/decode.py
     fused LBS + projection + binning + composite      sings_hybrid.py:398-428, gs_renderer_single.py:12-107   sings_amd/skinned.py
     clamp + L1 + SSIM                                 losses/loss.py:55-69         sings_amd/photo_loss.py
+    LPIPS-VGG patch term (optional)                   losses/loss.py:71-80         sings_amd/lpips.py
     regularisers (optional)                           gs_trainer.py:355-399        sings_amd/regularizers.py
     backward through all of it
 
@@ -28,6 +29,7 @@ import torch
 
 from . import decode as _dec
 from .decode import decode_attributes
+from .lpips import lpips_patch_loss
 from .photo_loss import photometric_loss, photometric_loss_frames
 from .skinned import rasterize_skinned_frames, rasterize_skinned_gaussians
 
@@ -139,8 +141,10 @@ def capture_step(fn, warmup=3, device=None):
 class AvatarStep(torch.nn.Module):
     def __init__(self, xyz_anchor, lbs_weights, triplane, geometry_dec, appearance_dec, l1_w=0.8, ssim_w=0.2,
                  thickness_factor=1.0, scaling_multiplier=None, l2_norm=None, gaussian_connect=None, gaussian_connect_w=0.0,
-                 overlap_regularisers=True, defer_regulariser_join=False):
+                 overlap_regularisers=True, defer_regulariser_join=False, lpips=None, lpips_w=0.0, lpips_patch_size=128):
         super().__init__()
+        # the LPIPS patch term (loss.py:71-80): a sings_amd.lpips.LPIPS, its weight (human.loss.lpips_w) and patch size
+        self.lpips, self.lpips_w, self.lpips_patch_size = lpips, float(lpips_w), int(lpips_patch_size)
         self.overlap_regularisers, self._side = bool(overlap_regularisers), None
         self.defer_regulariser_join = bool(defer_regulariser_join)
         self.xyz = torch.nn.Parameter(xyz_anchor.detach().clone())
@@ -194,7 +198,8 @@ class AvatarStep(torch.nn.Module):
         if self.xyz_gradient_accum is not None:
             self.enable_densification_stats()
 
-    def forward(self, A_cano2pose, raster_settings, gt_rgb, mask, bg_color, smpl_scale=None, transl=None):
+    def forward(self, A_cano2pose, raster_settings, gt_rgb, mask, bg_color, smpl_scale=None, transl=None, lpips_origins=None,
+                lpips_bg=None):
         """-> (loss, loss_dict, extras).  ``A_cano2pose`` [J,4,4]: one frame per step (the reference's step); [K,J,4,4]: a chunk
         of K <= 16 frames of the step's Gaussians -- ONE attribute decode, the K frames rendered, compared (``gt_rgb`` / ``mask``
         [K,...] or one for all) and differentiated in one call per direction, the photometric terms summed over the frames,
@@ -203,6 +208,9 @@ class AvatarStep(torch.nn.Module):
         ``self.backward(loss_dict, extras)``, which runs both, joins the regularisers' side stream and fills
         ``loss_dict["loss"]``.  Until then the regulariser entries of ``loss_dict`` live on that UNJOINED stream: do not read
         them (``.item()``, logging) before ``backward`` -- or call ``self.join_regularisers(loss_dict)`` first.
+        With ``lpips`` and ``lpips_w`` > 0 set, ``lpips_origins`` ([n,2] / [K,n,2] device int (row, col) patch corners:
+        ``sings_amd.lpips.PatchSampler``) adds ``loss_dict['lpips_patch']``; ``lpips_bg`` is the random background of the
+        term (the reference's ``torch.rand_like(pred_img)``; drawn here when None).
         Inside a HIP-graph capture: use ``sings_amd.train_step.capture_step`` (it refuses, with an error instead of a dead
         process, a captured callable that returns tensors still carrying their autograd graph), and keep the regularisers on
         the ONE side stream this module owns (``GaussiansEdgeLoss.finish`` refuses any other stream while capturing)."""
@@ -287,10 +295,20 @@ class AvatarStep(torch.nn.Module):
             extras = dict(extras, per_frame=per_frame)
         else:
             loss_dict, extras = photometric_loss(color, gt_rgb, mask, bg_color, self.l1_w, self.ssim_w)
+        if self.lpips is not None and self.lpips_w > 0.0 and lpips_origins is not None:
+            # behind the l1 / ssim pair: their shared _AddScalars node stays as it is, this term is added after it
+            bg_rand = torch.rand_like(color) if lpips_bg is None else lpips_bg
+            lp = lpips_patch_loss(color, gt_rgb, mask, bg_color, bg_rand, lpips_origins, self.lpips_patch_size, self.lpips,
+                                  self.lpips_w)
+            loss_dict["lpips_patch"] = lp.sum() if frames else lp
+            if frames:
+                extras["per_frame"] = dict(extras["per_frame"], lpips_patch=lp)
         if defer:
             # two roots, no join: the regularisers' gradients are waited for where they are consumed (AvatarStep.backward)
             vals = [v.reshape(()) for v in loss_dict.values()]
-            photo_root = _AddScalars.apply(vals[0], vals[1]) if len(vals) == 2 else torch.stack(vals).sum()
+            photo_root = _AddScalars.apply(vals[0], vals[1]) if len(vals) >= 2 else torch.stack(vals).sum()
+            for v in vals[2:]:
+                photo_root = photo_root + v
             # the regularisers, ISSUED last (the main chain keeps its queue in the graph executor, sings_amd/decode.py "capture
             # order") but waiting only for what they read: L2Norm and the k-NN grids for the decode, the k-NN QUERY -- 9 waves per
             # SIMD on every CU for 0.23 ms -- for the raster forward.  (Measured, profiles/r05_graph_queues.log: the executor starts

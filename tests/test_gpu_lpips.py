@@ -1,0 +1,325 @@
+"""LPIPS-VGG on the GPU (csrc/sg_lpips.hip through sings_amd.lpips) against the fp64 oracle of tests/lpips_case.py, the patch term
+against vectors from the reference's own loss.py / sampler.py, determinism, the K-frame form and the training step with the term.
+
+Bounds: value relative error <= 2e-5; dL/din0 |delta| <= 2e-4 |ref| + 2e-5 max|ref| for all but the elements where fp32 and fp64
+take different ReLU / max-pool branches (_check_grad)."""
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import lpips_case as lc
+from sings_amd import lpips as L
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+G = np.load(os.path.join(os.path.dirname(__file__), "golden", "lpips_golden.npz"))
+ERRORS = {}
+
+
+def _model(wt):
+    return L.LPIPS.from_tensors(wt["convs"], wt["lins"], wt["shift"], wt["scale"], device=DEV)
+
+
+def _check_value(name, got, ref):
+    got = got.detach().double().cpu().reshape(-1); ref = ref.detach().double().reshape(-1)
+    rel = ((got - ref).abs() / ref.abs()).max().item()
+    ERRORS[name + " value rel"] = rel
+    print(f"{name}: value rel err {rel:.3e}")
+    assert rel <= 2e-5, (name, rel)
+
+
+def _check_grad(name, got, ref, strict=True):
+    """strict: every element within 2e-4 |ref| + 2e-5 max|ref|.  Where a ReLU input or two max-pool candidates lie within fp32
+    round-off of each other, fp32 and fp64 take different branches and the gradient moves by a whole branch's share over that
+    branch's receptive field (torch's own fp32 path against the same oracle at 4 x 128^2: 1 % of the elements over the bound, the
+    worst 1224x over it).  Cases that hit such a branch (strict=False): relative L2 error <= 5e-2, largest error <= 0.2 max|ref|."""
+    got = got.detach().double().cpu(); ref = ref.detach().double()
+    assert torch.isfinite(got).all()
+    bound = 2e-4 * ref.abs() + 2e-5 * ref.abs().max()
+    err = (got - ref).abs()
+    over = (err > bound).double().mean().item()
+    rel_max = (err.max() / ref.abs().max()).item()
+    rel_l2 = (torch.linalg.vector_norm(got - ref) / torch.linalg.vector_norm(ref)).item()
+    ERRORS[name + " grad"] = (over, rel_max, rel_l2)
+    print(f"{name}: grad elements over the bound {over:.4%}, max|d| / max|ref| {rel_max:.3e}, relative L2 {rel_l2:.3e}")
+    if strict:
+        assert over == 0.0, (name, over, rel_max)
+    else:
+        assert rel_l2 <= 5e-2 and rel_max <= 0.2, (name, rel_max, rel_l2)
+
+
+def _run(wt, x0, x1, normalize=False, grad=True, seed_up=0):
+    m = _model(wt)
+    a = x0.to(DEV).requires_grad_(grad)
+    v = m(a, x1.to(DEV), normalize=normalize)
+    assert v.shape == (x0.shape[0], 1, 1, 1)
+    up = None
+    if grad:
+        up = torch.from_numpy(np.random.RandomState(seed_up).uniform(0.5, 1.5, x0.shape[0]).astype(np.float32))
+        v.backward(up.to(DEV).reshape(-1, 1, 1, 1))
+    r0 = x0.double().requires_grad_(grad)
+    ref = lc.lpips_ref(wt, r0, x1.double(), normalize)
+    if grad:
+        ref.backward(up.double().reshape(-1, 1, 1, 1))
+    return v, a.grad if grad else None, ref, r0.grad if grad else None
+
+
+def test_four_patches_128():
+    wt = lc.make_weights(0)
+    g = torch.Generator().manual_seed(0)
+    x0 = torch.rand(4, 3, 128, 128, generator=g); x1 = (x0 + 0.1 * torch.randn(4, 3, 128, 128, generator=g)).clamp(0, 1)
+    v, d, rv, rd = _run(wt, x0, x1)
+    _check_value("4x128^2", v, rv)
+    _check_grad("4x128^2", d, rd, strict=False)               # (ReLU / pool branch flips of fp32 against fp64: _check_grad)
+
+
+def test_odd_sizes_at_every_pool_and_normalize():
+    wt = lc.make_weights(1)
+    g = torch.Generator().manual_seed(1)
+    x0 = torch.rand(2, 3, 37, 53, generator=g); x1 = torch.rand(2, 3, 37, 53, generator=g)
+    for normalize in (False, True):
+        v, d, rv, rd = _run(wt, x0, x1, normalize=normalize)
+        _check_value(f"37x53 normalize={normalize}", v, rv)
+        _check_grad(f"37x53 normalize={normalize}", d, rd)
+    # a 3-D input is one image
+    m = _model(wt)
+    v3 = m(x0[0].to(DEV), x1[0].to(DEV))
+    assert v3.shape == (1, 1, 1, 1)
+
+
+def test_full_frame_forward_512x896():
+    wt = lc.make_weights(2)
+    g = torch.Generator().manual_seed(2)
+    x0 = torch.rand(1, 3, 512, 896, generator=g); x1 = (x0 + 0.05 * torch.randn(1, 3, 512, 896, generator=g)).clamp(0, 1)
+    with torch.no_grad():
+        v = _model(wt)(x0.to(DEV), x1.to(DEV))
+        rv = lc.lpips_ref(wt, x0.double(), x1.double())
+    _check_value("512x896 forward", v, rv)
+
+
+def test_constant_colour_patch_pooling_ties():
+    wt = lc.make_weights(3)
+    x0 = torch.empty(2, 3, 64, 64)
+    x0[0] = torch.tensor([0.8, 0.6, 0.3]).reshape(3, 1, 1)          # constant: equal positive values in every pool window
+    x0[1] = torch.tensor([0.1, 0.9, 0.5]).reshape(3, 1, 1)
+    x1 = torch.rand(2, 3, 64, 64, generator=torch.Generator().manual_seed(3))
+    v, d, rv, rd = _run(wt, x0, x1)
+    _check_value("constant colour", v, rv)
+    _check_grad("constant colour", d, rd, strict=False)       # (ties broken by the round-off of each side's own sums)
+
+
+def test_all_zero_feature_vectors_give_the_reference_zero_gradient():
+    wt = lc.make_weights(4, conv5_3_bias=-1e3)                       # relu5_3 is zero everywhere
+    g = torch.Generator().manual_seed(4)
+    x0 = torch.rand(2, 3, 64, 64, generator=g); x1 = torch.rand(2, 3, 64, 64, generator=g)
+    with torch.no_grad():
+        f = lc.features(wt, (x0.double() - wt["shift"].double()) / wt["scale"].double())
+    assert (f[4] == 0).all()
+    v, d, rv, rd = _run(wt, x0, x1)
+    assert torch.isfinite(rd).all()
+    _check_value("zero relu5_3", v, rv)
+    _check_grad("zero relu5_3", d, rd)
+
+
+def test_two_runs_are_bit_identical_and_batch_independent():
+    wt = lc.make_weights(0)
+    m = _model(wt)
+    g = torch.Generator().manual_seed(6)
+    x0 = torch.rand(3, 3, 48, 64, generator=g).to(DEV); x1 = torch.rand(3, 3, 48, 64, generator=g).to(DEV)
+    outs = []
+    for _ in range(2):
+        a = x0.clone().requires_grad_(True)
+        v = m(a, x1)
+        v.sum().backward()
+        outs.append((v.detach().clone(), a.grad.clone()))
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    a = x0[1:2].clone().requires_grad_(True)                        # the same image alone: the same bits
+    v = m(a, x1[1:2]); v.sum().backward()
+    assert torch.equal(v.detach().reshape(-1), outs[0][0].reshape(-1)[1:2]) and torch.equal(a.grad[0], outs[0][1][1])
+
+
+def test_in1_requiring_grad_raises():
+    m = _model(lc.make_weights(0))
+    x = torch.rand(1, 3, 32, 32, device=DEV)
+    with pytest.raises(ValueError):
+        m(x, x.clone().requires_grad_(True))
+    with pytest.raises(ValueError):
+        m(torch.rand(1, 3, 15, 32, device=DEV), torch.rand(1, 3, 15, 32, device=DEV))
+
+
+def _golden_case(seed):
+    raw, gt, mask, bg = lc.golden_inputs(seed)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    return t(raw), t(gt), t(mask), t(bg), t(G[f"s{seed}_bg_rand"]), t(G[f"s{seed}_origins"])
+
+
+@pytest.mark.parametrize("seed", (3, 11, 21))
+def test_patch_loss_matches_reference_golden(seed):
+    m = _model(lc.make_weights(int(G["weights_seed"])))
+    raw, gt, mask, bg, bgr, org = _golden_case(seed)
+    r = raw.clone().requires_grad_(True)
+    loss = L.lpips_patch_loss(r, gt, mask, bg, bgr, org, int(G["patch_size"]), m, float(G["lpips_w"]))
+    assert loss.dim() == 0
+    loss.backward()
+    _check_value(f"patch loss s{seed}", loss, torch.tensor(float(G[f"s{seed}_lpips_patch"]), dtype=torch.float64))
+    _check_grad(f"patch loss s{seed}", r.grad, torch.from_numpy(G[f"s{seed}_grad"]).double(), strict=seed != 21)   # (s21: a flip)
+
+
+def test_patch_loss_untrusted_origins_stay_in_bounds():
+    m = _model(lc.make_weights(0))
+    raw, gt, mask, bg, bgr, _ = _golden_case(3)
+    org = torch.tensor([[-50, 10], [10**6, -7], [90, 79], [0, 0]], dtype=torch.int32, device=DEV)
+    r = raw.clone().requires_grad_(True)
+    loss = L.lpips_patch_loss(r, gt, mask, bg, bgr, org, 32, m, 1.0)
+    loss.backward()
+    clamped = torch.tensor([[0, 10], [64, 0], [64, 48], [0, 0]], dtype=torch.int32, device=DEV)
+    r2 = raw.clone().requires_grad_(True)
+    loss2 = L.lpips_patch_loss(r2, gt, mask, bg, bgr, clamped, 32, m, 1.0)
+    loss2.backward()
+    assert torch.equal(loss, loss2) and torch.equal(r.grad, r2.grad)
+
+
+def test_k_frame_form_is_bit_equal_to_single_calls():
+    m = _model(lc.make_weights(int(G["weights_seed"])))
+    cases = [_golden_case(s) for s in (3, 11, 21)]
+    raws = torch.stack([c[0] for c in cases]).requires_grad_(True)
+    per = L.lpips_patch_loss(raws, torch.stack([c[1] for c in cases]), torch.stack([c[2] for c in cases]), cases[0][3],
+                             torch.stack([c[4] for c in cases]), torch.stack([c[5] for c in cases]), 32, m, 0.7)
+    assert per.shape == (3,)
+    per.sum().backward()
+    for k, (raw, gt, mask, _, bgr, org) in enumerate(cases):
+        r = raw.clone().requires_grad_(True)
+        one = L.lpips_patch_loss(r, gt, mask, cases[0][3], bgr, org, 32, m, 0.7)
+        one.backward()
+        assert torch.equal(one, per[k].detach()), k
+        assert torch.equal(r.grad, raws.grad[k]), k
+
+
+# ---- the training step with the term -------------------------------------------------------------------------------------------
+def _avatar(lpips=None, lpips_w=0.0):
+    from sings_amd.decode import AppearanceDecoder, GeometryDecoder, HexPlaneField
+    from sings_amd.rasterizer import GaussianRasterizationSettings
+    from sings_amd.scene import avatar_scene
+    from sings_amd.train_step import AvatarStep
+    torch.manual_seed(5)
+    s = avatar_scene(N=6000, J=24, W=128, H=224, seed=5)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    cfg = {'grid_dimensions': 2, 'input_coordinate_dim': 3, 'output_coordinate_dim': 32, 'resolution': [16, 16, 16], 'multires': [1, 2]}
+    tri = HexPlaneField(cfg, bounds=1.2, device=DEV); geo = GeometryDecoder(64).to(DEV); app = AppearanceDecoder(64).to(DEV)
+    with torch.no_grad():
+        geo.scales[2].bias.fill_(-4.5); geo.xyz_offsets.weight.mul_(0.01); geo.xyz_offsets.bias.zero_()
+    kw = {} if lpips is None else {"lpips": lpips, "lpips_w": lpips_w, "lpips_patch_size": 32}
+    step = AvatarStep(t(s["xyz_canon"]), t(s["lbs_weights"]), tri, geo, app, **kw).to(DEV)
+    cam = s["cam"]
+    rset = GaussianRasterizationSettings(
+        image_height=s["H"], image_width=s["W"], tanfovx=math.tan(cam["fovx"] * 0.5), tanfovy=math.tan(cam["fovy"] * 0.5), bg=t(s["bg"]),
+        scale_modifier=1.0, viewmatrix=t(cam["world_view_transform"]), projmatrix=t(cam["full_proj_transform"]), sh_degree=0,
+        campos=t(cam["camera_center"]), prefiltered=False, debug=False)
+    from sings_amd.body import joint_transforms
+    rs = np.random.RandomState(1)
+    A = joint_transforms(t(rs.normal(0, 0.15, 72).astype(np.float32)), t(s["joints_rest"]), tuple(s["parents"]))
+    gt = torch.rand(3, s["H"], s["W"], device=DEV, generator=torch.Generator(DEV).manual_seed(2))
+    yy, xx = np.mgrid[0:s["H"], 0:s["W"]]
+    mask = t((((xx - s["W"] / 2) / (s["W"] / 2.5)) ** 2 + ((yy - s["H"] / 2) / (s["H"] / 2.2)) ** 2 < 1).astype(np.float32))
+    args = dict(A=A, rset=rset, gt=gt, mask=mask, bg=t(s["bg"]), sc=t(s["smpl_scale"]), tr=t(s["transl"]))
+    return step, args
+
+
+def _origins_and_bg(args, seed=0):
+    H, W = args["gt"].shape[1:]
+    np.random.seed(seed)
+    org = torch.from_numpy(L.PatchSampler(num_patch=4, patch_size=32, ratio_mask=0.9).origins(args["mask"])).to(DEV)
+    bgr = torch.rand(3, H, W, device=DEV, generator=torch.Generator(DEV).manual_seed(seed))
+    return org, bgr
+
+
+def test_step_with_lpips_matches_the_oracle_chain():
+    wt = lc.make_weights(0)
+    step, a = _avatar(_model(wt), 0.9)
+    params = [p for p in step.parameters() if p.requires_grad]
+    org, bgr = _origins_and_bg(a)
+    loss, ld, ex = step(a["A"], a["rset"], a["gt"], a["mask"], a["bg"], smpl_scale=a["sc"], transl=a["tr"], lpips_origins=org,
+                        lpips_bg=bgr)
+    assert "lpips_patch" in ld
+    loss.backward()
+    got = [p.grad.clone() for p in params]
+    # the oracle chain: the same step without the term, the term's gradient w.r.t. the render from the fp64 oracle
+    for p in params:
+        p.grad = None
+    step.lpips_w = 0.0
+    loss0, ld0, ex0 = step(a["A"], a["rset"], a["gt"], a["mask"], a["bg"], smpl_scale=a["sc"], transl=a["tr"], lpips_origins=org,
+                           lpips_bg=bgr)
+    assert "lpips_patch" not in ld0
+    raw = ex0["render_raw"].detach().cpu().requires_grad_(True)
+    ref = lc.patch_loss_ref(wt, raw, a["gt"].cpu(), a["mask"].cpu(), a["bg"].cpu(), bgr.cpu(), org.cpu(), 32, 0.9)
+    ref.backward()
+    _check_value("step lpips_patch", ld["lpips_patch"], ref.detach())
+    torch.autograd.backward([loss0, ex0["render_raw"]], [torch.ones((), device=DEV), raw.grad.to(DEV)])
+    for p, g in zip(params, got):
+        r = p.grad
+        d = (g - r).abs().max().item()
+        assert d <= 2e-2 * r.abs().max().item() + 1e-12, d             # (branch flips of fp32 vs fp64: _check_grad)
+
+
+def test_step_with_zero_weight_is_bit_equal_to_the_step_without_it():
+    step0, a = _avatar()
+    params0 = [p for p in step0.parameters() if p.requires_grad]
+    loss0, ld0, _ = step0(a["A"], a["rset"], a["gt"], a["mask"], a["bg"], smpl_scale=a["sc"], transl=a["tr"])
+    loss0.backward()
+    step1, a1 = _avatar(_model(lc.make_weights(0)), 0.0)
+    params1 = [p for p in step1.parameters() if p.requires_grad]
+    org, bgr = _origins_and_bg(a1)
+    loss1, ld1, _ = step1(a1["A"], a1["rset"], a1["gt"], a1["mask"], a1["bg"], smpl_scale=a1["sc"], transl=a1["tr"],
+                          lpips_origins=org, lpips_bg=bgr)
+    loss1.backward()
+    assert set(ld0) == set(ld1) and torch.equal(loss0, loss1)
+    for p, q in zip(params0, params1):
+        assert torch.allclose(p.grad, q.grad, rtol=1e-5, atol=1e-12)      # (tri-plane backward: atomics order)
+
+
+def test_step_with_lpips_replays_from_a_hip_graph():
+    from sings_amd import overflow as ov, rasterizer as rz
+    step, a = _avatar(_model(lc.make_weights(0)), 1.0)
+    params = [p for p in step.parameters() if p.requires_grad]
+    org_s, bg_s = [x.clone() for x in _origins_and_bg(a, 0)]
+    inputs = [_origins_and_bg(a, s) for s in (0, 1)]
+
+    def body():
+        for p in params:
+            p.grad = None
+        loss, ld, ex = step(a["A"], a["rset"], a["gt"], a["mask"], a["bg"], smpl_scale=a["sc"], transl=a["tr"], lpips_origins=org_s,
+                            lpips_bg=bg_s)
+        loss.backward()
+        return {k: v.detach().clone() for k, v in ld.items()}
+
+    hint = dict(ov._capacity_hint)
+    try:
+        ref = []
+        for o, b in inputs:
+            org_s.copy_(o); bg_s.copy_(b)
+            ld = body(); torch.cuda.synchronize()
+            ref.append((ld, [p.grad.clone() for p in params]))
+        assert not torch.equal(ref[0][0]["lpips_patch"], ref[1][0]["lpips_patch"])
+        rz.set_deferred_overflow_check(True, capacity_pairs=int(max(ov._capacity_hint.values()) * 1.5))
+        side = torch.cuda.Stream(DEV); side.wait_stream(torch.cuda.current_stream(DEV))
+        with torch.cuda.stream(side):
+            body()
+        torch.cuda.current_stream(DEV).wait_stream(side); torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            out = body()
+        for k in (0, 1, 0):
+            org_s.copy_(inputs[k][0]); bg_s.copy_(inputs[k][1])
+            g.replay(); torch.cuda.synchronize()
+            assert rz.check_deferred_overflow(DEV) > 0
+            assert torch.equal(out["lpips_patch"], ref[k][0]["lpips_patch"]), k
+            assert torch.equal(out["l1"], ref[k][0]["l1"]) and torch.equal(out["ssim"], ref[k][0]["ssim"]), k
+            for p, r in zip(params, ref[k][1]):
+                d = (p.grad - r).abs().max().item()
+                assert d <= 1e-5 * r.abs().max().item() + 1e-12, (k, d)      # (tri-plane sums: atomics order)
+    finally:
+        rz.set_deferred_overflow_check(False)
+        rz.reset_overflow_state(); ov._capacity_hint.update(hint)
