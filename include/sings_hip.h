@@ -554,8 +554,8 @@ int sg_weight_grad(int N, int Cout, int Cin, const float *dz, const float *x, vo
  * Each call takes the parameters of its plain counterpart plus aux_ws: one view's aux workspace of sg_aux_layout's size, written
  * by the forward and read and written by the backward (kept between them like image_ws).  These calls are single-frame and accept
  * SG_FLAG_SHORT_LISTS, SG_FLAG_LONG_ROWS and SG_FLAG_WS_CLEAN; the other flags are refused (status 1, sg_last_error) before
- * anything is launched.  Capacity overflow and hint violations are reported exactly as by the plain calls.  dL_ddepth / dL_dalpha
- * [H,W] may each be NULL (zero). */
+ * anything is launched, and so is a NULL aux_ws (also when P <= 0).  Capacity overflow and hint violations are reported exactly as by
+ * the plain calls.  dL_ddepth / dL_dalpha [H,W] may each be NULL (zero). */
 int sg_aux_layout(int P, int width, int height, size_t capacity_pairs, size_t *aux_bytes);
 int sg_rasterize_forward_aux(const SgRasterSettings *s, int P, const float *means3D, const float *shs,
                              const float *colors_precomp, const float *opacities, const float *scales,

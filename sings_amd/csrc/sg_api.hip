@@ -3,6 +3,7 @@
 #include "sg_common.h"
 
 #include <chrono>
+#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <thread>
@@ -16,6 +17,17 @@ static int sg_fail(const char *what, hipError_t e)
 {
     snprintf(g_err, sizeof g_err, "%s: %s", what, e == hipSuccess ? "invalid argument" : hipGetErrorString(e));
     return 1;
+}
+
+// sg_fail of an argument error whose text is formatted (the entry point's name first: "%s: ...", who)
+static int sg_failf(const char *fmt, ...)
+{
+    char msg[256];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(msg, sizeof msg, fmt, ap);
+    va_end(ap);
+    return sg_fail(msg, hipSuccess);
 }
 
 #define SG_CHECK_LAST(what, s, st)                                           \
@@ -214,43 +226,43 @@ static int sg_read_counts(const void *binning_ws, size_t bin_stride, int K, int6
     return 0;
 }
 
+// Which depth / alpha maps an entry point adds to its colour path: none, one view's (the single-frame *_aux calls) or K frames'
+// (the *_frames_aux calls: frame f's aux workspace and maps at the SgAuxFwd / SgAuxBwd strides).
+enum SgAux { SG_AUX_NONE, SG_AUX_ONE, SG_AUX_FRAMES };
+
 // The flags the depth / alpha entry points accept: the learned list hints and the clean-workspace promise.  THROUGHPUT, the
 // FORWARD_BINNING / FORWARD_COMPOSITE split and SH_PLANAR select kernels or layouts that have no AUX variant.
 // The K-frame entry points (`frames`) also accept THROUGHPUT: their composites are the frames kernels, which have AUX variants.
-static int sg_aux_flags(const char *who, int flags, bool frames = false)
+static int sg_aux_flags(const char *who, int flags, bool frames)
 {
     static const struct { int bit; const char *name; } refused[] = {
         { SG_FLAG_THROUGHPUT, "SG_FLAG_THROUGHPUT" }, { SG_FLAG_FORWARD_BINNING, "SG_FLAG_FORWARD_BINNING" },
         { SG_FLAG_FORWARD_COMPOSITE, "SG_FLAG_FORWARD_COMPOSITE" }, { SG_FLAG_SH_PLANAR, "SG_FLAG_SH_PLANAR" } };
-    char msg[200];
     for (const auto &r : refused)
-        if ((flags & r.bit) && !(frames && r.bit == SG_FLAG_THROUGHPUT)) {
-            snprintf(msg, sizeof msg, "%s: %s is not supported with depth / alpha maps", who, r.name);
-            return sg_fail(msg, hipSuccess);
-        }
+        if ((flags & r.bit) && !(frames && r.bit == SG_FLAG_THROUGHPUT))
+            return sg_failf("%s: %s is not supported with depth / alpha maps", who, r.name);
     const int known = SG_FLAG_SHORT_LISTS | SG_FLAG_LONG_ROWS | SG_FLAG_WS_CLEAN | (frames ? SG_FLAG_THROUGHPUT : 0);
-    if (flags & ~known) { snprintf(msg, sizeof msg, "%s: unknown flags 0x%x", who, flags & ~known); return sg_fail(msg, hipSuccess); }
+    if (flags & ~known) return sg_failf("%s: unknown flags 0x%x", who, flags & ~known);
     return 0;
 }
 
-extern "C" int sg_aux_layout(int P, int width, int height, size_t cap, size_t *aux_bytes)
-{
-    SgLayout L;
-    if (!aux_bytes) return sg_fail("sg_aux_layout", hipSuccess);
-    if (sg_layout(P, width, height, cap, &L)) return 1;          // (the same size checks)
-    *aux_bytes = sg_aux_bytes(cap);
-    return 0;
-}
-
-// K consecutive single-view aux workspaces (frame f's at + f sg_aux_bytes)
-extern "C" int sg_frames_aux_layout(int P, int width, int height, size_t cap, int K, size_t *aux_bytes)
+// K consecutive single-view aux workspaces (frame f's at + f sg_aux_bytes); `null_msg`: the error of a null aux_bytes
+static int sg_aux_layout_k(int P, int width, int height, size_t cap, int K, size_t *aux_bytes, const char *null_msg)
 {
     SgLayout L;
     if (K < 1 || K > SG_MAX_FRAMES) return sg_fail("sg_frames_aux_layout: K must be 1..16", hipSuccess);
-    if (!aux_bytes) return sg_fail("sg_frames_aux_layout: null pointer", hipSuccess);
-    if (sg_layout(P, width, height, cap, &L)) return 1;
+    if (!aux_bytes) return sg_fail(null_msg, hipSuccess);
+    if (sg_layout(P, width, height, cap, &L)) return 1;          // (the same size checks)
     *aux_bytes = sg_aux_bytes(cap) * (size_t)K;
     return 0;
+}
+extern "C" int sg_aux_layout(int P, int width, int height, size_t cap, size_t *aux_bytes)
+{
+    return sg_aux_layout_k(P, width, height, cap, 1, aux_bytes, "sg_aux_layout");
+}
+extern "C" int sg_frames_aux_layout(int P, int width, int height, size_t cap, int K, size_t *aux_bytes)
+{
+    return sg_aux_layout_k(P, width, height, cap, K, aux_bytes, "sg_frames_aux_layout: null pointer");
 }
 
 static int sg_forward_impl(const char *who, const SgRasterSettings *s, const SgFrameBatch *fb, int P, const SgSkinInputs *skin,
@@ -258,43 +270,40 @@ static int sg_forward_impl(const char *who, const SgRasterSettings *s, const SgF
                            const float *scales, const float *rotations, const float *cov3D_precomp, void *geom_ws, void *binning_ws,
                            size_t cap, void *image_ws, float *out_color, int32_t *radii, float *posed_xyz, float *posed_rotq,
                            float *posed_scales, int write_point_keys, int64_t *num_rendered_host, void *stream,
-                           void *aux_ws = nullptr, float *out_depth = nullptr, float *out_alpha = nullptr, bool aux_frames = false)
+                           SgAux aux = SG_AUX_NONE, void *aux_ws = nullptr, float *out_depth = nullptr, float *out_alpha = nullptr)
 {
     hipStream_t st = (hipStream_t)stream;
     SgCam c;
-    char msg[160];
-    if (sg_make_cam(s, &c)) { snprintf(msg, sizeof msg, "%s: bad settings", who); return sg_fail(msg, hipSuccess); }
-    if (aux_ws) {
-        if (sg_aux_flags(who, c.flags, aux_frames)) return 1;
-        if (!out_depth || !out_alpha) { snprintf(msg, sizeof msg, "%s: null pointer (out_depth / out_alpha)", who); return sg_fail(msg, hipSuccess); }
+    if (aux && !aux_ws) return sg_failf("%s: null pointer (aux_ws)", who);
+    if (sg_make_cam(s, &c)) return sg_failf("%s: bad settings", who);
+    if (aux) {
+        if (sg_aux_flags(who, c.flags, aux == SG_AUX_FRAMES)) return 1;
+        if (!out_depth || !out_alpha) return sg_failf("%s: null pointer (out_depth / out_alpha)", who);
     }
     if (skin) {
-        if (sg_check_skin(skin, P, true)) { snprintf(msg, sizeof msg, "%s: bad skin inputs (J in 1..64, ext_tfs all or none)", who); return sg_fail(msg, hipSuccess); }
-        if (P < 0 || !geom_ws || !binning_ws || !image_ws || !out_color || (P > 0 && (!shs || !opacities || !scales || !radii))) {
-            snprintf(msg, sizeof msg, "%s: null pointer", who); return sg_fail(msg, hipSuccess);
-        }
-        if (s->sh_coeffs < (s->sh_degree + 1) * (s->sh_degree + 1)) { snprintf(msg, sizeof msg, "%s: sh_coeffs smaller than (sh_degree+1)^2", who); return sg_fail(msg, hipSuccess); }
+        if (sg_check_skin(skin, P, true)) return sg_failf("%s: bad skin inputs (J in 1..64, ext_tfs all or none)", who);
+        if (P < 0 || !geom_ws || !binning_ws || !image_ws || !out_color || (P > 0 && (!shs || !opacities || !scales || !radii)))
+            return sg_failf("%s: null pointer", who);
+        if (s->sh_coeffs < (s->sh_degree + 1) * (s->sh_degree + 1)) return sg_failf("%s: sh_coeffs smaller than (sh_degree+1)^2", who);
     } else {
-        if (P < 0 || !geom_ws || !binning_ws || !image_ws || !out_color || (P > 0 && (!means3D || !opacities || !radii))) {
-            snprintf(msg, sizeof msg, "%s: null pointer", who); return sg_fail(msg, hipSuccess);
-        }
-        if (P > 0 && ((shs != nullptr) == (colors_precomp != nullptr))) { snprintf(msg, sizeof msg, "%s: provide exactly one of shs / colors_precomp", who); return sg_fail(msg, hipSuccess); }
-        if (P > 0 && (((scales != nullptr) && (rotations != nullptr)) == (cov3D_precomp != nullptr))) {
-            snprintf(msg, sizeof msg, "%s: provide exactly one of (scales,rotations) / cov3D_precomp", who); return sg_fail(msg, hipSuccess);
-        }
-        if (shs && (s->sh_coeffs < (s->sh_degree + 1) * (s->sh_degree + 1))) { snprintf(msg, sizeof msg, "%s: sh_coeffs smaller than (sh_degree+1)^2", who); return sg_fail(msg, hipSuccess); }
+        if (P < 0 || !geom_ws || !binning_ws || !image_ws || !out_color || (P > 0 && (!means3D || !opacities || !radii)))
+            return sg_failf("%s: null pointer", who);
+        if (P > 0 && ((shs != nullptr) == (colors_precomp != nullptr))) return sg_failf("%s: provide exactly one of shs / colors_precomp", who);
+        if (P > 0 && (((scales != nullptr) && (rotations != nullptr)) == (cov3D_precomp != nullptr)))
+            return sg_failf("%s: provide exactly one of (scales,rotations) / cov3D_precomp", who);
+        if (shs && (s->sh_coeffs < (s->sh_degree + 1) * (s->sh_degree + 1))) return sg_failf("%s: sh_coeffs smaller than (sh_degree+1)^2", who);
     }
     SgLayout L;
     sg_layout(P, c.W, c.H, cap, &L);
     SgBatch bt;
-    if (sg_make_batch(fb, P, c, L, cap, &bt)) { snprintf(msg, sizeof msg, "%s: bad frame batch (K in 1..16, camera_stride 0|1, transl_stride 0|3)", who); return sg_fail(msg, hipSuccess); }
+    if (sg_make_batch(fb, P, c, L, cap, &bt)) return sg_failf("%s: bad frame batch (K in 1..16, camera_stride 0|1, transl_stride 0|3)", who);
     SgGeom g = sg_geom_view(geom_ws, L);
     SgBin b = sg_bin_view(binning_ws, L);
     SgImg im = sg_img_view(image_ws, L);
     // header + tile counters: zeroed here unless the caller vouches for them (SG_FLAG_WS_CLEAN; the forward composite
     // leaves them zeroed for the next call).  (The early pair count -- one mapped host word -- serves single-frame calls.)
     const bool do_bin = !(c.flags & SG_FLAG_FORWARD_COMPOSITE), do_comp = !(c.flags & SG_FLAG_FORWARD_BINNING);
-    if (!do_bin && !do_comp) { snprintf(msg, sizeof msg, "%s: SG_FLAG_FORWARD_BINNING and SG_FLAG_FORWARD_COMPOSITE exclude each other", who); return sg_fail(msg, hipSuccess); }
+    if (!do_bin && !do_comp) return sg_failf("%s: SG_FLAG_FORWARD_BINNING and SG_FLAG_FORWARD_COMPOSITE exclude each other", who);
     if (do_bin) {
         if (bt.K == 1) sg_arm_count(s, &c, num_rendered_host);
         if (!(c.flags & SG_FLAG_WS_CLEAN)) {
@@ -310,7 +319,7 @@ static int sg_forward_impl(const char *who, const SgRasterSettings *s, const SgF
     if (do_comp) {
         SgAuxFwd ax = sg_aux_fwd_view(aux_ws, g, out_depth, out_alpha);
         ax.ws = sg_aux_bytes(cap); ax.map = (size_t)c.W * (size_t)c.H;       // (frame f of a K-frame call; unused by one frame)
-        sg_launch_render_fwd(c, bt, g, b, cap, im, out_color, write_point_keys, st, aux_ws ? &ax : nullptr);
+        sg_launch_render_fwd(c, bt, g, b, cap, im, out_color, write_point_keys, st, aux ? &ax : nullptr);
         SG_CHECK_LAST("render_fwd", s, st);
     }
     if (!do_bin) return 0;
@@ -355,6 +364,134 @@ extern "C" int sg_read_num_rendered_frames(const void *binning_ws, int P, int wi
     return sg_read_counts(binning_ws, L.bin_bytes, K, num_rendered_host, stream);
 }
 
+// ---- backward ----------------------------------------------------------------------------------------------------------------
+// Every backward entry point checks, in this order: settings, the flags of the maps, accumulate (refused with the maps), skin inputs,
+// aux_ws (sg_bwd_check); then returns 0 for P <= 0, checks its other pointers and last its frame batch (sg_bwd_layout).
+static int sg_bwd_check(const char *who, const SgRasterSettings *s, SgCam *c, SgAux aux, int accumulate, bool skinned,
+                        const SgSkinInputs *skin, int P, const void *aux_ws)
+{
+    if (sg_make_cam(s, c)) return sg_failf("%s: bad settings", who);
+    if (aux && sg_aux_flags(who, c->flags, aux == SG_AUX_FRAMES)) return 1;
+    if (aux && accumulate) return sg_failf("%s: accumulate != 0 is not supported with depth / alpha maps", who);
+    if (skinned && sg_check_skin(skin, P, false)) return sg_failf("%s: bad skin inputs (ext_tfs are forward-only)", who);
+    if (aux && !aux_ws) return sg_failf("%s: null pointer (aux_ws)", who);
+    return 0;
+}
+static int sg_bwd_layout(const char *who, const SgFrameBatch *fb, int P, const SgCam &c, size_t cap, SgLayout *L, SgBatch *bt)
+{
+    sg_layout(P, c.W, c.H, cap, L);
+    return sg_make_batch(fb, P, c, *L, cap, bt) ? sg_failf("%s: bad frame batch", who) : 0;
+}
+
+// first half: per-tile composite -> one gradient record per (tile, Gaussian) pair in bwd_ws; with the maps also the dL/dz plane
+// of aux_ws (of every frame's aux workspace)
+static int sg_records_impl(const char *who, const SgRasterSettings *s, const SgFrameBatch *fb, int P, const void *geom_ws,
+                           const void *binning_ws, size_t cap, const void *image_ws, void *bwd_ws, const float *dL_dout_color,
+                           void *stream, SgAux aux = SG_AUX_NONE, void *aux_ws = nullptr, const float *dL_ddepth = nullptr,
+                           const float *dL_dalpha = nullptr)
+{
+    hipStream_t st = (hipStream_t)stream;
+    SgCam c;
+    SgLayout L;
+    SgBatch bt;
+    if (sg_bwd_check(who, s, &c, aux, 0, false, nullptr, P, aux_ws)) return 1;
+    if (P <= 0) return 0;
+    if (!geom_ws || !binning_ws || !image_ws || !bwd_ws || !dL_dout_color) return sg_failf("%s: null pointer", who);
+    if (sg_bwd_layout(who, fb, P, c, cap, &L, &bt)) return 1;
+    SgGeom g = sg_geom_view((void *)geom_ws, L);
+    SgBin b = sg_bin_view((void *)binning_ws, L);
+    SgImg im = sg_img_view((void *)image_ws, L);
+    SgAuxBwd ax = sg_aux_bwd_view(aux_ws, cap, g, dL_ddepth, dL_dalpha);
+    if (aux == SG_AUX_FRAMES) { ax.ws = sg_aux_bytes(cap); ax.map = (size_t)c.W * (size_t)c.H; }
+    sg_launch_render_bwd(c, bt, g, b, cap, im, dL_dout_color, sg_rec_view(bwd_ws, cap), st, aux ? &ax : nullptr);
+    SG_CHECK_LAST(aux ? "render_bwd_aux" : "render_bwd", s, st);
+    return 0;
+}
+
+// second half: per Gaussian, the sum of its records (with the maps: and of its dL/dz) and the chain rule; accumulate != 0: += into
+// the gradient outputs
+static int sg_gaussians_impl(const char *who, const SgRasterSettings *s, const SgFrameBatch *fb, int P, const float *means3D,
+                             const float *shs, const float *colors_precomp, const float *opacities, const float *scales,
+                             const float *rotations, const float *cov3D_precomp, const int32_t *radii, const void *geom_ws,
+                             const void *binning_ws, size_t cap, void *bwd_ws, int accumulate, float *dL_dmeans3D,
+                             float *dL_dmeans2D, float *dL_dsh, float *dL_dcolors, float *dL_dopacity, float *dL_dscales,
+                             float *dL_drotations, float *dL_dcov3D, void *stream, SgAux aux = SG_AUX_NONE, void *aux_ws = nullptr)
+{
+    hipStream_t st = (hipStream_t)stream;
+    SgCam c;
+    SgLayout L;
+    SgBatch bt;
+    if (sg_bwd_check(who, s, &c, aux, accumulate, false, nullptr, P, aux_ws)) return 1;
+    if (P <= 0) return 0;
+    if (!means3D || !radii || !geom_ws || !binning_ws || !bwd_ws || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacity)
+        return sg_failf("%s: null pointer", who);
+    if (shs && !dL_dsh) return sg_failf("%s: dL_dsh missing", who);
+    if (sg_bwd_layout(who, fb, P, c, cap, &L, &bt)) return 1;
+    SgGeom g = sg_geom_view((void *)geom_ws, L);
+    SgBin b = sg_bin_view((void *)binning_ws, L);
+    sg_launch_preprocess_bwd(c, bt, P, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, g,
+                             sg_rec_view(bwd_ws, cap), cap, b.header, sg_lds_hist(c.gx, c.gy) ? b.rec_valid : nullptr,
+                             bt.K > 1 ? (float4 *)((char *)bwd_ws + (size_t)bt.K * L.bwd_bytes) : nullptr,     // (sg_frames_layout: the a9 block)
+                             dL_dmeans3D, dL_dmeans2D, shs ? dL_dsh : nullptr,
+                             dL_dcolors, dL_dopacity, cov3D_precomp ? nullptr : dL_dscales,
+                             cov3D_precomp ? nullptr : dL_drotations, dL_dcov3D, accumulate, st, sg_aux_dz(aux_ws, cap));
+    SG_CHECK_LAST(aux ? "preprocess_bwd_aux" : "preprocess_bwd", s, st);
+    return 0;
+}
+
+// the skinned second half: the LBS-fused per-Gaussian backward (frame f's dL/dz plane, K frames: at + f sg_aux_bytes)
+static int sg_skin_gaussians_impl(const char *who, const SgRasterSettings *s, const SgFrameBatch *fb, int P, const SgSkinInputs *skin,
+                                  const float *shs, const float *scales, const int32_t *radii, const void *geom_ws,
+                                  const void *binning_ws, size_t cap, const void *bwd_ws, float *skin_ws, int accumulate,
+                                  const float *dL_dposed_xyz_in, const float *dL_dposed_rotq_in, float *dL_dxyz_canon,
+                                  float *dL_drot_canon, float *dL_dscales, float *dL_dopacity, float *dL_dsh, float *dL_dmeans2D,
+                                  float *dL_dA, float *dL_dtransl, void *stream, SgAux aux = SG_AUX_NONE, void *aux_ws = nullptr)
+{
+    hipStream_t st = (hipStream_t)stream;
+    SgCam c;
+    SgLayout L;
+    SgBatch bt;
+    if (sg_bwd_check(who, s, &c, aux, accumulate, true, skin, P, aux_ws)) return 1;
+    if (P <= 0) return 0;
+    if (!shs || !scales || !radii || !geom_ws || !binning_ws || !bwd_ws || !skin_ws || !dL_dxyz_canon || !dL_dscales ||
+        !dL_dopacity || !dL_dsh || !dL_dmeans2D || !dL_dA)
+        return sg_failf("%s: null pointer", who);
+    if (sg_bwd_layout(who, fb, P, c, cap, &L, &bt)) return 1;
+    SgGeom g = sg_geom_view((void *)geom_ws, L);
+    SgBin b = sg_bin_view((void *)binning_ws, L);
+    sg_launch_skin_bwd(c, bt, P, skin, shs, scales, radii, g, sg_rec_view(bwd_ws, cap), cap, b.header, sg_lds_hist(c.gx, c.gy) ? b.rec_valid : nullptr,
+                       dL_dposed_xyz_in, dL_dposed_rotq_in,
+                       skin_ws, dL_dxyz_canon, dL_drot_canon, dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA,
+                       dL_dtransl, accumulate, st, sg_aux_dz(aux_ws, cap), aux == SG_AUX_FRAMES ? sg_aux_bytes(cap) : 0);
+    SG_CHECK_LAST(aux ? "skin_bwd_aux" : "skin_bwd", s, st);
+    return 0;
+}
+
+// the whole backward of one view (sg_rasterize_backward / _aux): every pointer of both halves is checked before the first launch
+static int sg_rasterize_backward_impl(const char *who, const SgRasterSettings *s, int P, const float *means3D, const float *shs,
+                                      const float *colors_precomp, const float *opacities, const float *scales,
+                                      const float *rotations, const float *cov3D_precomp, const int32_t *radii,
+                                      const void *geom_ws, const void *binning_ws, size_t cap, const void *image_ws,
+                                      void *bwd_ws, const float *dL_dout_color, float *dL_dmeans3D, float *dL_dmeans2D,
+                                      float *dL_dsh, float *dL_dcolors, float *dL_dopacity, float *dL_dscales,
+                                      float *dL_drotations, float *dL_dcov3D, void *stream, SgAux aux = SG_AUX_NONE,
+                                      void *aux_ws = nullptr, const float *dL_ddepth = nullptr, const float *dL_dalpha = nullptr)
+{
+    SgCam c;
+    if (sg_bwd_check(who, s, &c, aux, 0, false, nullptr, P, aux_ws)) return 1;
+    if (P <= 0) return 0;
+    if (!means3D || !radii || !geom_ws || !binning_ws || !image_ws || !bwd_ws || !dL_dout_color || !dL_dmeans3D ||
+        !dL_dmeans2D || !dL_dopacity)
+        return sg_failf("%s: null pointer", who);
+    if (shs && !dL_dsh) return sg_failf("%s: dL_dsh missing", who);
+    int rc = sg_records_impl(who, s, &SG_ONE_FRAME, P, geom_ws, binning_ws, cap, image_ws, bwd_ws, dL_dout_color, stream, aux, aux_ws,
+                             dL_ddepth, dL_dalpha);
+    if (rc) return rc;
+    return sg_gaussians_impl(who, s, &SG_ONE_FRAME, P, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii,
+                             geom_ws, binning_ws, cap, bwd_ws, 0, dL_dmeans3D, dL_dmeans2D, dL_dsh, dL_dcolors, dL_dopacity,
+                             dL_dscales, dL_drotations, dL_dcov3D, stream, aux, aux_ws);
+}
+
 extern "C" int sg_rasterize_backward(const SgRasterSettings *s, int P, const float *means3D, const float *shs,
                                      const float *colors_precomp, const float *opacities, const float *scales,
                                      const float *rotations, const float *cov3D_precomp, const int32_t *radii,
@@ -363,50 +500,26 @@ extern "C" int sg_rasterize_backward(const SgRasterSettings *s, int P, const flo
                                      float *dL_dmeans2D, float *dL_dsh, float *dL_dcolors, float *dL_dopacity,
                                      float *dL_dscales, float *dL_drotations, float *dL_dcov3D, void *stream)
 {
-    SgCam c;
-    if (sg_make_cam(s, &c)) return sg_fail("sg_rasterize_backward: bad settings", hipSuccess);
-    if (P <= 0) return 0;
-    if (!means3D || !radii || !geom_ws || !binning_ws || !image_ws || !bwd_ws || !dL_dout_color || !dL_dmeans3D ||
-        !dL_dmeans2D || !dL_dopacity)
-        return sg_fail("sg_rasterize_backward: null pointer", hipSuccess);
-    if (shs && !dL_dsh) return sg_fail("sg_rasterize_backward: dL_dsh missing", hipSuccess);
-    int rc = sg_rasterize_backward_records(s, P, geom_ws, binning_ws, cap, image_ws, bwd_ws, dL_dout_color, stream);
-    if (rc) return rc;
-    return sg_rasterize_backward_gaussians(s, P, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii,
-                                           geom_ws, binning_ws, cap, bwd_ws, 0, dL_dmeans3D, dL_dmeans2D, dL_dsh, dL_dcolors,
-                                           dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, stream);
+    return sg_rasterize_backward_impl("sg_rasterize_backward", s, P, means3D, shs, colors_precomp, opacities, scales, rotations,
+                                      cov3D_precomp, radii, geom_ws, binning_ws, cap, image_ws, bwd_ws, dL_dout_color, dL_dmeans3D,
+                                      dL_dmeans2D, dL_dsh, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, stream);
 }
 
-// first half of the backward: per-tile composite -> one gradient record per (tile, Gaussian) pair in bwd_ws
 extern "C" int sg_rasterize_backward_records_frames(const SgRasterSettings *s, const SgFrameBatch *fb, int P, const void *geom_ws,
                                                     const void *binning_ws, size_t cap, const void *image_ws, void *bwd_ws,
                                                     const float *dL_dout_color, void *stream)
 {
-    hipStream_t st = (hipStream_t)stream;
-    SgCam c;
-    if (sg_make_cam(s, &c)) return sg_fail("sg_rasterize_backward_records: bad settings", hipSuccess);
-    if (P <= 0) return 0;
-    if (!geom_ws || !binning_ws || !image_ws || !bwd_ws || !dL_dout_color)
-        return sg_fail("sg_rasterize_backward_records: null pointer", hipSuccess);
-    SgLayout L;
-    sg_layout(P, c.W, c.H, cap, &L);
-    SgBatch bt;
-    if (sg_make_batch(fb, P, c, L, cap, &bt)) return sg_fail("sg_rasterize_backward_records: bad frame batch", hipSuccess);
-    SgGeom g = sg_geom_view((void *)geom_ws, L);
-    SgBin b = sg_bin_view((void *)binning_ws, L);
-    SgImg im = sg_img_view((void *)image_ws, L);
-    sg_launch_render_bwd(c, bt, g, b, cap, im, dL_dout_color, sg_rec_view(bwd_ws, cap), st);
-    SG_CHECK_LAST("render_bwd", s, st);
-    return 0;
+    return sg_records_impl("sg_rasterize_backward_records_frames", s, fb, P, geom_ws, binning_ws, cap, image_ws, bwd_ws, dL_dout_color,
+                           stream);
 }
 extern "C" int sg_rasterize_backward_records(const SgRasterSettings *s, int P, const void *geom_ws, const void *binning_ws,
                                              size_t cap, const void *image_ws, void *bwd_ws, const float *dL_dout_color,
                                              void *stream)
 {
-    return sg_rasterize_backward_records_frames(s, &SG_ONE_FRAME, P, geom_ws, binning_ws, cap, image_ws, bwd_ws, dL_dout_color, stream);
+    return sg_records_impl("sg_rasterize_backward_records", s, &SG_ONE_FRAME, P, geom_ws, binning_ws, cap, image_ws, bwd_ws,
+                           dL_dout_color, stream);
 }
 
-// second half: per Gaussian, the sum of its records and the chain rule; accumulate != 0: += into the gradient outputs
 extern "C" int sg_rasterize_backward_gaussians_frames(const SgRasterSettings *s, const SgFrameBatch *fb, int P, const float *means3D,
                                                       const float *shs, const float *colors_precomp, const float *opacities,
                                                       const float *scales, const float *rotations, const float *cov3D_precomp,
@@ -415,27 +528,9 @@ extern "C" int sg_rasterize_backward_gaussians_frames(const SgRasterSettings *s,
                                                       float *dL_dsh, float *dL_dcolors, float *dL_dopacity, float *dL_dscales,
                                                       float *dL_drotations, float *dL_dcov3D, void *stream)
 {
-    hipStream_t st = (hipStream_t)stream;
-    SgCam c;
-    if (sg_make_cam(s, &c)) return sg_fail("sg_rasterize_backward_gaussians: bad settings", hipSuccess);
-    if (P <= 0) return 0;
-    if (!means3D || !radii || !geom_ws || !binning_ws || !bwd_ws || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacity)
-        return sg_fail("sg_rasterize_backward_gaussians: null pointer", hipSuccess);
-    if (shs && !dL_dsh) return sg_fail("sg_rasterize_backward_gaussians: dL_dsh missing", hipSuccess);
-    SgLayout L;
-    sg_layout(P, c.W, c.H, cap, &L);
-    SgBatch bt;
-    if (sg_make_batch(fb, P, c, L, cap, &bt)) return sg_fail("sg_rasterize_backward_gaussians: bad frame batch", hipSuccess);
-    SgGeom g = sg_geom_view((void *)geom_ws, L);
-    SgBin b = sg_bin_view((void *)binning_ws, L);
-    sg_launch_preprocess_bwd(c, bt, P, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, g,
-                             sg_rec_view(bwd_ws, cap), cap, b.header, sg_lds_hist(c.gx, c.gy) ? b.rec_valid : nullptr,
-                             bt.K > 1 ? (float4 *)((char *)bwd_ws + (size_t)bt.K * L.bwd_bytes) : nullptr,     // (sg_frames_layout: the a9 block)
-                             dL_dmeans3D, dL_dmeans2D, shs ? dL_dsh : nullptr,
-                             dL_dcolors, dL_dopacity, cov3D_precomp ? nullptr : dL_dscales,
-                             cov3D_precomp ? nullptr : dL_drotations, dL_dcov3D, accumulate, st);
-    SG_CHECK_LAST("preprocess_bwd", s, st);
-    return 0;
+    return sg_gaussians_impl("sg_rasterize_backward_gaussians_frames", s, fb, P, means3D, shs, colors_precomp, opacities, scales,
+                             rotations, cov3D_precomp, radii, geom_ws, binning_ws, cap, bwd_ws, accumulate, dL_dmeans3D, dL_dmeans2D,
+                             dL_dsh, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, stream);
 }
 extern "C" int sg_rasterize_backward_gaussians(const SgRasterSettings *s, int P, const float *means3D, const float *shs,
                                                const float *colors_precomp, const float *opacities, const float *scales,
@@ -445,10 +540,10 @@ extern "C" int sg_rasterize_backward_gaussians(const SgRasterSettings *s, int P,
                                                float *dL_dcolors, float *dL_dopacity, float *dL_dscales, float *dL_drotations,
                                                float *dL_dcov3D, void *stream)
 {
-    return sg_rasterize_backward_gaussians_frames(s, &SG_ONE_FRAME, P, means3D, shs, colors_precomp, opacities, scales, rotations,
-                                                  cov3D_precomp, radii, geom_ws, binning_ws, cap, (void *)bwd_ws /* K = 1: read only */, accumulate, dL_dmeans3D,
-                                                  dL_dmeans2D, dL_dsh, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D,
-                                                  stream);
+    return sg_gaussians_impl("sg_rasterize_backward_gaussians", s, &SG_ONE_FRAME, P, means3D, shs, colors_precomp, opacities, scales,
+                             rotations, cov3D_precomp, radii, geom_ws, binning_ws, cap, (void *)bwd_ws /* K = 1: read only */,
+                             accumulate, dL_dmeans3D, dL_dmeans2D, dL_dsh, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations,
+                             dL_dcov3D, stream);
 }
 
 extern "C" size_t sg_skin_ws_floats(int P) { return sg_skin_slab_floats(P > 0 ? P : 1, 1); }
@@ -474,6 +569,29 @@ extern "C" int sg_skinned_forward_frames(const SgRasterSettings *s, const SgFram
                            num_rendered_host, stream);
 }
 
+// the whole skinned backward of one view (sg_skinned_backward / _aux): every pointer of both halves is checked before the first launch
+static int sg_skinned_backward_impl(const char *who, const SgRasterSettings *s, int P, const SgSkinInputs *skin, const float *shs,
+                                    const float *scales, const int32_t *radii, const void *geom_ws, const void *binning_ws, size_t cap,
+                                    const void *image_ws, void *bwd_ws, float *skin_ws, const float *dL_dout_color,
+                                    const float *dL_dposed_xyz_in, const float *dL_dposed_rotq_in, float *dL_dxyz_canon,
+                                    float *dL_drot_canon, float *dL_dscales, float *dL_dopacity, float *dL_dsh, float *dL_dmeans2D,
+                                    float *dL_dA, float *dL_dtransl, void *stream, SgAux aux = SG_AUX_NONE, void *aux_ws = nullptr,
+                                    const float *dL_ddepth = nullptr, const float *dL_dalpha = nullptr)
+{
+    SgCam c;
+    if (sg_bwd_check(who, s, &c, aux, 0, true, skin, P, aux_ws)) return 1;
+    if (P <= 0) return 0;
+    if (!shs || !scales || !radii || !geom_ws || !binning_ws || !image_ws || !bwd_ws || !skin_ws || !dL_dout_color ||
+        !dL_dxyz_canon || !dL_dscales || !dL_dopacity || !dL_dsh || !dL_dmeans2D || !dL_dA)
+        return sg_failf("%s: null pointer", who);
+    int rc = sg_records_impl(who, s, &SG_ONE_FRAME, P, geom_ws, binning_ws, cap, image_ws, bwd_ws, dL_dout_color, stream, aux, aux_ws,
+                             dL_ddepth, dL_dalpha);
+    if (rc) return rc;
+    return sg_skin_gaussians_impl(who, s, &SG_ONE_FRAME, P, skin, shs, scales, radii, geom_ws, binning_ws, cap, bwd_ws, skin_ws, 0,
+                                  dL_dposed_xyz_in, dL_dposed_rotq_in, dL_dxyz_canon, dL_drot_canon, dL_dscales, dL_dopacity, dL_dsh,
+                                  dL_dmeans2D, dL_dA, dL_dtransl, stream, aux, aux_ws);
+}
+
 extern "C" int sg_skinned_backward(const SgRasterSettings *s, int P, const SgSkinInputs *skin, const float *shs,
                                    const float *opacities, const float *scales, const int32_t *radii,
                                    const void *geom_ws, const void *binning_ws, size_t cap, const void *image_ws,
@@ -483,18 +601,9 @@ extern "C" int sg_skinned_backward(const SgRasterSettings *s, int P, const SgSki
                                    float *dL_dmeans2D, float *dL_dA, float *dL_dtransl, void *stream)
 {
     (void)opacities;
-    SgCam c;
-    if (sg_make_cam(s, &c)) return sg_fail("sg_skinned_backward: bad settings", hipSuccess);
-    if (sg_check_skin(skin, P, false)) return sg_fail("sg_skinned_backward: bad skin inputs (ext_tfs are forward-only)", hipSuccess);
-    if (P <= 0) return 0;
-    if (!shs || !scales || !radii || !geom_ws || !binning_ws || !image_ws || !bwd_ws || !skin_ws || !dL_dout_color ||
-        !dL_dxyz_canon || !dL_dscales || !dL_dopacity || !dL_dsh || !dL_dmeans2D || !dL_dA)
-        return sg_fail("sg_skinned_backward: null pointer", hipSuccess);
-    int rc = sg_rasterize_backward_records(s, P, geom_ws, binning_ws, cap, image_ws, bwd_ws, dL_dout_color, stream);
-    if (rc) return rc;
-    return sg_skinned_backward_gaussians(s, P, skin, shs, opacities, scales, radii, geom_ws, binning_ws, cap, bwd_ws, skin_ws, 0,
-                                         dL_dposed_xyz_in, dL_dposed_rotq_in, dL_dxyz_canon, dL_drot_canon, dL_dscales, dL_dopacity,
-                                         dL_dsh, dL_dmeans2D, dL_dA, dL_dtransl, stream);
+    return sg_skinned_backward_impl("sg_skinned_backward", s, P, skin, shs, scales, radii, geom_ws, binning_ws, cap, image_ws, bwd_ws,
+                                    skin_ws, dL_dout_color, dL_dposed_xyz_in, dL_dposed_rotq_in, dL_dxyz_canon, dL_drot_canon,
+                                    dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA, dL_dtransl, stream);
 }
 
 extern "C" int sg_skinned_backward_gaussians_frames(const SgRasterSettings *s, const SgFrameBatch *fb, int P, const SgSkinInputs *skin,
@@ -507,26 +616,9 @@ extern "C" int sg_skinned_backward_gaussians_frames(const SgRasterSettings *s, c
                                                     float *dL_dtransl, void *stream)
 {
     (void)opacities;
-    hipStream_t st = (hipStream_t)stream;
-    SgCam c;
-    if (sg_make_cam(s, &c)) return sg_fail("sg_skinned_backward_gaussians: bad settings", hipSuccess);
-    if (sg_check_skin(skin, P, false)) return sg_fail("sg_skinned_backward_gaussians: bad skin inputs (ext_tfs are forward-only)", hipSuccess);
-    if (P <= 0) return 0;
-    if (!shs || !scales || !radii || !geom_ws || !binning_ws || !bwd_ws || !skin_ws || !dL_dxyz_canon || !dL_dscales ||
-        !dL_dopacity || !dL_dsh || !dL_dmeans2D || !dL_dA)
-        return sg_fail("sg_skinned_backward_gaussians: null pointer", hipSuccess);
-    SgLayout L;
-    sg_layout(P, c.W, c.H, cap, &L);
-    SgBatch bt;
-    if (sg_make_batch(fb, P, c, L, cap, &bt)) return sg_fail("sg_skinned_backward_gaussians: bad frame batch", hipSuccess);
-    SgGeom g = sg_geom_view((void *)geom_ws, L);
-    SgBin b = sg_bin_view((void *)binning_ws, L);
-    sg_launch_skin_bwd(c, bt, P, skin, shs, scales, radii, g, sg_rec_view(bwd_ws, cap), cap, b.header, sg_lds_hist(c.gx, c.gy) ? b.rec_valid : nullptr,
-                       dL_dposed_xyz_in, dL_dposed_rotq_in,
-                       skin_ws, dL_dxyz_canon, dL_drot_canon, dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA,
-                       dL_dtransl, accumulate, st);
-    SG_CHECK_LAST("skin_bwd", s, st);
-    return 0;
+    return sg_skin_gaussians_impl("sg_skinned_backward_gaussians_frames", s, fb, P, skin, shs, scales, radii, geom_ws, binning_ws, cap,
+                                  bwd_ws, skin_ws, accumulate, dL_dposed_xyz_in, dL_dposed_rotq_in, dL_dxyz_canon, dL_drot_canon,
+                                  dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA, dL_dtransl, stream);
 }
 extern "C" int sg_skinned_backward_gaussians(const SgRasterSettings *s, int P, const SgSkinInputs *skin, const float *shs,
                                              const float *opacities, const float *scales, const int32_t *radii,
@@ -536,9 +628,10 @@ extern "C" int sg_skinned_backward_gaussians(const SgRasterSettings *s, int P, c
                                              float *dL_dscales, float *dL_dopacity, float *dL_dsh, float *dL_dmeans2D,
                                              float *dL_dA, float *dL_dtransl, void *stream)
 {
-    return sg_skinned_backward_gaussians_frames(s, &SG_ONE_FRAME, P, skin, shs, opacities, scales, radii, geom_ws, binning_ws, cap,
-                                                bwd_ws, skin_ws, accumulate, dL_dposed_xyz_in, dL_dposed_rotq_in, dL_dxyz_canon,
-                                                dL_drot_canon, dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA, dL_dtransl, stream);
+    (void)opacities;
+    return sg_skin_gaussians_impl("sg_skinned_backward_gaussians", s, &SG_ONE_FRAME, P, skin, shs, scales, radii, geom_ws, binning_ws,
+                                  cap, bwd_ws, skin_ws, accumulate, dL_dposed_xyz_in, dL_dposed_rotq_in, dL_dxyz_canon, dL_drot_canon,
+                                  dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA, dL_dtransl, stream);
 }
 
 // ---- depth and alpha maps (ABI 8) ----------------------------------------------------------------------------------------------
@@ -549,10 +642,9 @@ extern "C" int sg_rasterize_forward_aux(const SgRasterSettings *s, int P, const 
                                         int32_t *radii, int write_point_keys, int64_t *num_rendered_host, void *aux_ws,
                                         float *out_depth, float *out_alpha, void *stream)
 {
-    if (!aux_ws) return sg_fail("sg_rasterize_forward_aux: null pointer (aux_ws)", hipSuccess);
     return sg_forward_impl("sg_rasterize_forward_aux", s, &SG_ONE_FRAME, P, nullptr, means3D, shs, colors_precomp, opacities, scales,
                            rotations, cov3D_precomp, geom_ws, binning_ws, cap, image_ws, out_color, radii, nullptr, nullptr, nullptr,
-                           write_point_keys, num_rendered_host, stream, aux_ws, out_depth, out_alpha);
+                           write_point_keys, num_rendered_host, stream, SG_AUX_ONE, aux_ws, out_depth, out_alpha);
 }
 
 extern "C" int sg_skinned_forward_aux(const SgRasterSettings *s, int P, const SgSkinInputs *skin, const float *shs,
@@ -561,27 +653,9 @@ extern "C" int sg_skinned_forward_aux(const SgRasterSettings *s, int P, const Sg
                                       float *posed_rotq, float *posed_scales, int64_t *num_rendered_host, void *aux_ws,
                                       float *out_depth, float *out_alpha, void *stream)
 {
-    if (!aux_ws) return sg_fail("sg_skinned_forward_aux: null pointer (aux_ws)", hipSuccess);
     return sg_forward_impl("sg_skinned_forward_aux", s, &SG_ONE_FRAME, P, skin, nullptr, shs, nullptr, opacities, scales, nullptr, nullptr,
                            geom_ws, binning_ws, cap, image_ws, out_color, radii, posed_xyz, posed_rotq, posed_scales, 0,
-                           num_rendered_host, stream, aux_ws, out_depth, out_alpha);
-}
-
-// backward composite with the depth / alpha adjoints: gradient records + the dL/dz plane of aux_ws
-static int sg_records_aux(const char *who, const SgRasterSettings *s, const SgCam &c, int P, const void *geom_ws, const void *binning_ws,
-                          size_t cap, const void *image_ws, void *bwd_ws, const float *dL_dout_color, void *aux_ws,
-                          const float *dL_ddepth, const float *dL_dalpha, hipStream_t st)
-{
-    SgLayout L;
-    sg_layout(P, c.W, c.H, cap, &L);
-    SgBatch bt = sg_batch_one(P);
-    SgGeom g = sg_geom_view((void *)geom_ws, L);
-    SgBin b = sg_bin_view((void *)binning_ws, L);
-    SgImg im = sg_img_view((void *)image_ws, L);
-    const SgAuxBwd ax = sg_aux_bwd_view(aux_ws, cap, g, dL_ddepth, dL_dalpha);
-    sg_launch_render_bwd(c, bt, g, b, cap, im, dL_dout_color, sg_rec_view(bwd_ws, cap), st, &ax);
-    SG_CHECK_LAST(who, s, st);
-    return 0;
+                           num_rendered_host, stream, SG_AUX_ONE, aux_ws, out_depth, out_alpha);
 }
 
 extern "C" int sg_rasterize_backward_aux(const SgRasterSettings *s, int P, const float *means3D, const float *shs,
@@ -593,31 +667,10 @@ extern "C" int sg_rasterize_backward_aux(const SgRasterSettings *s, int P, const
                                          float *dL_dscales, float *dL_drotations, float *dL_dcov3D, void *aux_ws,
                                          const float *dL_ddepth, const float *dL_dalpha, void *stream)
 {
-    (void)opacities;
-    hipStream_t st = (hipStream_t)stream;
-    SgCam c;
-    if (sg_make_cam(s, &c)) return sg_fail("sg_rasterize_backward_aux: bad settings", hipSuccess);
-    if (sg_aux_flags("sg_rasterize_backward_aux", c.flags)) return 1;
-    if (P <= 0) return 0;
-    if (!means3D || !radii || !geom_ws || !binning_ws || !image_ws || !bwd_ws || !dL_dout_color || !dL_dmeans3D ||
-        !dL_dmeans2D || !dL_dopacity || !aux_ws)
-        return sg_fail("sg_rasterize_backward_aux: null pointer", hipSuccess);
-    if (shs && !dL_dsh) return sg_fail("sg_rasterize_backward_aux: dL_dsh missing", hipSuccess);
-    int rc = sg_records_aux("render_bwd_aux", s, c, P, geom_ws, binning_ws, cap, image_ws, bwd_ws, dL_dout_color, aux_ws, dL_ddepth,
-                            dL_dalpha, st);
-    if (rc) return rc;
-    SgLayout L;
-    sg_layout(P, c.W, c.H, cap, &L);
-    SgGeom g = sg_geom_view((void *)geom_ws, L);
-    SgBin b = sg_bin_view((void *)binning_ws, L);
-    const SgAuxBwd ax = sg_aux_bwd_view(aux_ws, cap, g, dL_ddepth, dL_dalpha);
-    sg_launch_preprocess_bwd(c, sg_batch_one(P), P, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, g,
-                             sg_rec_view(bwd_ws, cap), cap, b.header, sg_lds_hist(c.gx, c.gy) ? b.rec_valid : nullptr, nullptr,
-                             dL_dmeans3D, dL_dmeans2D, shs ? dL_dsh : nullptr,
-                             dL_dcolors, dL_dopacity, cov3D_precomp ? nullptr : dL_dscales,
-                             cov3D_precomp ? nullptr : dL_drotations, dL_dcov3D, 0, st, ax.dz);
-    SG_CHECK_LAST("preprocess_bwd_aux", s, st);
-    return 0;
+    return sg_rasterize_backward_impl("sg_rasterize_backward_aux", s, P, means3D, shs, colors_precomp, opacities, scales, rotations,
+                                      cov3D_precomp, radii, geom_ws, binning_ws, cap, image_ws, bwd_ws, dL_dout_color, dL_dmeans3D,
+                                      dL_dmeans2D, dL_dsh, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D, stream,
+                                      SG_AUX_ONE, aux_ws, dL_ddepth, dL_dalpha);
 }
 
 extern "C" int sg_skinned_backward_aux(const SgRasterSettings *s, int P, const SgSkinInputs *skin, const float *shs,
@@ -630,29 +683,10 @@ extern "C" int sg_skinned_backward_aux(const SgRasterSettings *s, int P, const S
                                        const float *dL_dalpha, void *stream)
 {
     (void)opacities;
-    hipStream_t st = (hipStream_t)stream;
-    SgCam c;
-    if (sg_make_cam(s, &c)) return sg_fail("sg_skinned_backward_aux: bad settings", hipSuccess);
-    if (sg_aux_flags("sg_skinned_backward_aux", c.flags)) return 1;
-    if (sg_check_skin(skin, P, false)) return sg_fail("sg_skinned_backward_aux: bad skin inputs (ext_tfs are forward-only)", hipSuccess);
-    if (P <= 0) return 0;
-    if (!shs || !scales || !radii || !geom_ws || !binning_ws || !image_ws || !bwd_ws || !skin_ws || !dL_dout_color ||
-        !dL_dxyz_canon || !dL_dscales || !dL_dopacity || !dL_dsh || !dL_dmeans2D || !dL_dA || !aux_ws)
-        return sg_fail("sg_skinned_backward_aux: null pointer", hipSuccess);
-    int rc = sg_records_aux("render_bwd_aux", s, c, P, geom_ws, binning_ws, cap, image_ws, bwd_ws, dL_dout_color, aux_ws, dL_ddepth,
-                            dL_dalpha, st);
-    if (rc) return rc;
-    SgLayout L;
-    sg_layout(P, c.W, c.H, cap, &L);
-    SgGeom g = sg_geom_view((void *)geom_ws, L);
-    SgBin b = sg_bin_view((void *)binning_ws, L);
-    const SgAuxBwd ax = sg_aux_bwd_view(aux_ws, cap, g, dL_ddepth, dL_dalpha);
-    sg_launch_skin_bwd(c, sg_batch_one(P), P, skin, shs, scales, radii, g, sg_rec_view(bwd_ws, cap), cap, b.header,
-                       sg_lds_hist(c.gx, c.gy) ? b.rec_valid : nullptr, dL_dposed_xyz_in, dL_dposed_rotq_in,
-                       skin_ws, dL_dxyz_canon, dL_drot_canon, dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA,
-                       dL_dtransl, 0, st, ax.dz);
-    SG_CHECK_LAST("skin_bwd_aux", s, st);
-    return 0;
+    return sg_skinned_backward_impl("sg_skinned_backward_aux", s, P, skin, shs, scales, radii, geom_ws, binning_ws, cap, image_ws, bwd_ws,
+                                    skin_ws, dL_dout_color, dL_dposed_xyz_in, dL_dposed_rotq_in, dL_dxyz_canon, dL_drot_canon,
+                                    dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA, dL_dtransl, stream, SG_AUX_ONE, aux_ws,
+                                    dL_ddepth, dL_dalpha);
 }
 
 // ---- depth and alpha maps of K frames (ABI 8, entry points added) ----------------------------------------------------------------
@@ -662,40 +696,19 @@ extern "C" int sg_skinned_forward_frames_aux(const SgRasterSettings *s, const Sg
                                              float *posed_xyz, float *posed_rotq, float *posed_scales, int64_t *num_rendered_host,
                                              void *aux_ws, float *out_depth, float *out_alpha, void *stream)
 {
-    if (!aux_ws) return sg_fail("sg_skinned_forward_frames_aux: null pointer (aux_ws)", hipSuccess);
     return sg_forward_impl("sg_skinned_forward_frames_aux", s, fb, P, skin, nullptr, shs, nullptr, opacities, scales, nullptr, nullptr,
                            geom_ws, binning_ws, cap, image_ws, out_color, radii, posed_xyz, posed_rotq, posed_scales, 0,
-                           num_rendered_host, stream, aux_ws, out_depth, out_alpha, true);
+                           num_rendered_host, stream, SG_AUX_FRAMES, aux_ws, out_depth, out_alpha);
 }
 
-// the K frames' backward composites with the depth / alpha adjoints (whichever op produced the frames): gradient records + the
-// dL/dz plane of every frame's aux workspace
+// the K frames' backward composites with the depth / alpha adjoints (whichever op produced the frames)
 extern "C" int sg_rasterize_backward_records_frames_aux(const SgRasterSettings *s, const SgFrameBatch *fb, int P, const void *geom_ws,
                                                         const void *binning_ws, size_t cap, const void *image_ws, void *bwd_ws,
                                                         const float *dL_dout_color, void *aux_ws, const float *dL_ddepth,
                                                         const float *dL_dalpha, void *stream)
 {
-    static const char *who = "sg_rasterize_backward_records_frames_aux";
-    hipStream_t st = (hipStream_t)stream;
-    SgCam c;
-    char msg[160];
-    if (sg_make_cam(s, &c)) { snprintf(msg, sizeof msg, "%s: bad settings", who); return sg_fail(msg, hipSuccess); }
-    if (sg_aux_flags(who, c.flags, true)) return 1;
-    if (!aux_ws) { snprintf(msg, sizeof msg, "%s: null pointer (aux_ws)", who); return sg_fail(msg, hipSuccess); }
-    if (P <= 0) return 0;
-    if (!geom_ws || !binning_ws || !image_ws || !bwd_ws || !dL_dout_color) { snprintf(msg, sizeof msg, "%s: null pointer", who); return sg_fail(msg, hipSuccess); }
-    SgLayout L;
-    sg_layout(P, c.W, c.H, cap, &L);
-    SgBatch bt;
-    if (sg_make_batch(fb, P, c, L, cap, &bt)) { snprintf(msg, sizeof msg, "%s: bad frame batch", who); return sg_fail(msg, hipSuccess); }
-    SgGeom g = sg_geom_view((void *)geom_ws, L);
-    SgBin b = sg_bin_view((void *)binning_ws, L);
-    SgImg im = sg_img_view((void *)image_ws, L);
-    SgAuxBwd ax = sg_aux_bwd_view(aux_ws, cap, g, dL_ddepth, dL_dalpha);
-    ax.ws = sg_aux_bytes(cap); ax.map = (size_t)c.W * (size_t)c.H;
-    sg_launch_render_bwd(c, bt, g, b, cap, im, dL_dout_color, sg_rec_view(bwd_ws, cap), st, &ax);
-    SG_CHECK_LAST("render_bwd_aux", s, st);
-    return 0;
+    return sg_records_impl("sg_rasterize_backward_records_frames_aux", s, fb, P, geom_ws, binning_ws, cap, image_ws, bwd_ws,
+                           dL_dout_color, stream, SG_AUX_FRAMES, aux_ws, dL_ddepth, dL_dalpha);
 }
 
 extern "C" int sg_skinned_backward_gaussians_frames_aux(const SgRasterSettings *s, const SgFrameBatch *fb, int P, const SgSkinInputs *skin,
@@ -707,32 +720,10 @@ extern "C" int sg_skinned_backward_gaussians_frames_aux(const SgRasterSettings *
                                                         float *dL_dopacity, float *dL_dsh, float *dL_dmeans2D, float *dL_dA,
                                                         float *dL_dtransl, void *aux_ws, void *stream)
 {
-    static const char *who = "sg_skinned_backward_gaussians_frames_aux";
     (void)opacities;
-    hipStream_t st = (hipStream_t)stream;
-    SgCam c;
-    char msg[160];
-    if (sg_make_cam(s, &c)) { snprintf(msg, sizeof msg, "%s: bad settings", who); return sg_fail(msg, hipSuccess); }
-    if (sg_aux_flags(who, c.flags, true)) return 1;
-    if (accumulate) { snprintf(msg, sizeof msg, "%s: accumulate != 0 is not supported with depth / alpha maps", who); return sg_fail(msg, hipSuccess); }
-    if (sg_check_skin(skin, P, false)) { snprintf(msg, sizeof msg, "%s: bad skin inputs (ext_tfs are forward-only)", who); return sg_fail(msg, hipSuccess); }
-    if (!aux_ws) { snprintf(msg, sizeof msg, "%s: null pointer (aux_ws)", who); return sg_fail(msg, hipSuccess); }
-    if (P <= 0) return 0;
-    if (!shs || !scales || !radii || !geom_ws || !binning_ws || !bwd_ws || !skin_ws || !dL_dxyz_canon || !dL_dscales ||
-        !dL_dopacity || !dL_dsh || !dL_dmeans2D || !dL_dA) { snprintf(msg, sizeof msg, "%s: null pointer", who); return sg_fail(msg, hipSuccess); }
-    SgLayout L;
-    sg_layout(P, c.W, c.H, cap, &L);
-    SgBatch bt;
-    if (sg_make_batch(fb, P, c, L, cap, &bt)) { snprintf(msg, sizeof msg, "%s: bad frame batch", who); return sg_fail(msg, hipSuccess); }
-    SgGeom g = sg_geom_view((void *)geom_ws, L);
-    SgBin b = sg_bin_view((void *)binning_ws, L);
-    const SgAuxBwd ax = sg_aux_bwd_view(aux_ws, cap, g, nullptr, nullptr);
-    sg_launch_skin_bwd(c, bt, P, skin, shs, scales, radii, g, sg_rec_view(bwd_ws, cap), cap, b.header, sg_lds_hist(c.gx, c.gy) ? b.rec_valid : nullptr,
-                       dL_dposed_xyz_in, dL_dposed_rotq_in,
-                       skin_ws, dL_dxyz_canon, dL_drot_canon, dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA,
-                       dL_dtransl, 0, st, ax.dz, sg_aux_bytes(cap));
-    SG_CHECK_LAST("skin_bwd_aux", s, st);
-    return 0;
+    return sg_skin_gaussians_impl("sg_skinned_backward_gaussians_frames_aux", s, fb, P, skin, shs, scales, radii, geom_ws, binning_ws,
+                                  cap, bwd_ws, skin_ws, accumulate, dL_dposed_xyz_in, dL_dposed_rotq_in, dL_dxyz_canon, dL_drot_canon,
+                                  dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA, dL_dtransl, stream, SG_AUX_FRAMES, aux_ws);
 }
 
 __global__ void sg_mark_visible_kernel(int P, const float *__restrict__ means3D, const float *__restrict__ view,

@@ -162,11 +162,13 @@ static inline SgAuxFwd sg_aux_fwd_view(void *aux_ws, const SgGeom &g, float *out
     a.ws = 0; a.map = 0;
     return a;
 }
+// the dL/dz plane of (the first frame's) aux workspace; null without one
+static inline float *sg_aux_dz(void *aux_ws, size_t cap) { return aux_ws ? (float *)((char *)aux_ws + sg_aux_ckd_bytes(cap)) : nullptr; }
 static inline SgAuxBwd sg_aux_bwd_view(void *aux_ws, size_t cap, const SgGeom &g, const float *dL_ddepth, const float *dL_dalpha)
 {
     SgAuxBwd a;
     a.depth = g.depth; a.ckD = (const float *)aux_ws; a.dL_ddepth = dL_ddepth; a.dL_dalpha = dL_dalpha;
-    a.dz = (float *)((char *)aux_ws + sg_aux_ckd_bytes(cap));
+    a.dz = sg_aux_dz(aux_ws, cap);
     a.ws = 0; a.map = 0;
     return a;
 }
@@ -225,7 +227,6 @@ struct SgBatch {
     size_t geom, bin, img, rec;    // bytes between consecutive frames' workspaces
     size_t image;                  // floats of one [3,H,W] image (out_color / dL_dout_color of frame f at + f image)
 };
-static inline SgBatch sg_batch_one(int P) { SgBatch b; b.K = 1; b.cam_stride = 0; b.transl_stride = 0; b.P = P; b.geom = b.bin = b.img = b.rec = 0; b.image = 0; return b; }
 // Linear workgroup id -> (Gaussian block, frame) for the per-Gaussian FORWARD kernels.  Workgroups are dealt round-robin to the 8
 // XCDs (id % 8); inside an XCD the K frames of one Gaussian block take consecutive slots, so the block's canonical inputs (means,
 // scales, SH rows, 4 J bytes of skinning weights per Gaussian) are fetched from HBM by the first of them and served by that XCD's

@@ -103,14 +103,19 @@ def _empty_to_none(t):
 
 
 class _RasterizeGaussians(torch.autograd.Function):
+    """The drop-in op; ``return_aux``: also the depth and alpha maps (include/sings_hip.h, "depth and alpha maps"), returning
+    (color, radii, depth, alpha), depth / alpha [1,H,W]."""
+
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                raster_settings, write_point_keys=False):
+                raster_settings, write_point_keys=False, return_aux=False):
         lib = _lib.load()
         dev = means3D.device
         if dev.type != "cuda":
             raise RuntimeError("sings_amd rasterizer runs on the MI355X only (tensors must be on a 'cuda' "
                                "device); there is no CPU fallback")
+        if return_aux:
+            ctx.set_materialize_grads(False)
         rs = raster_settings
         means3D = _f32(means3D, "means3D", dev)
         sh = _f32(_empty_to_none(sh), "sh", dev)
@@ -126,12 +131,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         s = _settings_struct(rs, dev, M, keep)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+        if return_aux:
+            depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+            alpha = torch.empty((1, H, W), dtype=torch.float32, device=dev)
         radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        need_bwd = any(ctx.needs_input_grad[:8])
-        L = geom = binning = img = bufs = None
+        need_bwd = any(ctx.needs_input_grad[:8]) and not return_aux     # (the maps' backward allocates its own buffers)
+        L = geom = binning = img = bufs = aux = None
 
         def launch(cap, flags, sync):
-            nonlocal L, geom, binning, img, bufs
+            nonlocal L, geom, binning, img, bufs, aux
             L = _lib.layout(P, W, H, cap)
             geom = torch.empty(L.geom_bytes, dtype=torch.uint8, device=dev)
             binning = torch.empty(L.bin_bytes, dtype=torch.uint8, device=dev)
@@ -151,10 +159,15 @@ class _RasterizeGaussians(torch.autograd.Function):
                                          cov3Ds_precomp is not None)
             nr = C.c_int64(0)
             s.flags = flags
-            _lib.check(lib.sg_rasterize_forward(
-                C.byref(s), P, _ptr(means3D), _ptr(sh), _ptr(colors_precomp), _ptr(opacities), _ptr(scales),
-                _ptr(rotations), _ptr(cov3Ds_precomp), _ptr(geom), _ptr(binning), cap, _ptr(img),
-                _ptr(color), _ptr(radii), int(bool(write_point_keys)), C.byref(nr) if sync else None, stream), "forward")
+            args = (C.byref(s), P, _ptr(means3D), _ptr(sh), _ptr(colors_precomp), _ptr(opacities), _ptr(scales),
+                    _ptr(rotations), _ptr(cov3Ds_precomp), _ptr(geom), _ptr(binning), cap, _ptr(img),
+                    _ptr(color), _ptr(radii), int(bool(write_point_keys)), C.byref(nr) if sync else None)
+            if return_aux:
+                aux = torch.empty(_lib.aux_layout(P, W, H, cap), dtype=torch.uint8, device=dev)
+                _lib.check(lib.sg_rasterize_forward_aux(*args, _ptr(aux), _ptr(depth), _ptr(alpha), stream),
+                           "forward (depth / alpha maps)")
+            else:
+                _lib.check(lib.sg_rasterize_forward(*args, stream), "forward")
             return (int(nr.value),) if sync else None
 
         cap, counts = overflow.run_forward(
@@ -177,15 +190,17 @@ class _RasterizeGaussians(torch.autograd.Function):
                               opacities, scales if scales is not None else z,
                               rotations if rotations is not None else z,
                               cov3Ds_precomp if cov3Ds_precomp is not None else z,
-                              radii, geom, binning, img)
+                              radii, geom, binning, img, *((aux,) if return_aux else ()))
         ctx.mark_non_differentiable(radii)
+        if return_aux:
+            return color, radii, depth, alpha
         return color, radii
 
     @staticmethod
-    def backward(ctx, grad_out_color, _grad_radii=None):
+    def backward(ctx, grad_color, _grad_radii=None, grad_depth=None, grad_alpha=None):
         lib = _lib.load()
-        (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, radii, geom, binning,
-         img) = ctx.saved_tensors
+        (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, radii, geom, binning, img,
+         *aux) = ctx.saved_tensors
         has_sh, has_col, has_scale, has_cov = ctx.flags
         rs = ctx.raster_settings
         dev = means3D.device
@@ -193,110 +208,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         H, W = int(rs.image_height), int(rs.image_width)
         s, keep = ctx.settings_struct
         s.count_signal = None; s.count_signal_host = None
-        g = _f32(grad_out_color, "grad_out_color", dev)
+        g = (torch.zeros((3, H, W), dtype=torch.float32, device=dev) if grad_color is None      # (return_aux: not materialised)
+             else _f32(grad_color, "grad_out_color", dev))
+        gD = None if grad_depth is None else _f32(grad_depth, "grad_depth", dev)
+        gA = None if grad_alpha is None else _f32(grad_alpha, "grad_alpha", dev)
         held, ctx.bwd_bufs = ctx.bwd_bufs, None
         bufs = None if held is None else held.take()
         if bufs is None:
             bufs = _backward_buffers(dev, P, ctx.sh_coeffs, ctx.bwd_bytes, has_sh, has_col, has_scale, has_cov)
         dmeans3D, dmeans2D, dopac, dsh, dcol, dscales, drots, dcov, bwd_ws = bufs
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.sg_rasterize_backward(
-                C.byref(s), P, _ptr(means3D), _ptr(sh) if has_sh else None,
-                _ptr(colors_precomp) if has_col else None, _ptr(opacities),
-                _ptr(scales) if has_scale else None, _ptr(rotations) if has_scale else None,
-                _ptr(cov3Ds_precomp) if has_cov else None, _ptr(radii), _ptr(geom), _ptr(binning), ctx.capacity,
-                _ptr(img), _ptr(bwd_ws), _ptr(g), _ptr(dmeans3D), _ptr(dmeans2D), _ptr(dsh), _ptr(dcol),
-                _ptr(dopac), _ptr(dscales), _ptr(drots), _ptr(dcov), stream), "backward")
-        return (dmeans3D, dmeans2D, dsh, dcol, dopac.view_as(opacities), dscales, drots, dcov, None, None)
-
-
-class _RasterizeGaussiansAux(torch.autograd.Function):
-    """The drop-in op with the depth and alpha maps (include/sings_hip.h, "depth and alpha maps"): returns (color, radii, depth,
-    alpha), depth / alpha [1,H,W].  Same inputs, validation, capacity growth and learned list hints as _RasterizeGaussians."""
-
-    @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings):
-        lib = _lib.load()
-        dev = means3D.device
-        if dev.type != "cuda":
-            raise RuntimeError("sings_amd rasterizer runs on the MI355X only (tensors must be on a 'cuda' "
-                               "device); there is no CPU fallback")
-        ctx.set_materialize_grads(False)
-        rs = raster_settings
-        means3D = _f32(means3D, "means3D", dev)
-        sh = _f32(_empty_to_none(sh), "sh", dev)
-        colors_precomp = _f32(_empty_to_none(colors_precomp), "colors_precomp", dev)
-        opacities = _f32(opacities, "opacities", dev)
-        scales = _f32(_empty_to_none(scales), "scales", dev)
-        rotations = _f32(_empty_to_none(rotations), "rotations", dev)
-        cov3Ds_precomp = _f32(_empty_to_none(cov3Ds_precomp), "cov3Ds_precomp", dev)
-        P = int(means3D.shape[0])
-        H, W = int(rs.image_height), int(rs.image_width)
-        M = int(sh.shape[1]) if sh is not None else 0
-        keep = []
-        s = _settings_struct(rs, dev, M, keep)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
-        depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
-        alpha = torch.empty((1, H, W), dtype=torch.float32, device=dev)
-        radii = torch.empty((P,), dtype=torch.int32, device=dev)
-        L = geom = binning = img = aux = None
-
-        def launch(cap, flags, sync):
-            nonlocal L, geom, binning, img, aux
-            L = _lib.layout(P, W, H, cap)
-            geom = torch.empty(L.geom_bytes, dtype=torch.uint8, device=dev)
-            binning = torch.empty(L.bin_bytes, dtype=torch.uint8, device=dev)
-            img = torch.empty(L.img_bytes, dtype=torch.uint8, device=dev)
-            aux = torch.empty(_lib.aux_layout(P, W, H, cap), dtype=torch.uint8, device=dev)
-            nr = C.c_int64(0)
-            s.flags = flags
-            _lib.check(lib.sg_rasterize_forward_aux(
-                C.byref(s), P, _ptr(means3D), _ptr(sh), _ptr(colors_precomp), _ptr(opacities), _ptr(scales),
-                _ptr(rotations), _ptr(cov3Ds_precomp), _ptr(geom), _ptr(binning), cap, _ptr(img),
-                _ptr(color), _ptr(radii), 0, C.byref(nr) if sync else None, _ptr(aux), _ptr(depth), _ptr(alpha), stream),
-                "forward (depth / alpha maps)")
-            return (int(nr.value),) if sync else None
-
-        cap, counts = overflow.run_forward(      # exactly the drop-in's policy (see _RasterizeGaussians.forward)
-            dev, P, W, H, s, launch, lambda: binning[:8].view(torch.int32), debug=rs.debug,
-            hints=(_lib.FLAG_SHORT_LISTS, _lib.FLAG_LONG_ROWS), hints_need_sync=True, early_count=True)
-        ctx.raster_settings = rs
-        ctx.num_rendered = None if counts is None else counts[0]
-        ctx.capacity = cap
-        ctx.sh_coeffs = M
-        ctx.bwd_bytes = int(L.bwd_bytes)
-        ctx.settings_struct = (s, keep)
-        ctx.flags = (sh is not None, colors_precomp is not None, scales is not None, cov3Ds_precomp is not None)
-        z = torch.empty(0, device=dev)
-        ctx.save_for_backward(means3D, sh if sh is not None else z,
-                              colors_precomp if colors_precomp is not None else z,
-                              opacities, scales if scales is not None else z,
-                              rotations if rotations is not None else z,
-                              cov3Ds_precomp if cov3Ds_precomp is not None else z,
-                              radii, geom, binning, img, aux)
-        ctx.mark_non_differentiable(radii)
-        return color, radii, depth, alpha
-
-    @staticmethod
-    def backward(ctx, grad_color, _grad_radii, grad_depth, grad_alpha):
-        lib = _lib.load()
-        (means3D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, radii, geom, binning, img,
-         aux) = ctx.saved_tensors
-        has_sh, has_col, has_scale, has_cov = ctx.flags
-        rs = ctx.raster_settings
-        dev = means3D.device
-        P = int(means3D.shape[0])
-        H, W = int(rs.image_height), int(rs.image_width)
-        s, keep = ctx.settings_struct
-        s.count_signal = None; s.count_signal_host = None
-        g = (torch.zeros((3, H, W), dtype=torch.float32, device=dev) if grad_color is None
-             else _f32(grad_color, "grad_out_color", dev))
-        gD = None if grad_depth is None else _f32(grad_depth, "grad_depth", dev)
-        gA = None if grad_alpha is None else _f32(grad_alpha, "grad_alpha", dev)
-        dmeans3D, dmeans2D, dopac, dsh, dcol, dscales, drots, dcov, bwd_ws = _backward_buffers(
-            dev, P, ctx.sh_coeffs, ctx.bwd_bytes, has_sh, has_col, has_scale, has_cov)
         args = (C.byref(s), P, _ptr(means3D), _ptr(sh) if has_sh else None,
                 _ptr(colors_precomp) if has_col else None, _ptr(opacities),
                 _ptr(scales) if has_scale else None, _ptr(rotations) if has_scale else None,
@@ -308,17 +228,17 @@ class _RasterizeGaussiansAux(torch.autograd.Function):
             if gD is None and gA is None:       # neither map carries a gradient: the plain backward, bit for bit
                 _lib.check(lib.sg_rasterize_backward(*args, stream), "backward")
             else:
-                _lib.check(lib.sg_rasterize_backward_aux(*args, _ptr(aux), _ptr(gD), _ptr(gA), stream),
+                _lib.check(lib.sg_rasterize_backward_aux(*args, _ptr(aux[0]), _ptr(gD), _ptr(gA), stream),
                            "backward (depth / alpha maps)")
-        return (dmeans3D, dmeans2D, dsh, dcol, dopac.view_as(opacities), dscales, drots, dcov, None)
+        return (dmeans3D, dmeans2D, dsh, dcol, dopac.view_as(opacities), dscales, drots, dcov, None, None, None)
 
 
 def rasterize_gaussians_aux(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                             raster_settings):
     """(color, radii, depth, alpha): ``rasterize_gaussians`` plus the accumulated depth sum_i z_i alpha_i T_i and the alpha map
     1 - T_final, both [1,H,W] and differentiable (expected depth = depth / alpha)."""
-    return _RasterizeGaussiansAux.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
-                                        cov3Ds_precomp, raster_settings)
+    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations,
+                                     cov3Ds_precomp, raster_settings, False, True)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,

@@ -44,26 +44,34 @@ def _skin_struct(dev, xyz_canon, rotmat_canon, lbs_weights, A, smpl_scale, trans
     return k
 
 
+def _canonical_inputs(xyz_canon, rotmat_canon, scales, opacities, shs):
+    """The canonical Gaussians of both skinned ops, checked and converted: (device, xyz_canon, rotmat_canon as the kernels read it
+    -- None, [N,9] or [N,6] --, the shape rotmat_canon came in (its gradient's), scales, opacities, shs)."""
+    dev = xyz_canon.device
+    if dev.type != "cuda":
+        raise RuntimeError("sings_amd fused LBS+raster runs on the MI355X only; there is no CPU fallback")
+    xyz_canon = _f32(xyz_canon, "xyz_canon", dev)
+    rot_shape = None if rotmat_canon is None else tuple(rotmat_canon.shape)
+    if rotmat_canon is not None:
+        rotmat_canon = _f32(rotmat_canon, "rotmat_canon", dev)
+        if rotmat_canon.shape[-2:] == (3, 3):
+            rotmat_canon = rotmat_canon.reshape(-1, 9)
+        elif rotmat_canon.dim() != 2 or rotmat_canon.shape[1] not in (6, 9):
+            raise RuntimeError(f"rotmat_canon must be [N,3,3], [N,9] or [N,6] (6-D form), got {tuple(rotmat_canon.shape)}")
+    return (dev, xyz_canon, rotmat_canon, rot_shape, _f32(scales, "scales", dev), _f32(opacities, "opacities", dev),
+            _f32(shs, "shs", dev))
+
+
 class _RasterizeSkinnedGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz_canon, rotmat_canon, scales, opacities, shs, A, transl, lbs_weights, smpl_scale, ext_tfs,
                 raster_settings, return_posed, means2D=None, return_aux=False):
         lib = _lib.load()
-        dev = xyz_canon.device
-        if dev.type != "cuda":
-            raise RuntimeError("sings_amd fused LBS+raster runs on the MI355X only; there is no CPU fallback")
+        dev, xyz_canon, rotmat_canon, rot_shape, scales, opacities, shs = _canonical_inputs(xyz_canon, rotmat_canon, scales,
+                                                                                            opacities, shs)
         if return_aux:
             ctx.set_materialize_grads(False)
         rs = raster_settings
-        xyz_canon = _f32(xyz_canon, "xyz_canon", dev)
-        rot_shape = None if rotmat_canon is None else tuple(rotmat_canon.shape)
-        if rotmat_canon is not None:
-            rotmat_canon = _f32(rotmat_canon, "rotmat_canon", dev)
-            if rotmat_canon.shape[-2:] == (3, 3):
-                rotmat_canon = rotmat_canon.reshape(-1, 9)
-            elif rotmat_canon.dim() != 2 or rotmat_canon.shape[1] not in (6, 9):
-                raise RuntimeError(f"rotmat_canon must be [N,3,3], [N,9] or [N,6] (6-D form), got {tuple(rotmat_canon.shape)}")
-        scales = _f32(scales, "scales", dev); opacities = _f32(opacities, "opacities", dev); shs = _f32(shs, "shs", dev)
         P = int(xyz_canon.shape[0]); H, W = int(rs.image_height), int(rs.image_width); M = int(shs.shape[1])
         keep = []
         s = _settings_struct(rs, dev, M, keep)
@@ -204,21 +212,11 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
                 means2D=None, return_aux=False):
         from .engine import _frame_batch
         lib = _lib.load()
-        dev = xyz_canon.device
-        if dev.type != "cuda":
-            raise RuntimeError("sings_amd fused LBS+raster runs on the MI355X only; there is no CPU fallback")
+        dev, xyz_canon, rotmat_canon, rot_shape, scales, opacities, shs = _canonical_inputs(xyz_canon, rotmat_canon, scales,
+                                                                                            opacities, shs)
         if return_aux:
             ctx.set_materialize_grads(False)
         rs = raster_settings
-        xyz_canon = _f32(xyz_canon, "xyz_canon", dev)
-        rot_shape = None if rotmat_canon is None else tuple(rotmat_canon.shape)
-        if rotmat_canon is not None:
-            rotmat_canon = _f32(rotmat_canon, "rotmat_canon", dev)
-            if rotmat_canon.shape[-2:] == (3, 3):
-                rotmat_canon = rotmat_canon.reshape(-1, 9)
-            elif rotmat_canon.dim() != 2 or rotmat_canon.shape[1] not in (6, 9):
-                raise RuntimeError(f"rotmat_canon must be [N,3,3], [N,9] or [N,6] (6-D form), got {tuple(rotmat_canon.shape)}")
-        scales = _f32(scales, "scales", dev); opacities = _f32(opacities, "opacities", dev); shs = _f32(shs, "shs", dev)
         A = _f32(A, "A", dev)
         K = int(A.shape[0])
         if A.dim() < 3 or not 1 <= K <= _lib.MAX_FRAMES:

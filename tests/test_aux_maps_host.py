@@ -62,10 +62,10 @@ def _fwd(lib, st):
     return lib.sg_rasterize_forward_aux(C.byref(st), 1, f, f, None, f, f, f, None, f, f, 10, f, f, f, 0, None, f, f, f, None)
 
 
-def _bwd(lib, st):
+def _bwd(lib, st, P=1, aux=FAKE):
     f = FAKE
-    return lib.sg_rasterize_backward_aux(C.byref(st), 1, f, f, None, f, f, f, None, f, f, f, 10, f, f, f, f, f, f, None, f,
-                                         f, f, None, f, None, None, None)
+    return lib.sg_rasterize_backward_aux(C.byref(st), P, f, f, None, f, f, f, None, f, f, f, 10, f, f, f, f, f, f, None, f,
+                                         f, f, None, aux, None, None, None)
 
 
 def _skin_fwd(lib, st):
@@ -76,13 +76,13 @@ def _skin_fwd(lib, st):
     return lib.sg_skinned_forward_aux(C.byref(st), 1, C.byref(k), f, f, f, f, f, 10, f, f, f, None, None, None, None, f, f, f, None)
 
 
-def _skin_bwd(lib, st):
+def _skin_bwd(lib, st, P=1, aux=FAKE):
     from sings_amd import _lib
     k = _lib.SgSkinInputs(); k.J = 24; k.rot_format = 0
     k.xyz_canon = k.lbs_weights = k.A = 0x1000
     f = FAKE
-    return lib.sg_skinned_backward_aux(C.byref(st), 1, C.byref(k), f, f, f, f, f, f, 10, f, f, f, f, None, None, f, None, f, f, f,
-                                       f, f, None, f, None, None, None)
+    return lib.sg_skinned_backward_aux(C.byref(st), P, C.byref(k), f, f, f, f, f, f, 10, f, f, f, f, None, None, f, None, f, f, f,
+                                       f, f, None, aux, None, None, None)
 
 
 CALLS = {"sg_rasterize_forward_aux": _fwd, "sg_rasterize_backward_aux": _bwd, "sg_skinned_forward_aux": _skin_fwd,
@@ -119,6 +119,19 @@ def test_aux_forward_requires_its_workspace_and_maps():
     assert rc != 0 and b"aux_ws" in lib.sg_last_error()
     rc = lib.sg_rasterize_forward_aux(C.byref(st), 1, f, f, None, f, f, f, None, f, f, 10, f, f, f, 0, None, f, None, f, None)
     assert rc != 0 and b"out_depth" in lib.sg_last_error()
+
+
+@pytest.mark.parametrize("P", [1, 0, -1])
+@pytest.mark.parametrize("name", ["sg_rasterize_backward_aux", "sg_skinned_backward_aux"])
+def test_aux_backward_requires_its_workspace_even_without_gaussians(name, P):
+    """A null aux_ws is refused before the P <= 0 early return (the order of the K-frame calls); with it, P <= 0 does nothing."""
+    from sings_amd import _lib
+    lib = _lib.load()
+    assert CALLS[name](lib, _settings(), P=P, aux=None) != 0
+    err = lib.sg_last_error().decode()
+    assert name in err and "null pointer (aux_ws)" in err
+    if P <= 0:
+        assert CALLS[name](lib, _settings(), P=P) == 0
 
 
 def test_python_signatures():

@@ -72,8 +72,8 @@ def check(s, tag):
 
 def aux_abi(s, dLc, gD, gA, flags=0, capacity=None, pad=0, sentinel=0.0, geometry=None, colors=None):
     """One forward + backward of the depth / alpha maps through the C ABI (sg_rasterize_forward_aux / _backward_aux), as
-    _RasterizeGaussiansAux runs them but with the caller's SG_FLAG_* promise.  `pad` > 0 places out_depth / out_alpha and the
-    dL_ddepth / dL_dalpha planes `pad` floats into buffers `pad` floats longer than [H,W] on both sides, filled with `sentinel`
+    _RasterizeGaussians with return_aux runs them but with the caller's SG_FLAG_* promise.  `pad` > 0 places out_depth / out_alpha
+    and the dL_ddepth / dL_dalpha planes `pad` floats into buffers `pad` floats longer than [H,W] on both sides, filled with `sentinel`
     (gD / gA given as [H,W]).  `geometry`: None (scales + rotations) or a cov3D_precomp array; `colors`: colors_precomp instead of
     the SH.  -> dict of tensors (the padded buffers whole: depth_buf, alpha_buf), R = NUM_RENDERED_LONG_LIST on a refusal."""
     from sings_amd import _lib
