@@ -14,47 +14,135 @@ from . import _lib
 from .rasterizer import _settings_struct, _ptr
 
 
-class RasterEngine:
-    # flat gradient layout (floats per Gaussian): means3D 3, scales 3, rotations 4, opacity 1, sh 3*M
-    def __init__(self, P, W, H, sh_coeffs, device, capacity_pairs, grad_flat=None):
+def _raster_fields(M):
+    """Flat gradient layout of the un-skinned engines: (view, floats per Gaussian; None: no view, the attribute is None)."""
+    return [("d_means3D", 3), ("d_scales", 3), ("d_rots", 4), ("d_opacity", 1), ("d_sh", 3 * M if M else None)]
+
+
+def _skinned_fields(M, with_rot, rot_width):
+    """... of the LBS-fused engines (the reference's tensor shapes); ``rot_width`` 9: rotation matrices, 6: the decoder's 6-D form."""
+    return [("d_xyz", 3), ("d_scales", 3), ("d_opacity", 1), ("d_sh", 3 * M), ("d_rot", int(rot_width) if with_rot else None)]
+
+
+class _Engine:
+    """What every engine shares: the workspaces of its K frames (K = 1 for the single-frame engines), the flat gradient buffer and
+    its views, the flag word of the forward, the settings struct and the ViewBatch chain of the backward."""
+
+    def __init__(self, P, W, H, sh_coeffs, device, capacity_pairs, K=None):
+        """``K`` None: a single-frame engine (K = 1; ``color``, ``radii`` and ``d_means2D`` have no frame axis).  The workspaces
+        of K frames are K consecutive single-frame workspaces in one allocation each (``sg_frames_layout``)."""
         self.lib = _lib.load()
-        self.P, self.W, self.H, self.M = int(P), int(W), int(H), int(sh_coeffs)
+        if K is not None and not 1 <= K <= _lib.MAX_FRAMES:
+            raise ValueError(f"K must be 1..{_lib.MAX_FRAMES}")
+        self.P, self.W, self.H, self.M, self.cap = int(P), int(W), int(H), int(sh_coeffs), int(capacity_pairs)
+        self.K = 1 if K is None else int(K)
         self.dev = torch.device(device)
-        self.cap = int(capacity_pairs)
-        L = _lib.layout(self.P, self.W, self.H, self.cap)
+        L = _lib.SgLayout()
+        sizes = [C.c_size_t() for _ in range(4)]
+        _lib.check(self.lib.sg_frames_layout(self.P, self.W, self.H, self.cap, self.K, C.byref(L), *[C.byref(x) for x in sizes]),
+                   "sg_frames_layout")
         self.L = L
         u8 = dict(dtype=torch.uint8, device=self.dev)
-        self.geom = torch.empty(L.geom_bytes, **u8)
-        self.binning = torch.empty(L.bin_bytes, **u8)
-        self.binning[:L.bin_ranges].zero_()                  # counters zeroed ONCE; every forward leaves them zeroed
-        self._clean = True                                   # (SG_FLAG_WS_CLEAN: no per-call zeroing launch)
-        self.img = torch.empty(L.img_bytes, **u8)
-        self.bwd_ws = torch.empty(L.bwd_bytes, **u8)
+        self.geom = torch.empty(sizes[0].value, **u8)
+        self.binning = torch.empty(sizes[1].value, **u8)
+        self.binning.view(self.K, L.bin_bytes)[:, :L.bin_ranges].zero_()     # counters zeroed ONCE; every forward leaves them zeroed
+        self._clean = True                                                    # (SG_FLAG_WS_CLEAN: no per-call zeroing launch)
+        self.img = torch.empty(sizes[2].value, **u8)
+        self.bwd_ws = torch.empty(sizes[3].value, **u8)
+        lead = () if K is None else (self.K,)
         f32 = dict(dtype=torch.float32, device=self.dev)
-        self.color = torch.empty((3, self.H, self.W), **f32)
-        self.radii = torch.empty((self.P,), dtype=torch.int32, device=self.dev)
-        per = 3 + 3 + 4 + 1 + 3 * self.M
-        # grad_flat: optional caller-owned storage (one row of a [views, P*per] buffer when several engines render the
-        # views of one step concurrently and their gradients are summed in one pass)
-        if grad_flat is not None and (grad_flat.numel() != self.P * per or grad_flat.dtype != torch.float32
-                                      or not grad_flat.is_contiguous() or grad_flat.device != self.dev):
-            raise ValueError(f"grad_flat must be a contiguous fp32 tensor of {self.P * per} elements on {self.dev}")
-        self.grad_flat = torch.empty(self.P * per, **f32) if grad_flat is None else grad_flat.view(-1)
+        self.color = torch.empty(lead + (3, self.H, self.W), **f32)
+        self.radii = torch.empty(lead + (self.P,), dtype=torch.int32, device=self.dev)
+        self.d_means2D = torch.empty(lead + (self.P, 3), **f32)     # densification statistic, not reduced as a weight grad
+        self._keep, self._s = [], None
+        self._rows = 0                    # list-length hints of set_camera (SG_FLAG_SHORT_LISTS / LONG_ROWS; read by the avatar parity)
+        self._chain = None                # inside ViewBatch.run: callable -> (accumulate, wait-for event, done event)
+        # SG_FLAG_THROUGHPUT (no latency-only work): K frames share the chip; a ViewBatch that keeps several views in flight sets it
+        self.throughput = K is not None
+
+    def _gradients(self, fields, grad_flat, sh_planar):
+        """Carve the flat gradient buffer into ``fields`` (view, floats per Gaussian).  ``sh_planar``: the SH block is
+        coefficient-major, [M,P,3] (SG_FLAG_SH_PLANAR), and LAST -- the kernels write only the (sh_degree + 1)^2 planes in use, so
+        the step's gradient is the PREFIX ``grad_flat[:active_floats(deg)]`` (10 floats per Gaussian at degree 0 instead of 55 for
+        the avatar): that prefix is what is folded and all-reduced; the rest stays zero (zeroed here, once, when the engine owns
+        the buffer -- a caller-owned buffer must come zeroed).  ``grad_flat``: optional caller-owned storage (one row of a
+        [views, P*per] buffer when several engines render the views of one step concurrently and their gradients are summed in
+        one pass)."""
+        self.sh_planar = bool(sh_planar)
+        if self.sh_planar:
+            fields = [f for f in fields if f[0] != "d_sh"] + [f for f in fields if f[0] == "d_sh"]
+        self._fields = fields
+        own = grad_flat is None
+        self.rebind_gradients(torch.empty(self.P * sum(w or 0 for _, w in fields), dtype=torch.float32, device=self.dev) if own
+                              else grad_flat)
+        if own and self.sh_planar and self.d_sh is not None:
+            self.d_sh.zero_()
+
+    def rebind_gradients(self, grad_flat):
+        """Point the gradient views at another flat buffer (several engines of one step sharing ONE buffer: FramePipeline)."""
+        P, n = self.P, self.P * sum(w or 0 for _, w in self._fields)
+        dev = self.geom.device            # (where the workspaces are: ``self.dev`` may name a device without its index, "cuda")
+        if grad_flat.numel() != n or grad_flat.dtype != torch.float32 or not grad_flat.is_contiguous() or grad_flat.device != dev:
+            raise ValueError(f"grad_flat must be a contiguous fp32 tensor of {n} elements on {dev}")
+        self.grad_flat = grad_flat.view(-1)
         o = 0
-        def carve(n, *shape):
-            nonlocal o
-            v = self.grad_flat[o:o + n].view(*shape); o += n
-            return v
-        self.d_means3D = carve(self.P * 3, self.P, 3)
-        self.d_scales = carve(self.P * 3, self.P, 3)
-        self.d_rots = carve(self.P * 4, self.P, 4)
-        self.d_opacity = carve(self.P, self.P, 1)
-        self.d_sh = carve(self.P * 3 * self.M, self.P, self.M, 3) if self.M else None
-        self.d_means2D = torch.empty((self.P, 3), **f32)      # densification statistic, not reduced as a weight grad
-        self._keep = []
-        self._s = None
-        self._chain = None                                    # inside ViewBatch.run: callable -> (accumulate, wait-for event, done event)
-        self.throughput = False                               # SG_FLAG_THROUGHPUT: set by a ViewBatch that keeps several views in flight
+        for name, w in self._fields:
+            shape = ((self.M, P, 3) if self.sh_planar else (P, self.M, 3)) if name == "d_sh" else (P, w)
+            setattr(self, name, None if w is None else self.grad_flat[o:o + P * w].view(shape))
+            o += P * (w or 0)
+
+    def active_floats(self, sh_degree):
+        """Length of the prefix of ``grad_flat`` that carries the step's gradient (everything, unless ``sh_planar``)."""
+        if not self.sh_planar:
+            return self.grad_flat.numel()
+        return self.P * sum(w or 0 for name, w in self._fields if name != "d_sh") + (int(sh_degree) + 1) ** 2 * self.P * 3
+
+    def set_camera(self, raster_settings, long_rows=False):
+        """``long_rows``: the caller knows (from a sizing pass) that no tile list exceeds 16384 entries: direct binning on images of
+        few tiles (SG_FLAG_LONG_ROWS, include/sings_hip.h; a longer list: ``num_rendered()`` = NUM_RENDERED_LONG_LIST, the frame
+        rendered the background: call set_camera again without the hint)."""
+        self._camera(raster_settings, _lib.FLAG_LONG_ROWS if long_rows else 0)
+
+    def _camera(self, raster_settings, rows):
+        keep = []
+        self._s = _settings_struct(raster_settings, self.dev, self.M, keep)
+        self._keep, self._rows = keep, rows
+
+    def _flags(self):
+        """The flag word of a forward."""
+        return (self._rows | (_lib.FLAG_SH_PLANAR if self.sh_planar else 0) | (_lib.FLAG_THROUGHPUT if self.throughput else 0)
+                | (_lib.FLAG_WS_CLEAN if self._clean else 0))
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def _chain_begin(self, accumulate):
+        """Before the per-Gaussian half of a backward: (accumulate, done event).  Inside a ``ViewBatch`` whose views share a gradient
+        row, the view ADDS to the row iff an earlier view of the step wrote it (``accumulate=1``), and with one row across streams it
+        first waits for the per-Gaussian half of the view in front of it in the step's chain."""
+        acc, after, done = self._chain() if self._chain is not None else (False, None, None)
+        if after is not None:
+            torch.cuda.current_stream(self.dev).wait_event(after)
+        return bool(accumulate) or bool(acc), done
+
+    def _chain_end(self, done):
+        """After the per-Gaussian half: the next view of the chain may go."""
+        if done is not None:
+            done.record(torch.cuda.current_stream(self.dev))
+
+    def num_rendered(self):
+        nr = C.c_int64(0)
+        _lib.check(self.lib.sg_read_num_rendered(_ptr(self.binning), C.byref(nr), self._stream()), "read R")
+        return int(nr.value)
+
+
+class RasterEngine(_Engine):
+    """One view per call (sg_rasterize_*).  Flat gradient layout (floats per Gaussian): means3D 3, scales 3, rotations 4,
+    opacity 1, sh 3*M."""
+
+    def __init__(self, P, W, H, sh_coeffs, device, capacity_pairs, grad_flat=None):
+        super().__init__(P, W, H, sh_coeffs, device, capacity_pairs)
+        self._gradients(_raster_fields(self.M), grad_flat, sh_planar=False)
 
     def set_camera(self, raster_settings, short_lists=False, long_rows=False):
         """``short_lists``: the caller knows (from a sizing pass over this scene) that no tile list exceeds 1024 entries (what the
@@ -62,16 +150,11 @@ class RasterEngine:
         frame is binned directly (SG_FLAG_SHORT_LISTS).  ``long_rows``: images of few tiles -- no list exceeds 16384 entries: direct
         binning there (SG_FLAG_LONG_ROWS).  A longer list makes ``num_rendered()`` return ``_lib.NUM_RENDERED_LONG_LIST`` (the frame
         rendered the background): call set_camera again without the hint."""
-        self._keep = []
-        self._s = _settings_struct(raster_settings, self.dev, self.M, self._keep)
-        self._hint = (_lib.FLAG_SHORT_LISTS if short_lists else 0) | (_lib.FLAG_LONG_ROWS if long_rows else 0)
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        self._camera(raster_settings, (_lib.FLAG_SHORT_LISTS if short_lists else 0) | (_lib.FLAG_LONG_ROWS if long_rows else 0))
 
     def forward(self, means3D, shs, opacities, scales, rotations, sync_num_rendered=False):
         nr = C.c_int64(-1)
-        self._s.flags = self._hint | (_lib.FLAG_WS_CLEAN if self._clean else 0) | (_lib.FLAG_THROUGHPUT if self.throughput else 0)
+        self._s.flags = self._flags()
         self._clean = False                                  # (stays False if the call below raises)
         _lib.check(self.lib.sg_rasterize_forward(
             C.byref(self._s), self.P, _ptr(means3D), _ptr(shs), None, _ptr(opacities), _ptr(scales), _ptr(rotations),
@@ -80,28 +163,20 @@ class RasterEngine:
         self._clean = True
         return int(nr.value)
 
-    def backward(self, means3D, shs, opacities, scales, rotations, dL_dcolor):
+    def backward(self, means3D, shs, opacities, scales, rotations, dL_dcolor, accumulate=False):
         """Composite backward (gradient records of this view), then the per-Gaussian chain rule into the gradient buffer.
-        Inside a ``ViewBatch`` whose views share ONE gradient buffer (``chain``) the second half first waits for the view in
-        front of this one in the step's chain and ADDS to the buffer (``sg_rasterize_backward_gaussians(accumulate=1)``)."""
+        ``accumulate``: ADD to the buffer (``sg_rasterize_backward_gaussians(accumulate=1)``); so does a view inside a ``ViewBatch``
+        whose row an earlier view of the step wrote (see ``_chain_begin``)."""
         _lib.check(self.lib.sg_rasterize_backward_records(
             C.byref(self._s), self.P, _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.img), _ptr(self.bwd_ws),
             _ptr(dL_dcolor), self._stream()), "backward (records)")
-        accumulate, after, done = self._chain() if self._chain is not None else (False, None, None)
-        if after is not None:
-            torch.cuda.current_stream(self.dev).wait_event(after)
+        accumulate, done = self._chain_begin(accumulate)
         _lib.check(self.lib.sg_rasterize_backward_gaussians(
             C.byref(self._s), self.P, _ptr(means3D), _ptr(shs), None, _ptr(opacities), _ptr(scales), _ptr(rotations),
             None, _ptr(self.radii), _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.bwd_ws), int(accumulate),
             _ptr(self.d_means3D), _ptr(self.d_means2D), _ptr(self.d_sh), None, _ptr(self.d_opacity),
             _ptr(self.d_scales), _ptr(self.d_rots), None, self._stream()), "backward (gaussians)")
-        if done is not None:
-            done.record(torch.cuda.current_stream(self.dev))
-
-    def num_rendered(self):
-        nr = C.c_int64(0)
-        _lib.check(self.lib.sg_read_num_rendered(_ptr(self.binning), C.byref(nr), self._stream()), "read R")
-        return int(nr.value)
+        self._chain_end(done)
 
     def capture(self, means3D, shs, opacities, scales, rotations, dL_dcolor=None):
         """Record one step (forward, + backward when dL_dcolor is given) into a HIP graph and return it; ``graph.replay()``
@@ -125,95 +200,31 @@ class RasterEngine:
         return g
 
 
-def _carve_skinned(self, carve, with_rot, rot_width, own):
-    """Gradient views of the LBS-fused engines.  Default (the reference's tensor shapes): xyz 3P, scales 3P, opacity P, sh [P,M,3],
-    [rot].  ``sh_planar``: xyz, scales, opacity, [rot], then the SH gradient COEFFICIENT-major, [M,P,3] (SG_FLAG_SH_PLANAR) -- the
-    kernels write only the (sh_degree + 1)^2 planes in use, so the step's gradient is the PREFIX ``grad_flat[:active_floats(deg)]``
-    (10 floats per Gaussian at degree 0 instead of 55): that prefix is what is folded and all-reduced; the rest stays zero (zeroed
-    here, once, when the engine owns the buffer -- a caller-owned buffer must come zeroed)."""
-    P, M = self.P, self.M
-    self.d_xyz = carve(P * 3, P, 3); self.d_scales = carve(P * 3, P, 3); self.d_opacity = carve(P, P, 1)
-    if self.sh_planar:
-        self.d_rot = carve(P * rot_width, P, rot_width) if with_rot else None
-        self.d_sh = carve(P * 3 * M, M, P, 3)
-        if own:
-            self.d_sh.zero_()
-    else:
-        self.d_sh = carve(P * 3 * M, P, M, 3)
-        self.d_rot = carve(P * rot_width, P, rot_width) if with_rot else None
-    self._head = P * 7 + (P * rot_width if with_rot else 0)
-
-
-def _active_floats(self, sh_degree):
-    """Length of the prefix of ``grad_flat`` that carries the step's gradient (everything, unless ``sh_planar``)."""
-    if not self.sh_planar:
-        return self.grad_flat.numel()
-    return self._head + (int(sh_degree) + 1) ** 2 * self.P * 3
-
-
-class SkinnedEngine:
+class SkinnedEngine(_Engine):
     """Same idea for the LBS-fused path (sg_skinned_forward / backward): canonical Gaussians + per-frame joint
     transforms in, image + flat canonical-Gaussian gradient buffer out.  Flat layout (floats): xyz_canon 3P,
-    scales 3P, opacity P, sh 3MP, [rot_canon 9P].  dL/dA [J,16] and dL/dtransl [3] are per-frame (not all-reduced)."""
+    scales 3P, opacity P, sh 3MP, [rot_canon 9P] (``sh_planar``: the SH block last).  dL/dA [J,16] and dL/dtransl [3] are
+    per-frame (not all-reduced)."""
 
     def __init__(self, P, J, W, H, sh_coeffs, device, capacity_pairs, with_rot=False, grad_flat=None, rot_width=9, sh_planar=False):
-        self.lib = _lib.load()
-        self.P, self.J, self.W, self.H, self.M = int(P), int(J), int(W), int(H), int(sh_coeffs)
-        self.sh_planar = bool(sh_planar)
-        self.dev = torch.device(device)
-        self.cap = int(capacity_pairs)
-        L = _lib.layout(self.P, self.W, self.H, self.cap)
-        self.L = L
-        u8 = dict(dtype=torch.uint8, device=self.dev)
+        super().__init__(P, W, H, sh_coeffs, device, capacity_pairs)
+        self.J = int(J)
         f32 = dict(dtype=torch.float32, device=self.dev)
-        self.geom = torch.empty(L.geom_bytes, **u8); self.binning = torch.empty(L.bin_bytes, **u8)
-        self.binning[:L.bin_ranges].zero_(); self._clean = True          # SG_FLAG_WS_CLEAN, as in RasterEngine
-        self.img = torch.empty(L.img_bytes, **u8); self.bwd_ws = torch.empty(L.bwd_bytes, **u8)
         self.skin_ws = torch.empty(int(self.lib.sg_skin_ws_floats(self.P)), **f32)
-        self.color = torch.empty((3, self.H, self.W), **f32)
-        self.radii = torch.empty((self.P,), dtype=torch.int32, device=self.dev)
-        rot_width = int(rot_width)                               # 9: rotation matrices, 6: the decoder's 6-D form
-        per = 3 + 3 + 1 + 3 * self.M + (rot_width if with_rot else 0)
-        if grad_flat is not None and (grad_flat.numel() != self.P * per or grad_flat.dtype != torch.float32
-                                      or not grad_flat.is_contiguous() or grad_flat.device != self.dev):
-            raise ValueError(f"grad_flat must be a contiguous fp32 tensor of {self.P * per} elements on {self.dev}")
-        self.grad_flat = torch.empty(self.P * per, **f32) if grad_flat is None else grad_flat.view(-1)
-        o = 0
-
-        def carve(n, *shape):
-            nonlocal o
-            v = self.grad_flat[o:o + n].view(*shape); o += n
-            return v
-        _carve_skinned(self, carve, with_rot, rot_width, grad_flat is None)
-        self.d_means2D = torch.empty((self.P, 3), **f32)
+        self._gradients(_skinned_fields(self.M, with_rot, rot_width), grad_flat, sh_planar)
         self.d_A = torch.empty((self.J, 16), **f32); self.d_transl = torch.empty(3, **f32)
-        self._keep = []; self._s = None; self._k = None
-        self._chain = None
-        self.throughput = False
-
-    def set_camera(self, raster_settings, long_rows=False):
-        """``long_rows``: the caller knows (from a sizing pass) that no tile list of this avatar exceeds 16384 entries: direct binning
-        (SG_FLAG_LONG_ROWS, include/sings_hip.h; a longer list: ``num_rendered()`` = NUM_RENDERED_LONG_LIST, background frame)."""
-        self._keep = []
-        self._s = _settings_struct(raster_settings, self.dev, self.M, self._keep)
-        self._rows = _lib.FLAG_LONG_ROWS if long_rows else 0
-
-    active_floats = _active_floats
+        self._k = None
 
     def set_frame(self, xyz_canon, rotmat_canon, lbs_weights, A, smpl_scale, transl, ext_tfs=None):
         from .skinned import _skin_struct
         self._kkeep = []
         self._k = _skin_struct(self.dev, xyz_canon, rotmat_canon, lbs_weights, A, smpl_scale, transl, ext_tfs, self._kkeep)
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-
     def forward(self, shs, opacities, scales, sync_num_rendered=False, posed_out=None):
         """``posed_out``: optional (xyz [P,3], quaternions [P,4], scales [P,3]) fp32 tensors that also receive the posed values
         (what SinGS.forward returns: sings_hybrid.py:400-419); the render itself never reads them back."""
         nr = C.c_int64(-1)
-        self._s.flags = ((_lib.FLAG_WS_CLEAN if self._clean else 0) | (_lib.FLAG_THROUGHPUT if self.throughput else 0) |
-                         (_lib.FLAG_SH_PLANAR if self.sh_planar else 0) | getattr(self, "_rows", 0))
+        self._s.flags = self._flags()
         self._clean = False
         pxyz, pq, psc = posed_out if posed_out is not None else (None, None, None)
         _lib.check(self.lib.sg_skinned_forward(
@@ -223,26 +234,18 @@ class SkinnedEngine:
         self._clean = True
         return int(nr.value)
 
-    def backward(self, shs, opacities, scales, dL_dcolor):
+    def backward(self, shs, opacities, scales, dL_dcolor, accumulate=False):
         """As ``RasterEngine.backward``: records of this frame, then (chained inside a ``ViewBatch``) the per-Gaussian half."""
         _lib.check(self.lib.sg_rasterize_backward_records(
             C.byref(self._s), self.P, _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.img), _ptr(self.bwd_ws),
             _ptr(dL_dcolor), self._stream()), "skinned backward (records)")
-        accumulate, after, done = self._chain() if self._chain is not None else (False, None, None)
-        if after is not None:
-            torch.cuda.current_stream(self.dev).wait_event(after)
+        accumulate, done = self._chain_begin(accumulate)
         _lib.check(self.lib.sg_skinned_backward_gaussians(
             C.byref(self._s), self.P, C.byref(self._k), _ptr(shs), _ptr(opacities), _ptr(scales), _ptr(self.radii),
             _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.bwd_ws), _ptr(self.skin_ws), int(accumulate),
             None, None, _ptr(self.d_xyz), _ptr(self.d_rot), _ptr(self.d_scales), _ptr(self.d_opacity),
             _ptr(self.d_sh), _ptr(self.d_means2D), _ptr(self.d_A), _ptr(self.d_transl), self._stream()), "skinned backward (gaussians)")
-        if done is not None:
-            done.record(torch.cuda.current_stream(self.dev))
-
-    def num_rendered(self):
-        nr = C.c_int64(0)
-        _lib.check(self.lib.sg_read_num_rendered(_ptr(self.binning), C.byref(nr), self._stream()), "read R")
-        return int(nr.value)
+        self._chain_end(done)
 
 
 class ViewBatch:
@@ -308,7 +311,7 @@ class ViewBatch:
         self._active_given = active is not None
         self._events = [torch.cuda.Event() for _ in self.engines] if self.chain else None
         for e in self.engines:                                # several views in flight: no latency-only work (SG_FLAG_THROUGHPUT)
-            e.throughput = self.n > 1 or getattr(e, "K", 1) > 1
+            e.throughput = self.n > 1 or e.K > 1
 
     def _link(self, v, e):
         # Resolved when the view's backward actually RUNS (engine.backward calls it once): the view adds to its row iff a
@@ -337,8 +340,8 @@ class ViewBatch:
         if not self._active_given:
             return
         for e in self.engines:
-            st = getattr(e, "_s", None)
-            if getattr(e, "sh_planar", False) and st is not None and e.active_floats(int(st.sh_degree)) > self.pipe.n:
+            st = e._s
+            if e.sh_planar and st is not None and e.active_floats(int(st.sh_degree)) > self.pipe.n:
                 raise RuntimeError(f"ViewBatch: an engine renders at SH degree {int(st.sh_degree)} but only the first {self.pipe.n} "
                                    f"floats of a gradient row are folded / all-reduced: call set_active({int(st.sh_degree)})")
 
@@ -382,60 +385,23 @@ def _frame_batch(K, camera_stride, transl_stride):
     return fb
 
 
-class _FramesBase:
+class _FramesEngine(_Engine):
     """K frames (poses and / or cameras) of the SAME Gaussians per call: ONE dispatch per kernel for the K frames (the ``*_frames``
     entry points of include/sings_hip.h).  The reference hands its model 16 frames per call (``SinGS.forward_chunk``,
     sings_hybrid.py:474-569) and then renders them one by one (gs_trainer.py:684-714); a frame-parallel step renders K frames of the
-    same canonical Gaussians per rank.  Workspaces are K consecutive single-frame workspaces in one allocation each; the
-    per-Gaussian backward sums the K frames' gradients in registers and writes the gradient row once, in frame order -- bit
-    for bit what K single-frame calls leave behind when the first writes the buffer and the others add (``accumulate=1``)."""
+    same canonical Gaussians per rank.  The per-Gaussian backward sums the K frames' gradients in registers and writes the gradient
+    row once, in frame order -- bit for bit what K single-frame calls leave behind when the first writes the buffer and the others
+    add (``accumulate=1``).  ``set_camera``: one camera for all K frames ([4,4] matrices) or one per frame (``viewmatrix`` /
+    ``projmatrix`` [K,4,4], ``campos`` [K,3]: the other fields are shared).  A batch of frames is one "view" of a ViewBatch."""
+    _fb = None                            # the frame batch of the calls (RasterFramesEngine.set_camera, SkinnedFramesEngine.set_frames)
+    _cam_stride = 0                       # 1: one camera per frame
 
-    def _alloc(self, P, W, H, K, cap):
-        self.lib = _lib.load()
-        if not 1 <= K <= _lib.MAX_FRAMES:
-            raise ValueError(f"K must be 1..{_lib.MAX_FRAMES}")
-        self.P, self.W, self.H, self.K, self.cap = int(P), int(W), int(H), int(K), int(cap)
-        L = _lib.SgLayout()
-        sizes = [C.c_size_t() for _ in range(4)]
-        _lib.check(self.lib.sg_frames_layout(self.P, self.W, self.H, self.cap, self.K, C.byref(L), *[C.byref(x) for x in sizes]),
-                   "sg_frames_layout")
-        self.L = L
-        u8 = dict(dtype=torch.uint8, device=self.dev)
-        self.geom = torch.empty(sizes[0].value, **u8)
-        self.binning = torch.empty(sizes[1].value, **u8)
-        self.binning.view(self.K, L.bin_bytes)[:, :L.bin_ranges].zero_()     # counters zeroed ONCE (SG_FLAG_WS_CLEAN afterwards)
-        self._clean = True
-        self.img = torch.empty(sizes[2].value, **u8)
-        self.bwd_ws = torch.empty(sizes[3].value, **u8)
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        self.color = torch.empty((self.K, 3, self.H, self.W), **f32)
-        self.radii = torch.empty((self.K, self.P), dtype=torch.int32, device=self.dev)
-        self.d_means2D = torch.empty((self.K, self.P, 3), **f32)
-        self._keep, self._s, self._fb, self._cam_stride = [], None, None, 0
-        self.throughput = True            # K frames share the chip: no latency-only work (SG_FLAG_THROUGHPUT), as in ViewBatch
-        self._chain = None                # inside ViewBatch.run (a batch of frames is one "view" of the ViewBatch): see RasterEngine
-
-    def _chain_state(self, accumulate):
-        """(accumulate, done event) for this backward: inside a ViewBatch the batch adds to its gradient row iff an earlier batch
-        of the step wrote it (and, with one row across streams, waits for that batch's per-Gaussian half first)."""
-        acc, after, done = self._chain() if self._chain is not None else (False, None, None)
-        if after is not None:
-            torch.cuda.current_stream(self.dev).wait_event(after)
-        return bool(accumulate) or bool(acc), done
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-
-    def set_camera(self, raster_settings, long_rows=False):
-        """One camera for all K frames ([4,4] matrices) or one per frame (``viewmatrix`` / ``projmatrix`` [K,4,4], ``campos``
-        [K,3]: the other fields are shared).  ``long_rows``: SG_FLAG_LONG_ROWS (see SkinnedEngine.set_camera)."""
-        self._rows = _lib.FLAG_LONG_ROWS if long_rows else 0
-        self._keep = []
+    def _camera(self, raster_settings, rows):
         vm = raster_settings.viewmatrix
         per_frame = vm.dim() == 3
         if per_frame and (vm.shape[0] != self.K or raster_settings.projmatrix.shape[0] != self.K or raster_settings.campos.shape[0] != self.K):
             raise ValueError(f"per-frame cameras must be stacked [{self.K},4,4] / [{self.K},3]")
-        self._s = _settings_struct(raster_settings, self.dev, self.M, self._keep)
+        super()._camera(raster_settings, rows)
         self._cam_stride = 1 if per_frame else 0
 
     def num_rendered(self):
@@ -444,15 +410,8 @@ class _FramesBase:
                                                         self._stream()), "read R")
         return [int(v) for v in nr]
 
-    def _flags(self):
-        f = ((_lib.FLAG_WS_CLEAN if self._clean else 0) | (_lib.FLAG_THROUGHPUT if self.throughput else 0) |
-             (_lib.FLAG_SH_PLANAR if getattr(self, "sh_planar", False) else 0) | getattr(self, "_rows", 0))
-        return f
 
-    active_floats = _active_floats
-
-
-class SkinnedFramesEngine(_FramesBase):
+class SkinnedFramesEngine(_FramesEngine):
     """LBS-fused path, K posed frames of the same canonical Gaussians per call.  Flat gradient layout as ``SkinnedEngine``
     (xyz_canon 3P, scales 3P, opacity P, sh 3MP, [rot_canon]); per frame: ``color`` [K,3,H,W], ``radii`` [K,P], ``d_means2D``
     [K,P,3], ``d_A`` [K,J,16], ``d_transl`` [K,3].  ``aux``: the forward also writes ``depth`` and ``alpha`` [K,1,H,W] (the
@@ -460,13 +419,11 @@ class SkinnedFramesEngine(_FramesBase):
 
     def __init__(self, P, J, W, H, sh_coeffs, K, device, capacity_pairs, with_rot=False, grad_flat=None, rot_width=9, sh_planar=False,
                  aux=False):
-        self.dev = torch.device(device)
-        self.J, self.M = int(J), int(sh_coeffs)
-        self.sh_planar = bool(sh_planar)
         self.aux = bool(aux)
-        if self.aux and self.sh_planar:
+        if self.aux and sh_planar:
             raise ValueError("SkinnedFramesEngine: the depth / alpha maps (aux=True) do not support sh_planar")
-        self._alloc(P, W, H, K, capacity_pairs)
+        super().__init__(P, W, H, sh_coeffs, device, capacity_pairs, K)
+        self.J = int(J)
         f32 = dict(dtype=torch.float32, device=self.dev)
         self.aux_ws = self.depth = self.alpha = None
         if self.aux:
@@ -474,35 +431,9 @@ class SkinnedFramesEngine(_FramesBase):
             self.depth = torch.empty((self.K, 1, self.H, self.W), **f32)
             self.alpha = torch.empty((self.K, 1, self.H, self.W), **f32)
         self.skin_ws = torch.empty(int(self.lib.sg_skin_ws_floats_frames(self.P, self.K)), **f32)
-        rot_width = int(rot_width)
-        per = 3 + 3 + 1 + 3 * self.M + (rot_width if with_rot else 0)
-        if grad_flat is not None and (grad_flat.numel() != self.P * per or grad_flat.dtype != torch.float32
-                                      or not grad_flat.is_contiguous() or grad_flat.device != self.dev):
-            raise ValueError(f"grad_flat must be a contiguous fp32 tensor of {self.P * per} elements on {self.dev}")
-        self.grad_flat = torch.empty(self.P * per, **f32) if grad_flat is None else grad_flat.view(-1)
-        o = 0
-
-        def carve(n, *shape):
-            nonlocal o
-            v = self.grad_flat[o:o + n].view(*shape); o += n
-            return v
-        _carve_skinned(self, carve, with_rot, rot_width, grad_flat is None)
+        self._gradients(_skinned_fields(self.M, with_rot, rot_width), grad_flat, sh_planar)
         self.d_A = torch.empty((self.K, self.J, 16), **f32); self.d_transl = torch.empty((self.K, 3), **f32)
         self._k = None
-
-    def rebind_gradients(self, grad_flat):
-        """Point the gradient views at another flat buffer (several engines of one step sharing ONE buffer: FramePipeline)."""
-        if grad_flat.numel() != self.grad_flat.numel() or grad_flat.dtype != torch.float32 or not grad_flat.is_contiguous():
-            raise ValueError("rebind_gradients: a contiguous fp32 buffer of the same size")
-        with_rot, rw = self.d_rot is not None, (self.d_rot.shape[1] if self.d_rot is not None else 0)
-        self.grad_flat = grad_flat.view(-1)
-        o = 0
-
-        def carve(n, *shape):
-            nonlocal o
-            v = self.grad_flat[o:o + n].view(*shape); o += n
-            return v
-        _carve_skinned(self, carve, with_rot, rw, False)
 
     def set_frames(self, xyz_canon, rotmat_canon, lbs_weights, A, smpl_scale, transl):
         """``A``: [K,J,4,4] / [K,J,16] joint transforms of the K frames; ``transl``: [K,3] (one per frame), [3] (shared) or None."""
@@ -584,64 +515,39 @@ class SkinnedFramesEngine(_FramesBase):
     def backward_gaussians(self, shs, opacities, scales, accumulate=False):
         """Second half: record sums + the per-Gaussian chain rule summed over the K frames (latency-bound).  ``aux`` engines add
         every frame's dL/dz to its posed means and write the gradients (no ``accumulate``)."""
-        accumulate, done = self._chain_state(accumulate)
+        accumulate, done = self._chain_begin(accumulate)
         if self.aux and accumulate:
             raise ValueError("SkinnedFramesEngine: the depth / alpha maps (aux=True) write the gradients (no accumulate)")
         args = (C.byref(self._s), C.byref(self._fb), self.P, C.byref(self._k), _ptr(shs), _ptr(opacities), _ptr(scales),
                 _ptr(self.radii), _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.bwd_ws), _ptr(self.skin_ws),
-                int(bool(accumulate)), None, None, _ptr(self.d_xyz), _ptr(self.d_rot), _ptr(self.d_scales), _ptr(self.d_opacity),
+                int(accumulate), None, None, _ptr(self.d_xyz), _ptr(self.d_rot), _ptr(self.d_scales), _ptr(self.d_opacity),
                 _ptr(self.d_sh), _ptr(self.d_means2D), _ptr(self.d_A), _ptr(self.d_transl))
         if self.aux:
             _lib.check(self.lib.sg_skinned_backward_gaussians_frames_aux(*args, _ptr(self.aux_ws), self._stream()),
                        "skinned backward (gaussians, frames, depth / alpha maps)")
         else:
             _lib.check(self.lib.sg_skinned_backward_gaussians_frames(*args, self._stream()), "skinned backward (gaussians, frames)")
-        if done is not None:
-            done.record(torch.cuda.current_stream(self.dev))
+        self._chain_end(done)
 
 
-class RasterFramesEngine(_FramesBase):
+class RasterFramesEngine(_FramesEngine):
     """Un-skinned path: K cameras of the same Gaussians per call (``sg_rasterize_*_frames``).  Flat gradient layout as
-    ``RasterEngine``; ``color`` [K,3,H,W], ``radii`` [K,P], ``d_means2D`` [K,P,3]."""
+    ``RasterEngine`` (``sh_planar``: dL/dsh coefficient-major [M,P,3]); ``color`` [K,3,H,W], ``radii`` [K,P], ``d_means2D`` [K,P,3]."""
 
     def __init__(self, P, W, H, sh_coeffs, K, device, capacity_pairs, grad_flat=None, sh_planar=False):
-        self.dev = torch.device(device)
-        self.M = int(sh_coeffs)
-        self.sh_planar = bool(sh_planar)        # dL/dsh coefficient-major [M,P,3] (the SH block is LAST in this layout: the planes in
-        self._alloc(P, W, H, K, capacity_pairs)  # use are a prefix of it, active_floats(deg) floats of grad_flat carry gradient)
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        per = 3 + 3 + 4 + 1 + 3 * self.M
-        if grad_flat is not None and (grad_flat.numel() != self.P * per or grad_flat.dtype != torch.float32
-                                      or not grad_flat.is_contiguous() or grad_flat.device != self.dev):
-            raise ValueError(f"grad_flat must be a contiguous fp32 tensor of {self.P * per} elements on {self.dev}")
-        self.grad_flat = torch.empty(self.P * per, **f32) if grad_flat is None else grad_flat.view(-1)
-        o = 0
-
-        def carve(n, *shape):
-            nonlocal o
-            v = self.grad_flat[o:o + n].view(*shape); o += n
-            return v
-        self.d_means3D = carve(self.P * 3, self.P, 3); self.d_scales = carve(self.P * 3, self.P, 3)
-        self.d_rots = carve(self.P * 4, self.P, 4); self.d_opacity = carve(self.P, self.P, 1)
-        self._head = o
-        if not self.M:
-            self.d_sh = None
-        elif self.sh_planar:
-            self.d_sh = carve(self.P * 3 * self.M, self.M, self.P, 3)
-        else:
-            self.d_sh = carve(self.P * 3 * self.M, self.P, self.M, 3)
-        self._hint = 0
+        super().__init__(P, W, H, sh_coeffs, device, capacity_pairs, K)
+        self._gradients(_raster_fields(self.M), grad_flat, sh_planar)
 
     def set_camera(self, raster_settings, short_lists=False, long_rows=False):
-        super().set_camera(raster_settings, long_rows=long_rows)
-        self._hint = _lib.FLAG_SHORT_LISTS if short_lists else 0
+        """As ``RasterEngine.set_camera``, with one camera or K."""
+        self._camera(raster_settings, (_lib.FLAG_SHORT_LISTS if short_lists else 0) | (_lib.FLAG_LONG_ROWS if long_rows else 0))
         self._fb = _frame_batch(self.K, self._cam_stride, 0)
 
     def forward(self, means3D, shs, opacities, scales, rotations, sync_num_rendered=False):
         if self._s is None or self._fb is None:
             raise RuntimeError("RasterFramesEngine: set_camera() first")
         nr = (C.c_int64 * self.K)()
-        self._s.flags = self._hint | self._flags()
+        self._s.flags = self._flags()
         self._clean = False
         _lib.check(self.lib.sg_rasterize_forward_frames(
             C.byref(self._s), C.byref(self._fb), self.P, _ptr(means3D), _ptr(shs), None, _ptr(opacities), _ptr(scales),
@@ -654,14 +560,13 @@ class RasterFramesEngine(_FramesBase):
         _lib.check(self.lib.sg_rasterize_backward_records_frames(
             C.byref(self._s), C.byref(self._fb), self.P, _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.img),
             _ptr(self.bwd_ws), _ptr(dL_dcolor), self._stream()), "backward (records, frames)")
-        accumulate, done = self._chain_state(accumulate)
+        accumulate, done = self._chain_begin(accumulate)
         _lib.check(self.lib.sg_rasterize_backward_gaussians_frames(
             C.byref(self._s), C.byref(self._fb), self.P, _ptr(means3D), _ptr(shs), None, _ptr(opacities), _ptr(scales),
             _ptr(rotations), None, _ptr(self.radii), _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.bwd_ws),
-            int(bool(accumulate)), _ptr(self.d_means3D), _ptr(self.d_means2D), _ptr(self.d_sh), None, _ptr(self.d_opacity),
+            int(accumulate), _ptr(self.d_means3D), _ptr(self.d_means2D), _ptr(self.d_sh), None, _ptr(self.d_opacity),
             _ptr(self.d_scales), _ptr(self.d_rots), None, self._stream()), "backward (gaussians, frames)")
-        if done is not None:
-            done.record(torch.cuda.current_stream(self.dev))
+        self._chain_end(done)
 
 
 class FramePipeline:

@@ -126,6 +126,7 @@ class FrameAnimator:
         self.n = max(1, int(streams))
         self.streams = [torch.cuda.Stream(self.dev) for _ in range(self.n)]
         self.engs, self.shape, self.cap = [], None, 0
+        self._fengs, self._fshape, self._fcap = [], None, 0             # (the K-frame engines: _frame_engines)
         # SG_FLAG_LONG_ROWS (direct binning of few-tile frames: no tile list beyond 16384 entries), passed optimistically: every path
         # below reads the frames' counts before it hands an image out, and a frame that reports NUM_RENDERED_LONG_LIST is rendered
         # again without the hint -- which then stays off
@@ -157,6 +158,19 @@ class FrameAnimator:
             return _grown(need)
         return cap if long_list else None
 
+    def _launch(self, e, job, bg_color, scaling_modifier, cur):
+        """One frame on the current stream: ``job`` (a tuple of ``render_round``) through engine ``e`` -> the clamped image, for
+        use on stream ``cur``."""
+        cam, A, transl, smpl_scale, ext = job
+        c = self.canon
+        e.color = torch.empty((3, e.H, e.W), dtype=torch.float32, device=self.dev)    # handed to the caller
+        e.set_camera(_settings(cam, bg_color, scaling_modifier, c['active_sh_degree']), long_rows=self.long_rows)
+        e.set_frame(c['xyz_canon'], c.get('rotmat_canon'), c['lbs_weights'], A, smpl_scale, transl, ext)
+        e.forward(c['shs'], c['opacity'], c['scales'])
+        img = torch.clamp(e.color, 0.0, 1.0)
+        img.record_stream(cur)
+        return img
+
     def render_round(self, jobs, bg_color, scaling_modifier=1.0):
         """jobs: up to ``streams`` tuples (camera dict, A_cano2pose [J,4,4], transl | None, smpl_scale | None,
         ext_tfs | None) -> list of clamped images [3,H,W] (the keys 'render' of get_render_pkg_fused)."""
@@ -172,14 +186,9 @@ class FrameAnimator:
             outs = []
             for st in self.streams[:len(jobs)]:
                 st.wait_stream(cur)
-            for (cam, A, transl, smpl_scale, ext), e, st in zip(jobs, engs, self.streams):
+            for job, e, st in zip(jobs, engs, self.streams):
                 with torch.cuda.stream(st):
-                    e.color = torch.empty((3, H, W), dtype=torch.float32, device=self.dev)    # handed to the caller
-                    e.set_camera(_settings(cam, bg_color, scaling_modifier, c['active_sh_degree']), long_rows=self.long_rows)
-                    e.set_frame(c['xyz_canon'], c.get('rotmat_canon'), c['lbs_weights'], A, smpl_scale, transl, ext)
-                    e.forward(c['shs'], c['opacity'], c['scales'])
-                    outs.append(torch.clamp(e.color, 0.0, 1.0))
-                    outs[-1].record_stream(cur)
+                    outs.append(self._launch(e, job, bg_color, scaling_modifier, cur))
             for st in self.streams[:len(jobs)]:
                 cur.wait_stream(st)
             cap = self._settle([e.num_rendered() for e in engs[:len(jobs)]], self.cap)
@@ -201,7 +210,7 @@ class FrameAnimator:
         q = deque()
 
         def submit(i, job):
-            cam, A, transl, smpl_scale, ext = job
+            cam, A = job[0], job[1]
             J = int(A.reshape(-1, 16).shape[0])
             W, H = int(cam['image_width']), int(cam['image_height'])
             cap = _capacity_floor(self.cap, P, W, H)
@@ -210,16 +219,11 @@ class FrameAnimator:
             e, st = self._engines(J, W, H, cap)[i % self.n], self.streams[i % self.n]
             st.wait_stream(cur)                                  # the job's tensors were produced on the caller's stream
             with torch.cuda.stream(st):
-                e.color = torch.empty((3, H, W), dtype=torch.float32, device=self.dev)
-                e.set_camera(_settings(cam, bg_color, scaling_modifier, c['active_sh_degree']), long_rows=self.long_rows)
-                e.set_frame(c['xyz_canon'], c.get('rotmat_canon'), c['lbs_weights'], A, smpl_scale, transl, ext)
-                e.forward(c['shs'], c['opacity'], c['scales'])
-                img = torch.clamp(e.color, 0.0, 1.0)
+                img = self._launch(e, job, bg_color, scaling_modifier, cur)
                 slot = slots[i % len(slots)]
                 slot.copy_(e.binning[:8].view(torch.int32), non_blocking=True)      # header words 0, 1 = pair count R, flags
                 ev = torch.cuda.Event()
                 ev.record(st)
-            img.record_stream(cur)
             q.append((i, job, img, ev, slot, e.cap))          # (the capacity THIS frame was rendered with)
 
         def pop():
@@ -251,7 +255,7 @@ class FrameAnimator:
         P, M = int(c['xyz_canon'].shape[0]), int(c['shs'].shape[1])
         rot = c.get('rotmat_canon')
         key = (P, J, W, H, M, K, None if rot is None else int(rot.reshape(P, -1).shape[1]), bool(aux))
-        if getattr(self, "_fshape", None) != key or cap > getattr(self, "_fcap", 0):
+        if self._fshape != key or cap > self._fcap:
             self._fengs = []
             self._fengs = [SkinnedFramesEngine(P, J, W, H, M, K, self.dev, capacity_pairs=cap, with_rot=rot is not None,
                                                rot_width=9 if rot is None else key[6], aux=aux) for _ in range(self.n)]
@@ -310,7 +314,7 @@ class FrameAnimator:
                     raise ValueError("render_frames_batched: one smpl_scale per batch of frames")
             J = int(batch[0][1].reshape(-1, 16).shape[0])
             W, H = int(batch[0][0]['image_width']), int(batch[0][0]['image_height'])
-            cap = _capacity_floor(getattr(self, "_fcap", 0), P, W, H)
+            cap = _capacity_floor(self._fcap, P, W, H)
             engs = self._frame_engines(J, W, H, K, cap, return_aux)
             e, st = engs[state['b'] % self.n], self.streams[state['b'] % self.n]
             state['b'] += 1

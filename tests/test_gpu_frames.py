@@ -71,8 +71,7 @@ def test_skinned_frames_equal_single_frame_calls_bit_for_bit(K, per_frame_camera
         ref.set_frame(ins["xyz"], ins["rot"], ins["w"], A[f], ins["smpl_scale"], transl[f])
         R = ref.forward(ins["sh"], ins["op"], ins["sc"], sync_num_rendered=True)
         assert 0 < R <= cap
-        ref._chain = (lambda f=f: (f > 0, None, None))
-        ref.backward(ins["sh"], ins["op"], ins["sc"], dL[f])
+        ref.backward(ins["sh"], ins["op"], ins["sc"], dL[f], accumulate=f > 0)
         torch.cuda.synchronize()
         per_frame.append([x.clone() for x in (ref.color, ref.radii, ref.d_means2D, ref.d_A, ref.d_transl)] + [R])
     ref_grad = ref.grad_flat.clone()
@@ -253,8 +252,7 @@ def test_two_batches_of_a_step_share_one_gradient_buffer():
     for f in range(K):
         ref.set_frame(ins["xyz"], None, ins["w"], A[f], ins["smpl_scale"], transl[f])
         ref.forward(ins["sh"], ins["op"], ins["sc"])
-        ref._chain = (lambda f=f: (f > 0, None, None))
-        ref.backward(ins["sh"], ins["op"], ins["sc"], dL[f])
+        ref.backward(ins["sh"], ins["op"], ins["sc"], dL[f], accumulate=f > 0)
     torch.cuda.synchronize()
     flat = torch.empty_like(ref.grad_flat)
     a = SkinnedFramesEngine(N, J, W, H, 16, 4, dev, cap, grad_flat=flat)
@@ -297,8 +295,7 @@ def test_raster_frames_equal_single_camera_calls_bit_for_bit(K, deg, W, H):
     for f in range(K):
         ref.set_camera(settings(t(views[f]), t(projs[f]), t(cps[f])))
         R = ref.forward(*ins, sync_num_rendered=True)
-        ref._chain = (lambda f=f: (f > 0, None, None))
-        ref.backward(*ins, dL[f])
+        ref.backward(*ins, dL[f], accumulate=f > 0)
         torch.cuda.synchronize()
         per.append((ref.color.clone(), ref.radii.clone(), ref.d_means2D.clone(), R))
     eng = RasterFramesEngine(N, W, H, 16, K, dev, cap)
@@ -340,8 +337,7 @@ def test_raster_two_batches_of_a_step_share_one_gradient_buffer(deg, W, H):
     for f in range(K):
         ref.set_camera(settings(t(views[f]), t(projs[f]), t(cps[f])))
         ref.forward(*ins)
-        ref._chain = (lambda f=f: (f > 0, None, None))
-        ref.backward(*ins, dL[f])
+        ref.backward(*ins, dL[f], accumulate=f > 0)
     torch.cuda.synchronize()
     flat = torch.full_like(ref.grad_flat, float("nan"))
     a = RasterFramesEngine(N, W, H, 16, 3, dev, cap, grad_flat=flat)
@@ -407,8 +403,7 @@ def test_a_step_of_four_launches_on_two_streams_sums_like_twelve_single_views():
                 v = b * K + f
                 ref.set_camera(settings(t(views[v]), t(projs[v]), t(cps[v])))
                 ref.forward(*ins)
-                ref._chain = (lambda first=first: (not first, None, None))
-                ref.backward(*ins, dL[v])
+                ref.backward(*ins, dL[v], accumulate=not first)
                 first = False
         torch.cuda.synchronize()
         ref_rows.append(ref.grad_flat.clone())
@@ -618,8 +613,7 @@ def test_planar_sh_gradients_are_the_reference_layout_transposed(K):
             if planar and accumulate:
                 e.d_sh[1:].zero_()                                   # (planes not in use: never written, must come zeroed)
             e.forward(ins["sh"], ins["op"], ins["sc"])
-            e._chain = lambda: (accumulate, None, None)
-            e.backward(ins["sh"], ins["op"], ins["sc"], dL[0])
+            e.backward(ins["sh"], ins["op"], ins["sc"], dL[0], accumulate=accumulate)
         else:
             e = SkinnedFramesEngine(N, J, W, H, 16, K, dev, cap, sh_planar=planar)
             e.set_camera(one[0]); e.set_frames(ins["xyz"], None, ins["w"], A, ins["smpl_scale"], transl)
