@@ -94,7 +94,8 @@ typedef struct SgLayout {
  * sg_aux_layout, sg_rasterize_forward_aux / _backward_aux, sg_skinned_forward_aux / _backward_aux added (nothing else changed);
  * entry points added since 8: sg_frames_aux_layout, sg_skinned_forward_frames_aux, sg_rasterize_backward_records_frames_aux,
  * sg_skinned_backward_gaussians_frames_aux (depth and alpha maps of K frames); sg_lpips_weights_layout, sg_lpips_ws_bytes,
- * sg_lpips_forward, sg_lpips_backward, sg_lpips_patch_gather, sg_lpips_patch_scatter (the LPIPS-VGG patch loss). */
+ * sg_lpips_forward, sg_lpips_backward, sg_lpips_patch_gather, sg_lpips_patch_scatter (the LPIPS-VGG patch loss),
+ * sg_lpips_ws_layout (its workspace pieces). */
 #define SG_ABI_VERSION 8
 int sg_abi_version(void);
 const char *sg_version(void);
@@ -629,6 +630,18 @@ int sg_skinned_backward_gaussians_frames_aux(const SgRasterSettings *s, const Sg
  * given the same sizes, weights and workspace, and nothing may write the workspace in between.  dL_dout [B] (device),
  * dL_din0 [B][3][H][W].  Bit-reproducible; a tile never spans two images, so an image's value and gradient do not depend on the
  * rest of the batch.  No host synchronisation.
+ * sg_lpips_backward's `ws` is const for every piece but g_0 and g_1 (below): it writes its running gradient into those two as
+ * scratch and leaves every other byte of the workspace as the forward left it.  Two backward calls on one workspace must
+ * therefore not overlap in time (the same stream, or ordered by events); one after the other they give the same bits.
+ * Workspace (sg_lpips_ws_layout: the byte offsets of its SG_LPIPS_WS_NUM_PIECES pieces, each 256-aligned, in this order; the sizes
+ * sg_lpips_ws_bytes refuses, it refuses too).  Level v = 0..4 is H_v x W_v, H_0 = H, H_v = floor(H_{v-1} / 2) (W likewise).
+ * Activations are NHWC fp32 over 2B images, in0's B images first, then in1's:
+ *   y_l     (l = 0..12)  [2B][H_v][W_v][Cout_l], conv l's output after its ReLU (v = conv l's level: 0 0 1 1 2 2 2 3 3 3 4 4 4)
+ *   pool_q  (q = 0..3)   [2B][H_{q+1}][W_{q+1}][C] fp32, the MaxPool2d(2, 2) of the last y of level q (C = 64, 128, 256, 512)
+ *   arg_q   (q = 0..3)   [2B][H_{q+1}][W_{q+1}][C] uint8, the window element pool_q took: (dy << 1) | dx, the first maximum in
+ *                        row-major window order (torch's `val > max || isnan(val)`)
+ *   dpix_k  (k = 0..4)   [B][H_k W_k] fp32, slice k's per-pixel head term sum_c lin_c (n0_c - n1_c)^2
+ *   g_0, g_1             [B][H W][64] fp32, the backward's scratch (the forward neither writes nor reads them)
  * Patches: raw [K][3][H][W] (the UNCLAMPED render), gt_rgb [K][3][H][W], mask [K][H][W], bg [3], bg_rand [K][3][H][W], origins
  * [K][n][2] int32 (row, col) of each patch's top-left corner -- device data, clamped into [0, H - patch] x [0, W - patch].
  * pred_patches / gt_patches [K n][3][patch][patch]:
@@ -637,8 +650,10 @@ int sg_skinned_backward_gaussians_frames_aux(const SgRasterSettings *s, const Sg
  * zero outside all patches, the clip's and the clamp's inclusive pass bands applied). */
 #define SG_LPIPS_NUM_OFFSETS 46
 #define SG_LPIPS_MIN_SIZE 16
+#define SG_LPIPS_WS_NUM_PIECES 28
 int sg_lpips_weights_layout(size_t *offsets, size_t *total_floats);
 int sg_lpips_ws_bytes(int B, int height, int width, size_t *bytes);
+int sg_lpips_ws_layout(int B, int height, int width, size_t *offsets, size_t *total_bytes);
 int sg_lpips_forward(int B, int height, int width, int normalize, const float *weights, const float *in0, const float *in1, void *ws,
                      float *out, void *stream);
 int sg_lpips_backward(int B, int height, int width, int normalize, const float *weights, const void *ws, const float *dL_dout,

@@ -68,8 +68,9 @@ EXPORTS = ("sg_abi_version", "sg_version", "sg_last_error", "sg_layout", "sg_ras
            "sg_aux_layout", "sg_rasterize_forward_aux", "sg_rasterize_backward_aux", "sg_skinned_forward_aux", "sg_skinned_backward_aux",
            "sg_frames_aux_layout", "sg_skinned_forward_frames_aux", "sg_rasterize_backward_records_frames_aux",
            "sg_skinned_backward_gaussians_frames_aux", "sg_lpips_weights_layout", "sg_lpips_ws_bytes", "sg_lpips_forward",
-           "sg_lpips_backward", "sg_lpips_patch_gather", "sg_lpips_patch_scatter")
+           "sg_lpips_backward", "sg_lpips_patch_gather", "sg_lpips_patch_scatter", "sg_lpips_ws_layout")
 LPIPS_NUM_OFFSETS = 46               # SG_LPIPS_NUM_OFFSETS
+LPIPS_WS_NUM_PIECES = 28             # SG_LPIPS_WS_NUM_PIECES
 LPIPS_MIN_SIZE = 16                  # SG_LPIPS_MIN_SIZE
 NUM_KERNELS = 8
 ABI_VERSION = 8                      # SG_ABI_VERSION
@@ -218,12 +219,13 @@ def load():
     # LPIPS-VGG (entry points added to ABI 8)
     lib.sg_lpips_weights_layout.argtypes = [C.POINTER(sz), C.POINTER(sz)]
     lib.sg_lpips_ws_bytes.argtypes = [i32, i32, i32, C.POINTER(sz)]
+    lib.sg_lpips_ws_layout.argtypes = [i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]
     lib.sg_lpips_forward.argtypes = [i32, i32, i32, i32] + [vp] * 6
     lib.sg_lpips_backward.argtypes = [i32, i32, i32, i32] + [vp] * 5
     lib.sg_lpips_patch_gather.argtypes = [i32] * 5 + [vp] * 9
     lib.sg_lpips_patch_scatter.argtypes = [i32] * 5 + [vp] * 7
-    for f in ("sg_lpips_weights_layout", "sg_lpips_ws_bytes", "sg_lpips_forward", "sg_lpips_backward", "sg_lpips_patch_gather",
-              "sg_lpips_patch_scatter"):
+    for f in ("sg_lpips_weights_layout", "sg_lpips_ws_bytes", "sg_lpips_ws_layout", "sg_lpips_forward", "sg_lpips_backward",
+              "sg_lpips_patch_gather", "sg_lpips_patch_scatter"):
         getattr(lib, f).restype = C.c_int
     for f in ("sg_layout", "sg_rasterize_forward", "sg_rasterize_backward", "sg_mark_visible",
               "sg_read_num_rendered", "sg_skinned_forward", "sg_skinned_backward"):

@@ -453,6 +453,21 @@ extern "C" int sg_lpips_ws_bytes(int B, int height, int width, size_t *bytes)
     return 0;
 }
 
+extern "C" int sg_lpips_ws_layout(int B, int height, int width, size_t *offsets, size_t *total_bytes)
+{
+    LpPlan p;
+    if (!offsets || !total_bytes) return sg_set_error("sg_lpips_ws_layout: null pointer");
+    if (!lp_plan(B, height, width, p)) return sg_set_error("sg_lpips_ws_layout: B must be >= 1, H and W >= 16 (and 2 B H W 64 < 2^31)");
+    size_t *o = offsets;                                                    // y_0..12, pool_0..3, arg_0..3, dpix_0..4, g_0..1
+    for (int l = 0; l < LP_NCONV; l++) *o++ = p.y[l];
+    for (int q = 0; q < 4; q++) *o++ = p.pool[q];
+    for (int q = 0; q < 4; q++) *o++ = p.arg[q];
+    for (int k = 0; k < 5; k++) *o++ = p.dpix[k];
+    for (int i = 0; i < 2; i++) *o++ = p.g[i];
+    *total_bytes = p.total;
+    return 0;
+}
+
 extern "C" int sg_lpips_forward(int B, int height, int width, int normalize, const float *packed, const float *in0, const float *in1,
                                 void *ws, float *out, void *stream)
 {

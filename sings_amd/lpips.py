@@ -73,6 +73,16 @@ def _ws_bytes(B, H, W):
     return int(n.value)
 
 
+def ws_layout(B, H, W):
+    """Byte offsets of the forward's workspace pieces (sg_lpips_ws_layout; include/sings_hip.h says what each holds):
+    -> dict(y=[13], pool=[4], arg=[4], dpix=[5], g=[2], total=bytes).  For tests and inspection."""
+    offs = (C.c_size_t * _lib.LPIPS_WS_NUM_PIECES)()
+    total = C.c_size_t(0)
+    _lib.check(_lib.load().sg_lpips_ws_layout(B, H, W, offs, C.byref(total)), "sg_lpips_ws_layout")
+    o = [int(v) for v in offs]
+    return {"y": o[0:13], "pool": o[13:17], "arg": o[17:21], "dpix": o[21:26], "g": o[26:28], "total": int(total.value)}
+
+
 def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 

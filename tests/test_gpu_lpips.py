@@ -264,6 +264,37 @@ def test_step_with_lpips_matches_the_oracle_chain():
         assert d <= 2e-2 * r.abs().max().item() + 1e-12, d             # (branch flips of fp32 vs fp64: _check_grad)
 
 
+def test_step_with_lpips_matches_the_pinned_chain():
+    """The step above with the term's dL/drender from the fp64 chain pinned to the kernels' own forward state on the step's own
+    render (tests/test_gpu_lpips_pinned.py patch_chain): no branch flips to allow for, so within 1e-3 max|ref|."""
+    import test_gpu_lpips_pinned as pin
+    wt = lc.make_weights(0)
+    m = _model(wt)
+    step, a = _avatar(m, 0.9)
+    params = [p for p in step.parameters() if p.requires_grad]
+    org, bgr = _origins_and_bg(a)
+    loss, ld, ex = step(a["A"], a["rset"], a["gt"], a["mask"], a["bg"], smpl_scale=a["sc"], transl=a["tr"], lpips_origins=org,
+                        lpips_bg=bgr)
+    loss.backward()
+    got = [p.grad.clone() for p in params]
+    for p in params:
+        p.grad = None
+    step.lpips_w = 0.0
+    loss0, ld0, ex0 = step(a["A"], a["rset"], a["gt"], a["mask"], a["bg"], smpl_scale=a["sc"], transl=a["tr"], lpips_origins=org,
+                           lpips_bg=bgr)
+    raw = ex0["render_raw"].detach().contiguous()
+    H, W = raw.shape[1:]
+    out, _, ref, _ = pin.patch_chain(m.packed, wt, raw[None], a["gt"].reshape(1, 3, H, W).contiguous(),
+                                     a["mask"].reshape(1, H, W).contiguous(), a["bg"].contiguous(), bgr.reshape(1, 3, H, W).contiguous(),
+                                     org.reshape(1, -1, 2).to(torch.int32).contiguous(), 32, 0.9)
+    assert torch.equal(ld["lpips_patch"], (out.reshape(1, -1).mean(1) * 0.9).reshape(()))
+    torch.autograd.backward([loss0, ex0["render_raw"]], [torch.ones((), device=DEV), ref[0].float()])
+    for p, g in zip(params, got):
+        r = p.grad
+        d = (g - r).abs().max().item()
+        assert d <= 1e-3 * r.abs().max().item() + 1e-12, d
+
+
 def test_step_with_zero_weight_is_bit_equal_to_the_step_without_it():
     step0, a = _avatar()
     params0 = [p for p in step0.parameters() if p.requires_grad]

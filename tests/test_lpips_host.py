@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 import torch
+import torch.nn.functional as F
 
 import lpips_case as lc
 from sings_amd import _lib
@@ -128,3 +129,116 @@ def test_python_surface_refuses_without_gpu_or_bad_use():
         m(x, x.clone().requires_grad_(True))
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         m(x, x)
+
+
+# ---- the pinned fp64 reference (lpips_case.read_state / check_layers / pinned_backward) and the workspace layout ---------------
+def _inputs(B, H, W, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.rand(B, 3, H, W, generator=g), torch.rand(B, 3, H, W, generator=g)
+
+
+@pytest.mark.parametrize("normalize", (False, True))
+def test_pinned_reference_is_the_oracle_on_its_own_state(normalize):
+    """On the fp64 oracle's own masks, pool choices and features, check_layers passes at round-off and pinned_backward is autograd."""
+    wt = lc.make_weights(7)
+    x0, x1 = _inputs(2, 37, 53, 7)
+    st = lc.oracle_state(wt, x0, x1, normalize)
+    res = lc.check_layers(wt, x0, x1, normalize, st)
+    assert max(res["conv"]) <= 1e-9 and max(res["head"]) <= 1e-9 and res["out"] <= 1e-9 and res["pool"] == [0] * 4, res
+    up = torch.tensor([0.7, 1.3], dtype=torch.float64)
+    r0 = x0.double().requires_grad_(True)
+    lc.lpips_ref(wt, r0, x1.double(), normalize).backward(up.reshape(-1, 1, 1, 1))
+    got = lc.pinned_backward(wt, st, up, normalize)
+    assert got.shape == r0.shape and (r0.grad != 0).any()
+    assert ((got - r0.grad).abs() <= 1e-10 * r0.grad.abs().max()).all()
+
+
+def test_pinned_bounds_hold_for_torch_fp32_at_the_training_shape():
+    """Calibration: torch's own fp32 CPU forward meets check_layers' bounds, and its fp32 autograd gradient meets the strict
+    per-element bound against the fp64 backward pinned to its masks -- at 128^2, where it fails the unpinned comparison."""
+    wt = lc.make_weights(0)
+    g = torch.Generator().manual_seed(0)
+    x0 = torch.rand(1, 3, 128, 128, generator=g); x1 = (x0 + 0.1 * torch.randn(1, 3, 128, 128, generator=g)).clamp(0, 1)
+    st = lc.oracle_state(wt, x0, x1, dtype=torch.float32)
+    res = lc.check_layers(wt, x0, x1, False, st)
+    up = torch.tensor([0.8])
+    a = x0.clone().requires_grad_(True)
+    lc.lpips_ref(wt, a, x1, dtype=torch.float32).backward(up.reshape(-1, 1, 1, 1))
+    ref = lc.pinned_backward(wt, st, up)
+    err = (a.grad.double() - ref).abs()
+    bound = 2e-4 * ref.abs() + 2e-5 * ref.abs().max()
+    print(f"torch fp32 at 128^2: worst conv ratio {max(res['conv']):.3g}, head {max(res['head']):.3g}, out {res['out']:.3g}; "
+          f"grad worst ratio {(err / bound).max().item():.3g}")
+    assert (err <= bound).all(), (err / bound).max().item()
+
+
+def test_pinned_checks_reject_a_wrong_layer_pool_or_mask():
+    wt = lc.make_weights(7)
+    x0, x1 = _inputs(2, 37, 53, 8)
+    up = torch.tensor([0.7, 1.3], dtype=torch.float64)
+    st = lc.oracle_state(wt, x0, x1)
+    base = lc.pinned_backward(wt, st, up)
+    # one conv 5 output off by 1e-3 of its magnitude sum
+    y = st["y"][5]
+    c, i, j = (int(v) for v in (y[1] > 0).nonzero()[100])
+    w, b = (t.double() for t in wt["convs"][5])
+    mag = b.abs()[c] + F.conv2d(st["y"][4][1:2].abs(), w.abs(), padding=1)[0, c, i, j]
+    bad = dict(st, y=list(st["y"]))
+    bad["y"][5] = y.clone(); bad["y"][5][1, c, i, j] += 1e-3 * mag
+    with pytest.raises(AssertionError, match=f"^conv 5: worst at image 1, channel {c}, row {i}, column {j}"):
+        lc.check_layers(wt, x0, x1, False, bad)
+    # one pool choice (of a window whose maximum is positive, so its ReLU passes the gradient) moved to another window element
+    a = st["arg"][1]
+    c, i, j = (int(v) for v in (st["pool"][1][0] > 0).nonzero()[40])
+    bad = dict(st, arg=list(st["arg"]))
+    bad["arg"][1] = a.clone(); bad["arg"][1][0, c, i, j] = (a[0, c, i, j] + 1) % 4
+    with pytest.raises(AssertionError, match=f"^pool 1: 1 elements wrong, first at image 0, channel {c}, pixel \\({i}, {j}\\)"):
+        lc.check_layers(wt, x0, x1, False, bad)
+    assert not torch.equal(lc.pinned_backward(wt, bad, up), base)
+    # one ReLU mask bit flipped (conv 4 is neither a slice output nor a pool input: only its mask reads it)
+    on = (st["y"][4][0] > 0).nonzero()[50]
+    bad = dict(st, y=list(st["y"]))
+    bad["y"][4] = st["y"][4].clone(); bad["y"][4][0, on[0], on[1], on[2]] = 0
+    assert not torch.equal(lc.pinned_backward(wt, bad, up), base)
+
+
+LAYOUT_SIZES = ((1, 16, 16), (2, 37, 53), (16, 128, 128), (1, 512, 896))
+
+
+@pytest.mark.parametrize("B,H,W", LAYOUT_SIZES)
+def test_ws_layout_pieces_tile_the_workspace(B, H, W):
+    lay = L.ws_layout(B, H, W)
+    assert lay["total"] == L._ws_bytes(B, H, W)
+    hs, ws = lc.level_sizes(H, W)
+    NI = 2 * B
+    pieces = ([(f"y{l}", lay["y"][l], NI * hs[v] * ws[v] * L.CONV_CHANNELS[l][1] * 4) for l, v in enumerate(lc.LEVEL)] +
+              [(f"pool{q}", lay["pool"][q], NI * hs[q + 1] * ws[q + 1] * lc.POOL_CH[q] * 4) for q in range(4)] +
+              [(f"arg{q}", lay["arg"][q], NI * hs[q + 1] * ws[q + 1] * lc.POOL_CH[q]) for q in range(4)] +
+              [(f"dpix{k}", lay["dpix"][k], B * hs[k] * ws[k] * 4) for k in range(5)] +
+              [(f"g{i}", lay["g"][i], B * H * W * 64 * 4) for i in range(2)])
+    assert len(pieces) == _lib.LPIPS_WS_NUM_PIECES
+    for kind in ("y", "pool", "arg", "dpix", "g"):
+        assert lay[kind] == sorted(lay[kind]), kind
+    assert max(o for _, o, _ in pieces[:-2]) < lay["g"][0]                       # the backward's scratch comes last
+    pieces.sort(key=lambda p: p[1])
+    assert pieces[0][1] == 0
+    for (n0, o0, s0), (n1, o1, _) in zip(pieces, pieces[1:]):
+        assert o0 % 256 == 0 and o0 + s0 <= o1, (n0, n1)
+    name, o, s = pieces[-1]
+    assert o % 256 == 0 and o + s <= lay["total"] < o + s + 256, name
+
+
+def test_ws_layout_refuses_what_ws_bytes_refuses():
+    lib = _lib.load()
+    offs = (C.c_size_t * _lib.LPIPS_WS_NUM_PIECES)()
+    n, t = C.c_size_t(0), C.c_size_t(0)
+    for B, H, W in ((0, 128, 128), (1, 15, 128), (1, 128, 15), (-1, 64, 64), (1, 16, 16), (1, 4096, 4096), (1, 4096, 4095),
+                    (2, 2048, 4096), (2, 2048, 4095), (1 << 20, 16, 16), (3, 37, 53)):
+        a = lib.sg_lpips_ws_bytes(B, H, W, C.byref(n))
+        t.value = 7
+        b = lib.sg_lpips_ws_layout(B, H, W, offs, C.byref(t))
+        assert (a == 0) == (b == 0), (B, H, W)
+        assert t.value == (n.value if a == 0 else 7), (B, H, W)
+        if b:
+            assert b"sg_lpips_ws_layout" in lib.sg_last_error()
+    assert lib.sg_lpips_ws_layout(1, 16, 16, None, C.byref(t)) != 0 and lib.sg_lpips_ws_layout(1, 16, 16, offs, None) != 0
