@@ -95,7 +95,9 @@ typedef struct SgLayout {
  * entry points added since 8: sg_frames_aux_layout, sg_skinned_forward_frames_aux, sg_rasterize_backward_records_frames_aux,
  * sg_skinned_backward_gaussians_frames_aux (depth and alpha maps of K frames); sg_lpips_weights_layout, sg_lpips_ws_bytes,
  * sg_lpips_forward, sg_lpips_backward, sg_lpips_patch_gather, sg_lpips_patch_scatter (the LPIPS-VGG patch loss),
- * sg_lpips_ws_layout (its workspace pieces). */
+ * sg_lpips_ws_layout (its workspace pieces); sg_frames_to_u8 (8-bit HWC frames).  Also since 8: SgFrameBatch.reserved became
+ * SgFrameBatch.placement (per-frame ext_tfs / smpl_scale in the skinned K-frame forward); 0, what every ABI-8 caller passes, keeps
+ * the earlier meaning. */
 #define SG_ABI_VERSION 8
 int sg_abi_version(void);
 const char *sg_version(void);
@@ -331,8 +333,20 @@ typedef struct SgFrameBatch {
     int32_t K;               /* frames in this call, 1..SG_MAX_FRAMES */
     int32_t camera_stride;   /* 0 | 1 */
     int32_t transl_stride;   /* 0 | 3 (floats) */
-    int32_t reserved;        /* 0 */
+    int32_t placement;       /* SG_PLACEMENT_* bits (0: one ext_tfs set and one smpl_scale for all K frames; before ABI 8's
+                                additions below this field was `reserved`, 0) */
 } SgFrameBatch;
+/* SgFrameBatch.placement (skinned K-frame FORWARD only: sg_skinned_forward_frames[_aux]): what the animation loop of the reference
+ * hands its model per frame (AnimDataset_opt.get_chunk -> SinGS.forward_chunk, sings_hybrid.py:512-553).
+ *   SG_PLACEMENT_EXT_TFS     skin->ext_trans [K,3], ext_rot [K,9], ext_scale [K]: frame f's placement at + 3 f / 9 f / f floats
+ *                            (needs all three pointers).  Without the bit one [3] / [9] / [1] set serves every frame.
+ *   SG_PLACEMENT_SMPL_SCALE  skin->smpl_scale [K]: frame f's scale at + f (needs smpl_scale).  Without it one [1] serves every frame.
+ * Per frame, the posed outputs (posed_xyz / posed_rotq / posed_scales [K,P,.]), images, radii and maps are bit for bit those of K
+ * single-frame sg_skinned_forward[_aux] calls with that frame's ext_tfs and smpl_scale.  Unknown bits, a bit without its pointers,
+ * and any bit in the K-frame backward entry points or sg_rasterize_forward_frames are refused (status 1, sg_last_error names the
+ * flag) before anything is launched: like ext_tfs, a per-frame placement or scale is forward-only. */
+#define SG_PLACEMENT_EXT_TFS 1
+#define SG_PLACEMENT_SMPL_SCALE 2
 /* sizes of the K-frame workspaces (K x the single-frame sizes, which are returned in *one; bwd: see above); any output pointer may
  * be NULL */
 int sg_frames_layout(int P, int width, int height, size_t capacity_pairs, int K, SgLayout *one, size_t *geom_bytes,
@@ -663,6 +677,14 @@ int sg_lpips_patch_gather(int K, int n, int patch, int height, int width, const 
                           void *stream);
 int sg_lpips_patch_scatter(int K, int n, int patch, int height, int width, const float *raw, const float *mask, const float *bg_rand,
                            const int32_t *origins, const float *dL_dpred_patches, float *dL_draw, void *stream);
+
+/* ---- frames out as 8-bit HWC (entry point added to ABI 8) -------------------------------------------------------------------------
+ * The last step of the reference's animation loop (gs_trainer.py:717-719: `(clamp(x, 0, 1) * 255).astype(uint8)`, then cvtColor to
+ * BGR) on the device, one launch for K frames: rgb [K,3,H,W] fp32 -> out [K,H,W,3] uint8, element by element
+ *   v = fminf(fmaxf(x, 0), 1);  out = (uint8_t)(v * 255.0f)      (one fp32 multiply, truncation; NaN -> 0, +inf -> 255)
+ * with the channels in RGB order, or BGR when bgr != 0.  Any K >= 1 (<= 65535), width, height >= 1 (odd sizes too); rgb and out must
+ * not overlap.  Bad sizes and NULL pointers are refused (status 1, sg_last_error) before anything is launched. */
+int sg_frames_to_u8(int K, int width, int height, const float *rgb, int bgr, uint8_t *out, void *stream);
 
 /* ---- optional per-kernel timing (bench / profiling only; process-global, not thread-safe).
  * When enabled, every kernel launch of forward/backward is bracketed by hipEvents on the

@@ -37,10 +37,14 @@ class SgSkinInputs(C.Structure):
 
 
 class SgFrameBatch(C.Structure):
-    _fields_ = [("K", C.c_int32), ("camera_stride", C.c_int32), ("transl_stride", C.c_int32), ("reserved", C.c_int32)]
+    _fields_ = [("K", C.c_int32), ("camera_stride", C.c_int32), ("transl_stride", C.c_int32), ("placement", C.c_int32)]
+    # the field's name before it carried the SG_PLACEMENT_* bits (always 0 then)
+    reserved = property(lambda self: self.placement, lambda self, v: setattr(self, "placement", v))
 
 
 MAX_FRAMES = 16                      # SG_MAX_FRAMES
+PLACEMENT_EXT_TFS = 1                # SG_PLACEMENT_EXT_TFS: ext_tfs [K,3] / [K,9] / [K], one set per frame
+PLACEMENT_SMPL_SCALE = 2             # SG_PLACEMENT_SMPL_SCALE: smpl_scale [K], one per frame
 
 
 class SgLinearSide(C.Structure):
@@ -68,7 +72,7 @@ EXPORTS = ("sg_abi_version", "sg_version", "sg_last_error", "sg_layout", "sg_ras
            "sg_aux_layout", "sg_rasterize_forward_aux", "sg_rasterize_backward_aux", "sg_skinned_forward_aux", "sg_skinned_backward_aux",
            "sg_frames_aux_layout", "sg_skinned_forward_frames_aux", "sg_rasterize_backward_records_frames_aux",
            "sg_skinned_backward_gaussians_frames_aux", "sg_lpips_weights_layout", "sg_lpips_ws_bytes", "sg_lpips_forward",
-           "sg_lpips_backward", "sg_lpips_patch_gather", "sg_lpips_patch_scatter", "sg_lpips_ws_layout")
+           "sg_lpips_backward", "sg_lpips_patch_gather", "sg_lpips_patch_scatter", "sg_lpips_ws_layout", "sg_frames_to_u8")
 LPIPS_NUM_OFFSETS = 46               # SG_LPIPS_NUM_OFFSETS
 LPIPS_WS_NUM_PIECES = 28             # SG_LPIPS_WS_NUM_PIECES
 LPIPS_MIN_SIZE = 16                  # SG_LPIPS_MIN_SIZE
@@ -227,6 +231,8 @@ def load():
     for f in ("sg_lpips_weights_layout", "sg_lpips_ws_bytes", "sg_lpips_ws_layout", "sg_lpips_forward", "sg_lpips_backward",
               "sg_lpips_patch_gather", "sg_lpips_patch_scatter"):
         getattr(lib, f).restype = C.c_int
+    # 8-bit HWC frames (entry point added to ABI 8)
+    lib.sg_frames_to_u8.argtypes = [i32, i32, i32, vp, i32, vp, vp]; lib.sg_frames_to_u8.restype = C.c_int
     for f in ("sg_layout", "sg_rasterize_forward", "sg_rasterize_backward", "sg_mark_visible",
               "sg_read_num_rendered", "sg_skinned_forward", "sg_skinned_backward"):
         getattr(lib, f).restype = C.c_int

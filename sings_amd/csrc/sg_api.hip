@@ -195,8 +195,28 @@ static int sg_make_batch(const SgFrameBatch *fb, int P, const SgCam &c, const Sg
     if (fb->camera_stride != 0 && fb->camera_stride != 1) return 1;
     if (fb->transl_stride != 0 && fb->transl_stride != 3) return 1;
     bt->K = fb->K; bt->cam_stride = fb->camera_stride; bt->transl_stride = fb->transl_stride; bt->P = P;
+    bt->placement = fb->placement;                                   // (checked by sg_check_placement)
     bt->geom = L.geom_bytes; bt->bin = L.bin_bytes; bt->img = L.img_bytes; bt->rec = sg_rec_bytes(cap);
     bt->image = (size_t)3 * (size_t)c.W * (size_t)c.H;
+    return 0;
+}
+
+// SgFrameBatch.placement (SG_PLACEMENT_*), checked before anything else of the frame batch is used: `skin` is the call's skin inputs
+// for the skinned K-frame forward, the only calls that take the bits; nullptr for every other entry point (any bit refused)
+static int sg_check_placement(const char *who, const SgFrameBatch *fb, const SgSkinInputs *skin)
+{
+    if (!fb || !fb->placement) return 0;
+    const int known = SG_PLACEMENT_EXT_TFS | SG_PLACEMENT_SMPL_SCALE;
+    if (fb->placement & ~known) return sg_failf("%s: unknown SgFrameBatch.placement bits 0x%x", who, fb->placement & ~known);
+    if (!skin) {
+        const char *flag = (fb->placement & SG_PLACEMENT_EXT_TFS) ? "SG_PLACEMENT_EXT_TFS" : "SG_PLACEMENT_SMPL_SCALE";
+        return sg_failf("%s: %s is not supported here (per-frame ext_tfs / smpl_scale are forward-only: the skinned K-frame forward)",
+                        who, flag);
+    }
+    if ((fb->placement & SG_PLACEMENT_EXT_TFS) && !(skin->ext_trans && skin->ext_rot && skin->ext_scale))
+        return sg_failf("%s: SG_PLACEMENT_EXT_TFS without ext_trans / ext_rot / ext_scale", who);
+    if ((fb->placement & SG_PLACEMENT_SMPL_SCALE) && !skin->smpl_scale)
+        return sg_failf("%s: SG_PLACEMENT_SMPL_SCALE without smpl_scale", who);
     return 0;
 }
 
@@ -282,10 +302,12 @@ static int sg_forward_impl(const char *who, const SgRasterSettings *s, const SgF
     }
     if (skin) {
         if (sg_check_skin(skin, P, true)) return sg_failf("%s: bad skin inputs (J in 1..64, ext_tfs all or none)", who);
+        if (sg_check_placement(who, fb, skin)) return 1;
         if (P < 0 || !geom_ws || !binning_ws || !image_ws || !out_color || (P > 0 && (!shs || !opacities || !scales || !radii)))
             return sg_failf("%s: null pointer", who);
         if (s->sh_coeffs < (s->sh_degree + 1) * (s->sh_degree + 1)) return sg_failf("%s: sh_coeffs smaller than (sh_degree+1)^2", who);
     } else {
+        if (sg_check_placement(who, fb, nullptr)) return 1;
         if (P < 0 || !geom_ws || !binning_ws || !image_ws || !out_color || (P > 0 && (!means3D || !opacities || !radii)))
             return sg_failf("%s: null pointer", who);
         if (P > 0 && ((shs != nullptr) == (colors_precomp != nullptr))) return sg_failf("%s: provide exactly one of shs / colors_precomp", who);
@@ -366,14 +388,16 @@ extern "C" int sg_read_num_rendered_frames(const void *binning_ws, int P, int wi
 
 // ---- backward ----------------------------------------------------------------------------------------------------------------
 // Every backward entry point checks, in this order: settings, the flags of the maps, accumulate (refused with the maps), skin inputs,
-// aux_ws (sg_bwd_check); then returns 0 for P <= 0, checks its other pointers and last its frame batch (sg_bwd_layout).
+// the frame batch's placement bits (forward-only: refused), aux_ws (sg_bwd_check); then returns 0 for P <= 0, checks its other
+// pointers and last the rest of its frame batch (sg_bwd_layout).
 static int sg_bwd_check(const char *who, const SgRasterSettings *s, SgCam *c, SgAux aux, int accumulate, bool skinned,
-                        const SgSkinInputs *skin, int P, const void *aux_ws)
+                        const SgSkinInputs *skin, int P, const void *aux_ws, const SgFrameBatch *fb)
 {
     if (sg_make_cam(s, c)) return sg_failf("%s: bad settings", who);
     if (aux && sg_aux_flags(who, c->flags, aux == SG_AUX_FRAMES)) return 1;
     if (aux && accumulate) return sg_failf("%s: accumulate != 0 is not supported with depth / alpha maps", who);
     if (skinned && sg_check_skin(skin, P, false)) return sg_failf("%s: bad skin inputs (ext_tfs are forward-only)", who);
+    if (sg_check_placement(who, fb, nullptr)) return 1;
     if (aux && !aux_ws) return sg_failf("%s: null pointer (aux_ws)", who);
     return 0;
 }
@@ -394,7 +418,7 @@ static int sg_records_impl(const char *who, const SgRasterSettings *s, const SgF
     SgCam c;
     SgLayout L;
     SgBatch bt;
-    if (sg_bwd_check(who, s, &c, aux, 0, false, nullptr, P, aux_ws)) return 1;
+    if (sg_bwd_check(who, s, &c, aux, 0, false, nullptr, P, aux_ws, fb)) return 1;
     if (P <= 0) return 0;
     if (!geom_ws || !binning_ws || !image_ws || !bwd_ws || !dL_dout_color) return sg_failf("%s: null pointer", who);
     if (sg_bwd_layout(who, fb, P, c, cap, &L, &bt)) return 1;
@@ -421,7 +445,7 @@ static int sg_gaussians_impl(const char *who, const SgRasterSettings *s, const S
     SgCam c;
     SgLayout L;
     SgBatch bt;
-    if (sg_bwd_check(who, s, &c, aux, accumulate, false, nullptr, P, aux_ws)) return 1;
+    if (sg_bwd_check(who, s, &c, aux, accumulate, false, nullptr, P, aux_ws, fb)) return 1;
     if (P <= 0) return 0;
     if (!means3D || !radii || !geom_ws || !binning_ws || !bwd_ws || !dL_dmeans3D || !dL_dmeans2D || !dL_dopacity)
         return sg_failf("%s: null pointer", who);
@@ -451,7 +475,7 @@ static int sg_skin_gaussians_impl(const char *who, const SgRasterSettings *s, co
     SgCam c;
     SgLayout L;
     SgBatch bt;
-    if (sg_bwd_check(who, s, &c, aux, accumulate, true, skin, P, aux_ws)) return 1;
+    if (sg_bwd_check(who, s, &c, aux, accumulate, true, skin, P, aux_ws, fb)) return 1;
     if (P <= 0) return 0;
     if (!shs || !scales || !radii || !geom_ws || !binning_ws || !bwd_ws || !skin_ws || !dL_dxyz_canon || !dL_dscales ||
         !dL_dopacity || !dL_dsh || !dL_dmeans2D || !dL_dA)
@@ -478,7 +502,7 @@ static int sg_rasterize_backward_impl(const char *who, const SgRasterSettings *s
                                       void *aux_ws = nullptr, const float *dL_ddepth = nullptr, const float *dL_dalpha = nullptr)
 {
     SgCam c;
-    if (sg_bwd_check(who, s, &c, aux, 0, false, nullptr, P, aux_ws)) return 1;
+    if (sg_bwd_check(who, s, &c, aux, 0, false, nullptr, P, aux_ws, &SG_ONE_FRAME)) return 1;
     if (P <= 0) return 0;
     if (!means3D || !radii || !geom_ws || !binning_ws || !image_ws || !bwd_ws || !dL_dout_color || !dL_dmeans3D ||
         !dL_dmeans2D || !dL_dopacity)
@@ -579,7 +603,7 @@ static int sg_skinned_backward_impl(const char *who, const SgRasterSettings *s, 
                                     const float *dL_ddepth = nullptr, const float *dL_dalpha = nullptr)
 {
     SgCam c;
-    if (sg_bwd_check(who, s, &c, aux, 0, true, skin, P, aux_ws)) return 1;
+    if (sg_bwd_check(who, s, &c, aux, 0, true, skin, P, aux_ws, &SG_ONE_FRAME)) return 1;
     if (P <= 0) return 0;
     if (!shs || !scales || !radii || !geom_ws || !binning_ws || !image_ws || !bwd_ws || !skin_ws || !dL_dout_color ||
         !dL_dxyz_canon || !dL_dscales || !dL_dopacity || !dL_dsh || !dL_dmeans2D || !dL_dA)

@@ -223,6 +223,7 @@ struct SgBatch {
     int K;                         // frames in this launch
     int cam_stride;                // 0: one camera for all frames; 1: frame f reads view + 16 f, proj + 16 f, campos + 3 f
     int transl_stride;             // floats between the frames' translations (0 or 3)
+    int placement;                 // SG_PLACEMENT_* (skinned forward): per-frame ext_tfs / smpl_scale, read by sg_skin_frame
     int P;                         // Gaussians (radii / means2D of frame f at + f P)
     size_t geom, bin, img, rec;    // bytes between consecutive frames' workspaces
     size_t image;                  // floats of one [3,H,W] image (out_color / dL_dout_color of frame f at + f image)

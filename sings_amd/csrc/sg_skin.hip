@@ -243,11 +243,16 @@ __device__ __forceinline__ void sg_load_A(const SgSkin &k, float *__restrict__ s
     for (int i = threadIdx.x; i < Jp * 16; i += blockDim.x) sA[i] = i < k.J * 16 ? k.A[i] : 0.0f;
 }
 
-// frame f of a launch of bt.K frames: joint transforms A + 16 J f, translation + transl_stride f (sg_frame for the rest)
+// frame f of a launch of bt.K frames: joint transforms A + 16 J f, translation + transl_stride f, and with the SG_PLACEMENT_* bits
+// (forward only) ext_tfs + (3, 9, 1) f and smpl_scale + f (sg_frame for the rest)
 __device__ __forceinline__ SgSkin sg_skin_frame(SgSkin k, int frame, const SgBatch &bt)
 {
     k.A += (size_t)frame * k.J * 16;
     if (k.transl) k.transl += (size_t)frame * bt.transl_stride;
+    if ((bt.placement & SG_PLACEMENT_EXT_TFS) && k.ext_rot) {
+        k.ext_trans += 3 * frame; k.ext_rot += 9 * frame; k.ext_scale += frame;
+    }
+    if ((bt.placement & SG_PLACEMENT_SMPL_SCALE) && k.smpl_scale) k.smpl_scale += frame;
     return k;
 }
 

@@ -379,10 +379,25 @@ class ViewBatch:
         return self.pipe.reduce()
 
 
-def _frame_batch(K, camera_stride, transl_stride):
+def _frame_batch(K, camera_stride, transl_stride, placement=0):
     fb = _lib.SgFrameBatch()
-    fb.K, fb.camera_stride, fb.transl_stride, fb.reserved = int(K), int(camera_stride), int(transl_stride), 0
+    fb.K, fb.camera_stride, fb.transl_stride, fb.placement = int(K), int(camera_stride), int(transl_stride), int(placement)
     return fb
+
+
+def _frame_rows(t, K, width, name):
+    """An input of K frames that may be shared -> (tensor, per_frame): ONE set of ``width`` floats for every frame (``width``
+    elements -- a leading 1 included -- or an ``.expand`` view, stride 0 along the frames: its first row, not copied), or K rows
+    [K, width] (per_frame True)."""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name} must be a tensor")
+    if t.numel() == width:
+        return t.reshape(width), False
+    if t.dim() >= 1 and t.shape[0] == K and t[0].numel() == width:
+        if t.stride(0) == 0:
+            return t[0].reshape(width), False
+        return t.reshape(K, width), True
+    raise ValueError(f"{name} must be [{width}] (one for all frames) or [{K},{width}] (one per frame), got {tuple(t.shape)}")
 
 
 class _FramesEngine(_Engine):
@@ -434,9 +449,15 @@ class SkinnedFramesEngine(_FramesEngine):
         self._gradients(_skinned_fields(self.M, with_rot, rot_width), grad_flat, sh_planar)
         self.d_A = torch.empty((self.K, self.J, 16), **f32); self.d_transl = torch.empty((self.K, 3), **f32)
         self._k = None
+        self._forward_only = False        # set_frames: the frames carry ext_tfs or a per-frame smpl_scale (no backward)
 
-    def set_frames(self, xyz_canon, rotmat_canon, lbs_weights, A, smpl_scale, transl):
-        """``A``: [K,J,4,4] / [K,J,16] joint transforms of the K frames; ``transl``: [K,3] (one per frame), [3] (shared) or None."""
+    def set_frames(self, xyz_canon, rotmat_canon, lbs_weights, A, smpl_scale, transl, ext_tfs=None):
+        """``A``: [K,J,4,4] / [K,J,16] joint transforms of the K frames; ``transl``: [K,3] (one per frame), [3] (shared) or None.
+        ``smpl_scale``: None, [1] (shared) or [K] / [K,1] (one per frame).  ``ext_tfs``: None or the placement (trans, rotmat, scale)
+        of sings_hybrid.py:421-428, shared ([3], [3,3], [1], or with a leading 1) or one per frame ([K,3], [K,3,3], [K,1]); an
+        ``.expand`` view (the reference's AnimDataset_opt.get_chunk) is passed as the one shared set it is.  Per-frame sets reach
+        the kernels as SgFrameBatch.placement bits (include/sings_hip.h, SG_PLACEMENT_*).  A placement or a per-frame scale is
+        forward-only, as in the reference (no_grad): ``backward*`` then raises."""
         from .skinned import _skin_struct
         A = A.reshape(self.K, -1, 16)
         if A.shape[1] != self.J:
@@ -451,14 +472,31 @@ class SkinnedFramesEngine(_FramesEngine):
                 tstride = 3
             else:
                 raise ValueError(f"transl must be [{self.K},3] or [3]")
+        placement = 0
+        if smpl_scale is not None:
+            smpl_scale, per = _frame_rows(smpl_scale, self.K, 1, "smpl_scale")
+            placement |= _lib.PLACEMENT_SMPL_SCALE if per else 0
+        if ext_tfs is not None:
+            rows = [_frame_rows(x, self.K, w, n) for x, w, n in zip(ext_tfs, (3, 9, 1), ("ext trans", "ext rotmat", "ext scale"))]
+            if any(per for _, per in rows):                  # (one set per frame for all three: a shared one is repeated)
+                ext_tfs = tuple(x if per else x.reshape(1, -1).expand(self.K, -1) for x, per in rows)
+                placement |= _lib.PLACEMENT_EXT_TFS
+            else:
+                ext_tfs = tuple(x for x, _ in rows)
         # (_skin_struct reads J from A's row count: hand it frame 0, the pointer is the base of the K stacked frames)
         self._k = _skin_struct(self.dev, xyz_canon, rotmat_canon, lbs_weights, A[0], smpl_scale,
-                               None if transl is None else transl.reshape(-1)[:3], None, self._kkeep)
+                               None if transl is None else transl.reshape(-1)[:3], ext_tfs, self._kkeep)
         A = A.contiguous()
         self._kkeep += [A, transl]
         self._k.A = A.data_ptr()
         self._k.transl = None if transl is None else transl.data_ptr()
-        self._fb = _frame_batch(self.K, self._cam_stride, tstride)
+        self._fb = _frame_batch(self.K, self._cam_stride, tstride, placement)
+        self._forward_only = ext_tfs is not None or bool(placement)
+
+    def _check_backward(self):
+        if self._forward_only:
+            raise RuntimeError("SkinnedFramesEngine: these frames carry ext_tfs or a per-frame smpl_scale, which are forward-only "
+                               "(set_frames without them to differentiate)")
 
     def forward(self, shs, opacities, scales, sync_num_rendered=False, phase=None, posed_out=None):
         """``phase``: None = the whole forward; "binning" / "composite" = its two halves as separate calls on the same workspaces
@@ -501,6 +539,7 @@ class SkinnedFramesEngine(_FramesEngine):
     def backward_records(self, dL_dcolor, dL_ddepth=None, dL_dalpha=None):
         """First half of ``backward``: the per-tile composite backward of the K frames (VALU-bound).  ``aux`` engines also take the
         maps' adjoints (and write every frame's dL/dz plane into ``aux_ws``)."""
+        self._check_backward()
         if not self.aux and (dL_ddepth is not None or dL_dalpha is not None):
             raise ValueError("SkinnedFramesEngine: dL_ddepth / dL_dalpha need an engine built with aux=True")
         args = (C.byref(self._s), C.byref(self._fb), self.P, _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.img),
@@ -515,6 +554,7 @@ class SkinnedFramesEngine(_FramesEngine):
     def backward_gaussians(self, shs, opacities, scales, accumulate=False):
         """Second half: record sums + the per-Gaussian chain rule summed over the K frames (latency-bound).  ``aux`` engines add
         every frame's dL/dz to its posed means and write the gradients (no ``accumulate``)."""
+        self._check_backward()
         accumulate, done = self._chain_begin(accumulate)
         if self.aux and accumulate:
             raise ValueError("SkinnedFramesEngine: the depth / alpha maps (aux=True) write the gradients (no accumulate)")

@@ -105,6 +105,51 @@ def forward_chunk(gs_attrs, lbs_weights, A_t2pose, inv_A_t2cano=None, transl=Non
     }
 
 
+def frames_to_u8(img, bgr=False):
+    """[3,H,W] or [K,3,H,W] fp32 frames on the GPU -> uint8 [H,W,3] / [K,H,W,3] on the GPU: the reference's last step,
+    ``(clamp(x, 0, 1) * 255).astype(uint8)`` (+ cvtColor to BGR with ``bgr``: gs_trainer.py:717-719), in ONE launch
+    (sg_frames_to_u8; NaN gives 0).  A quarter of the fp32 bytes to copy to the host."""
+    import ctypes as C
+    from .rasterizer import _ptr
+    if not torch.is_tensor(img) or img.device.type != "cuda":
+        raise RuntimeError("sings_amd.posed.frames_to_u8 runs on the MI355X only; there is no CPU fallback")
+    if img.dtype != torch.float32 or img.dim() not in (3, 4) or img.shape[-3] != 3:
+        raise ValueError(f"frames_to_u8: fp32 [3,H,W] or [K,3,H,W] expected, got {img.dtype} {tuple(img.shape)}")
+    x = img.contiguous()
+    K, H, W = (1 if x.dim() == 3 else int(x.shape[0])), int(x.shape[-2]), int(x.shape[-1])
+    out = torch.empty(tuple(x.shape[:-3]) + (H, W, 3), dtype=torch.uint8, device=x.device)
+    if out.numel() == 0:
+        return out
+    _lib.check(_lib.load().sg_frames_to_u8(K, W, H, _ptr(x), int(bool(bgr)), _ptr(out),
+                                           C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "frames_to_u8")
+    return out
+
+
+_OUT = {"float32": None, "rgb8": False, "bgr8": True}      # out= of the animation paths -> frames_to_u8(bgr=...)
+
+
+def _out_bgr(out):
+    if out not in _OUT:
+        raise ValueError(f"out must be one of {sorted(_OUT)}, got {out!r}")
+    return _OUT[out]
+
+
+def _shared(ts):
+    """The tensors of a batch's frames are one and the same values: the same object, or views of the same memory (the frames'
+    rows of an ``.expand`` view)."""
+    t0 = ts[0]
+    return all(t is t0 or (t.data_ptr() == t0.data_ptr() and t.shape == t0.shape and t.stride() == t0.stride()
+                           and t.dtype == t0.dtype) for t in ts)
+
+
+def _batch_rows(ts, K, width):
+    """Per-frame inputs of a batch of k <= K frames -> one shared tensor (every frame's is the same) or [K, width] rows, the tail
+    padded with the last frame's (as A and transl are)."""
+    if _shared(ts):
+        return ts[0]
+    return torch.stack([t.reshape(width) for t in ts] + [ts[-1].reshape(width)] * (K - len(ts))).contiguous()
+
+
 def _capacity_floor(cap, P, W, H):                   # the FrameAnimator's engines: 8 pairs per Gaussian + 1 per tile, at least
     return max(cap, 8 * P + ((W + 15) // 16) * ((H + 15) // 16), 1 << 16)
 
@@ -262,16 +307,20 @@ class FrameAnimator:
             self._fshape, self._fcap = key, cap
         return self._fengs
 
-    def render_frames_batched(self, jobs, bg_color, frames_per_launch=8, scaling_modifier=1.0, return_aux=False):
+    def render_frames_batched(self, jobs, bg_color, frames_per_launch=8, scaling_modifier=1.0, out="float32", return_aux=False):
         """``render_frames`` with K = ``frames_per_launch`` consecutive frames per DISPATCH: the reference's chunk
         (``SinGS.forward_chunk``, sings_hybrid.py:474-569, rendered one frame at a time at gs_trainer.py:684-714) goes through
         every kernel of the forward once -- canonical inputs read once for the K poses, K frames' worth of workgroups for the
-        latency-bound kernels.  One launch per stream in flight.  Jobs as in ``render_round`` but WITHOUT ``ext_tfs`` (the K-frame
-        entry points take none) and with one ``smpl_scale`` for the batch; the cameras of a batch may differ.  Yields
-        (index, clamped image) in order; images are bit-identical to the per-frame path's.  ``return_aux``: yields (index, image,
-        depth [1,H,W], alpha [1,H,W]) -- the maps of ``get_render_pkg_fused(return_aux=True)``, re-rendered fallbacks included."""
+        latency-bound kernels.  One launch per stream in flight.  Jobs as in ``render_round``; every frame may have its own camera,
+        ``smpl_scale`` and ``ext_tfs`` (a batch's values are stacked -- one per frame, SgFrameBatch.placement -- unless its frames
+        share one: the same tensor, or rows of an ``.expand`` view).  A frame without ``smpl_scale`` / ``ext_tfs`` starts a new batch
+        when its neighbour has one.  Yields (index, clamped image) in order; images are bit-identical to the per-frame path's.
+        ``out``: "float32" (the clamped [3,H,W] image), "rgb8" / "bgr8" (uint8 [H,W,3], ``frames_to_u8``: one conversion launch
+        per batch).  ``return_aux``: yields (index, image, depth [1,H,W], alpha [1,H,W]) -- the maps of
+        ``get_render_pkg_fused(return_aux=True)``, re-rendered fallbacks included; the maps stay fp32."""
         from collections import deque
         c = self.canon
+        bgr = _out_bgr(out)
         K = max(1, min(int(frames_per_launch), 16))
         cur = torch.cuda.current_stream(self.dev)
         P = int(c['xyz_canon'].shape[0])
@@ -285,6 +334,10 @@ class FrameAnimator:
             tr = None
             if batch[0][2] is not None:
                 tr = torch.stack([j[2].reshape(3) for j in batch] + [batch[-1][2].reshape(3)] * (K - k)).contiguous()
+            sc = None if batch[0][3] is None else _batch_rows([j[3] for j in batch], K, 1)
+            ext = None
+            if batch[0][4] is not None:
+                ext = tuple(_batch_rows([j[4][n] for j in batch], K, w) for n, w in enumerate((3, 9, 1)))
             st.wait_stream(cur)                                  # the jobs' tensors were produced on the caller's stream
             with torch.cuda.stream(st):
                 rs = _settings(cams[0], bg_color, scaling_modifier, c['active_sh_degree'])
@@ -294,9 +347,10 @@ class FrameAnimator:
                                      projmatrix=torch.stack([cm['full_proj_transform'] for cm in pad]).contiguous(),
                                      campos=torch.stack([cm['camera_center'] for cm in pad]).contiguous())
                 e.set_camera(rs, long_rows=self.long_rows)
-                e.set_frames(c['xyz_canon'], c.get('rotmat_canon'), c['lbs_weights'], A, batch[0][3], tr)
+                e.set_frames(c['xyz_canon'], c.get('rotmat_canon'), c['lbs_weights'], A, sc, tr, ext)
                 e.forward(c['shs'], c['opacity'], c['scales'])
-                img = torch.clamp(e.color, 0.0, 1.0)             # [K,3,H,W]: a new tensor, the engine's image buffer is reused
+                # [K,3,H,W] (or [K,H,W,3] uint8): a new tensor, the engine's image buffer is reused
+                img = torch.clamp(e.color, 0.0, 1.0) if bgr is None else frames_to_u8(e.color, bgr)
                 maps = (e.depth.clone(), e.alpha.clone()) if return_aux else None      # (so are its map buffers)
                 ev = torch.cuda.Event(); ev.record(st)
             img.record_stream(cur)
@@ -306,12 +360,6 @@ class FrameAnimator:
             return (img, maps), ev
 
         def submit(i0, batch):
-            for j in batch:
-                if j[4] is not None:
-                    raise ValueError("render_frames_batched: ext_tfs are not supported by the K-frame entry points "
-                                     "(use render_frames)")
-                if j[3] is not batch[0][3] and not (j[3] is not None and batch[0][3] is not None and torch.equal(j[3], batch[0][3])):
-                    raise ValueError("render_frames_batched: one smpl_scale per batch of frames")
             J = int(batch[0][1].reshape(-1, 16).shape[0])
             W, H = int(batch[0][0]['image_width']), int(batch[0][0]['image_height'])
             cap = _capacity_floor(self._fcap, P, W, H)
@@ -347,8 +395,14 @@ class FrameAnimator:
                 else:
                     yield i0 + k, img[k]
 
+        kind = lambda job: (job[3] is None, job[4] is None)     # (frames with and without scale / placement: separate batches)
         batch, i0, i = [], 0, 0
         for i, job in enumerate(jobs):
+            if batch and kind(job) != kind(batch[0]):
+                while len(q) >= self.n:
+                    yield from pop()
+                submit(i0, batch)
+                batch = []
             if not batch:
                 i0 = i
             batch.append(job)
@@ -367,19 +421,28 @@ class FrameAnimator:
 
 @torch.no_grad()
 def animate_chunk(canon, poses, joints_rest, A_t2cano, cameras, bg_color, transl=None, smpl_scale=None, ext_tfs=None,
-                  parents=SMPL_PARENTS, chunk_size=16, streams=1, animator=None, frames_per_launch=1, return_aux=False):
+                  parents=SMPL_PARENTS, chunk_size=16, streams=1, animator=None, frames_per_launch=1, out="float32",
+                  return_aux=False):
     """Renders frames ``poses[f]`` with camera dict ``cameras[f]`` (or one shared dict); yields (f, image[3,H,W]).
 
     canon: dict(xyz_canon, rotmat_canon|None, scales, opacity, shs, lbs_weights, active_sh_degree);
-    transl [F,3] or None; ext_tfs: per-frame tuple (trans[F,3], rotmat[F,3,3], scale[F,1]) or None.
+    transl [F,3] or None; smpl_scale: [1] (every frame) or [F,1] / [F] (one per frame: AnimDataset_opt.get_chunk) or None;
+    ext_tfs: per-frame tuple (trans[F,3], rotmat[F,3,3], scale[F,1]) -- the reference's ``.expand`` views of one placement
+    included -- or None.
     streams > 1 (or an existing ``animator``): that many frames in flight (FrameAnimator); same images.
-    frames_per_launch = K > 1 (without ext_tfs): K consecutive frames per DISPATCH (FrameAnimator.render_frames_batched), one such
-    launch per stream in flight; same images.
-    return_aux: yields (f, image, depth [1,H,W], alpha [1,H,W]) -- the maps of get_render_pkg_fused(return_aux=True) -- on the
+    frames_per_launch = K > 1: K consecutive frames per DISPATCH (FrameAnimator.render_frames_batched), one such launch per stream
+    in flight, with or without ext_tfs / per-frame smpl_scale; same images.
+    out: "float32" (clamped [3,H,W]) or "rgb8" / "bgr8": uint8 [H,W,3] on the GPU (frames_to_u8: one launch per batch of K frames,
+    per frame elsewhere) -- the reference's (clamp * 255).astype(uint8) + cvtColor (gs_trainer.py:717-719).
+    return_aux: yields (f, image, depth [1,H,W], alpha [1,H,W]) -- the maps of get_render_pkg_fused(return_aux=True), fp32 -- on the
     K-frame path and on the plain per-frame loop; the ``streams`` > 1 per-frame path (render_frames) has no maps: ValueError."""
     F = poses.shape[0]
+    bgr = _out_bgr(out)
+    to_out = (lambda img: img) if bgr is None else (lambda img: frames_to_u8(img, bgr))
     inv_cano = torch.inverse(A_t2cano)
-    batched = int(frames_per_launch) > 1 and ext_tfs is None
+    batched = int(frames_per_launch) > 1
+    # one smpl_scale per frame ([F,1] / [F]: frame f's row) or one for all
+    scale_of = (lambda f: smpl_scale) if smpl_scale is None or smpl_scale.numel() == 1 else (lambda f: smpl_scale.reshape(-1, 1)[f])
     if animator is None and (streams > 1 or batched):
         animator = FrameAnimator(canon, streams)
     if animator is not None:
@@ -394,16 +457,17 @@ def animate_chunk(canon, poses, joints_rest, A_t2cano, cameras, bg_color, transl
                 for i in range(A.shape[0]):
                     f = c0 + i
                     yield (cameras[f] if isinstance(cameras, (list, tuple)) else cameras, A[i],
-                           None if transl is None else transl[f], smpl_scale,
+                           None if transl is None else transl[f], scale_of(f),
                            None if ext_tfs is None else (ext_tfs[0][f], ext_tfs[1][f], ext_tfs[2][f]))
         if batched:
-            yield from animator.render_frames_batched(jobs(), bg_color, frames_per_launch=int(frames_per_launch),
+            yield from animator.render_frames_batched(jobs(), bg_color, frames_per_launch=int(frames_per_launch), out=out,
                                                       return_aux=return_aux)
         elif return_aux:
             raise ValueError("animate_chunk: return_aux needs frames_per_launch > 1 or the per-frame loop (streams=1, no animator); "
                              "FrameAnimator.render_frames has no depth / alpha maps")
         else:
-            yield from animator.render_frames(jobs(), bg_color)
+            for f, img in animator.render_frames(jobs(), bg_color):
+                yield f, to_out(img)
         return
     for c0 in range(0, F, chunk_size):
         A = joint_transforms_batch(poses[c0:c0 + chunk_size], joints_rest, parents) @ inv_cano[None]
@@ -411,9 +475,9 @@ def animate_chunk(canon, poses, joints_rest, A_t2cano, cameras, bg_color, transl
             f = c0 + i
             cam = cameras[f] if isinstance(cameras, (list, tuple)) else cameras
             ext = None if ext_tfs is None else (ext_tfs[0][f], ext_tfs[1][f], ext_tfs[2][f])
-            pkg = get_render_pkg_fused(cam, canon, A[i], bg_color, smpl_scale=smpl_scale,
+            pkg = get_render_pkg_fused(cam, canon, A[i], bg_color, smpl_scale=scale_of(f),
                                        transl=None if transl is None else transl[f], ext_tfs=ext, return_aux=return_aux)
             if return_aux:
-                yield f, pkg["render"], pkg["depth"], pkg["alpha"]
+                yield f, to_out(pkg["render"]), pkg["depth"], pkg["alpha"]
             else:
-                yield f, pkg["render"]
+                yield f, to_out(pkg["render"])
