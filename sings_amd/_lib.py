@@ -3,6 +3,10 @@
 The product path has no CPU fallback: if the HIP library is missing or cannot be loaded this
 module raises, loudly.  Build it with ``python -c "import __graft_entry__ as g; g.build()"`` or
 ``make -C sings_amd/csrc``.
+
+This module declares the boundary: the structs, the constants and ``_PROTOTYPES``, the one table every function's ``argtypes`` /
+``restype`` come from.  How tensors, cameras, skin inputs and frame batches become arguments of these functions is
+``sings_amd/_marshal.py``.
 """
 import ctypes as C
 import os
@@ -57,22 +61,106 @@ class SgTriplane(C.Structure):
                 ("aabb", (C.c_float * 3) * 2), ("feature_minor", C.c_int), ("reserved", C.c_int)]
 
 
-# every symbol include/sings_hip.h declares
-EXPORTS = ("sg_abi_version", "sg_version", "sg_last_error", "sg_layout", "sg_rasterize_forward", "sg_rasterize_backward",
-           "sg_rasterize_backward_records", "sg_rasterize_backward_gaussians", "sg_skinned_backward_gaussians",
-           "sg_mark_visible", "sg_read_num_rendered", "sg_signal_alloc", "sg_signal_free", "sg_profile_enable", "sg_profile_collect",
-           "sg_kernel_name", "sg_skin_ws_floats", "sg_skinned_forward", "sg_skinned_backward",
-           "sg_photo_loss_ws_bytes", "sg_photo_loss", "sg_photo_loss_backward", "sg_reg_ws_bytes", "sg_region_laplacian", "sg_rows_laplacian", "sg_mesh_edge_loss",
-           "sg_l2norm_reg", "sg_knn_ws_bytes", "sg_gaussian_edge_loss", "sg_gaussian_edge_prepare", "sg_gaussian_edge_finish", "sg_joint_transforms", "sg_joint_transforms_backward", "sg_lbs_forward", "sg_lbs_backward", "sg_matrix_to_quaternion", "sg_matrix_to_quaternion_backward", "sg_rotation_convert", "sg_rotation_convert_backward", "sg_quaternion_multiply", "sg_quaternion_multiply_backward", "sg_triplane_ws_bytes", "sg_triplane_bwd_ws_bytes", "sg_triplane_forward",
-           "sg_triplane_backward", "sg_triplane_backward_prepare", "sg_triplane_backward_prepared", "sg_bias_act_ws_bytes", "sg_bias_act_forward", "sg_bias_act_backward", "sg_scales_head_forward", "sg_scales_head_backward",
-           "sg_weight_grad_ws_bytes", "sg_weight_grad", "sg_linear_forward", "sg_linear_backward", "sg_linear_backward_accumulate", "sg_linear_backward_fan", "sg_copy_probe",
-           "sg_frames_layout", "sg_rasterize_forward_frames", "sg_skinned_forward_frames", "sg_read_num_rendered_frames", "sg_photo_loss_backward_frames",
-           "sg_rasterize_backward_records_frames", "sg_rasterize_backward_gaussians_frames", "sg_skin_ws_floats_frames",
-           "sg_skinned_backward_gaussians_frames", "sg_photo_loss_frames",
-           "sg_aux_layout", "sg_rasterize_forward_aux", "sg_rasterize_backward_aux", "sg_skinned_forward_aux", "sg_skinned_backward_aux",
-           "sg_frames_aux_layout", "sg_skinned_forward_frames_aux", "sg_rasterize_backward_records_frames_aux",
-           "sg_skinned_backward_gaussians_frames_aux", "sg_lpips_weights_layout", "sg_lpips_ws_bytes", "sg_lpips_forward",
-           "sg_lpips_backward", "sg_lpips_patch_gather", "sg_lpips_patch_scatter", "sg_lpips_ws_layout", "sg_frames_to_u8")
+# The C ABI, one entry per function of include/sings_hip.h in the header's order: "<return>: <parameters>", a letter per type (_CTYPE
+# below), a count behind it for a run of the same type ("p9": nine raw device pointers).  load() applies it in one loop, so every
+# function has explicit argtypes AND restype; tests/test_abi.py holds every entry to the header's prototype.
+_PROTOTYPES = {
+    "sg_abi_version": "i:",
+    "sg_version": "s:",
+    "sg_last_error": "s:",
+    "sg_layout": "i: i3 z L",
+    "sg_rasterize_forward": "i: S i p9 z p3 i n p",
+    "sg_rasterize_backward": "i: S i p10 z p12",
+    "sg_rasterize_backward_records": "i: S i p2 z p4",
+    "sg_rasterize_backward_gaussians": "i: S i p10 z p i p9",
+    "sg_mark_visible": "i: i p5",
+    "sg_read_num_rendered": "i: p n p",
+    "sg_signal_alloc": "i: i V2",
+    "sg_signal_free": "i: p",
+    "sg_skin_ws_floats": "z: i",
+    "sg_lbs_forward": "i: i2 p6",
+    "sg_lbs_backward": "i: i2 p9",
+    "sg_joint_transforms": "i: i2 p6",
+    "sg_joint_transforms_backward": "i: i2 p8",
+    "sg_matrix_to_quaternion": "i: i p3",
+    "sg_matrix_to_quaternion_backward": "i: i p4",
+    "sg_rotation_convert": "i: i2 p3",
+    "sg_rotation_convert_backward": "i: i2 p4",
+    "sg_quaternion_multiply": "i: i p4",
+    "sg_quaternion_multiply_backward": "i: i p6",
+    "sg_skinned_forward": "i: S i K p5 z p6 n p",
+    "sg_skinned_backward": "i: S i K p6 z p15",
+    "sg_skinned_backward_gaussians": "i: S i K p6 z p2 i p11",
+    "sg_frames_layout": "i: i3 z i L Z4",
+    "sg_rasterize_forward_frames": "i: S F i p9 z p3 n p",
+    "sg_skinned_forward_frames": "i: S F i K p5 z p6 n p",
+    "sg_read_num_rendered_frames": "i: p i3 z i n p",
+    "sg_rasterize_backward_records_frames": "i: S F i p2 z p4",
+    "sg_rasterize_backward_gaussians_frames": "i: S F i p10 z p i p9",
+    "sg_skin_ws_floats_frames": "z: i2",
+    "sg_skinned_backward_gaussians_frames": "i: S F i K p6 z p2 i p11",
+    "sg_photo_loss_frames": "i: i3 f2 p2 z p z p8",
+    "sg_photo_loss_backward_frames": "i: i3 f2 p2 z p z p3 i p2",
+    "sg_photo_loss_ws_bytes": "z: i2",
+    "sg_photo_loss": "i: i2 f2 p11",
+    "sg_photo_loss_backward": "i: i2 f2 p8",
+    "sg_reg_ws_bytes": "z: i",
+    "sg_region_laplacian": "i: i2 p11",
+    "sg_rows_laplacian": "i: i3 p14",
+    "sg_mesh_edge_loss": "i: i2 p8",
+    "sg_l2norm_reg": "i: i p11",
+    "sg_knn_ws_bytes": "z: i",
+    "sg_gaussian_edge_loss": "i: i2 p8",
+    "sg_gaussian_edge_prepare": "i: i p3",
+    "sg_gaussian_edge_finish": "i: i2 p7",
+    "sg_triplane_ws_bytes": "z: T",
+    "sg_triplane_bwd_ws_bytes": "z: T i",
+    "sg_triplane_forward": "i: T i p4",
+    "sg_triplane_backward": "i: T i p3 G p2",
+    "sg_triplane_backward_prepare": "i: T i p3",
+    "sg_triplane_backward_prepared": "i: T i p3 G p2",
+    "sg_bias_act_ws_bytes": "z: i2",
+    "sg_bias_act_forward": "i: i3 p6",
+    "sg_bias_act_backward": "i: i3 p7",
+    "sg_scales_head_forward": "i: i p4",
+    "sg_scales_head_backward": "i: i p5",
+    "sg_linear_forward": "i: i4 p7",
+    "sg_linear_backward": "i: i4 p7",
+    "sg_linear_backward_accumulate": "i: i4 p7",
+    "sg_linear_backward_fan": "i: i4 p5 D p",
+    "sg_weight_grad_ws_bytes": "z: i3",
+    "sg_weight_grad": "i: i3 p6",
+    "sg_aux_layout": "i: i3 z Z",
+    "sg_rasterize_forward_aux": "i: S i p9 z p3 i n p4",
+    "sg_rasterize_backward_aux": "i: S i p10 z p15",
+    "sg_skinned_forward_aux": "i: S i K p5 z p6 n p4",
+    "sg_skinned_backward_aux": "i: S i K p6 z p18",
+    "sg_frames_aux_layout": "i: i3 z i Z",
+    "sg_skinned_forward_frames_aux": "i: S F i K p5 z p6 n p4",
+    "sg_rasterize_backward_records_frames_aux": "i: S F i p2 z p7",
+    "sg_skinned_backward_gaussians_frames_aux": "i: S F i K p6 z p2 i p12",
+    "sg_lpips_weights_layout": "i: Z2",
+    "sg_lpips_ws_bytes": "i: i3 Z",
+    "sg_lpips_ws_layout": "i: i3 Z2",
+    "sg_lpips_forward": "i: i4 p6",
+    "sg_lpips_backward": "i: i4 p5",
+    "sg_lpips_patch_gather": "i: i5 p9",
+    "sg_lpips_patch_scatter": "i: i5 p7",
+    "sg_frames_to_u8": "i: i3 p i p2",
+    "sg_profile_enable": "i: i",
+    "sg_copy_probe": "i: p2 z i p",
+    "sg_profile_collect": "i: d n i",
+    "sg_kernel_name": "s: i",
+}
+_P = C.POINTER
+_CTYPE = {"i": C.c_int, "z": C.c_size_t, "f": C.c_float, "s": C.c_char_p,
+          "p": C.c_void_p,                        # a raw device pointer (or NULL), and the stream
+          "S": _P(SgRasterSettings), "F": _P(SgFrameBatch), "K": _P(SgSkinInputs), "L": _P(SgLayout), "T": _P(SgTriplane),
+          "D": _P(SgLinearSide),                  # SgLinearSide[2]
+          "n": _P(C.c_int64), "Z": _P(C.c_size_t), "d": _P(C.c_double),     # host outputs (one value or an array)
+          "V": _P(C.c_void_p),                    # void **
+          "G": _P(C.c_void_p * 3 * 4)}            # float *d_planes[4][3]
+EXPORTS = tuple(_PROTOTYPES)         # every symbol include/sings_hip.h declares
 LPIPS_NUM_OFFSETS = 46               # SG_LPIPS_NUM_OFFSETS
 LPIPS_WS_NUM_PIECES = 28             # SG_LPIPS_WS_NUM_PIECES
 LPIPS_MIN_SIZE = 16                  # SG_LPIPS_MIN_SIZE
@@ -94,6 +182,12 @@ HDR_FLAG_OVERFLOW = 1               # more pairs than the capacity of the call
 HDR_FLAG_LONG_LIST = 2              # a tile list longer than a flag of the call promised (SG_FLAG_SHORT_LISTS / SG_FLAG_LONG_ROWS)
 
 
+def _ctypes_of(signature):
+    """"i: S i p9" -> (c_int, [POINTER(SgRasterSettings), c_int, c_void_p x 9])."""
+    ret, _, params = signature.partition(":")
+    return _CTYPE[ret], [_CTYPE[t[0]] for t in params.split() for _ in range(int(t[1:] or 1))]
+
+
 def load():
     global _lib
     if _lib is not None:
@@ -106,136 +200,13 @@ def load():
     # copy PyTorch-ROCm already loaded (loading ours first makes the two runtimes disagree about devices).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    vp, i32, sz = C.c_void_p, C.c_int, C.c_size_t
-    lib.sg_version.restype = C.c_char_p
-    lib.sg_abi_version.restype = C.c_int
+    # (asked first, as the `int f(void)` ctypes assumes of an undeclared function: a library of another ABI may lack table entries)
     if lib.sg_abi_version() != ABI_VERSION:
         raise RuntimeError(f"sings_amd: {LIB_PATH} speaks ABI {lib.sg_abi_version()}, this host code ABI {ABI_VERSION} "
                            "(include/sings_hip.h SG_ABI_VERSION): rebuild with `make -C sings_amd/csrc`")
-    lib.sg_last_error.restype = C.c_char_p
-    lib.sg_layout.argtypes = [i32, i32, i32, sz, C.POINTER(SgLayout)]
-    lib.sg_rasterize_forward.argtypes = ([C.POINTER(SgRasterSettings), i32] + [vp] * 7 +
-                                         [vp, vp, sz, vp, vp, vp, i32, C.POINTER(C.c_int64), vp])
-    lib.sg_rasterize_backward.argtypes = ([C.POINTER(SgRasterSettings), i32] + [vp] * 7 +
-                                          [vp, vp, vp, sz, vp, vp, vp] + [vp] * 8 + [vp])
-    lib.sg_rasterize_backward_records.argtypes = [C.POINTER(SgRasterSettings), i32, vp, vp, sz, vp, vp, vp, vp]
-    lib.sg_rasterize_backward_gaussians.argtypes = ([C.POINTER(SgRasterSettings), i32] + [vp] * 7 + [vp, vp, vp, sz, vp, i32] +
-                                                    [vp] * 8 + [vp])
-    lib.sg_skinned_backward_gaussians.argtypes = ([C.POINTER(SgRasterSettings), i32, C.POINTER(SgSkinInputs)] + [vp] * 3 +
-                                                  [vp, vp, vp, sz, vp, vp, i32] + [vp] * 2 + [vp] * 8 + [vp])
-    for f in ("sg_rasterize_backward_records", "sg_rasterize_backward_gaussians", "sg_skinned_backward_gaussians"):
-        getattr(lib, f).restype = C.c_int
-    lib.sg_mark_visible.argtypes = [i32, vp, vp, vp, vp, vp]
-    lib.sg_read_num_rendered.argtypes = [vp, C.POINTER(C.c_int64), vp]
-    lib.sg_signal_alloc.argtypes = [i32, C.POINTER(vp), C.POINTER(vp)]; lib.sg_signal_alloc.restype = C.c_int
-    lib.sg_signal_free.argtypes = [vp]; lib.sg_signal_free.restype = C.c_int
-    lib.sg_profile_enable.argtypes = [i32]
-    lib.sg_profile_collect.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_int64), i32]
-    lib.sg_copy_probe.argtypes = [vp, vp, sz, i32, vp]; lib.sg_copy_probe.restype = C.c_int
-    # K frames per call (include/sings_hip.h, "K frames of the SAME Gaussians per call")
-    FB = C.POINTER(SgFrameBatch)
-    lib.sg_frames_layout.argtypes = [i32, i32, i32, sz, i32, C.POINTER(SgLayout)] + [C.POINTER(sz)] * 4
-    lib.sg_rasterize_forward_frames.argtypes = ([C.POINTER(SgRasterSettings), FB, i32] + [vp] * 7 +
-                                                [vp, vp, sz, vp, vp, vp, C.POINTER(C.c_int64), vp])
-    lib.sg_skinned_forward_frames.argtypes = ([C.POINTER(SgRasterSettings), FB, i32, C.POINTER(SgSkinInputs)] + [vp] * 3 +
-                                              [vp, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int64), vp])
-    lib.sg_read_num_rendered_frames.argtypes = [vp, i32, i32, i32, sz, i32, C.POINTER(C.c_int64), vp]
-    lib.sg_rasterize_backward_records_frames.argtypes = [C.POINTER(SgRasterSettings), FB, i32, vp, vp, sz, vp, vp, vp, vp]
-    lib.sg_rasterize_backward_gaussians_frames.argtypes = ([C.POINTER(SgRasterSettings), FB, i32] + [vp] * 7 +
-                                                           [vp, vp, vp, sz, vp, i32] + [vp] * 8 + [vp])
-    lib.sg_skin_ws_floats_frames.argtypes = [i32, i32]; lib.sg_skin_ws_floats_frames.restype = sz
-    lib.sg_skinned_backward_gaussians_frames.argtypes = ([C.POINTER(SgRasterSettings), FB, i32, C.POINTER(SgSkinInputs)] + [vp] * 3 +
-                                                         [vp, vp, vp, sz, vp, vp, i32] + [vp] * 2 + [vp] * 8 + [vp])
-    lib.sg_photo_loss_frames.argtypes = [i32, i32, i32, C.c_float, C.c_float, vp, vp, sz, vp, sz] + [vp] * 8
-    lib.sg_photo_loss_backward_frames.argtypes = [i32, i32, i32, C.c_float, C.c_float, vp, vp, sz, vp, sz, vp, vp, vp, i32, vp, vp]
-    for f in ("sg_frames_layout", "sg_rasterize_forward_frames", "sg_skinned_forward_frames", "sg_read_num_rendered_frames",
-              "sg_rasterize_backward_records_frames", "sg_rasterize_backward_gaussians_frames",
-              "sg_skinned_backward_gaussians_frames", "sg_photo_loss_frames"):
-        getattr(lib, f).restype = C.c_int
-    lib.sg_kernel_name.argtypes = [i32]
-    lib.sg_kernel_name.restype = C.c_char_p
-    lib.sg_skin_ws_floats.argtypes = [i32]
-    lib.sg_skin_ws_floats.restype = sz
-    lib.sg_skinned_forward.argtypes = ([C.POINTER(SgRasterSettings), i32, C.POINTER(SgSkinInputs)] + [vp] * 3 +
-                                       [vp, vp, sz, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_int64), vp])
-    lib.sg_skinned_backward.argtypes = ([C.POINTER(SgRasterSettings), i32, C.POINTER(SgSkinInputs)] + [vp] * 3 +
-                                        [vp, vp, vp, sz, vp, vp, vp] + [vp] * 3 + [vp] * 8 + [vp])
-    lib.sg_photo_loss_ws_bytes.argtypes = [i32, i32]
-    lib.sg_photo_loss_ws_bytes.restype = sz
-    lib.sg_photo_loss.argtypes = [i32, i32, C.c_float, C.c_float] + [vp] * 11
-    lib.sg_photo_loss.restype = C.c_int
-    lib.sg_photo_loss_backward.argtypes = [i32, i32, C.c_float, C.c_float] + [vp] * 8
-    lib.sg_photo_loss_backward.restype = C.c_int
-    lib.sg_matrix_to_quaternion.argtypes = [i32, vp, vp, vp]; lib.sg_matrix_to_quaternion.restype = C.c_int
-    lib.sg_matrix_to_quaternion_backward.argtypes = [i32, vp, vp, vp, vp]; lib.sg_matrix_to_quaternion_backward.restype = C.c_int
-    lib.sg_joint_transforms.argtypes = [i32, i32] + [vp] * 6; lib.sg_joint_transforms.restype = C.c_int
-    lib.sg_joint_transforms_backward.argtypes = [i32, i32] + [vp] * 8; lib.sg_joint_transforms_backward.restype = C.c_int
-    lib.sg_lbs_forward.argtypes = [i32, i32] + [vp] * 6; lib.sg_lbs_forward.restype = C.c_int
-    lib.sg_lbs_backward.argtypes = [i32, i32] + [vp] * 9; lib.sg_lbs_backward.restype = C.c_int
-    lib.sg_triplane_ws_bytes.argtypes = [C.POINTER(SgTriplane)]; lib.sg_triplane_ws_bytes.restype = sz
-    lib.sg_triplane_bwd_ws_bytes.argtypes = [C.POINTER(SgTriplane), i32]; lib.sg_triplane_bwd_ws_bytes.restype = sz
-    lib.sg_triplane_forward.argtypes = [C.POINTER(SgTriplane), i32, vp, vp, vp, vp]
-    lib.sg_triplane_backward.argtypes = [C.POINTER(SgTriplane), i32, vp, vp, vp, C.POINTER(C.c_void_p * 3 * 4), vp, vp]
-    lib.sg_triplane_backward_prepared.argtypes = lib.sg_triplane_backward.argtypes
-    lib.sg_triplane_backward_prepare.argtypes = [C.POINTER(SgTriplane), i32, vp, vp, vp]
-    lib.sg_bias_act_ws_bytes.argtypes = [i32, i32]; lib.sg_bias_act_ws_bytes.restype = sz
-    lib.sg_bias_act_forward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp]
-    lib.sg_bias_act_backward.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-    lib.sg_scales_head_forward.argtypes = [i32, vp, vp, vp, vp]; lib.sg_scales_head_forward.restype = C.c_int
-    lib.sg_scales_head_backward.argtypes = [i32, vp, vp, vp, vp, vp]; lib.sg_scales_head_backward.restype = C.c_int
-    for f in ("sg_triplane_forward", "sg_triplane_backward", "sg_triplane_backward_prepare", "sg_triplane_backward_prepared",
-              "sg_bias_act_forward", "sg_bias_act_backward"):
-        getattr(lib, f).restype = C.c_int
-    lib.sg_weight_grad_ws_bytes.argtypes = [i32, i32, i32]; lib.sg_weight_grad_ws_bytes.restype = sz
-    lib.sg_weight_grad.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp]; lib.sg_weight_grad.restype = C.c_int
-    lib.sg_linear_forward.argtypes = [i32, i32, i32, i32] + [vp] * 7; lib.sg_linear_forward.restype = C.c_int
-    lib.sg_linear_backward.argtypes = [i32, i32, i32, i32] + [vp] * 7; lib.sg_linear_backward.restype = C.c_int
-    lib.sg_linear_backward_accumulate.argtypes = [i32, i32, i32, i32] + [vp] * 7; lib.sg_linear_backward_accumulate.restype = C.c_int
-    lib.sg_linear_backward_fan.argtypes = [i32, i32, i32, i32] + [vp] * 5 + [C.POINTER(SgLinearSide), vp]
-    lib.sg_linear_backward_fan.restype = C.c_int
-    lib.sg_reg_ws_bytes.argtypes = [i32]; lib.sg_reg_ws_bytes.restype = sz
-    lib.sg_knn_ws_bytes.argtypes = [i32]; lib.sg_knn_ws_bytes.restype = sz
-    lib.sg_region_laplacian.argtypes = [i32, i32] + [vp] * 11
-    lib.sg_rows_laplacian.argtypes = [i32, i32, i32] + [vp] * 14
-    lib.sg_mesh_edge_loss.argtypes = [i32, i32] + [vp] * 8
-    lib.sg_l2norm_reg.argtypes = [i32] + [vp] * 11
-    lib.sg_gaussian_edge_loss.argtypes = [i32, i32] + [vp] * 8
-    lib.sg_gaussian_edge_prepare.argtypes = [i32, vp, vp, vp]
-    lib.sg_gaussian_edge_finish.argtypes = [i32, i32] + [vp] * 7
-    for f in ("sg_region_laplacian", "sg_rows_laplacian", "sg_mesh_edge_loss", "sg_l2norm_reg", "sg_gaussian_edge_loss", "sg_gaussian_edge_prepare",
-              "sg_gaussian_edge_finish"):
-        getattr(lib, f).restype = C.c_int
-    # depth and alpha maps (ABI 8): the plain calls' parameters + the aux workspace (+ the two maps / their gradients) before the stream
-    lib.sg_aux_layout.argtypes = [i32, i32, i32, sz, C.POINTER(sz)]
-    lib.sg_rasterize_forward_aux.argtypes = lib.sg_rasterize_forward.argtypes[:-1] + [vp, vp, vp, vp]
-    lib.sg_rasterize_backward_aux.argtypes = lib.sg_rasterize_backward.argtypes[:-1] + [vp, vp, vp, vp]
-    lib.sg_skinned_forward_aux.argtypes = lib.sg_skinned_forward.argtypes[:-1] + [vp, vp, vp, vp]
-    lib.sg_skinned_backward_aux.argtypes = lib.sg_skinned_backward.argtypes[:-1] + [vp, vp, vp, vp]
-    # ... of K frames (entry points added to ABI 8): the plain K-frame calls' parameters + the same additions
-    lib.sg_frames_aux_layout.argtypes = [i32, i32, i32, sz, i32, C.POINTER(sz)]
-    lib.sg_skinned_forward_frames_aux.argtypes = lib.sg_skinned_forward_frames.argtypes[:-1] + [vp, vp, vp, vp]
-    lib.sg_rasterize_backward_records_frames_aux.argtypes = lib.sg_rasterize_backward_records_frames.argtypes[:-1] + [vp, vp, vp, vp]
-    lib.sg_skinned_backward_gaussians_frames_aux.argtypes = lib.sg_skinned_backward_gaussians_frames.argtypes[:-1] + [vp, vp]
-    for f in ("sg_aux_layout", "sg_rasterize_forward_aux", "sg_rasterize_backward_aux", "sg_skinned_forward_aux", "sg_skinned_backward_aux",
-              "sg_frames_aux_layout", "sg_skinned_forward_frames_aux", "sg_rasterize_backward_records_frames_aux",
-              "sg_skinned_backward_gaussians_frames_aux"):
-        getattr(lib, f).restype = C.c_int
-    # LPIPS-VGG (entry points added to ABI 8)
-    lib.sg_lpips_weights_layout.argtypes = [C.POINTER(sz), C.POINTER(sz)]
-    lib.sg_lpips_ws_bytes.argtypes = [i32, i32, i32, C.POINTER(sz)]
-    lib.sg_lpips_ws_layout.argtypes = [i32, i32, i32, C.POINTER(sz), C.POINTER(sz)]
-    lib.sg_lpips_forward.argtypes = [i32, i32, i32, i32] + [vp] * 6
-    lib.sg_lpips_backward.argtypes = [i32, i32, i32, i32] + [vp] * 5
-    lib.sg_lpips_patch_gather.argtypes = [i32] * 5 + [vp] * 9
-    lib.sg_lpips_patch_scatter.argtypes = [i32] * 5 + [vp] * 7
-    for f in ("sg_lpips_weights_layout", "sg_lpips_ws_bytes", "sg_lpips_ws_layout", "sg_lpips_forward", "sg_lpips_backward",
-              "sg_lpips_patch_gather", "sg_lpips_patch_scatter"):
-        getattr(lib, f).restype = C.c_int
-    # 8-bit HWC frames (entry point added to ABI 8)
-    lib.sg_frames_to_u8.argtypes = [i32, i32, i32, vp, i32, vp, vp]; lib.sg_frames_to_u8.restype = C.c_int
-    for f in ("sg_layout", "sg_rasterize_forward", "sg_rasterize_backward", "sg_mark_visible",
-              "sg_read_num_rendered", "sg_skinned_forward", "sg_skinned_backward"):
-        getattr(lib, f).restype = C.c_int
+    for name, signature in _PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = _ctypes_of(signature)
     _lib = lib
     return lib
 

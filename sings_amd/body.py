@@ -9,6 +9,9 @@ joints are computed once per shape and cached by the caller.  Gradients w.r.t. t
 """
 import torch
 
+from . import _lib
+from ._marshal import _ptr, _stream
+
 SMPL_PARENTS = (-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21)   # smpl_layer.py:269-272
 
 
@@ -28,36 +31,30 @@ class _JointTransforms(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pose, joints_rest, parents_t, post):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         B, J = int(pose.shape[0]), int(joints_rest.shape[0])
         pose = pose.contiguous().float(); jr = joints_rest.contiguous().float()
         post = None if post is None else post.contiguous().float()
         A = torch.empty((B, J, 4, 4), dtype=torch.float32, device=pose.device)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         with torch.cuda.device(pose.device):
-            _lib.check(lib.sg_joint_transforms(B, J, p(pose), p(jr), p(parents_t), p(post), p(A),
-                                               C.c_void_p(torch.cuda.current_stream(pose.device).cuda_stream)), "joint transforms")
+            _lib.check(lib.sg_joint_transforms(B, J, _ptr(pose), _ptr(jr), _ptr(parents_t), _ptr(post), _ptr(A),
+                                               _stream(pose.device)), "joint transforms")
         ctx.save_for_backward(pose, jr, parents_t, post if post is not None else torch.empty(0, device=pose.device))
         ctx.has_post = post is not None
         return A
 
     @staticmethod
     def backward(ctx, dA):
-        import ctypes as C
-        from . import _lib
         lib = _lib.load()
         pose, jr, parents_t, post = ctx.saved_tensors
         B, J = int(pose.shape[0]), int(jr.shape[0])
         dA = dA.contiguous().float()
         dpose = torch.empty_like(pose)
         dj = torch.empty((B, J, 3), dtype=torch.float32, device=pose.device) if ctx.needs_input_grad[1] else None
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         with torch.cuda.device(pose.device):
-            _lib.check(lib.sg_joint_transforms_backward(B, J, p(pose), p(jr), p(parents_t), p(post) if ctx.has_post else None, p(dA),
-                                                        p(dpose), p(dj), C.c_void_p(torch.cuda.current_stream(pose.device).cuda_stream)),
-                       "joint transforms backward")
+            _lib.check(lib.sg_joint_transforms_backward(B, J, _ptr(pose), _ptr(jr), _ptr(parents_t),
+                                                        _ptr(post) if ctx.has_post else None, _ptr(dA), _ptr(dpose), _ptr(dj),
+                                                        _stream(pose.device)), "joint transforms backward")
         return dpose, None if dj is None else dj.sum(0), None, None
 
 

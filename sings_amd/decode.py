@@ -19,13 +19,9 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .rasterizer import _ptr
+from ._marshal import _ptr, _stream
 
 ACT_NONE, ACT_GELU, ACT_SIGMOID, ACT_SOFTPLUS_REF = 0, 1, 2, 3
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def _is_feature_minor(p):

@@ -4,14 +4,16 @@ This is what a training loop that owns its buffers (and bench.py) calls: workspa
 flat gradient buffer are sized once for 288 GB-class HBM and reused every step, the capacity
 for (tile, Gaussian) pairs is a fixed upper bound, and nothing synchronises inside a step.  The
 gradient tensors are views into ONE flat fp32 buffer so that frame-parallel training can
-all-reduce them with a single RCCL call (see sings_amd/dp.py).
+all-reduce them with a single RCCL call (see sings_amd/dp.py).  The engines fill the structs of the C ABI through
+sings_amd/_marshal.py, the same functions the autograd ops use.
 """
 import ctypes as C
 
 import torch
 
 from . import _lib
-from .rasterizer import _settings_struct, _ptr
+from ._marshal import _camera_stride, _frame_batch, _frame_rows, _ptr, _settings_struct, _skin_frames, _skin_struct
+from ._marshal import _stream as _current_stream
 
 
 def _raster_fields(M):
@@ -114,7 +116,7 @@ class _Engine:
                 | (_lib.FLAG_WS_CLEAN if self._clean else 0))
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        return _current_stream(self.dev)
 
     def _chain_begin(self, accumulate):
         """Before the per-Gaussian half of a backward: (accumulate, done event).  Inside a ``ViewBatch`` whose views share a gradient
@@ -216,7 +218,6 @@ class SkinnedEngine(_Engine):
         self._k = None
 
     def set_frame(self, xyz_canon, rotmat_canon, lbs_weights, A, smpl_scale, transl, ext_tfs=None):
-        from .skinned import _skin_struct
         self._kkeep = []
         self._k = _skin_struct(self.dev, xyz_canon, rotmat_canon, lbs_weights, A, smpl_scale, transl, ext_tfs, self._kkeep)
 
@@ -379,27 +380,6 @@ class ViewBatch:
         return self.pipe.reduce()
 
 
-def _frame_batch(K, camera_stride, transl_stride, placement=0):
-    fb = _lib.SgFrameBatch()
-    fb.K, fb.camera_stride, fb.transl_stride, fb.placement = int(K), int(camera_stride), int(transl_stride), int(placement)
-    return fb
-
-
-def _frame_rows(t, K, width, name):
-    """An input of K frames that may be shared -> (tensor, per_frame): ONE set of ``width`` floats for every frame (``width``
-    elements -- a leading 1 included -- or an ``.expand`` view, stride 0 along the frames: its first row, not copied), or K rows
-    [K, width] (per_frame True)."""
-    if not torch.is_tensor(t):
-        raise TypeError(f"{name} must be a tensor")
-    if t.numel() == width:
-        return t.reshape(width), False
-    if t.dim() >= 1 and t.shape[0] == K and t[0].numel() == width:
-        if t.stride(0) == 0:
-            return t[0].reshape(width), False
-        return t.reshape(K, width), True
-    raise ValueError(f"{name} must be [{width}] (one for all frames) or [{K},{width}] (one per frame), got {tuple(t.shape)}")
-
-
 class _FramesEngine(_Engine):
     """K frames (poses and / or cameras) of the SAME Gaussians per call: ONE dispatch per kernel for the K frames (the ``*_frames``
     entry points of include/sings_hip.h).  The reference hands its model 16 frames per call (``SinGS.forward_chunk``,
@@ -412,12 +392,9 @@ class _FramesEngine(_Engine):
     _cam_stride = 0                       # 1: one camera per frame
 
     def _camera(self, raster_settings, rows):
-        vm = raster_settings.viewmatrix
-        per_frame = vm.dim() == 3
-        if per_frame and (vm.shape[0] != self.K or raster_settings.projmatrix.shape[0] != self.K or raster_settings.campos.shape[0] != self.K):
-            raise ValueError(f"per-frame cameras must be stacked [{self.K},4,4] / [{self.K},3]")
+        stride = _camera_stride(raster_settings, self.K, ValueError)
         super()._camera(raster_settings, rows)
-        self._cam_stride = 1 if per_frame else 0
+        self._cam_stride = stride
 
     def num_rendered(self):
         nr = (C.c_int64 * self.K)()
@@ -458,20 +435,12 @@ class SkinnedFramesEngine(_FramesEngine):
         ``.expand`` view (the reference's AnimDataset_opt.get_chunk) is passed as the one shared set it is.  Per-frame sets reach
         the kernels as SgFrameBatch.placement bits (include/sings_hip.h, SG_PLACEMENT_*).  A placement or a per-frame scale is
         forward-only, as in the reference (no_grad): ``backward*`` then raises."""
-        from .skinned import _skin_struct
         A = A.reshape(self.K, -1, 16)
         if A.shape[1] != self.J:
             raise ValueError(f"A must be [{self.K},{self.J},16]")
         self._kkeep = []
-        tstride = 0
         if transl is not None:
             transl = transl.contiguous().float()
-            if transl.numel() == 3:
-                tstride = 0
-            elif transl.numel() == 3 * self.K:
-                tstride = 3
-            else:
-                raise ValueError(f"transl must be [{self.K},3] or [3]")
         placement = 0
         if smpl_scale is not None:
             smpl_scale, per = _frame_rows(smpl_scale, self.K, 1, "smpl_scale")
@@ -483,15 +452,8 @@ class SkinnedFramesEngine(_FramesEngine):
                 placement |= _lib.PLACEMENT_EXT_TFS
             else:
                 ext_tfs = tuple(x for x, _ in rows)
-        # (_skin_struct reads J from A's row count: hand it frame 0, the pointer is the base of the K stacked frames)
-        self._k = _skin_struct(self.dev, xyz_canon, rotmat_canon, lbs_weights, A[0], smpl_scale,
-                               None if transl is None else transl.reshape(-1)[:3], ext_tfs, self._kkeep)
-        A = A.contiguous()
-        self._kkeep += [A, transl]
-        self._k.A = A.data_ptr()
-        self._k.transl = None if transl is None else transl.data_ptr()
-        self._fb = _frame_batch(self.K, self._cam_stride, tstride, placement)
-        self._forward_only = ext_tfs is not None or bool(placement)
+        self._k, self._fb, self._forward_only = _skin_frames(self.dev, xyz_canon, rotmat_canon, lbs_weights, A, smpl_scale, transl,
+                                                             ext_tfs, self._cam_stride, self._kkeep, ValueError, placement)
 
     def _check_backward(self):
         if self._forward_only:

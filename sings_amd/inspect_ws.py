@@ -9,7 +9,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .rasterizer import _settings_struct, _ptr
+from ._marshal import _ptr, _settings_struct, _stream
 
 
 def forward_with_state(rs, means3D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -28,7 +28,7 @@ def forward_with_state(rs, means3D, opacities, shs=None, colors_precomp=None, sc
     means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp = map(
         c, (means3D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp))
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _stream(dev)
         while True:
             L = _lib.layout(P, W, H, cap)
             geom = torch.zeros(L.geom_bytes, dtype=torch.uint8, device=dev)

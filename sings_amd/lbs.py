@@ -13,16 +13,11 @@ sings_hybrid.py:57); with ``disable_posedirs=False`` the offsets are computed as
 matmul, in torch on the GPU) before the kernel.  ``lbs_weights`` must not require a gradient (the reference detaches
 them, sings_hybrid.py:724).
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._marshal import _ptr, _stream
 from .body import rodrigues
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class _Lbs(torch.autograd.Function):
@@ -38,7 +33,7 @@ class _Lbs(torch.autograd.Function):
         T = torch.empty((N, 4, 4), dtype=torch.float32, device=v.device)
         verts = torch.empty((N, 3), dtype=torch.float32, device=v.device)
         with torch.cuda.device(v.device):
-            st = C.c_void_p(torch.cuda.current_stream(v.device).cuda_stream)
+            st = _stream(v.device)
             _lib.check(lib.sg_lbs_forward(N, J, _ptr(w), _ptr(A), _ptr(v), _ptr(T), _ptr(verts), st), "lbs forward")
         ctx.save_for_backward(A, v, w)
         return verts, T
@@ -55,7 +50,7 @@ class _Lbs(torch.autograd.Function):
         dA = torch.empty((J, 4, 4), dtype=torch.float32, device=dev)
         ws = torch.empty(int(lib.sg_skin_ws_floats(N)), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            st = _stream(dev)
             _lib.check(lib.sg_lbs_backward(N, J, _ptr(w), _ptr(A), _ptr(v), _ptr(dT), _ptr(dverts), _ptr(ws), _ptr(dv), _ptr(dA), st),
                        "lbs backward")
         return dA, dv, None

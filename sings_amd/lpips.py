@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .rasterizer import _ptr
+from ._marshal import _ptr, _stream
 
 CONV_CHANNELS = ((3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256), (256, 512), (512, 512), (512, 512),
                  (512, 512), (512, 512), (512, 512))           # VGG16 `features` convs up to relu5_3: (Cin, Cout)
@@ -81,10 +81,6 @@ def ws_layout(B, H, W):
     _lib.check(_lib.load().sg_lpips_ws_layout(B, H, W, offs, C.byref(total)), "sg_lpips_ws_layout")
     o = [int(v) for v in offs]
     return {"y": o[0:13], "pool": o[13:17], "arg": o[17:21], "dpix": o[21:26], "g": o[26:28], "total": int(total.value)}
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 class _LPIPSFn(torch.autograd.Function):

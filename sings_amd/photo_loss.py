@@ -15,12 +15,10 @@ weights for the two terms the gradient kernel runs again with them as device sca
 synchronisation anywhere.  The LPIPS patch term: sings_amd/lpips.py.
 No CPU fallback: the HIP library must be present.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
-from .rasterizer import _ptr
+from ._marshal import _ptr, _stream
 
 
 def _same_upstream(a, b):
@@ -73,7 +71,7 @@ class _PhotoLoss(torch.autograd.Function):
         # both -- is then one multiplication by that scalar instead of a second march over the image.
         unit = torch.empty_like(raw) if ctx.needs_input_grad[0] else None
         with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _stream(dev)
             _lib.check(lib.sg_photo_loss(W, H, float(l1_w), float(ssim_w), _ptr(raw), _ptr(gt_rgb), _ptr(mask), _ptr(bg),
                                          _ptr(ws), _ptr(pred), _ptr(gt), _ptr(losses), None, _ptr(unit), stream),
                        "photo loss")
@@ -105,7 +103,7 @@ class _PhotoLoss(torch.autograd.Function):
         up = torch.stack([g_l1.reshape(()).float(), g_ssim.reshape(()).float()])
         out = torch.empty_like(raw)
         with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _stream(dev)
             _lib.check(lib.sg_photo_loss_backward(W, H, l1_w, ssim_w, _ptr(raw), _ptr(gt_rgb), _ptr(mask), _ptr(bg), _ptr(ws),
                                                   _ptr(up), _ptr(out), stream), "photo loss backward")
         return out, None, None, None, None, None, None
@@ -151,7 +149,7 @@ class _PhotoLossFrames(torch.autograd.Function):
         losses = torch.empty((K, 4), dtype=torch.float32, device=dev)
         unit = torch.empty_like(raw) if ctx.needs_input_grad[0] else None       # (gradient for unit upstream weights: see _PhotoLoss)
         with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _stream(dev)
             _lib.check(lib.sg_photo_loss_frames(K, W, H, float(l1_w), float(ssim_w), _ptr(raw), _ptr(gt_rgb), gt_stride, _ptr(mask),
                                                 mask_stride, _ptr(bg), _ptr(ws), None, None, _ptr(losses), None, _ptr(unit), stream),
                        "photo loss (frames)")
@@ -175,7 +173,7 @@ class _PhotoLossFrames(torch.autograd.Function):
         up = up.contiguous()                                                   # [K,2]: a pair of weights per frame, device memory
         out = torch.empty_like(raw)
         with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _stream(dev)
             _lib.check(lib.sg_photo_loss_backward_frames(K, W, H, l1_w, ssim_w, _ptr(raw), _ptr(gt_rgb), gt_stride, _ptr(mask), mask_stride,
                                                          _ptr(bg), _ptr(ws), _ptr(up), 2, _ptr(out), stream), "photo loss backward (frames)")
         return out, None, None, None, None, None
@@ -210,7 +208,7 @@ class PhotoLossEngine:
         self.grad = torch.empty(shape(3, self.H, self.W), dtype=torch.float32, device=self.dev)
 
     def __call__(self, raw, gt_rgb, mask, bg):
-        stream = C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        stream = _stream(self.dev)
         hw = self.H * self.W
         gt_stride = 3 * hw if gt_rgb.numel() == self.K * 3 * hw and self.K > 1 else 0
         mask_stride = hw if mask.numel() == self.K * hw and self.K > 1 else 0

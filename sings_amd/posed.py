@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._marshal import _ptr, _stream
 from .body import SMPL_PARENTS, rodrigues
 from .renderer import _settings, get_render_pkg_fused
 
@@ -110,7 +111,6 @@ def frames_to_u8(img, bgr=False):
     ``(clamp(x, 0, 1) * 255).astype(uint8)`` (+ cvtColor to BGR with ``bgr``: gs_trainer.py:717-719), in ONE launch
     (sg_frames_to_u8; NaN gives 0).  A quarter of the fp32 bytes to copy to the host."""
     import ctypes as C
-    from .rasterizer import _ptr
     if not torch.is_tensor(img) or img.device.type != "cuda":
         raise RuntimeError("sings_amd.posed.frames_to_u8 runs on the MI355X only; there is no CPU fallback")
     if img.dtype != torch.float32 or img.dim() not in (3, 4) or img.shape[-3] != 3:
@@ -121,7 +121,7 @@ def frames_to_u8(img, bgr=False):
     if out.numel() == 0:
         return out
     _lib.check(_lib.load().sg_frames_to_u8(K, W, H, _ptr(x), int(bool(bgr)), _ptr(out),
-                                           C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)), "frames_to_u8")
+                                           _stream(x.device)), "frames_to_u8")
     return out
 
 

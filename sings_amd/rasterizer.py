@@ -6,7 +6,8 @@ gs_renderer_multiple.py:6-9; package = install_all.sh:22): ``GaussianRasterizati
 ``rasterize_gaussians`` and the ``_RasterizeGaussians`` autograd.Function, with the upstream
 argument order and gradient order ``(means3D, means2D, sh, colors_precomp, opacities, scales,
 rotations, cov3Ds_precomp, None)``.  The compute is the hand-written gfx950 library behind the
-C ABI of include/sings_hip.h -- there is no CPU / eager fallback.
+C ABI of include/sings_hip.h -- there is no CPU / eager fallback.  The op's tensors, its camera and the stream become
+C arguments through sings_amd/_marshal.py, as in every other module that calls the library.
 """
 import ctypes as C
 from typing import NamedTuple
@@ -15,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, overflow
+from ._marshal import _f32, _ptr, _settings_struct, _stream
 # The pair capacity, the overflow-check modes and the learned list-length hints live in sings_amd/overflow.py; INTEGRATION.md §2
 # documents importing the mode switches from here.  Its state tables stay reachable here too, as the very objects that module
 # updates in place (never rebound), for code written against this module (benchkit/leg_train.py reads _capacity_hint).
@@ -35,37 +37,6 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: torch.Tensor
     prefiltered: bool
     debug: bool
-
-
-def _ptr(t):
-    return None if t is None or t.numel() == 0 else C.c_void_p(t.data_ptr())
-
-
-def _f32(t, name, dev):
-    if t is None:
-        return None
-    if not torch.is_tensor(t):
-        raise TypeError(f"{name} must be a tensor")
-    if t.device != dev:
-        raise RuntimeError(f"{name} is on {t.device}, expected {dev}")
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be float32 (got {t.dtype})")
-    return t.contiguous()
-
-
-def _settings_struct(rs, dev, sh_coeffs, keep):
-    bg = _f32(rs.bg, "bg", dev); vm = _f32(rs.viewmatrix, "viewmatrix", dev)
-    pm = _f32(rs.projmatrix, "projmatrix", dev); cp = _f32(rs.campos, "campos", dev)
-    keep.extend([bg, vm, pm, cp])
-    s = _lib.SgRasterSettings()
-    s.image_height = int(rs.image_height); s.image_width = int(rs.image_width)
-    s.tanfovx = float(rs.tanfovx); s.tanfovy = float(rs.tanfovy)
-    s.scale_modifier = float(rs.scale_modifier)
-    s.sh_degree = int(rs.sh_degree); s.sh_coeffs = int(sh_coeffs)
-    s.prefiltered = int(bool(rs.prefiltered)); s.debug = int(bool(rs.debug)); s.flags = 0
-    s.bg = bg.data_ptr(); s.viewmatrix = vm.data_ptr(); s.projmatrix = pm.data_ptr(); s.campos = cp.data_ptr()
-    s.count_signal = None; s.count_signal_host = None
-    return s
 
 
 def _backward_buffers(dev, P, M, bwd_bytes, has_sh, has_col, has_scale, has_cov):
@@ -129,7 +100,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         M = int(sh.shape[1]) if sh is not None else 0
         keep = []
         s = _settings_struct(rs, dev, M, keep)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _stream(dev)
         color = torch.empty((3, H, W), dtype=torch.float32, device=dev)
         if return_aux:
             depth = torch.empty((1, H, W), dtype=torch.float32, device=dev)
@@ -224,7 +195,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 _ptr(img), _ptr(bwd_ws), _ptr(g), _ptr(dmeans3D), _ptr(dmeans2D), _ptr(dsh), _ptr(dcol),
                 _ptr(dopac), _ptr(dscales), _ptr(drots), _ptr(dcov))
         with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _stream(dev)
             if gD is None and gA is None:       # neither map carries a gradient: the plain backward, bit for bit
                 _lib.check(lib.sg_rasterize_backward(*args, stream), "backward")
             else:
@@ -262,8 +233,7 @@ class GaussianRasterizer(nn.Module):
             pm = _f32(rs.projmatrix, "projmatrix", dev)
             out = torch.empty(pos.shape[0], dtype=torch.uint8, device=dev)
             with torch.cuda.device(dev):
-                _lib.check(lib.sg_mark_visible(int(pos.shape[0]), _ptr(pos), _ptr(vm), _ptr(pm), _ptr(out),
-                                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                _lib.check(lib.sg_mark_visible(int(pos.shape[0]), _ptr(pos), _ptr(vm), _ptr(pm), _ptr(out), _stream(dev)),
                            "mark_visible")
         return out.bool()
 

@@ -13,17 +13,11 @@ Each returns a 0-dim loss tensor with autograd; the gradient is computed in the 
 scaled in backward.  Static graph structure (CSR of same-label edges, degrees, per-vertex region scale) is built once on
 the host with numpy, like ``reset_laplacians`` does with torch.  No CPU fallback.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
-from .rasterizer import _ptr
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+from ._marshal import _ptr, _stream
 
 
 def _need_gpu(t, what):

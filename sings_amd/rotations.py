@@ -12,11 +12,10 @@ Inputs are fp32 tensors on the GPU with any leading batch shape; gradients are w
 reference expressions.  There is NO CPU / eager path: host tensors raise (the torch restatement used to check these
 kernels lives in oracle/rotations_oracle.py and is test infrastructure).
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._marshal import _ptr, _stream
 
 _Q2M, _R6D2M, _AA2Q, _Q2AA = 0, 1, 2, 3           # SG_ROT_* of include/sings_hip.h
 _WIDTH = {_Q2M: (4, 9), _R6D2M: (6, 9), _AA2Q: (3, 4), _Q2AA: (4, 3)}
@@ -34,14 +33,6 @@ def _check(t, width, name):
     return t.contiguous()
 
 
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
-
-
 class _Convert(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, op):
@@ -51,7 +42,7 @@ class _Convert(torch.autograd.Function):
         out = torch.empty(x.shape[:-1] + (no,), dtype=torch.float32, device=x.device)
         if n:
             with torch.cuda.device(x.device):
-                _lib.check(lib.sg_rotation_convert(op, n, _p(x), _p(out), _stream(x.device)), "rotation convert")
+                _lib.check(lib.sg_rotation_convert(op, n, _ptr(x), _ptr(out), _stream(x.device)), "rotation convert")
         ctx.op = op
         ctx.save_for_backward(x)
         return out
@@ -66,7 +57,7 @@ class _Convert(torch.autograd.Function):
         dx = torch.empty_like(x)
         if n:
             with torch.cuda.device(x.device):
-                _lib.check(lib.sg_rotation_convert_backward(ctx.op, n, _p(x), _p(g), _p(dx), _stream(x.device)),
+                _lib.check(lib.sg_rotation_convert_backward(ctx.op, n, _ptr(x), _ptr(g), _ptr(dx), _stream(x.device)),
                            "rotation convert backward")
         return dx, None
 
@@ -79,7 +70,7 @@ class _M2Q(torch.autograd.Function):
         q = torch.empty(m.shape[:-2] + (4,), dtype=torch.float32, device=m.device)
         if n:
             with torch.cuda.device(m.device):
-                _lib.check(lib.sg_matrix_to_quaternion(n, _p(m), _p(q), _stream(m.device)), "matrix_to_quaternion")
+                _lib.check(lib.sg_matrix_to_quaternion(n, _ptr(m), _ptr(q), _stream(m.device)), "matrix_to_quaternion")
         ctx.save_for_backward(m)
         return q
 
@@ -91,7 +82,7 @@ class _M2Q(torch.autograd.Function):
         dm = torch.empty_like(m)
         if m.numel():
             with torch.cuda.device(m.device):
-                _lib.check(lib.sg_matrix_to_quaternion_backward(m.numel() // 9, _p(m), _p(dq), _p(dm), _stream(m.device)),
+                _lib.check(lib.sg_matrix_to_quaternion_backward(m.numel() // 9, _ptr(m), _ptr(dq), _ptr(dm), _stream(m.device)),
                            "matrix_to_quaternion backward")
         return dm
 
@@ -103,7 +94,7 @@ class _QMul(torch.autograd.Function):
         out = torch.empty_like(a)
         if a.numel():
             with torch.cuda.device(a.device):
-                _lib.check(lib.sg_quaternion_multiply(a.numel() // 4, _p(a), _p(b), _p(out), _stream(a.device)),
+                _lib.check(lib.sg_quaternion_multiply(a.numel() // 4, _ptr(a), _ptr(b), _ptr(out), _stream(a.device)),
                            "quaternion_multiply")
         ctx.save_for_backward(a, b)
         return out
@@ -116,7 +107,7 @@ class _QMul(torch.autograd.Function):
         da, db = torch.empty_like(a), torch.empty_like(b)
         if a.numel():
             with torch.cuda.device(a.device):
-                _lib.check(lib.sg_quaternion_multiply_backward(a.numel() // 4, _p(a), _p(b), _p(g), _p(da), _p(db),
+                _lib.check(lib.sg_quaternion_multiply_backward(a.numel() // 4, _ptr(a), _ptr(b), _ptr(g), _ptr(da), _ptr(db),
                                                                _stream(a.device)), "quaternion_multiply backward")
         return da, db
 

@@ -8,40 +8,15 @@ blended T[N,4,4] never reach HBM.  Gradients flow to xyz_canon, rotmat_canon, sc
 ``A`` (hence body_pose / global_orient through the SMPL chain in torch) and ``transl``.
 
 Pair capacity, overflow check and the learned long-rows hint: ``sings_amd.overflow`` (``run_forward``), the same policy as the
-drop-in rasterizer's, with the per-op differences spelled out at the two calls below.
+drop-in rasterizer's, with the per-op differences spelled out at the two calls below.  The skin inputs and the frame batch of a
+call are filled by sings_amd/_marshal.py (``_skin_struct``, ``_skin_frames``), shared with the engines.
 """
 import ctypes as C
 
 import torch
 
 from . import _lib, overflow
-from .rasterizer import _f32, _ptr, _settings_struct
-
-
-def _skin_struct(dev, xyz_canon, rotmat_canon, lbs_weights, A, smpl_scale, transl, ext_tfs, keep):
-    """rotmat_canon: None (isotropic), [N,9] / [N,3,3] rotation matrices, or [N,6] in the decoder's 6-D form
-    (rotation_6d_to_matrix then runs inside the kernels)."""
-    k = _lib.SgSkinInputs()
-    A = _f32(A, "A", dev).reshape(-1, 16)
-    k.J = int(A.shape[0])
-    k.rot_format = 1 if (rotmat_canon is not None and rotmat_canon.shape[-1] == 6 and rotmat_canon.dim() == 2) else 0
-    lbs_weights = _f32(lbs_weights, "lbs_weights", dev)
-    if lbs_weights.shape != (xyz_canon.shape[0], k.J):
-        raise RuntimeError(f"lbs_weights must be [N,{k.J}], got {tuple(lbs_weights.shape)}")
-    ts = [xyz_canon, rotmat_canon, lbs_weights, A,
-          None if smpl_scale is None else _f32(smpl_scale, "smpl_scale", dev).reshape(-1),
-          None if transl is None else _f32(transl, "transl", dev).reshape(-1)]
-    if ext_tfs is not None:
-        tr, rm, sc = ext_tfs
-        ts += [_f32(tr, "ext trans", dev).reshape(-1), _f32(rm, "ext rotmat", dev).reshape(-1),
-               _f32(sc, "ext scale", dev).reshape(-1)]
-    else:
-        ts += [None, None, None]
-    keep.extend(ts)
-    for name, t in zip(("xyz_canon", "rot_canon", "lbs_weights", "A", "smpl_scale", "transl", "ext_trans", "ext_rot",
-                        "ext_scale"), ts):
-        setattr(k, name, None if t is None else t.data_ptr())
-    return k
+from ._marshal import _camera_stride, _f32, _ptr, _settings_struct, _skin_frames, _skin_struct, _stream
 
 
 def _canonical_inputs(xyz_canon, rotmat_canon, scales, opacities, shs):
@@ -81,7 +56,7 @@ class _RasterizeSkinnedGaussians(torch.autograd.Function):
         e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
         pxyz, pq, psc = (e(P, 3), e(P, 4), e(P, 3)) if return_posed else (None, None, None)
         depth, alpha = (e(1, H, W), e(1, H, W)) if return_aux else (None, None)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _stream(dev)
         geom = binning = img = aux = None
 
         def launch(cap, flags, sync):
@@ -162,7 +137,7 @@ class _RasterizeSkinnedGaussians(torch.autograd.Function):
             L = _lib.layout(P, W, H, ctx.cap)
             bwd_ws = torch.empty(L.bwd_bytes, dtype=torch.uint8, device=dev)
             skin_ws = e(int(lib.sg_skin_ws_floats(P)))
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _stream(dev)
             args = (C.byref(s), P, C.byref(k), _ptr(shs), _ptr(opacities), _ptr(scales), _ptr(radii), _ptr(geom),
                     _ptr(binning), ctx.cap, _ptr(img), _ptr(bwd_ws), _ptr(skin_ws), _ptr(g_color), _ptr(g_pxyz), _ptr(g_pq),
                     _ptr(d_xyz), _ptr(d_rot), _ptr(d_scales), _ptr(d_op), _ptr(d_sh), _ptr(d_m2d), _ptr(d_A), _ptr(d_tr))
@@ -210,7 +185,6 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz_canon, rotmat_canon, scales, opacities, shs, A, transl, lbs_weights, smpl_scale, raster_settings,
                 means2D=None, return_aux=False):
-        from .engine import _frame_batch
         lib = _lib.load()
         dev, xyz_canon, rotmat_canon, rot_shape, scales, opacities, shs = _canonical_inputs(xyz_canon, rotmat_canon, scales,
                                                                                             opacities, shs)
@@ -222,30 +196,18 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
         if A.dim() < 3 or not 1 <= K <= _lib.MAX_FRAMES:
             raise RuntimeError(f"A must be [K,J,4,4] / [K,J,16] with K in 1..{_lib.MAX_FRAMES}, got {tuple(A.shape)}")
         A16 = A.reshape(K, -1, 16)
-        tstride = 0
-        if transl is not None:
-            transl = _f32(transl, "transl", dev)
-            if transl.numel() == 3 * K and K > 1:
-                tstride = 3
-            elif transl.numel() != 3:
-                raise RuntimeError(f"transl must be [{K},3] or [3], got {tuple(transl.shape)}")
-        vm = rs.viewmatrix
-        cam_stride = 1 if vm.dim() == 3 else 0
-        if cam_stride and (vm.shape[0] != K or rs.projmatrix.shape[0] != K or rs.campos.shape[0] != K):
-            raise RuntimeError(f"per-frame cameras must be stacked [{K},4,4] / [{K},3]")
+        transl = _f32(transl, "transl", dev)
+        cam_stride = _camera_stride(rs, K, RuntimeError)
         P = int(xyz_canon.shape[0]); H, W = int(rs.image_height), int(rs.image_width); M = int(shs.shape[1])
         keep = []
         s = _settings_struct(rs, dev, M, keep)
-        k = _skin_struct(dev, xyz_canon, rotmat_canon, lbs_weights, A16[0], smpl_scale,
-                         None if transl is None else transl.reshape(-1)[:3], None, keep)
-        k.A = A16.data_ptr()
-        k.transl = None if transl is None else transl.data_ptr()
-        fb = _frame_batch(K, cam_stride, tstride)
+        k, fb, _ = _skin_frames(dev, xyz_canon, rotmat_canon, lbs_weights, A16, smpl_scale, transl, None, cam_stride, keep,
+                                RuntimeError)
         color = torch.empty((K, 3, H, W), dtype=torch.float32, device=dev)
         radii = torch.empty((K, P), dtype=torch.int32, device=dev)
         depth, alpha = ((torch.empty((K, 1, H, W), dtype=torch.float32, device=dev),
                          torch.empty((K, 1, H, W), dtype=torch.float32, device=dev)) if return_aux else (None, None))
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = _stream(dev)
         L = geom = binning = img = sizes = aux = None
 
         def launch(cap, flags, sync):
@@ -276,7 +238,7 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
             early_count=False)                # one early-count word holds one frame's count: the K counts are read after the call
         if nr is None:
             nr = [0] * K
-        ctx.rs, ctx.cap, ctx.M, ctx.K, ctx.fb = rs, cap, M, K, (cam_stride, tstride)
+        ctx.rs, ctx.cap, ctx.M, ctx.K, ctx.fb = rs, cap, M, K, (cam_stride, fb.transl_stride)
         ctx.num_rendered = [int(v) for v in nr]
         ctx.has_rot = rotmat_canon is not None
         ctx.rot_shape = rot_shape
@@ -294,7 +256,6 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_color, _g_radii=None, g_depth=None, g_alpha=None):
-        from .engine import _frame_batch
         lib = _lib.load()
         xyz_canon, rotmat_canon, scales, opacities, shs, A16, transl, radii, geom, binning, img = ctx.saved_tensors
         lbs_weights, smpl_scale, A_shape, transl_shape, bwd_bytes = ctx.aux
@@ -304,11 +265,8 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
         keep = []
         s = _settings_struct(rs, dev, ctx.M, keep)
         s.flags = _lib.FLAG_THROUGHPUT
-        k = _skin_struct(dev, xyz_canon, rotmat_canon if ctx.has_rot else None, lbs_weights, A16[0], smpl_scale,
-                         transl.reshape(-1)[:3] if transl_shape is not None else None, None, keep)
-        k.A = A16.data_ptr()
-        k.transl = transl.data_ptr() if transl_shape is not None else None
-        fb = _frame_batch(K, *ctx.fb)
+        k, fb, _ = _skin_frames(dev, xyz_canon, rotmat_canon if ctx.has_rot else None, lbs_weights, A16, smpl_scale,
+                                transl if transl_shape is not None else None, None, ctx.fb[0], keep, RuntimeError)
         e = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
         d_xyz, d_scales, d_op, d_sh, d_m2d = e(P, 3), e(P, 3), e(P, 1), e(P, ctx.M, 3), e(K, P, 3)
         d_rot = e(P, int(rotmat_canon.shape[1])) if ctx.has_rot else None
@@ -323,7 +281,7 @@ class _RasterizeSkinnedFrames(torch.autograd.Function):
         with torch.cuda.device(dev):
             bwd_ws = torch.empty(bwd_bytes, dtype=torch.uint8, device=dev)
             skin_ws = e(int(lib.sg_skin_ws_floats_frames(P, K)))
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = _stream(dev)
             rec = (C.byref(s), C.byref(fb), P, _ptr(geom), _ptr(binning), ctx.cap, _ptr(img), _ptr(bwd_ws), _ptr(g_color))
             gau = (C.byref(s), C.byref(fb), P, C.byref(k), _ptr(shs), _ptr(opacities), _ptr(scales), _ptr(radii), _ptr(geom), _ptr(binning),
                    ctx.cap, _ptr(bwd_ws), _ptr(skin_ws), 0, None, None, _ptr(d_xyz), _ptr(d_rot), _ptr(d_scales), _ptr(d_op), _ptr(d_sh),

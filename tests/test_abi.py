@@ -21,6 +21,47 @@ def test_library_exports_every_declared_symbol(repo_root):
     assert b"gfx950" in lib.sg_version()
 
 
+def test_every_prototype_of_the_header_is_bound_with_its_types(repo_root):
+    """Each ``int | size_t | const char * sg_x(...)`` of include/sings_hip.h against the argtypes / restype the LOADED library object
+    carries: the same number of parameters, each of the same class (int / int32_t: a 32-bit int, size_t, float, anything with
+    ``*`` or ``[``: a pointer -- to the very struct class where the header names one of the six structs), the same return type."""
+    import ctypes as C
+    from sings_amd import _lib
+    hdr = open(os.path.join(repo_root, "include", "sings_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", "", hdr)
+    protos = re.findall(r"\b(int|size_t|const\s+char\s*\*)\s*(sg_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr)
+    assert protos and len({n for _, n, _ in protos}) == len(protos)
+    assert {n for _, n, _ in protos} == set(_lib.EXPORTS)
+    structs = {n: getattr(_lib, n) for n in ("SgRasterSettings", "SgFrameBatch", "SgSkinInputs", "SgLayout", "SgTriplane",
+                                             "SgLinearSide")}
+    pointer_bases = (C._Pointer, C.c_void_p, C.c_char_p)
+    scalars = {"int": C.c_int, "int32_t": C.c_int, "size_t": C.c_size_t, "float": C.c_float}
+    assert C.sizeof(C.c_int) == 4
+    lib = _lib.load()
+    bad = []
+    for ret, name, params in protos:
+        fn = getattr(lib, name)
+        want_ret = {"int": C.c_int, "size_t": C.c_size_t}.get(ret, C.c_char_p)
+        if fn.restype is not want_ret:
+            bad.append(f"{name}: restype {fn.restype}, the header returns {ret}")
+        params = [] if params.strip() in ("", "void") else [p.strip() for p in params.split(",")]
+        argtypes = fn.argtypes or ()                                 # (never declared: None)
+        if len(argtypes) != len(params):
+            bad.append(f"{name}: {len(argtypes)} argtypes, the header has {len(params)} parameters")
+            continue
+        for i, (p, t) in enumerate(zip(params, argtypes)):
+            if "*" in p or "[" in p:
+                named = [c for n, c in structs.items() if re.search(rf"\b{n}\b", p)]
+                ok = (t is C.POINTER(named[0])) if named else issubclass(t, pointer_bases)
+            else:
+                words = [w for w in re.findall(r"\w+", p) if w not in ("const", "unsigned")]
+                ok = t is scalars.get(words[0])
+            if not ok:
+                bad.append(f"{name}: parameter {i} `{p}` is bound as {t}")
+    assert not bad, "\n".join(bad)
+
+
 def test_layout_is_consistent():
     from sings_amd import _lib
     L = _lib.layout(1000, 1920, 1080, 50000)

@@ -208,7 +208,7 @@ def test_python_surface():
 
 
 def test_frame_rows_shared_or_per_frame():
-    from sings_amd.engine import _frame_rows
+    from sings_amd._marshal import _frame_rows
     K = 5
     t, per = _frame_rows(torch.tensor([0.5]).expand(K, 1), K, 1, "s")          # the reference's .expand: shared, not copied
     assert not per and t.shape == (1,)

@@ -301,8 +301,8 @@ def test_capacity_overflow_fallback_keeps_the_placement():
 def test_backward_refuses_placement_and_per_frame_scale():
     import ctypes as C
     from sings_amd import _lib
-    from sings_amd.engine import SkinnedFramesEngine, _frame_batch
-    from sings_amd.rasterizer import _ptr
+    from sings_amd.engine import SkinnedFramesEngine
+    from sings_amd._marshal import _frame_batch, _ptr
     dev = _dev()
     N, J, W, H, K = 2000, 52, 160, 288, 3
     s, ins, A, transl, one, stacked, dL = _avatar(N, J, W, H, 2, K, False, False)

@@ -418,7 +418,7 @@ def test_posed_side_outputs_of_a_k_frame_forward():
     import ctypes as C
     from sings_amd import _lib
     from sings_amd.engine import SkinnedFramesEngine
-    from sings_amd.rasterizer import _ptr
+    from sings_amd._marshal import _ptr
     dev = _dev()
     lib = _lib.load()
     N, J, W, H, K = 9000, 52, 128, 224, 4
@@ -452,8 +452,8 @@ def test_frames_through_the_c_abi_with_precomputed_colours_and_covariances():
     import ctypes as C
     from oracle import raster_oracle as ro
     from sings_amd import _lib
-    from sings_amd.engine import _frame_batch
-    from sings_amd.rasterizer import GaussianRasterizationSettings, _ptr, _settings_struct
+    from sings_amd._marshal import _frame_batch, _ptr, _settings_struct
+    from sings_amd.rasterizer import GaussianRasterizationSettings
     from sings_amd.scene import synthetic_scene
     dev = _dev()
     lib = _lib.load()

@@ -480,7 +480,7 @@ def test_capacity_overflow_is_reported_and_harmless():
     entries (workspaces poisoned with 0xFF here) and renders the background."""
     import ctypes as C
     from sings_amd import _lib
-    from sings_amd.rasterizer import _settings_struct, _ptr
+    from sings_amd._marshal import _settings_struct, _ptr
     dev = _dev()
     s = synthetic_scene(3000, 160, 128, 0, 9)
     s["scales"] = (s["scales"] * 30).astype(np.float32)

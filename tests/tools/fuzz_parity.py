@@ -77,7 +77,7 @@ def aux_abi(s, dLc, gD, gA, flags=0, capacity=None, pad=0, sentinel=0.0, geometr
     (gD / gA given as [H,W]).  `geometry`: None (scales + rotations) or a cov3D_precomp array; `colors`: colors_precomp instead of
     the SH.  -> dict of tensors (the padded buffers whole: depth_buf, alpha_buf), R = NUM_RENDERED_LONG_LIST on a refusal."""
     from sings_amd import _lib
-    from sings_amd.rasterizer import _settings_struct, _ptr
+    from sings_amd._marshal import _settings_struct, _ptr
     lib = _lib.load()
     rs = settings(s)
     H, W = s["H"], s["W"]
