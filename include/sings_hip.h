@@ -95,7 +95,8 @@ typedef struct SgLayout {
  * entry points added since 8: sg_frames_aux_layout, sg_skinned_forward_frames_aux, sg_rasterize_backward_records_frames_aux,
  * sg_skinned_backward_gaussians_frames_aux (depth and alpha maps of K frames); sg_lpips_weights_layout, sg_lpips_ws_bytes,
  * sg_lpips_forward, sg_lpips_backward, sg_lpips_patch_gather, sg_lpips_patch_scatter (the LPIPS-VGG patch loss),
- * sg_lpips_ws_layout (its workspace pieces); sg_frames_to_u8 (8-bit HWC frames).  Also since 8: SgFrameBatch.reserved became
+ * sg_lpips_ws_layout (its workspace pieces); sg_frames_to_u8 (8-bit HWC frames); sg_adam_chunk_elements, sg_adam_step (the fused Adam
+ * step).  Also since 8: SgFrameBatch.reserved became
  * SgFrameBatch.placement (per-frame ext_tfs / smpl_scale in the skinned K-frame forward); 0, what every ABI-8 caller passes, keeps
  * the earlier meaning. */
 #define SG_ABI_VERSION 8
@@ -685,6 +686,26 @@ int sg_lpips_patch_scatter(int K, int n, int patch, int height, int width, const
  * with the channels in RGB order, or BGR when bgr != 0.  Any K >= 1 (<= 65535), width, height >= 1 (odd sizes too); rgb and out must
  * not overlap.  Bad sizes and NULL pointers are refused (status 1, sg_last_error) before anything is launched. */
 int sg_frames_to_u8(int K, int width, int height, const float *rgb, int bgr, uint8_t *out, void *stream);
+
+/* ---- fused Adam step (entry points added to ABI 8) ----------------------------------------------------------------------------------
+ * `torch.optim.Adam.step()` (single-tensor formulation; no weight decay, no amsgrad, not maximize) over EVERY parameter of every
+ * group in ONE launch, capturable: whatever changes from step to step is read from device memory.
+ *   segments  [n_segments][4] int64   one record per parameter tensor: its address, its offset in the arena (floats), its element
+ *                                     count, its group.  The parameter is n dense floats (any memory order: the arena slot and the
+ *                                     moments hold the same order)
+ *   chunks    [n_chunks][2]   int32   (segment, first element): elements [first, min(first + sg_adam_chunk_elements(), count)) of
+ *                                     the segment; the caller's table covers every element of every segment exactly once
+ *   hyper     [n_groups][8]   fp32    row of a group: w1 = 1 - beta1, b2 = beta2, w2 = 1 - beta2, c2 = sqrt(1 - beta2^t), eps,
+ *                                     neg_step = -(lr_t / (1 - beta1^t)), two unused; computed in double, rounded once
+ *   grad_flat, exp_avg, exp_avg_sq    the flat gradient arena and the two moment buffers of its layout (16-byte aligned, distinct)
+ * Per element, in fp32, in exactly this order (nothing contracted, correctly rounded division and square root, denormals kept;
+ * NaN / Inf propagate):
+ *   m' = m + (g - m) * w1;   v' = v * b2 + (w2 * g) * g;   d = sqrt(v') / c2 + eps;   p' = p + (neg_step * m') / d
+ * NULL pointers, negative counts, n_groups < 1 and misaligned or identical flat buffers are refused (status 1, sg_last_error) before
+ * anything is launched; n_chunks == 0 launches nothing.  The tables' CONTENTS are the caller's: they are not read on the host. */
+size_t sg_adam_chunk_elements(void);
+int sg_adam_step(int n_segments, int n_chunks, int n_groups, const int64_t *segments, const int32_t *chunks, const float *hyper,
+                 const float *grad_flat, float *exp_avg, float *exp_avg_sq, void *stream);
 
 /* ---- optional per-kernel timing (bench / profiling only; process-global, not thread-safe).
  * When enabled, every kernel launch of forward/backward is bracketed by hipEvents on the

@@ -147,6 +147,8 @@ _PROTOTYPES = {
     "sg_lpips_patch_gather": "i: i5 p9",
     "sg_lpips_patch_scatter": "i: i5 p7",
     "sg_frames_to_u8": "i: i3 p i p2",
+    "sg_adam_chunk_elements": "z:",
+    "sg_adam_step": "i: i3 p7",
     "sg_profile_enable": "i: i",
     "sg_copy_probe": "i: p2 z i p",
     "sg_profile_collect": "i: d n i",

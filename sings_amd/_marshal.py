@@ -121,3 +121,18 @@ def _skin_frames(dev, xyz_canon, rotmat_canon, lbs_weights, A, smpl_scale, trans
         tstride = 3
     k = _skin_struct(dev, xyz_canon, rotmat_canon, lbs_weights, A, smpl_scale, transl, ext_tfs, keep, J=J)
     return k, _frame_batch(K, camera_stride, tstride, placement), ext_tfs is not None or bool(placement)
+
+
+def adam_step(segments, chunks, hyper, grad_flat, exp_avg, exp_avg_sq):
+    """``sg_adam_step`` on torch's current stream: ``segments`` [S,4] int64, ``chunks`` [C,2] int32 and ``hyper`` [G,8] fp32 are
+    device tensors (``sings_amd.optim.build_tables`` / ``hyper_row``), the other three the flat fp32 buffers of one layout."""
+    dev = grad_flat.device
+    for name, t, dt in (("segments", segments, torch.int64), ("chunks", chunks, torch.int32), ("hyper", hyper, torch.float32),
+                        ("grad_flat", grad_flat, torch.float32), ("exp_avg", exp_avg, torch.float32),
+                        ("exp_avg_sq", exp_avg_sq, torch.float32)):
+        if not t.is_cuda or t.device != dev or t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError(f"adam_step: {name} must be a contiguous {dt} tensor on {dev} (no CPU fallback)")
+    if exp_avg.numel() != grad_flat.numel() or exp_avg_sq.numel() != grad_flat.numel():
+        raise RuntimeError("adam_step: grad_flat, exp_avg and exp_avg_sq must have the same number of elements")
+    _lib.check(_lib.load().sg_adam_step(int(segments.shape[0]), int(chunks.shape[0]), int(hyper.shape[0]), _ptr(segments), _ptr(chunks),
+                                        _ptr(hyper), _ptr(grad_flat), _ptr(exp_avg), _ptr(exp_avg_sq), _stream(dev)), "sg_adam_step")

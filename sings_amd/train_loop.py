@@ -16,7 +16,8 @@ A topology change (or a new SH degree) invalidates everything that was sized or 
     the captured HIP graph          ``CapturedStep.replay`` raises until ``AvatarTrainer`` has captured the step again
     the gradient arena              ``decode.arena_sync`` raises for a stale registration; the trainer registers the new parameters
     the pair-capacity hint          re-measured with synchronous steps before the overflow check is deferred again
-    Adam's moments, the statistics  re-indexed (kept rows, zeros for the clones) / reset, as the reference does
+    Adam's moments, the statistics  re-indexed (kept rows, zeros for the clones) / reset, as the reference does (``FusedAdam.remap_rows``
+                                    rebuilds its flat moment buffers and tables for the new sizes)
     the frame-parallel collective   sized by the new flat buffer; the statistics are reduced (sum, sum, max) BEFORE the decision, so every
                                     rank takes the same one (``densify_decision`` is a pure function of the reduced statistics)
 
@@ -27,6 +28,7 @@ import torch
 
 from . import decode as _dec
 from . import overflow
+from .optim import FusedAdam
 from .train_step import capture_step
 
 
@@ -69,16 +71,31 @@ class AvatarTrainer:
     """``step(A, gt_rgb, mask)`` = one optimisation step on one posed frame (or a chunk [K,J,4,4]); ``densify_and_prune()`` /
     ``oneup_sh_degree()`` between steps.  ``use_graph``: the step (zero_grad, forward, backward) replays from a HIP graph that is
     captured again after every topology change; Adam and the statistics run outside it.  ``fp``: a ``sings_amd.dp.FrameParallel``
-    -- parameter gradients live in one flat arena buffer and are all-reduced, the statistics are reduced before a decision."""
+    -- parameter gradients live in one flat arena buffer and are all-reduced, the statistics are reduced before a decision.
+
+    ``optimizer``: ``"torch"`` (``torch.optim.Adam``, outside the graph) or ``"fused"`` (``sings_amd.optim.FusedAdam``: the gradient
+    arena is always created and ONE launch updates every parameter; without ``fp`` that launch is part of the step's body, so a
+    captured step contains it and only the host half -- step counts, the per-group rows -- runs outside; with ``fp`` it follows the
+    all-reduce).  ``lr_schedules``: ``{group name: fn(iteration)}``, applied to the optimiser's groups before every step."""
 
     def __init__(self, module, settings_fn, bg_color, lrs, smpl_scale=None, transl=None, use_graph=False, fp=None,
-                 sh_degree=0, max_sh_degree=3, betas=(0.9, 0.999), eps=1e-15):
+                 sh_degree=0, max_sh_degree=3, betas=(0.9, 0.999), eps=1e-15, optimizer="torch", lr_schedules=None):
         self.m, self.settings_fn, self.bg = module, settings_fn, bg_color
         self.smpl_scale, self.transl, self.use_graph, self.fp = smpl_scale, transl, bool(use_graph), fp
         self.sh_degree, self.max_sh_degree = int(sh_degree), int(max_sh_degree)
         self.lrs, self.betas, self.eps = dict(lrs), betas, eps
         self.dev = module.xyz.device
-        self.opt = torch.optim.Adam(self._groups(), betas=betas, eps=eps)
+        if optimizer not in ("torch", "fused"):
+            raise ValueError(f"AvatarTrainer: optimizer must be 'torch' or 'fused', got {optimizer!r}")
+        self.fused = optimizer == "fused"
+        self.lr_schedules = dict(lr_schedules or {})
+        unknown = set(self.lr_schedules) - set(self.lrs)
+        if unknown:
+            raise ValueError(f"AvatarTrainer: lr_schedules for unknown groups {sorted(unknown)}")
+        if self.fused:
+            self.opt = FusedAdam(self._groups(), betas=betas, eps=eps)        # (bound to the arena by _rebuild)
+        else:
+            self.opt = torch.optim.Adam(self._groups(), betas=betas, eps=eps)
         self.captured = self.flat = self.views = None
         self.iteration = 0
         self._static = {}
@@ -99,10 +116,12 @@ class AvatarTrainer:
         self.params = [p for g in self.opt.param_groups for p in g["params"]]
         m.enable_densification_stats()
         self.captured = None
-        if self.fp is not None:
+        if self.fp is not None or self.fused:
             n = sum(p.numel() for p in self.params)
             self.flat = torch.zeros(n, dtype=torch.float32, device=self.dev)
             self.views = _dec.set_gradient_arena(self.params, self.flat)
+        if self.fused:
+            self.opt.bind_arena(self.flat, self.views)
         if self.dev.type == "cuda":
             overflow.set_overflow_check("sync")                  # the next steps size the pair capacity for the new set
             overflow.reset_overflow_state()
@@ -119,6 +138,8 @@ class AvatarTrainer:
         else:
             loss.backward()
         self.m.add_densification_stats(ex)
+        if self.fused and self.fp is None:
+            self.opt.apply()                                     # (the Adam launch: part of the body, and so of a captured step)
         return {k: v.detach().reshape(()).clone() for k, v in ld.items()}
 
     def step(self, A, gt_rgb, mask, lpips_origins=None, lpips_bg=None):
@@ -139,14 +160,25 @@ class AvatarTrainer:
             for k, v in lp.items():
                 if v is not None:
                     s[k].copy_(v)
+        for g in self.opt.param_groups:
+            if g["name"] in self.lr_schedules:
+                g["lr"] = self.lr_schedules[g["name"]](self.iteration)
+        if self.fused:
+            self.opt.advance()                                   # host half: this step's rows are on their way before the body runs
         if self.use_graph and self._sizing == 0:
             if self.captured is None:
                 overflow.set_deferred_overflow_check(True, capacity_pairs=overflow.capacity_pairs(self.dev))
-                # (the capture's warm-up runs execute the body -- statistics included -- without being steps: put the statistics back)
-                keep = [x.clone() for x in (self.m.xyz_gradient_accum, self.m.denom, self.m.max_radii2D)]
+                # (the capture's warm-up runs execute the body -- statistics included -- without being steps: put the statistics back;
+                # with the fused optimiser in the body they update parameters and moments too: those go back as well)
+                live = [self.m.xyz_gradient_accum, self.m.denom, self.m.max_radii2D]
+                if self.fused and self.fp is None:
+                    live += [p.detach() for p in self.params] + [self.opt.exp_avg, self.opt.exp_avg_sq]
+                keep, steps = [x.clone() for x in live], (list(self.opt.steps) if self.fused else None)
                 self.captured = CapturedStep(self.m, self._body, warmup=2, device=self.dev)
-                for dst, src in zip((self.m.xyz_gradient_accum, self.m.denom, self.m.max_radii2D), keep):
+                for dst, src in zip(live, keep):
                     dst.copy_(src)
+                if self.fused:
+                    self.opt.steps[:] = steps
                 overflow.check_deferred_overflow(self.dev)
             ld = self.captured.replay()
         else:
@@ -156,7 +188,10 @@ class AvatarTrainer:
             _dec.arena_sync(self.params, self.views, True)
             self.fp.all_reduce_grads(self.flat)
             _dec.arena_sync(self.params, self.views, False)
-        self.opt.step()
+            if self.fused:
+                self.opt.apply(sync=False)                       # (the arena holds the reduced gradients)
+        if not self.fused:
+            self.opt.step()
         self.iteration += 1
         return ld
 
@@ -186,10 +221,12 @@ class AvatarTrainer:
             # Adam moments: kept rows for the survivors, zeros for the clones (cat_tensors_to_optimizer, _prune_optimizer)
             group = next(g for g in self.opt.param_groups if g["name"] == "xyz")
             old = group["params"][0]
-            state = self.opt.state.pop(old, None)
+            state = None if self.fused else self.opt.state.pop(old, None)
             new_xyz = torch.cat([old.detach(), old.detach()[clone]])[keep].clone()
             new_w = torch.cat([m.lbs_weights, m.lbs_weights[clone]])[keep].clone()
             m.set_topology(new_xyz, new_w)
+            if self.fused:
+                self.opt.remap_rows(old, m.xyz, clone, keep)
             group["params"][0] = m.xyz
             if state is not None:
                 for k in ("exp_avg", "exp_avg_sq"):
