@@ -96,7 +96,7 @@ typedef struct SgLayout {
  * sg_skinned_backward_gaussians_frames_aux (depth and alpha maps of K frames); sg_lpips_weights_layout, sg_lpips_ws_bytes,
  * sg_lpips_forward, sg_lpips_backward, sg_lpips_patch_gather, sg_lpips_patch_scatter (the LPIPS-VGG patch loss),
  * sg_lpips_ws_layout (its workspace pieces); sg_frames_to_u8 (8-bit HWC frames); sg_adam_chunk_elements, sg_adam_step (the fused Adam
- * step).  Also since 8: SgFrameBatch.reserved became
+ * step); sg_pose_transforms, sg_pose_transforms_backward (learned per-frame pose tables).  Also since 8: SgFrameBatch.reserved became
  * SgFrameBatch.placement (per-frame ext_tfs / smpl_scale in the skinned K-frame forward); 0, what every ABI-8 caller passes, keeps
  * the earlier meaning. */
 #define SG_ABI_VERSION 8
@@ -254,6 +254,31 @@ int sg_joint_transforms(int B, int J, const float *pose, const float *joints_res
                         float *A_out, void *stream);
 int sg_joint_transforms_backward(int B, int J, const float *pose, const float *joints_rest, const int32_t *parents,
                                  const float *post, const float *dA, float *dpose, float *djoints, void *stream);
+
+/* Learned per-frame SMPL(-H) poses (sings_hybrid.py:142-150, 370-399): a row of the 6-D pose tables -> A, ONE launch each way, the
+ * row named by an index in DEVICE memory (a launch captured into a HIP graph follows the index of the replay).
+ *   frame_idx      [K] int32, device     the table row of each of the K frames; a value outside [0, F) is clamped into it
+ *   global_orient  [F,6]                 6-D rotation of joint 0
+ *   body_pose      [F,SG_POSE_NB*6]      6-D rotations of body joints 1 .. SG_POSE_NB; the first NBu of them are used (joints 1 .. NBu)
+ *   tail_pose      [J-1-NBu,3]           constant axis-angle of joints NBu+1 .. J-1 (SMPL-H hands); NULL when J == NBu + 1
+ *   transl         [F,3] or NULL         gathered to transl_out [K,3] (both NULL or both given)
+ *   joints_rest [J,3], parents [J], post [J,16] or NULL: as sg_joint_transforms.  1 <= J <= 64, 0 <= NBu <= SG_POSE_NB, NBu < J.
+ * SMPL: J = 24, NBu = 23.  SMPL-H: J = 52, NBu = 21 (body_pose[:63], sings_hybrid.py:387-388), 30 tail rows.
+ * Per joint: rotation_6d_to_matrix -> matrix_to_quaternion -> quaternion_to_axis_angle (rotations.py:601-603: no quaternion
+ * standardisation), then sg_joint_transforms' chain -- bit for bit what those entry points give one after the other.
+ * Outputs: A_out [K,J,16], aa_out [K,J,3] (the axis-angle pose; backward reads it again).
+ * Backward: dA [K,J,16] (and d_transl_rows [K,3] with d_transl [F,3], both NULL or both given) -> DENSE d_global_orient [F,6],
+ * d_body_pose [F,SG_POSE_NB*6], d_transl [F,3]: every entry is written by the launch -- 0 for rows no frame names and for body joints
+ * beyond NBu -- so no memset precedes it.  No atomics: frames that name the same row are added in ascending position of frame_idx
+ * (bit-reproducible).  Only the selected quaternion candidate receives gradient (as sg_matrix_to_quaternion_backward). */
+#define SG_POSE_NB 23
+int sg_pose_transforms(int K, int F, int J, int NBu, const int32_t *frame_idx, const float *global_orient, const float *body_pose,
+                       const float *tail_pose, const float *transl, const float *joints_rest, const int32_t *parents,
+                       const float *post, float *A_out, float *aa_out, float *transl_out, void *stream);
+int sg_pose_transforms_backward(int K, int F, int J, int NBu, const int32_t *frame_idx, const float *global_orient,
+                                const float *body_pose, const float *aa, const float *joints_rest, const int32_t *parents,
+                                const float *post, const float *dA, const float *d_transl_rows, float *d_global_orient,
+                                float *d_body_pose, float *d_transl, void *stream);
 
 /* Stand-alone matrix_to_quaternion (sings/rec/utils/geometry/rotations.py:98-149; call site sings_hybrid.py:419):
  * matrices [N,9] row-major -> quaternions [N,4] (real first), bit-identical to the reference expression evaluated by

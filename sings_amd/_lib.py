@@ -47,6 +47,7 @@ class SgFrameBatch(C.Structure):
 
 
 MAX_FRAMES = 16                      # SG_MAX_FRAMES
+POSE_NB = 23                         # SG_POSE_NB: body joints per row of the body_pose table
 PLACEMENT_EXT_TFS = 1                # SG_PLACEMENT_EXT_TFS: ext_tfs [K,3] / [K,9] / [K], one set per frame
 PLACEMENT_SMPL_SCALE = 2             # SG_PLACEMENT_SMPL_SCALE: smpl_scale [K], one per frame
 
@@ -82,6 +83,8 @@ _PROTOTYPES = {
     "sg_lbs_backward": "i: i2 p9",
     "sg_joint_transforms": "i: i2 p6",
     "sg_joint_transforms_backward": "i: i2 p8",
+    "sg_pose_transforms": "i: i4 p12",
+    "sg_pose_transforms_backward": "i: i4 p13",
     "sg_matrix_to_quaternion": "i: i p3",
     "sg_matrix_to_quaternion_backward": "i: i p4",
     "sg_rotation_convert": "i: i2 p3",

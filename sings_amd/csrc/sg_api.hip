@@ -862,6 +862,40 @@ extern "C" int sg_joint_transforms_backward(int B, int J, const float *pose, con
     return e == hipSuccess ? 0 : sg_fail("sg_joint_transforms_backward", e);
 }
 
+// ---- learned per-frame pose tables -> A
+static bool sg_pose_shape_ok(int K, int F, int J, int NBu)
+{
+    return K >= 1 && F >= 1 && J >= 1 && J <= 64 && NBu >= 0 && NBu <= SG_POSE_NB && NBu < J;
+}
+extern "C" int sg_pose_transforms(int K, int F, int J, int NBu, const int32_t *frame_idx, const float *global_orient,
+                                  const float *body_pose, const float *tail_pose, const float *transl, const float *joints_rest,
+                                  const int32_t *parents, const float *post, float *A_out, float *aa_out, float *transl_out,
+                                  void *stream)
+{
+    if (!sg_pose_shape_ok(K, F, J, NBu) || !frame_idx || !global_orient || !body_pose || (J - 1 - NBu > 0 && !tail_pose) ||
+        !joints_rest || !parents || !A_out || !aa_out || (transl == nullptr) != (transl_out == nullptr))
+        return sg_fail("sg_pose_transforms: bad argument (1 <= J <= 64, 0 <= NBu <= 23, NBu < J; tail_pose for J - 1 - NBu joints; "
+                       "transl and transl_out together)", hipSuccess);
+    sg_launch_pose_transforms(K, F, J, NBu, (const int *)frame_idx, global_orient, body_pose, tail_pose, transl, joints_rest,
+                              (const int *)parents, post, A_out, aa_out, transl_out, (hipStream_t)stream);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : sg_fail("sg_pose_transforms", e);
+}
+extern "C" int sg_pose_transforms_backward(int K, int F, int J, int NBu, const int32_t *frame_idx, const float *global_orient,
+                                           const float *body_pose, const float *aa, const float *joints_rest, const int32_t *parents,
+                                           const float *post, const float *dA, const float *d_transl_rows, float *d_global_orient,
+                                           float *d_body_pose, float *d_transl, void *stream)
+{
+    if (!sg_pose_shape_ok(K, F, J, NBu) || !frame_idx || !global_orient || !body_pose || !aa || !joints_rest || !parents || !dA ||
+        !d_global_orient || !d_body_pose || (d_transl_rows == nullptr) != (d_transl == nullptr))
+        return sg_fail("sg_pose_transforms_backward: bad argument (1 <= J <= 64, 0 <= NBu <= 23, NBu < J; d_transl_rows and d_transl "
+                       "together)", hipSuccess);
+    sg_launch_pose_transforms_bwd(K, F, J, NBu, (const int *)frame_idx, global_orient, body_pose, aa, joints_rest, (const int *)parents,
+                                  post, dA, d_transl_rows, d_global_orient, d_body_pose, d_transl, (hipStream_t)stream);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : sg_fail("sg_pose_transforms_backward", e);
+}
+
 // ---- stand-alone matrix_to_quaternion (a11)
 extern "C" int sg_matrix_to_quaternion(int N, const float *matrices, float *quaternions, void *stream)
 {

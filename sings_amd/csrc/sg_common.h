@@ -316,6 +316,12 @@ void sg_launch_preprocess_bwd(const SgCam &c, const SgBatch &bt, int P, const fl
 void sg_zero_async(void *p, size_t bytes, hipStream_t st);
 void sg_launch_joint_transforms(int B, int J, const float *pose, const float *joints, const int *parents, const float *post,
                                 const float *dA, float *out0, float *out1, hipStream_t st);
+void sg_launch_pose_transforms(int K, int F, int J, int NBu, const int *frame_idx, const float *global_orient, const float *body_pose,
+                               const float *tail_pose, const float *transl, const float *joints, const int *parents, const float *post,
+                               float *A_out, float *aa_out, float *transl_out, hipStream_t st);
+void sg_launch_pose_transforms_bwd(int K, int F, int J, int NBu, const int *frame_idx, const float *global_orient, const float *body_pose,
+                                   const float *aa, const float *joints, const int *parents, const float *post, const float *dA,
+                                   const float *d_transl_rows, float *d_global_orient, float *d_body_pose, float *d_transl, hipStream_t st);
 void sg_launch_m2q(int N, const float *m, const float *dq, float *out, hipStream_t st);
 int sg_launch_rot_map(int op, int N, const float *in, const float *g, float *out, hipStream_t st);
 void sg_launch_qmul(int N, const float *a, const float *b, const float *g, float *out0, float *out1, hipStream_t st);

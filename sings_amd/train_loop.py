@@ -76,10 +76,33 @@ class AvatarTrainer:
     ``optimizer``: ``"torch"`` (``torch.optim.Adam``, outside the graph) or ``"fused"`` (``sings_amd.optim.FusedAdam``: the gradient
     arena is always created and ONE launch updates every parameter; without ``fp`` that launch is part of the step's body, so a
     captured step contains it and only the host half -- step counts, the per-group rows -- runs outside; with ``fp`` it follows the
-    all-reduce).  ``lr_schedules``: ``{group name: fn(iteration)}``, applied to the optimiser's groups before every step."""
+    all-reduce).  ``lr_schedules``: ``{group name: fn(iteration)}``, applied to the optimiser's groups before every step.
+
+    ``poses``: a ``sings_amd.pose.PoseTable`` -- the reference's ``optim_pose`` (sings_hybrid.py:142-150, 761-765).  Its learnable tables
+    join the optimiser as the groups ``"global_orient"`` and ``"body_pose"`` (the reference's ``lr.smpl_pose`` for both) and, if the
+    table was built with ``learn_transl``, ``"transl"`` (``lr.smpl_trans``); ``lrs`` must name each of them.  They are ordinary members
+    of ``params``: the gradient arena, the single ``sg_adam_step`` launch and the frame-parallel all-reduce cover them (each rank's
+    dense table gradient is zero outside its own frames' rows: the sum is the reference's gradient).  Adam is dense over the tables, as in
+    the reference: a row visited earlier keeps moving on its momentum, a row never visited has zero moments and does not move.  The
+    groups are not per-Gaussian: a densify / prune leaves their moments as they are.  ``step_frames(frame_idx, gt_rgb, mask)`` is the
+    step that reads ``A`` and ``transl`` from the tables; ``step(A, ...)`` stays what it was (the tables then take no part, and a
+    fused optimiser refuses parameters without a gradient).  With ``poses=None`` nothing changes."""
+
+    POSE_GROUPS = ("global_orient", "body_pose", "transl")
 
     def __init__(self, module, settings_fn, bg_color, lrs, smpl_scale=None, transl=None, use_graph=False, fp=None,
-                 sh_degree=0, max_sh_degree=3, betas=(0.9, 0.999), eps=1e-15, optimizer="torch", lr_schedules=None):
+                 sh_degree=0, max_sh_degree=3, betas=(0.9, 0.999), eps=1e-15, optimizer="torch", lr_schedules=None, poses=None):
+        learnable = self._pose_params(poses)
+        for what, names in (("lrs", lrs), ("lr_schedules", lr_schedules or {})):
+            extra = [n for n in self.POSE_GROUPS if n in names and n not in learnable]
+            if extra:
+                raise ValueError(f"AvatarTrainer: {what} for pose groups {extra} " +
+                                 ("need poses=PoseTable(...)" if poses is None else "that the PoseTable does not learn "
+                                  "(learn_pose / learn_transl)"))
+        missing = [n for n in learnable if n not in lrs]
+        if missing:
+            raise ValueError(f"AvatarTrainer: lrs has no entry for the pose groups {missing}")
+        self.poses = poses
         self.m, self.settings_fn, self.bg = module, settings_fn, bg_color
         self.smpl_scale, self.transl, self.use_graph, self.fp = smpl_scale, transl, bool(use_graph), fp
         self.sh_degree, self.max_sh_degree = int(sh_degree), int(max_sh_degree)
@@ -101,13 +124,23 @@ class AvatarTrainer:
         self._static = {}
         self._rebuild()
 
+    @classmethod
+    def _pose_params(cls, poses):
+        """{group name: parameter} of the tables ``poses`` learns ({} without poses)."""
+        if poses is None:
+            return {}
+        return {n: getattr(poses, n) for n in cls.POSE_GROUPS
+                if isinstance(getattr(poses, n), torch.nn.Parameter) and getattr(poses, n).requires_grad}
+
     # ---- pieces sized by the set of Gaussians
     def _groups(self):
         m = self.m
-        return [{"params": [m.xyz], "lr": self.lrs["xyz"], "name": "xyz"},
-                {"params": list(m.triplane.parameters()), "lr": self.lrs["triplane"], "name": "triplane"},
-                {"params": list(m.geometry_dec.parameters()), "lr": self.lrs["geometry"], "name": "geometry"},
-                {"params": list(m.appearance_dec.parameters()), "lr": self.lrs["appearance"], "name": "appearance"}]
+        groups = [{"params": [m.xyz], "lr": self.lrs["xyz"], "name": "xyz"},
+                  {"params": list(m.triplane.parameters()), "lr": self.lrs["triplane"], "name": "triplane"},
+                  {"params": list(m.geometry_dec.parameters()), "lr": self.lrs["geometry"], "name": "geometry"},
+                  {"params": list(m.appearance_dec.parameters()), "lr": self.lrs["appearance"], "name": "appearance"}]
+        # the pose tables (sized by the frames, not by the Gaussians): behind the others, one group each
+        return groups + [{"params": [p], "lr": self.lrs[n], "name": n} for n, p in self._pose_params(self.poses).items()]
 
     def _rebuild(self):
         """(Re)build what depends on the number of Gaussians / the SH degree: raster settings, statistics, arena, capacity hint, graph."""
@@ -131,7 +164,12 @@ class AvatarTrainer:
         for p in self.params:
             p.grad = None
         s = self._static
-        loss, ld, ex = self.m(s["A"], self.rs, s["gt"], s["mask"], self.bg, smpl_scale=self.smpl_scale, transl=self.transl,
+        A, transl = s.get("A"), self.transl
+        if s.get("idx") is not None:                             # the frames' rows of the pose tables: ONE launch, index on the device
+            A, transl = self.poses(s["idx"])
+            if s["single"]:
+                A, transl = A[0], transl[0]
+        loss, ld, ex = self.m(A, self.rs, s["gt"], s["mask"], self.bg, smpl_scale=self.smpl_scale, transl=transl,
                               lpips_origins=s.get("lp_origins"), lpips_bg=s.get("lp_bg"))
         if loss is None:
             self.m.backward(ld, ex)
@@ -145,18 +183,42 @@ class AvatarTrainer:
     def step(self, A, gt_rgb, mask, lpips_origins=None, lpips_bg=None):
         """``lpips_origins`` / ``lpips_bg``: the step's LPIPS patch corners and random background (``AvatarStep.forward``), copied
         in like the frame's inputs, so that a replayed graph reads this step's patches."""
+        return self._step({"A": A}, gt_rgb, mask, lpips_origins, lpips_bg)
+
+    def step_frames(self, frame_idx, gt_rgb, mask, lpips_origins=None, lpips_bg=None):
+        """One step on the frame(s) ``frame_idx`` of the pose tables: an int (one frame, the reference's step) or K indices (a
+        sequence or an integer tensor: a chunk [K,J,4,4]).  The index is copied into a static int32 device tensor like the other inputs
+        of the step, and the body reads ``A`` and the ``transl`` rows from ``poses`` there: a graph captured at one index replays at
+        any other.  (The trainer's constant ``transl`` is not used: the table's rows are.)"""
+        if self.poses is None:
+            raise RuntimeError("AvatarTrainer.step_frames needs poses=PoseTable(...)")
+        single = not torch.is_tensor(frame_idx) and not isinstance(frame_idx, (list, tuple))
+        idx = torch.as_tensor([frame_idx] if single else frame_idx).reshape(-1)
+        if idx.dtype in (torch.float16, torch.bfloat16, torch.float32, torch.float64, torch.bool) or idx.numel() < 1:
+            raise ValueError("AvatarTrainer.step_frames: frame_idx must be an int or K >= 1 integer indices")
+        if not idx.is_cuda:                                      # (indices that are already on the device are not read here)
+            F = int(self.poses.global_orient.shape[0])
+            if int(idx.min()) < 0 or int(idx.max()) >= F:
+                raise IndexError(f"AvatarTrainer.step_frames: frame index outside the table's {F} rows")
+        return self._step({"idx": idx.to(self.dev, torch.int32), "single": single}, gt_rgb, mask, lpips_origins, lpips_bg)
+
+    def _step(self, pose_in, gt_rgb, mask, lpips_origins, lpips_bg):
         s = self._static
+        key = "idx" if "idx" in pose_in else "A"
+        A = pose_in[key]
         lp = {"lp_origins": lpips_origins, "lp_bg": lpips_bg}
         lp = {k: (None if v is None else torch.as_tensor(v).to(self.dev)) for k, v in lp.items()}
         if lp["lp_origins"] is not None:
             lp["lp_origins"] = lp["lp_origins"].to(torch.int32)
         shapes = lambda d: tuple(None if d.get(k) is None else tuple(d[k].shape) for k in ("lp_origins", "lp_bg"))
-        if not s or s["A"].shape != A.shape or shapes(s) != shapes(lp):
-            s.update(A=A.clone(), gt=gt_rgb.clone(), mask=mask.clone())
+        if (not s or s.get(key) is None or s[key].shape != A.shape or s.get("single") != pose_in.get("single")
+                or shapes(s) != shapes(lp)):
+            s.update(A=None, idx=None, single=pose_in.get("single"))      # (the step reads A, or the tables' rows at idx: not both)
+            s.update({key: A.clone(), "gt": gt_rgb.clone(), "mask": mask.clone()})
             s.update({k: (None if v is None else v.clone()) for k, v in lp.items()})
             self.captured = None
         else:
-            s["A"].copy_(A); s["gt"].copy_(gt_rgb); s["mask"].copy_(mask)
+            s[key].copy_(A); s["gt"].copy_(gt_rgb); s["mask"].copy_(mask)
             for k, v in lp.items():
                 if v is not None:
                     s[k].copy_(v)

@@ -345,6 +345,8 @@ class AvatarStep(torch.nn.Module):
             loss_dict.update(reg)
             extras["loss_roots"] = (photo_root, reg_root)
             extras["staged"] = (attrs, use, inject, l2_grads)
+            # a pose that is itself learned (sings_amd.pose.PoseTable): the staged backward hands its gradients on
+            extras["pose_inputs"] = [t for t in (A_cano2pose, transl) if torch.is_tensor(t) and t.requires_grad]
             return None, loss_dict, {"render_raw": color, "radii": radii, "attrs": attrs, "viewspace_points": m2d, **extras}
         if side is not None:
             cur.wait_stream(side)                                # join before the loss terms meet
@@ -395,11 +397,13 @@ class AvatarStep(torch.nn.Module):
         names = [k for k, v in use.items() if torch.is_tensor(v) and v.requires_grad]
         leaves = [use[k] for k in names]
         m2d = extras.get("viewspace_points")
+        pose_in = extras.get("pose_inputs", [])
         # 1. the photometric gradients of the decoded attributes: loss, composite, LBS -- on this stream, issued first
-        got = torch.autograd.grad([photo_root], leaves + ([m2d] if m2d is not None else []), [one], allow_unused=True)
+        got = torch.autograd.grad([photo_root], leaves + pose_in + ([m2d] if m2d is not None else []), [one], allow_unused=True)
         if m2d is not None:
             m2d.grad = got[-1]                                   # (what add_densification_stats reads: the densifier's statistic)
         g = dict(zip(names, got))
+        pose_roots = [(t, x) for t, x in zip(pose_in, got[len(leaves):len(leaves) + len(pose_in)]) if x is not None]
         # 2. L2Norm's gradients (computed with its value, in front of the k-NN query on the side stream): ONE addition for the
         #    attributes that have both.  The k-NN regulariser's gradient (scales) is already in `inject`: it reaches the decoders'
         #    backward through the _Inject node, i.e. AFTER the appearance decoder's backward has been issued
@@ -420,7 +424,8 @@ class AvatarStep(torch.nn.Module):
             for x, y in zip(both_a, both_b):
                 x.add_(y)
         # 3. the decoders' backward: appearance decoder first (its nodes are the youngest), then the _Inject node waits for the side stream
-        roots = [(attrs[k], g[k]) for k in names if g.get(k) is not None]
+        #    (behind them the learned pose's dL/dA and dL/dtransl, if any: the oldest node of the step, one launch, reached last)
+        roots = [(attrs[k], g[k]) for k in names if g.get(k) is not None] + pose_roots
         torch.autograd.backward([r for r, _ in roots], [x for _, x in roots])
         cur.wait_stream(side)
         for v in list(loss_dict.values()) + [reg_root]:
