@@ -732,6 +732,43 @@ size_t sg_adam_chunk_elements(void);
 int sg_adam_step(int n_segments, int n_chunks, int n_groups, const int64_t *segments, const int32_t *chunks, const float *hyper,
                  const float *grad_flat, float *exp_avg, float *exp_avg_sq, void *stream);
 
+/* ---- mesh topology for the `hybrid` densification (entry points added to ABI 8) ---------------------------------------------------
+ * Replaces, on the device, `geometry_ops.subdivide_meshes` (geometry_ops.py:8-76) and the `trimesh.Trimesh(...).edges_unique` of
+ * sings_hybrid.py:1106-1110.  No library sort; every output is a pure function of the inputs (integer atomics are used for counts
+ * and for workspace slots only: no output depends on the order they land in), so two calls -- or two ranks -- give the same bits.
+ *
+ * Unique edges.  faces [F][3] int32 with corners in [0, V); flags [F] uint8 or NULL (every face).  An EDGE is (a, b) = (min, max) of
+ * two consecutive corners of a flagged face.  In ascending lexicographic order of (a, b) -- the order of
+ * `torch.unique(sorted_edges, dim=0)`:
+ *   edges       [E][2]  the unique edges
+ *   edge_faces  [E]     how many flagged faces hold each (a closed manifold: 2; a boundary: 1)
+ *   face_edges  [F][3]  for a flagged face the positions of its edges (v0v1, v1v2, v2v0) in `edges`; -1 for the others
+ * Two calls with ONE host read between them, because E sizes the outputs:
+ *   sg_mesh_edges_build  writes info[4] (device): E, the number of flagged faces, != 0 if a corner of ANY face is outside [0, V)
+ *                        (then nothing else is valid: do not call _emit), the number of edge instances (3 x flagged)
+ *   sg_mesh_edges_emit   E = the host's copy of info[0]; same V, F, faces, flags and the workspace as _build left it
+ * F == 0: E = 0 and nothing is launched; no face flagged: E = 0, face_edges all -1 (edges / edge_faces may be NULL when E == 0).
+ * Any valence: a row (the edges whose smaller endpoint is one vertex) of n instances costs n^2 loads, whatever n is.
+ * Refused (status 1, sg_last_error) before anything is launched: V or F < 0, V > 2^30 (the scan's range), F > (2^31 - 1) / 3,
+ * V + E >= 2^31 (a midpoint's index V + position must be an int32), NULL pointers.  sg_mesh_ws_bytes returns 0 for sizes it refuses.
+ *
+ * Selective subdivision (geometry_ops.py:41-58).  new_faces [F - Fs + 4 Fs][3]: the unflagged faces in their order, then for each
+ * flagged face, in order, (v0,m0,m2) (m0,v1,m1) (m2,m1,v2) (m0,m1,m2) with m_k = V + face_edges[f][k].  Fs = info[1].  Scans the
+ * flags itself: `ws` (sg_mesh_ws_bytes(V, F)) is scratch, nothing of an earlier call is read from it.
+ *
+ * Midpoint rows.  dst[e][c] = (src[edges[e][0]][c] + src[edges[e][1]][c]) * 0.5f -- one addition and one exact scaling: the bits of
+ * `values[unique_rows].mean(axis=1)`; sg_mesh_midpoints_i32: dst[e][c] = src[edges[e][0]][c], the value at the smaller endpoint
+ * (geometry_ops.py:66-69).  src [V][C], dst [E][C], any C >= 1 (16-byte rows move as vectors).  An endpoint outside [0, V) is not
+ * dereferenced (the row is zero). */
+size_t sg_mesh_ws_bytes(int V, int F);
+int sg_mesh_edges_build(int V, int F, const int32_t *faces, const uint8_t *flags, void *ws, int32_t *info, void *stream);
+int sg_mesh_edges_emit(int V, int F, int E, const int32_t *faces, const uint8_t *flags, const void *ws, int32_t *edges,
+                       int32_t *edge_faces, int32_t *face_edges, void *stream);
+int sg_mesh_subdivide(int V, int F, int Fs, const int32_t *faces, const uint8_t *flags, const int32_t *face_edges, void *ws,
+                      int32_t *new_faces, void *stream);
+int sg_mesh_midpoints(int V, int E, int C, const int32_t *edges, const float *src, float *dst, void *stream);
+int sg_mesh_midpoints_i32(int V, int E, int C, const int32_t *edges, const int32_t *src, int32_t *dst, void *stream);
+
 /* ---- optional per-kernel timing (bench / profiling only; process-global, not thread-safe).
  * When enabled, every kernel launch of forward/backward is bracketed by hipEvents on the
  * caller's stream.  sg_profile_collect synchronises, adds the elapsed milliseconds and launch

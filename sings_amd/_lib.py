@@ -152,6 +152,12 @@ _PROTOTYPES = {
     "sg_frames_to_u8": "i: i3 p i p2",
     "sg_adam_chunk_elements": "z:",
     "sg_adam_step": "i: i3 p7",
+    "sg_mesh_ws_bytes": "z: i2",
+    "sg_mesh_edges_build": "i: i2 p5",
+    "sg_mesh_edges_emit": "i: i3 p7",
+    "sg_mesh_subdivide": "i: i3 p6",
+    "sg_mesh_midpoints": "i: i3 p4",
+    "sg_mesh_midpoints_i32": "i: i3 p4",
     "sg_profile_enable": "i: i",
     "sg_copy_probe": "i: p2 z i p",
     "sg_profile_collect": "i: d n i",

@@ -136,3 +136,78 @@ def adam_step(segments, chunks, hyper, grad_flat, exp_avg, exp_avg_sq):
         raise RuntimeError("adam_step: grad_flat, exp_avg and exp_avg_sq must have the same number of elements")
     _lib.check(_lib.load().sg_adam_step(int(segments.shape[0]), int(chunks.shape[0]), int(hyper.shape[0]), _ptr(segments), _ptr(chunks),
                                         _ptr(hyper), _ptr(grad_flat), _ptr(exp_avg), _ptr(exp_avg_sq), _stream(dev)), "sg_adam_step")
+
+
+# ---- mesh topology (csrc/sg_mesh.hip)
+def _mesh_arg(t, name, dtype, dev, shape_tail=None):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"{name} must be a GPU tensor (no CPU fallback)")
+    if t.device != dev or t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError(f"{name} must be a contiguous {dtype} tensor on {dev}")
+    if shape_tail is not None and tuple(t.shape[1:]) != shape_tail:
+        raise ValueError(f"{name} must be [n, {', '.join(map(str, shape_tail))}], got {tuple(t.shape)}")
+    return t
+
+
+def mesh_unique_edges(faces, num_verts, flags=None):
+    """``sg_mesh_edges_build`` + ONE host read of (E, flagged faces, bad-index flag) + ``sg_mesh_edges_emit`` on torch's current
+    stream: ``faces`` [F,3] int32, ``flags`` [F] uint8 or None -> (edges [E,2], edge_faces [E], face_edges [F,3], Fs), all int32."""
+    dev = faces.device if torch.is_tensor(faces) else None
+    faces = _mesh_arg(faces, "faces", torch.int32, dev, (3,))
+    V, F = int(num_verts), int(faces.shape[0])
+    if flags is not None and tuple(_mesh_arg(flags, "flags", torch.uint8, dev).shape) != (F,):
+        raise ValueError(f"flags must be [{F}], got {tuple(flags.shape)}")
+    lib = _lib.load()
+    nbytes = int(lib.sg_mesh_ws_bytes(V, F))
+    if nbytes == 0:
+        raise ValueError(f"mesh_unique_edges: {V} vertices / {F} faces are outside what the kernels cover (V <= 2^30, 3 F < 2^31)")
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        info = torch.empty(4, dtype=torch.int32, device=dev)
+        _lib.check(lib.sg_mesh_edges_build(V, F, _ptr(faces), _ptr(flags), _ptr(ws), _ptr(info), _stream(dev)), "sg_mesh_edges_build")
+        E, Fs, bad, _ = info.tolist()                                 # the one host read: E sizes the outputs
+        if bad:
+            raise IndexError(f"mesh_unique_edges: a face indexes a vertex outside [0, {V})")
+        edges = torch.empty((E, 2), dtype=torch.int32, device=dev)
+        edge_faces = torch.empty(E, dtype=torch.int32, device=dev)
+        face_edges = torch.empty((F, 3), dtype=torch.int32, device=dev)
+        _lib.check(lib.sg_mesh_edges_emit(V, F, E, _ptr(faces), _ptr(flags), _ptr(ws), _ptr(edges), _ptr(edge_faces), _ptr(face_edges),
+                                          _stream(dev)), "sg_mesh_edges_emit")
+    return edges, edge_faces, face_edges, Fs
+
+
+def mesh_subdivide(faces, num_verts, flags, face_edges, num_flagged):
+    """``sg_mesh_subdivide``: -> new_faces [F - Fs + 4 Fs, 3] int32 (the unflagged faces, then four children per flagged face)."""
+    dev = faces.device if torch.is_tensor(faces) else None
+    faces = _mesh_arg(faces, "faces", torch.int32, dev, (3,))
+    V, F, Fs = int(num_verts), int(faces.shape[0]), int(num_flagged)
+    face_edges = _mesh_arg(face_edges, "face_edges", torch.int32, dev, (3,))
+    if flags is not None:
+        _mesh_arg(flags, "flags", torch.uint8, dev)
+    if face_edges.shape[0] != F or (flags is not None and tuple(flags.shape) != (F,)):
+        raise ValueError("mesh_subdivide: flags [F] and face_edges [F,3] must describe the faces")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(int(lib.sg_mesh_ws_bytes(V, F)), 1), dtype=torch.uint8, device=dev)
+        out = torch.empty((F - Fs + 4 * Fs, 3), dtype=torch.int32, device=dev)
+        _lib.check(lib.sg_mesh_subdivide(V, F, Fs, _ptr(faces), _ptr(flags), _ptr(face_edges), _ptr(ws), _ptr(out), _stream(dev)),
+                   "sg_mesh_subdivide")
+    return out
+
+
+def mesh_midpoints(edges, src):
+    """``sg_mesh_midpoints`` (fp32 ``src`` [V,C]: the endpoints' mean) / ``sg_mesh_midpoints_i32`` (int32: the smaller endpoint's
+    value) -> [E,C] of ``src``'s dtype."""
+    dev = edges.device if torch.is_tensor(edges) else None
+    edges = _mesh_arg(edges, "edges", torch.int32, dev, (2,))
+    if not torch.is_tensor(src) or src.dtype not in (torch.float32, torch.int32) or src.dim() != 2 or src.shape[1] < 1:
+        raise ValueError("mesh_midpoints: src must be a [V,C] float32 or int32 tensor, C >= 1")
+    src = _mesh_arg(src, "src", src.dtype, dev)
+    V, C, E = int(src.shape[0]), int(src.shape[1]), int(edges.shape[0])
+    lib = _lib.load()
+    fn, what = (lib.sg_mesh_midpoints, "sg_mesh_midpoints") if src.dtype == torch.float32 else (lib.sg_mesh_midpoints_i32,
+                                                                                                  "sg_mesh_midpoints_i32")
+    with torch.cuda.device(dev):
+        dst = torch.empty((E, C), dtype=src.dtype, device=dev)
+        _lib.check(fn(V, E, C, _ptr(edges), _ptr(src), _ptr(dst), _stream(dev)), what)
+    return dst

@@ -1,0 +1,370 @@
+// Mesh topology on the device for the reference's `hybrid` densification (sings_hybrid.py:1022-1150, geometry_ops.py:8-76): the
+// unique undirected edges of a (flagged) face set in lexicographic order -- the order of `torch.unique(sorted_edges, dim=0)`, so a
+// midpoint's index is the reference's --, the selective 1-to-4 subdivision, and the midpoint rows of per-vertex attributes.
+//
+// Not a throughput kernel: at SMPL scale (110 k vertices, 220 k faces) every array is a few MB and the cost is the launches and ONE
+// host read of (E, flagged faces).  What matters is that the output is a pure function of the input:
+//
+//   directed instances  every flagged face contributes its three edges as (a = min, b = max); an instance lives in the ROW of a.
+//                       count[a] (integer atomics: a sum of ones has no order), exclusive scan -> row starts (the three-step scan
+//                       of sg_reg.hip's k-NN cells), then every instance takes a slot of its row with a returning atomic.  WHICH slot
+//                       depends on arrival order; nothing that leaves this file does:
+//   rank by counting    an instance's place among the unique edges is computed from the row's CONTENTS, not from its slots: it
+//                       is a head if no instance at a smaller slot of the row holds the same b, its multiplicity is the number of
+//                       instances with its b, and the rank of its edge is the number of heads with a smaller b.  All three are
+//                       counts over a multiset, the same for every permutation of the row.  One lane per instance walks its row
+//                       (6 entries on average, L2-resident): a row of ANY length takes the same path -- a hub of valence n costs
+//                       O(n^2) loads, 25 k for the pole of an 80-column UV sphere, and there is no length at which another kernel
+//                       takes over.
+//   unique counts       heads per row (integer atomics again), scanned -> the first edge of every row; edge (a, b) = that + rank.
+//
+// The host reads info[] once between sg_mesh_edges_build and sg_mesh_edges_emit: E sizes the outputs.
+#include "sg_common.h"
+
+#define SG_MESH_THREADS 256
+#define SG_MESH_MAX_V (1 << 30)                  // the scan's block table and the 32-bit row offsets cover this many vertices
+#define SG_MESH_MAX_F 715827882                  // 3 F < 2^31: an instance index is an int
+
+// ---- exclusive scan of n uint32 (or of n flags) in three steps: 1024 entries per block, block sums, the sums scanned by one workgroup.
+// prefix(i) = out[i] + bsum[i >> 10].  Two independent jobs per launch (blockIdx.y).
+struct SgScanJob {
+    const uint32_t *in;         // values, or NULL:
+    const uint8_t *in8;         // flags (!= 0 counts 1), or NULL as well: every entry counts 1
+    uint32_t *out, *bsum;
+    int32_t *total;             // the sum of all n entries
+    int n;
+};
+struct SgScanJobs { SgScanJob j[2]; };
+
+__device__ __forceinline__ uint32_t sg_scan_value(const SgScanJob &J, int i)
+{
+    return J.in ? J.in[i] : (J.in8 ? (J.in8[i] != 0 ? 1u : 0u) : 1u);
+}
+__global__ void __launch_bounds__(256)
+sg_mesh_scan1_kernel(SgScanJobs JJ)
+{
+    __shared__ uint32_t sW[4];
+    const SgScanJob &J = JJ.j[blockIdx.y];
+    const int n = J.n;
+    if ((long long)blockIdx.x * 1024 >= n) return;                  // (uniform per workgroup)
+    const int base = blockIdx.x * 1024 + threadIdx.x * 4;
+    uint32_t v[4], s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) { v[k] = base + k < n ? sg_scan_value(J, base + k) : 0u; s += v[k]; }
+    uint32_t incl = s;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
+    if (lane == 63) sW[wave] = incl;
+    __syncthreads();
+    uint32_t off = 0;
+    for (int w = 0; w < wave; w++) off += sW[w];
+    uint32_t ex = off + incl - s;
+#pragma unroll
+    for (int k = 0; k < 4; k++) { if (base + k < n) J.out[base + k] = ex; ex += v[k]; }
+    if (threadIdx.x == 255) J.bsum[blockIdx.x] = ex;
+}
+__global__ void __launch_bounds__(1024)
+sg_mesh_scan2_kernel(SgScanJobs JJ)
+{
+    __shared__ uint32_t sW[16];
+    __shared__ uint32_t carry;
+    const SgScanJob &J = JJ.j[blockIdx.y];
+    const int nb = (int)(((long long)J.n + 1023) / 1024);
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (int b0 = 0; b0 < nb; b0 += 1024) {
+        const int i = b0 + threadIdx.x;
+        const uint32_t v = i < nb ? J.bsum[i] : 0u;
+        uint32_t incl = v;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
+        if (lane == 63) sW[wave] = incl;
+        __syncthreads();
+        uint32_t off = carry;
+        for (int w = 0; w < wave; w++) off += sW[w];
+        if (i < nb) J.bsum[i] = off + incl - v;
+        __syncthreads();
+        if (threadIdx.x == 1023) carry = off + incl;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *J.total = (int32_t)carry;
+}
+static void sg_mesh_scan(const SgScanJob &a, const SgScanJob *b, hipStream_t st)
+{
+    SgScanJobs JJ;
+    JJ.j[0] = a; JJ.j[1] = b ? *b : a;
+    const int nmax = b && b->n > a.n ? b->n : a.n;
+    const unsigned nb = (unsigned)(((long long)nmax + 1023) / 1024);
+    if (nb > 0)
+        hipLaunchKernelGGL(sg_mesh_scan1_kernel, dim3(nb, b ? 2 : 1), dim3(256), 0, st, JJ);
+    hipLaunchKernelGGL(sg_mesh_scan2_kernel, dim3(1, b ? 2 : 1), dim3(1024), 0, st, JJ);
+}
+
+// ---- workspace: uint32 words, every piece on a 256-byte boundary; the pieces that must start at zero come first
+struct SgMeshWs {
+    uint32_t *count, *cursor, *ucount;           // [V] each: instances per row, slots handed out, heads per row (zeroed per call)
+    uint32_t *start, *ebase;                     // [V]: scan of count / ucount (block-local part)
+    uint32_t *bsum_v, *bsum_u, *bsum_f;          // block sums of the three scans
+    uint32_t *frank;                             // [F]: flagged faces in front of f (block-local part)
+    uint32_t *row_b, *slot_row, *face_slot;      // [3F]: the b of a slot, its row, the slot of face edge (f, k)
+    uint32_t *head;                              // [3F]: multiplicity << 1 | head, per slot
+    int32_t *total;                              // [4]: totals of scans that report to nobody else
+    size_t zero_words, words;
+};
+static inline size_t sg_mesh_pad(size_t w) { return (w + 63) & ~(size_t)63; }
+static SgMeshWs sg_mesh_carve(void *ws, int V, int F)
+{
+    SgMeshWs w;
+    uint32_t *p = (uint32_t *)ws;
+    size_t o = 0;
+    const size_t v = sg_mesh_pad((size_t)V), f = sg_mesh_pad((size_t)F), f3 = sg_mesh_pad(3 * (size_t)F);
+    const size_t bv = sg_mesh_pad(((size_t)V + 1023) / 1024 + 1), bf = sg_mesh_pad(((size_t)F + 1023) / 1024 + 1);
+    w.count = p + o; o += v;  w.cursor = p + o; o += v;  w.ucount = p + o; o += v;
+    w.zero_words = o;
+    w.start = p + o; o += v;  w.ebase = p + o; o += v;
+    w.bsum_v = p + o; o += bv;  w.bsum_u = p + o; o += bv;  w.bsum_f = p + o; o += bf;
+    w.frank = p + o; o += f;
+    w.row_b = p + o; o += f3;  w.slot_row = p + o; o += f3;  w.face_slot = p + o; o += f3;  w.head = p + o; o += f3;
+    w.total = (int32_t *)(p + o); o += 64;
+    w.words = o;
+    return w;
+}
+static const char *sg_mesh_bad_sizes(int V, int F)
+{
+    if (V < 0 || F < 0) return "V and F must be >= 0";
+    if (V > SG_MESH_MAX_V) return "V beyond the scan's range (2^30 vertices)";
+    if (F > SG_MESH_MAX_F) return "F beyond 2^31 / 3 faces";
+    return nullptr;
+}
+extern "C" size_t sg_mesh_ws_bytes(int V, int F)
+{
+    if (sg_mesh_bad_sizes(V, F)) return 0;
+    return sg_mesh_carve(nullptr, V, F).words * sizeof(uint32_t);
+}
+
+// ---- the instances
+__device__ __forceinline__ bool sg_mesh_flagged(const uint8_t *__restrict__ flags, int f) { return !flags || flags[f] != 0; }
+// corners of face f; false (and nothing read further) when one of them is outside [0, V)
+__device__ __forceinline__ bool sg_mesh_face(const int32_t *__restrict__ faces, int f, int V, int v[3])
+{
+    v[0] = faces[3 * (size_t)f]; v[1] = faces[3 * (size_t)f + 1]; v[2] = faces[3 * (size_t)f + 2];
+    return (uint32_t)v[0] < (uint32_t)V && (uint32_t)v[1] < (uint32_t)V && (uint32_t)v[2] < (uint32_t)V;
+}
+__global__ void __launch_bounds__(SG_MESH_THREADS)
+sg_mesh_count_kernel(int V, int F, const int32_t *__restrict__ faces, const uint8_t *__restrict__ flags, uint32_t *__restrict__ count,
+                     int32_t *__restrict__ info)
+{
+    const int f = blockIdx.x * SG_MESH_THREADS + threadIdx.x;
+    if (f >= F) return;
+    int v[3];
+    if (!sg_mesh_face(faces, f, V, v)) { atomicOr(&info[2], 1); return; }       // (every face is checked: subdivision copies the others)
+    if (!sg_mesh_flagged(flags, f)) return;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const int p = v[k], q = v[(k + 1) % 3];
+        atomicAdd(&count[p < q ? p : q], 1u);
+    }
+}
+__global__ void __launch_bounds__(SG_MESH_THREADS)
+sg_mesh_fill_kernel(int V, int F, const int32_t *__restrict__ faces, const uint8_t *__restrict__ flags, SgMeshWs w)
+{
+    const int f = blockIdx.x * SG_MESH_THREADS + threadIdx.x;
+    if (f >= F) return;
+    int v[3];
+    if (!sg_mesh_face(faces, f, V, v) || !sg_mesh_flagged(flags, f)) return;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const int p = v[k], q = v[(k + 1) % 3];
+        const uint32_t a = (uint32_t)(p < q ? p : q), b = (uint32_t)(p < q ? q : p);
+        const uint32_t slot = w.start[a] + w.bsum_v[a >> 10] + atomicAdd(&w.cursor[a], 1u);      // < count's total <= 3F
+        w.row_b[slot] = b;
+        w.slot_row[slot] = a;
+        w.face_slot[3 * (size_t)f + k] = slot;
+    }
+}
+// one lane per slot: head flag and multiplicity from the row's contents; heads counted per row
+__global__ void __launch_bounds__(SG_MESH_THREADS)
+sg_mesh_heads_kernel(const int32_t *__restrict__ info, SgMeshWs w)
+{
+    const uint32_t t = blockIdx.x * SG_MESH_THREADS + threadIdx.x;
+    if (t >= (uint32_t)info[3]) return;
+    const uint32_t a = w.slot_row[t], b = w.row_b[t];
+    const uint32_t s0 = w.start[a] + w.bsum_v[a >> 10], len = w.count[a];
+    uint32_t before = 0, same = 0;
+    for (uint32_t j = 0; j < len; j++) {
+        const bool eq = w.row_b[s0 + j] == b;
+        same += eq ? 1u : 0u;
+        before += (eq && s0 + j < t) ? 1u : 0u;
+    }
+    w.head[t] = same << 1 | (before == 0 ? 1u : 0u);
+    if (before == 0) atomicAdd(&w.ucount[a], 1u);
+}
+// one lane per face edge: its edge's place = first edge of the row + heads of the row with a smaller b; the head writes the edge
+__global__ void __launch_bounds__(SG_MESH_THREADS)
+sg_mesh_emit_kernel(int V, int F, int E, const int32_t *__restrict__ faces, const uint8_t *__restrict__ flags, SgMeshWs w,
+                    int32_t *__restrict__ edges, int32_t *__restrict__ edge_faces, int32_t *__restrict__ face_edges)
+{
+    const size_t i = (size_t)blockIdx.x * SG_MESH_THREADS + threadIdx.x;
+    if (i >= 3 * (size_t)F) return;
+    const int f = (int)(i / 3);
+    int v[3];
+    if (!sg_mesh_face(faces, f, V, v) || !sg_mesh_flagged(flags, f)) { face_edges[i] = -1; return; }
+    const uint32_t t = w.face_slot[i];
+    const uint32_t a = w.slot_row[t], b = w.row_b[t];
+    const uint32_t s0 = w.start[a] + w.bsum_v[a >> 10], len = w.count[a];
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < len; j++)
+        rank += ((w.head[s0 + j] & 1u) && w.row_b[s0 + j] < b) ? 1u : 0u;
+    const uint32_t e = w.ebase[a] + w.bsum_u[a >> 10] + rank;
+    face_edges[i] = (int32_t)e;
+    const uint32_t h = w.head[t];
+    if ((h & 1u) && e < (uint32_t)E) {                                   // (E is the host's copy of info[0]: never past the outputs)
+        edges[2 * (size_t)e] = (int32_t)a; edges[2 * (size_t)e + 1] = (int32_t)b;
+        edge_faces[e] = (int32_t)(h >> 1);
+    }
+}
+
+extern "C" int sg_mesh_edges_build(int V, int F, const int32_t *faces, const uint8_t *flags, void *ws, int32_t *info, void *stream)
+{
+    const char *bad = sg_mesh_bad_sizes(V, F);
+    if (bad) return sg_set_error(bad, hipSuccess);
+    if (!info || (F > 0 && (!faces || !ws))) return sg_set_error("sg_mesh_edges_build: null pointer", hipSuccess);
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(info, 0, 4 * sizeof(int32_t), st);
+    if (e != hipSuccess) return sg_set_error("sg_mesh_edges_build (info)", e);
+    if (F == 0) return 0;                                                // E = 0, nothing to launch
+    if (V == 0) {                                                        // every index is outside an empty vertex set
+        e = hipMemsetAsync(info + 2, 1, 1, st);                          // (the low byte: info[2] = 1)
+        return e == hipSuccess ? 0 : sg_set_error("sg_mesh_edges_build (info)", e);
+    }
+    const SgMeshWs w = sg_mesh_carve(ws, V, F);
+    e = hipMemsetAsync(w.count, 0, w.zero_words * sizeof(uint32_t), st);
+    if (e != hipSuccess) return sg_set_error("sg_mesh_edges_build (workspace)", e);
+    const unsigned fb = ((unsigned)F + SG_MESH_THREADS - 1) / SG_MESH_THREADS;
+    const unsigned ib = (unsigned)((3 * (size_t)F + SG_MESH_THREADS - 1) / SG_MESH_THREADS);
+    hipLaunchKernelGGL(sg_mesh_count_kernel, dim3(fb), dim3(SG_MESH_THREADS), 0, st, V, F, faces, flags, w.count, info);
+    // rows (total -> info[3], the number of instances) and flagged faces (total -> info[1]) in the same two launches
+    const SgScanJob rows = {w.count, nullptr, w.start, w.bsum_v, info + 3, V};
+    const SgScanJob flg = {nullptr, flags, w.frank, w.bsum_f, info + 1, F};
+    sg_mesh_scan(rows, &flg, st);
+    hipLaunchKernelGGL(sg_mesh_fill_kernel, dim3(fb), dim3(SG_MESH_THREADS), 0, st, V, F, faces, flags, w);
+    hipLaunchKernelGGL(sg_mesh_heads_kernel, dim3(ib), dim3(SG_MESH_THREADS), 0, st, info, w);
+    const SgScanJob uniq = {w.ucount, nullptr, w.ebase, w.bsum_u, info, V};
+    sg_mesh_scan(uniq, nullptr, st);
+    e = hipGetLastError();
+    return e == hipSuccess ? 0 : sg_set_error("sg_mesh_edges_build", e);
+}
+
+extern "C" int sg_mesh_edges_emit(int V, int F, int E, const int32_t *faces, const uint8_t *flags, const void *ws, int32_t *edges,
+                                  int32_t *edge_faces, int32_t *face_edges, void *stream)
+{
+    const char *bad = sg_mesh_bad_sizes(V, F);
+    if (bad) return sg_set_error(bad, hipSuccess);
+    if (E < 0 || (size_t)E > 3 * (size_t)F) return sg_set_error("sg_mesh_edges_emit: E must be 0 .. 3 F", hipSuccess);
+    if ((long long)V + E >= (1ll << 31)) return sg_set_error("sg_mesh_edges_emit: V + E >= 2^31 (midpoint indices are int32)", hipSuccess);
+    if (F == 0) return 0;
+    if (V == 0) return sg_set_error("sg_mesh_edges_emit: faces without vertices", hipSuccess);
+    if (!faces || !ws || !face_edges || (E > 0 && (!edges || !edge_faces)))
+        return sg_set_error("sg_mesh_edges_emit: null pointer", hipSuccess);
+    const SgMeshWs w = sg_mesh_carve((void *)ws, V, F);
+    const unsigned ib = (unsigned)((3 * (size_t)F + SG_MESH_THREADS - 1) / SG_MESH_THREADS);
+    hipLaunchKernelGGL(sg_mesh_emit_kernel, dim3(ib), dim3(SG_MESH_THREADS), 0, (hipStream_t)stream, V, F, E, faces, flags, w, edges,
+                       edge_faces, face_edges);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : sg_set_error("sg_mesh_edges_emit", e);
+}
+
+// ---- selective subdivision (geometry_ops.py:41-58): the unflagged faces in their order, then four children per flagged face
+__global__ void __launch_bounds__(SG_MESH_THREADS)
+sg_mesh_subdivide_kernel(int V, int F, int Fs, const int32_t *__restrict__ faces, const uint8_t *__restrict__ flags,
+                         const int32_t *__restrict__ face_edges, const uint32_t *__restrict__ frank,
+                         const uint32_t *__restrict__ bsum_f, int32_t *__restrict__ out)
+{
+    const int f = blockIdx.x * SG_MESH_THREADS + threadIdx.x;
+    if (f >= F) return;
+    const uint32_t r = frank[f] + bsum_f[f >> 10];                       // flagged faces in front of f
+    const int v0 = faces[3 * (size_t)f], v1 = faces[3 * (size_t)f + 1], v2 = faces[3 * (size_t)f + 2];
+    if (!sg_mesh_flagged(flags, f)) {
+        const size_t o = (size_t)f - r;
+        if (o >= (size_t)(F - Fs)) return;                               // (a stale Fs: never past the output)
+        out[3 * o] = v0; out[3 * o + 1] = v1; out[3 * o + 2] = v2;
+        return;
+    }
+    if (r >= (uint32_t)Fs) return;
+    const int m0 = V + face_edges[3 * (size_t)f], m1 = V + face_edges[3 * (size_t)f + 1], m2 = V + face_edges[3 * (size_t)f + 2];
+    int32_t *o = out + 3 * ((size_t)(F - Fs) + 4 * (size_t)r);
+    o[0] = v0; o[1] = m0; o[2] = m2;
+    o[3] = m0; o[4] = v1; o[5] = m1;
+    o[6] = m2; o[7] = m1; o[8] = v2;
+    o[9] = m0; o[10] = m1; o[11] = m2;
+}
+extern "C" int sg_mesh_subdivide(int V, int F, int Fs, const int32_t *faces, const uint8_t *flags, const int32_t *face_edges, void *ws,
+                                 int32_t *new_faces, void *stream)
+{
+    const char *bad = sg_mesh_bad_sizes(V, F);
+    if (bad) return sg_set_error(bad, hipSuccess);
+    if (Fs < 0 || Fs > F) return sg_set_error("sg_mesh_subdivide: Fs must be 0 .. F", hipSuccess);
+    if ((size_t)(F - Fs) + 4 * (size_t)Fs > (size_t)SG_MESH_MAX_F) return sg_set_error("sg_mesh_subdivide: too many faces out", hipSuccess);
+    if (F == 0) return 0;
+    if (!faces || !ws || !new_faces || (Fs > 0 && !face_edges)) return sg_set_error("sg_mesh_subdivide: null pointer", hipSuccess);
+    hipStream_t st = (hipStream_t)stream;
+    const SgMeshWs w = sg_mesh_carve(ws, V, F);
+    // (the flags are scanned again: the call does not depend on what another call left in the workspace)
+    const SgScanJob flg = {nullptr, flags, w.frank, w.bsum_f, w.total, F};
+    sg_mesh_scan(flg, nullptr, st);
+    const unsigned fb = ((unsigned)F + SG_MESH_THREADS - 1) / SG_MESH_THREADS;
+    hipLaunchKernelGGL(sg_mesh_subdivide_kernel, dim3(fb), dim3(SG_MESH_THREADS), 0, st, V, F, Fs, faces, flags, face_edges, w.frank,
+                       w.bsum_f, new_faces);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : sg_set_error("sg_mesh_subdivide", e);
+}
+
+// ---- midpoint rows: dst[e] = (src[a] + src[b]) * 0.5f (one add, one exact scaling: the bits of `values[rows].mean(axis=1)`), or
+// src[a] for labels.  Rows of a multiple of four floats on 16-byte boundaries move as float4 (sg_skin.hip's weight rows); any other
+// width one float per lane, lanes consecutive over the flat [E, C] output.  An endpoint outside [0, V) is never dereferenced.
+template <typename T, bool MEAN>
+__global__ void __launch_bounds__(SG_MESH_THREADS)
+sg_mesh_midpoints_kernel(int V, size_t n, int width, const int32_t *__restrict__ edges, const T *__restrict__ src, T *__restrict__ dst)
+{
+    for (size_t i = (size_t)blockIdx.x * SG_MESH_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * SG_MESH_THREADS) {
+        const size_t e = i / (size_t)width, c = i - e * (size_t)width;
+        const int a = edges[2 * e], b = edges[2 * e + 1];
+        T r = {};
+        if ((uint32_t)a < (uint32_t)V && (uint32_t)b < (uint32_t)V) {
+            r = src[(size_t)a * width + c];
+            if constexpr (MEAN) r = (r + src[(size_t)b * width + c]) * 0.5f;
+        }
+        dst[i] = r;
+    }
+}
+// S: the scalar (float: the mean; int32_t: the smaller endpoint's value), S4: its 16-byte vector
+template <typename S, typename S4, bool MEAN>
+static int sg_mesh_midpoints_launch(const char *what, int V, int E, int C, const int32_t *edges, const S *src, S *dst, void *stream)
+{
+    if (V < 0 || E < 0 || C < 1) return sg_set_error("sg_mesh_midpoints: V, E >= 0 and C >= 1", hipSuccess);
+    if (E == 0) return 0;
+    if (!edges || !src || !dst) return sg_set_error("sg_mesh_midpoints: null pointer", hipSuccess);
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec = C % 4 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
+    const int width = vec ? C / 4 : C;
+    const size_t n = (size_t)E * width;
+    const size_t want = (n + SG_MESH_THREADS - 1) / SG_MESH_THREADS;
+    const unsigned blocks = (unsigned)(want < 65536 ? want : 65536);
+    if (vec)
+        hipLaunchKernelGGL((sg_mesh_midpoints_kernel<S4, MEAN>), dim3(blocks), dim3(SG_MESH_THREADS), 0, st, V, n, width, edges,
+                           (const S4 *)src, (S4 *)dst);
+    else
+        hipLaunchKernelGGL((sg_mesh_midpoints_kernel<S, MEAN>), dim3(blocks), dim3(SG_MESH_THREADS), 0, st, V, n, width, edges, src, dst);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : sg_set_error(what, e);
+}
+extern "C" int sg_mesh_midpoints(int V, int E, int C, const int32_t *edges, const float *src, float *dst, void *stream)
+{
+    return sg_mesh_midpoints_launch<float, float4, true>("sg_mesh_midpoints", V, E, C, edges, src, dst, stream);
+}
+extern "C" int sg_mesh_midpoints_i32(int V, int E, int C, const int32_t *edges, const int32_t *src, int32_t *dst, void *stream)
+{
+    return sg_mesh_midpoints_launch<int32_t, int4, false>("sg_mesh_midpoints_i32", V, E, C, edges, src, dst, stream);
+}

@@ -267,6 +267,15 @@ class FusedAdam:
                     g[key] = saved[key]
 
     # ---- a densify / prune of one parameter's rows
+    def append_rows(self, old, new):
+        """Parameter ``old`` [n, ...] becomes ``new`` [n + k, ...] whose first n rows are the old ones (a subdivision): the old rows'
+        moments are kept, the k new rows start at zero.  ``remap_rows`` with k appended rows and nothing dropped."""
+        k = int(new.shape[0]) - int(old.shape[0])
+        if k < 0:
+            raise ValueError(f"FusedAdam.append_rows: `new` has {int(new.shape[0])} rows, `old` {int(old.shape[0])}")
+        self.remap_rows(old, new, torch.zeros(k, dtype=torch.int64, device=self.dev),
+                        torch.ones(int(new.shape[0]), dtype=torch.bool, device=self.dev))
+
     def remap_rows(self, old, new, clone_mask, keep_mask):
         """Parameter ``old`` becomes ``new`` = ``cat([old, old[clone_mask]])[keep_mask]``: its moments become
         ``cat([m, zeros_like(m[clone_mask])])[keep_mask]`` (cat_tensors_to_optimizer / _prune_optimizer), every other parameter's are

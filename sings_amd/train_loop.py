@@ -7,9 +7,13 @@ number of Gaussians every pre-sized piece of the hot path was built for:
     ``oneupSHdegree`` every ``sh_interval`` steps                           gs_trainer.py:436-438
     densify (clone) + prune from the accumulated statistics,
     Adam moments carried over for the survivors                             gs_trainer.py:280-343, sings_hybrid.py:856-932, 968-1004
+    densify by selective subdivision of the anchors' mesh                   gs_trainer.py:219-222, 515-521, sings_hybrid.py:1022-1150
 
-The reference's ``hybrid`` strategy subdivides the SMPL mesh (trimesh / pytorch3d: its control plane, not built here); this module
-follows its ``vanilla`` strategy's clone + prune -- what matters for the hot path is THAT the set changes: P(t) != P(t-1).
+Two ways to change the set.  ``densify_and_prune`` follows the reference's ``vanilla`` strategy's clone + prune.
+``densify_and_subdivide`` (a trainer built with ``mesh=MeshState``) is its ``hybrid`` strategy, the one every shipped configuration
+sets: faces picked from the statistics are split 1-to-4 on the device (``sings_amd.topology``, csrc/sg_mesh.hip -- no trimesh, no
+host copy of the mesh), the midpoints become new anchors with interpolated skinning weights, labels and scales.  For the hot path
+what matters is THAT the set changes: P(t) != P(t-1).
 
 A topology change (or a new SH degree) invalidates everything that was sized or captured for the old set:
 
@@ -28,6 +32,7 @@ import torch
 
 from . import decode as _dec
 from . import overflow
+from . import topology as _topo
 from .optim import FusedAdam
 from .train_step import capture_step
 
@@ -86,12 +91,19 @@ class AvatarTrainer:
     the reference: a row visited earlier keeps moving on its momentum, a row never visited has zero moments and does not move.  The
     groups are not per-Gaussian: a densify / prune leaves their moments as they are.  ``step_frames(frame_idx, gt_rgb, mask)`` is the
     step that reads ``A`` and ``transl`` from the tables; ``step(A, ...)`` stays what it was (the tables then take no part, and a
-    fused optimiser refuses parameters without a gradient).  With ``poses=None`` nothing changes."""
+    fused optimiser refuses parameters without a gradient).  With ``poses=None`` nothing changes.
+
+    ``mesh``: a ``sings_amd.topology.MeshState`` over the anchors (faces, unique edges, vertex labels, level ids) -- what
+    ``densify_and_subdivide`` needs and keeps up to date.  With ``mesh=None`` nothing changes."""
 
     POSE_GROUPS = ("global_orient", "body_pose", "transl")
 
     def __init__(self, module, settings_fn, bg_color, lrs, smpl_scale=None, transl=None, use_graph=False, fp=None,
-                 sh_degree=0, max_sh_degree=3, betas=(0.9, 0.999), eps=1e-15, optimizer="torch", lr_schedules=None, poses=None):
+                 sh_degree=0, max_sh_degree=3, betas=(0.9, 0.999), eps=1e-15, optimizer="torch", lr_schedules=None, poses=None,
+                 mesh=None):
+        if mesh is not None and mesh.num_verts != int(module.xyz.shape[0]):
+            raise ValueError(f"AvatarTrainer: the mesh has {mesh.num_verts} vertices, the module {int(module.xyz.shape[0])} Gaussians")
+        self.mesh, self.last_subdivision = mesh, None
         learnable = self._pose_params(poses)
         for what, names in (("lrs", lrs), ("lr_schedules", lr_schedules or {})):
             extra = [n for n in self.POSE_GROUPS if n in names and n not in learnable]
@@ -296,3 +308,62 @@ class AvatarTrainer:
                 self.opt.state[m.xyz] = state
         self._rebuild()
         return clone, prune, n_old, int(m.xyz.shape[0])
+
+    def densify_and_subdivide(self, grad_threshold, scale_threshold, max_screen_size=None, max_n_gs=None, exclude=(6, 7), decision=None):
+        """``SinGS.densify_and_subdivide`` (sings_hybrid.py:1022-1150) from the accumulated (and, with ``fp``, reduced) statistics; ->
+        (selected_pts_mask, selected_faces_idx, N_old, N_new).  ``decision``: a (selected_pts_mask, selected_faces_idx) pair to apply
+        instead of ``topology.subdivide_decision`` (whose docstring names the reference's quirks that are kept).
+
+        The selected faces of ``mesh`` are split 1-to-4; their edge midpoints (of ``xyz_canon`` = anchor + offset) are appended to the
+        anchors with the endpoints' mean skinning weights, the smaller endpoint's label and -- through ``scaling_multiplier``, which
+        becomes per-Gaussian [N,1] -- the endpoints' mean scale, each clipped to 0.008 first; a selected old row is rescaled to the mean
+        scale of all points.  Zero Adam moments for the new rows, the old rows' kept; opacity reset on the new set.  The reference also
+        interpolates ``shs`` and never reads the result: not computed.  ``self.mesh`` then holds the new faces, labels, level ids and the
+        unique edges of the new faces; ``self.last_subdivision`` what the call interpolated (``interpolated_scales`` of the new rows)."""
+        if self.mesh is None:
+            raise RuntimeError("AvatarTrainer.densify_and_subdivide needs mesh=MeshState(...)")
+        m, mesh = self.m, self.mesh
+        if self.fp is not None:
+            self.fp.reduce_densification_stats(m.xyz_gradient_accum, m.denom, m.max_radii2D)
+        with torch.no_grad():
+            decode = lambda: _dec.decode_attributes(m.xyz, m.triplane, m.geometry_dec, m.appearance_dec, m.thickness_factor,
+                                                    m.scaling_multiplier)
+            attrs = decode()
+            # human_gs_out['scales_canon']: the decoded scales, times smpl_scale when the step has one (sings_hybrid.py:411-413, 455)
+            scales_canon = attrs["scales"] if self.smpl_scale is None else attrs["scales"] * self.smpl_scale.reshape(1, -1)
+            if decision is None:
+                decision = _topo.subdivide_decision(m.xyz_gradient_accum, m.denom, scales_canon, m.max_radii2D, mesh.vertex_label,
+                                                    mesh.faces, grad_threshold, scale_threshold, max_screen_size=max_screen_size,
+                                                    max_n_gs=max_n_gs, exclude=exclude)
+            selected, faces_idx = decision
+            selected, faces_idx = selected.to(self.dev), faces_idx.to(self.dev)
+            n_old = int(m.xyz.shape[0])
+            scales = scales_canon[:, :1]
+            sub_vertices, sub_faces, attr = _topo.subdivide_meshes(
+                attrs["xyz_canon"], mesh.faces, faces_idx,
+                {"vertex_label": mesh.vertex_label, "lbs_weights": m.lbs_weights, "scales": torch.clip(scales.mean(-1), max=0.008)})
+            n_new = int(sub_vertices.shape[0])
+            # new multipliers: selected old rows to the mean scale, ones for the new rows (:1127-1131)
+            sm = torch.cat([_topo.rescaled_multiplier(m.scaling_multiplier, scales_canon, selected),
+                            torch.ones((n_new - n_old, 1), dtype=torch.float32, device=self.dev)])
+            group = next(g for g in self.opt.param_groups if g["name"] == "xyz")
+            old = group["params"][0]
+            state = None if self.fused else self.opt.state.pop(old, None)
+            m.set_topology(torch.cat([old.detach(), sub_vertices[n_old:]]), attr["lbs_weights"], scaling_multiplier=sm)
+            mesh.replace(sub_faces, attr["vertex_label"])
+            if self.fused:
+                self.opt.append_rows(old, m.xyz)
+            group["params"][0] = m.xyz
+            if state:
+                for k in ("exp_avg", "exp_avg_sq"):
+                    state[k] = torch.cat([state[k], torch.zeros((n_new - n_old, 3), dtype=state[k].dtype, device=self.dev)])
+                self.opt.state[m.xyz] = state
+            # post process (:1136-1147): opacity reset on the new set, then the new rows' decoded mean scale := the interpolated one
+            if not getattr(m.appearance_dec, "fixed_opacity", False):
+                m.appearance_dec.reset_opacity(m.triplane(m.xyz))
+            interpolated = attr["scales"][n_old:]
+            new_scales = decode()["scales"][n_old:]
+            sm[n_old:] *= (interpolated / new_scales.mean(-1)).unsqueeze(1)
+            self.last_subdivision = {"interpolated_scales": interpolated, "n_old": n_old}
+        self._rebuild()
+        return selected, faces_idx, n_old, n_new
