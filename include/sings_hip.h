@@ -769,6 +769,42 @@ int sg_mesh_subdivide(int V, int F, int Fs, const int32_t *faces, const uint8_t 
 int sg_mesh_midpoints(int V, int E, int C, const int32_t *edges, const float *src, float *dst, void *stream);
 int sg_mesh_midpoints_i32(int V, int E, int C, const int32_t *edges, const int32_t *src, int32_t *dst, void *stream);
 
+/* ---- mesh simplification by edge collapse (sings_amd/csrc/sg_mesh.hip; added to ABI 8)
+ *
+ * Replaces, on the device, `geometry_ops.collapse_edges` (geometry_ops.py:79-167), the mesh half of `SinGS.prune_and_simplify`
+ * (sings_hybrid.py:1153-1257): num_collapse = (int)(n * collapse_rate) times -- n the number of distinct vertices in the selected edges,
+ * the product formed in double -- the longest live selected edge (v1 < v2) is collapsed: v2 is merged into v1, edges that touched v2 are
+ * relabelled, self-edges dropped, duplicates merged; the loop also ends when no edge is left.  A class is represented by its smallest
+ * vertex, whose position never changes: a length is always the distance of two INPUT positions, squared length
+ * (dx*dx + dy*dy) + dz*dz in fp32.  Longest: squared length larger, then a smaller, then b smaller -- the first row of a tie in a
+ * lexicographic list, as the reference's CPU argmax.  The whole loop is ONE launch of one workgroup that keeps the edges in LDS; no
+ * host read between iterations.  Then every face is mapped through the classes; a face with two equal corners is dropped; of faces on
+ * the same three vertices the one with the smallest index stays, with its own winding; vertices no remaining face holds are pruned
+ * (vertices that were isolated before included); faces are renumbered.  Faces and vertices keep their ORIGINAL order (the
+ * reference's face order is that of a host hash; nothing downstream reads it).  Every output is a pure function of the inputs.
+ *
+ *   verts           [V][3] fp32, finite       selected_edges  [Es][2] int32 rows 0 <= a < b < V (any order; duplicate rows are merged)
+ *   faces           [F][3] int32 in [0, V)    collapse_rate   HOST pointer to one double (the ABI's scalars are int, size_t, float;
+ *                                                              Python's int(n * rate) is a double product), finite and >= 0
+ * Two calls with ONE host read between them, because F' and V' size the outputs:
+ *   sg_mesh_collapse_build  writes info[8] (device): F' faces kept, V' vertices kept, collapses done, selected-edge flags (bit 0: a
+ *                           row not 0 <= a < b < V -- never dereferenced; bit 1: a non-finite vertex; either: nothing was collapsed),
+ *                           != 0 if a face corner is outside [0, V), n, num_collapse, the number of non-degenerate mapped faces.
+ *                           With info[3] or info[4] set nothing else is valid: do not call _emit.
+ *   sg_mesh_collapse_emit   Fn, Vn = the host's copies of info[0], info[1]; same V, F, faces and the workspace as _build left it:
+ *                           new_faces [Fn][3] (indices into the kept vertices), prune_mask [V] (1 = removed), survivors [Vn] (the kept
+ *                           vertices' old indices, ascending: new_verts = verts[survivors]).
+ * Refused (status 1, sg_last_error) before anything is launched: V < 1 or beyond 2^30, F < 0 or beyond (2^31 - 1) / 3, Es < 0,
+ * Es > sg_mesh_collapse_max_edges() (10 240: the reference skips above 2 * prune_max_n_gs_once = 10 000), a collapse_rate that is
+ * negative or not finite, NULL pointers.  sg_mesh_collapse_ws_bytes returns 0 for sizes it refuses; `ws` is scratch, initialised by
+ * kernels of the call itself. */
+int sg_mesh_collapse_max_edges(void);
+size_t sg_mesh_collapse_ws_bytes(int V, int F);
+int sg_mesh_collapse_build(int V, int F, int Es, const float *verts, const int32_t *selected_edges, const int32_t *faces,
+                           const double *collapse_rate, void *ws, int32_t *info, void *stream);
+int sg_mesh_collapse_emit(int V, int F, int Fn, int Vn, const int32_t *faces, const void *ws, int32_t *new_faces, uint8_t *prune_mask,
+                          int32_t *survivors, void *stream);
+
 /* ---- optional per-kernel timing (bench / profiling only; process-global, not thread-safe).
  * When enabled, every kernel launch of forward/backward is bracketed by hipEvents on the
  * caller's stream.  sg_profile_collect synchronises, adds the elapsed milliseconds and launch

@@ -158,6 +158,10 @@ _PROTOTYPES = {
     "sg_mesh_subdivide": "i: i3 p6",
     "sg_mesh_midpoints": "i: i3 p4",
     "sg_mesh_midpoints_i32": "i: i3 p4",
+    "sg_mesh_collapse_max_edges": "i:",
+    "sg_mesh_collapse_ws_bytes": "z: i2",
+    "sg_mesh_collapse_build": "i: i3 p3 d p3",
+    "sg_mesh_collapse_emit": "i: i4 p6",
     "sg_profile_enable": "i: i",
     "sg_copy_probe": "i: p2 z i p",
     "sg_profile_collect": "i: d n i",

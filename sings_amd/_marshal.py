@@ -211,3 +211,46 @@ def mesh_midpoints(edges, src):
         dst = torch.empty((E, C), dtype=src.dtype, device=dev)
         _lib.check(fn(V, E, C, _ptr(edges), _ptr(src), _ptr(dst), _stream(dev)), what)
     return dst
+
+
+def mesh_collapse_max_edges():
+    """``sg_mesh_collapse_max_edges``: the most selected edges one ``mesh_collapse`` takes (they stay resident in LDS)."""
+    return int(_lib.load().sg_mesh_collapse_max_edges())
+
+
+def mesh_collapse(verts, selected_edges, faces, collapse_rate):
+    """``sg_mesh_collapse_build`` + ONE host read of info[8] + ``sg_mesh_collapse_emit`` on torch's current stream: ``verts`` [V,3]
+    fp32, ``selected_edges`` [Es,2] and ``faces`` [F,3] int32 -> (new_faces [F',3] int32, prune_mask [V] uint8, survivors [V'] int32,
+    collapses done).  A selected row that is not 0 <= a < b < V or a non-finite vertex raises ValueError, a face corner outside
+    [0, V) IndexError."""
+    dev = verts.device if torch.is_tensor(verts) else None
+    verts = _mesh_arg(verts, "verts", torch.float32, dev, (3,))
+    selected_edges = _mesh_arg(selected_edges, "selected_edges", torch.int32, dev, (2,))
+    faces = _mesh_arg(faces, "faces", torch.int32, dev, (3,))
+    V, F, Es = int(verts.shape[0]), int(faces.shape[0]), int(selected_edges.shape[0])
+    lib = _lib.load()
+    cap = int(lib.sg_mesh_collapse_max_edges())
+    if Es > cap:
+        raise ValueError(f"mesh_collapse: {Es} selected edges, one call takes at most {cap}")
+    nbytes = int(lib.sg_mesh_collapse_ws_bytes(V, F))
+    if nbytes == 0:
+        raise ValueError(f"mesh_collapse: {V} vertices / {F} faces are outside what the kernels cover (1 <= V <= 2^30, 3 F < 2^31)")
+    rate = C.c_double(float(collapse_rate))
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        info = torch.empty(8, dtype=torch.int32, device=dev)
+        _lib.check(lib.sg_mesh_collapse_build(V, F, Es, _ptr(verts), _ptr(selected_edges), _ptr(faces), C.byref(rate), _ptr(ws), _ptr(info),
+                                              _stream(dev)), "sg_mesh_collapse_build")
+        Fn, Vn, done, bad_edge, bad_face = info.tolist()[:5]          # the one host read: F' and V' size the outputs
+        if bad_edge & 2:
+            raise ValueError("mesh_collapse: a vertex is not finite")
+        if bad_edge:
+            raise ValueError(f"mesh_collapse: a selected edge is not a row 0 <= a < b < {V}")
+        if bad_face:
+            raise IndexError(f"mesh_collapse: a face indexes a vertex outside [0, {V})")
+        new_faces = torch.empty((Fn, 3), dtype=torch.int32, device=dev)
+        prune_mask = torch.empty(V, dtype=torch.uint8, device=dev)
+        survivors = torch.empty(Vn, dtype=torch.int32, device=dev)
+        _lib.check(lib.sg_mesh_collapse_emit(V, F, Fn, Vn, _ptr(faces), _ptr(ws), _ptr(new_faces), _ptr(prune_mask), _ptr(survivors),
+                                             _stream(dev)), "sg_mesh_collapse_emit")
+    return new_faces, prune_mask, survivors, done

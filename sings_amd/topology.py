@@ -8,6 +8,11 @@ to split, the 1-to-4 split itself, the new vertices' attributes and the unique-e
                            ``trimesh.Trimesh(...).edges_unique`` of sings_hybrid.py:1106-1110 as a SET (below)
     MeshState              what a trainer carries between steps: faces, edges, vertex labels, level ids
 
+and of its pruning (``SinGS.prune_and_simplify``, sings_hybrid.py:1153-1257):
+
+    simplify_decision      sings_hybrid.py:1157-1222   pure torch: which vertices may go, which edges may collapse, or why not
+    collapse_edges         geometry_ops.py:79-167      drop-in: same arguments, same return tuple; the whole sequential loop is one launch
+
 Every output is a deterministic function of the inputs (no output depends on the order atomics land in): ranks of a frame-parallel
 run that hold the same reduced statistics build the same mesh, bit for bit.
 
@@ -113,6 +118,102 @@ def subdivide_meshes(vertices, faces, face_index=None, vertex_attributes=None):
     return new_vertices, new_faces, new_attributes
 
 
+def collapse_edges(verts, verts_attr, selected_edges, faces, collapse_rate=0.5, return_collapses=False):
+    """Drop-in for ``geometry_ops.collapse_edges``: ``int(n * collapse_rate)`` times (n: the distinct vertices of ``selected_edges``) the
+    longest live selected edge is collapsed into its smaller endpoint, which keeps its position and attributes; edges are relabelled,
+    self-edges dropped, duplicates merged; the loop ends early when no edge is left.  Faces are mapped, degenerate ones and all but the
+    first of those on the same three vertices dropped, unreferenced vertices (isolated ones included) pruned, faces renumbered.
+    -> (new_verts [V',3], new_faces [F',3] int64, new_verts_attr [V',...], prune_mask [V] bool); with ``return_collapses`` the number
+    of collapses done is appended.  ``new_verts`` / ``new_verts_attr`` are the survivors' input rows, bit for bit.
+
+    GPU tensors only; ``verts`` [V,3] float32 and finite (ValueError otherwise); ``selected_edges`` rows ``0 <= a < b < V`` (ValueError),
+    at most ``collapse_max_edges()`` of them (ValueError; 10 240 -- the reference's caller skips above 10 000); duplicate rows are
+    harmless, the row order does not matter.  One host read (F', V', collapses, the refusal flags), after which the refusals are
+    raised.  When no face survives: RuntimeError (the reference fails in ``vstack`` there).  ``smooth`` is not offered: the reference's
+    branch is a ``pass``.  The inputs are not written (the reference overwrites the deleted rows of ``verts`` / ``verts_attr`` in
+    place).
+
+    Deviations from the reference: (1) the surviving face rows are in their ORIGINAL order, the first occurrence of a vertex set
+    kept -- the reference's order is that of ``trimesh.grouping.unique_rows``' hash; (2) the longest edge is the one with the larger
+    squared length ``(dx*dx + dy*dy) + dz*dz`` (fp32), then the smaller ``a``, then the smaller ``b`` -- the reference's CPU ``argmax`` of
+    ``linalg.norm`` over a lexicographic list names the same edge on an exact tie; (3) among edges whose lengths agree to within fp32
+    rounding the order is this kernel's, not torch's; (4) trimesh's merging of coincident vertices is not reproduced (``unique_edges``
+    says the same)."""
+    for name, t in (("verts", verts), ("verts_attr", verts_attr), ("selected_edges", selected_edges), ("faces", faces)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError(f"sings_amd.topology: {name} must be a GPU tensor (no CPU fallback)")
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise ValueError("sings_amd.topology: verts must be [V,3] float32")
+    V = int(verts.shape[0])
+    if verts_attr.shape[0] != V:
+        raise ValueError(f"sings_amd.topology: verts_attr has {verts_attr.shape[0]} rows, the mesh {V} vertices")
+    if selected_edges.dim() != 2 or selected_edges.shape[1] != 2 or selected_edges.dtype not in (torch.int32, torch.int64):
+        raise ValueError("sings_amd.topology: selected_edges must be an [Es,2] int32 / int64 tensor")
+    if int(selected_edges.shape[0]) > collapse_max_edges():
+        raise ValueError(f"sings_amd.topology: {int(selected_edges.shape[0])} selected edges, one call takes at most {collapse_max_edges()}")
+    f32 = _faces_i32(faces, V)
+    sel = selected_edges
+    if sel.dtype == torch.int64 and sel.numel():
+        sel = sel.clamp(-1, V)                                       # (as _faces_i32: no aliasing in the conversion)
+    sel = sel.to(torch.int32).contiguous()
+    new_faces, prune_mask, survivors, done = _marshal.mesh_collapse(verts.detach().contiguous(), sel, f32, collapse_rate)
+    if new_faces.shape[0] == 0:
+        raise RuntimeError("sings_amd.topology: collapse_edges left no face")
+    rows = survivors.to(torch.int64)
+    out = (verts.detach()[rows], new_faces.to(torch.int64), verts_attr.detach()[rows], prune_mask.to(torch.bool))
+    return out + (done,) if return_collapses else out
+
+
+def collapse_max_edges():
+    """The most selected edges ``collapse_edges`` takes (``sg_mesh_collapse_max_edges``: they stay resident in LDS)."""
+    return _marshal.mesh_collapse_max_edges()
+
+
+def simplify_decision(xyz_gradient_accum, denom, opacity, scales, vertex_label, faces, opacity_threshold, scale_threshold,
+                      dead_grad=0.0005, large_scale=0.01, prune_max_n_gs_once=5000, min_n_gs=None, exclude=(6, 7)):
+    """-> (vert_mask [N] bool, selected_edges [Es,2] int64, skip_reason or None) -- sings_hybrid.py:1157-1222 as a PURE function of its
+    arguments (CPU or GPU tensors): every rank that holds the same reduced statistics takes the same decision.
+
+        skip     ``N <= min_n_gs``                                                          -> ``"min_n_gs"`` (mask all false, no edges)
+        points   ``opacity < opacity_threshold`` AND ``scales[:, :1] < scale_threshold`` (transparent and small); OR
+                 ``scales[:, :1] > large_scale`` AND ``accum / denom < dead_grad`` (big and dead); never a label in ``exclude``
+        faces    ALL corners selected
+        edges    the unique sorted edges of those faces that exactly two of THOSE faces share (``counts == 2``: the boundary of the
+                 selected region is excluded), in lexicographic order
+        skip     no edge (the reference tests "no point" first: the same outcome)            -> ``"no_edges"``
+                 more than ``2 * prune_max_n_gs_once`` edges                                 -> ``"too_many_edges"``
+
+    ``scales``: as in the reference's ``human_gs_out`` the decoded scale times ``smpl_scale`` when the step has one (its ``'scales'`` and
+    ``'scales_canon'`` are one tensor).  The reference's quirks: (1) NaN is NOT zeroed here (it is in ``subdivide_decision``): a NaN
+    gradient (0 / 0: never visible) compares false and is not "dead" -- kept; (2) its ``exclude`` argument is overwritten with
+    ``[6, 7]`` -- here (6, 7) is the default and another tuple (or None) is honoured; (3) ``min_n_gs=None``, its default, raises
+    TypeError there -- here it means no floor; (4) its ``max_n_gs_once`` is never read -- there is no such argument; (5) the
+    configuration's ``prune_collapse_rate`` never reaches its ``collapse_edges`` call, which always runs at 0.5."""
+    N = int(xyz_gradient_accum.shape[0])
+    dev = xyz_gradient_accum.device
+    none = torch.zeros((0, 2), dtype=torch.int64, device=dev)
+    if min_n_gs is not None and N <= min_n_gs:
+        return torch.zeros(N, dtype=torch.bool, device=dev), none, "min_n_gs"
+    s = scales[:, :1]
+    vert_mask = (opacity.reshape(N, 1) < opacity_threshold) & (s < scale_threshold)
+    grads = xyz_gradient_accum.reshape(N, 1) / denom.reshape(N, 1)
+    vert_mask = vert_mask | ((s > large_scale) & (grads < dead_grad))
+    vert_mask = vert_mask.reshape(-1)
+    if exclude is not None and len(exclude):
+        lab = vertex_label.reshape(-1)
+        vert_mask = vert_mask & ~torch.isin(lab, torch.as_tensor(list(exclude), dtype=lab.dtype, device=lab.device))
+    faces = faces.to(torch.int64)
+    face_mask = vert_mask[faces].all(dim=1)
+    e = torch.sort(faces[face_mask][:, [0, 1, 1, 2, 2, 0]].reshape(-1, 2), dim=1)[0]
+    unique, counts = torch.unique(e, dim=0, return_counts=True)
+    selected_edges = unique[counts == 2].reshape(-1, 2)
+    if selected_edges.shape[0] == 0:
+        return vert_mask, selected_edges, "no_edges"
+    if selected_edges.shape[0] > 2 * prune_max_n_gs_once:
+        return vert_mask, selected_edges, "too_many_edges"
+    return vert_mask, selected_edges, None
+
+
 def subdivide_decision(xyz_gradient_accum, denom, scales_canon, max_radii2D, vertex_label, faces, grad_threshold, scale_threshold,
                        max_screen_size=None, max_n_gs=None, exclude=(6, 7)):
     """-> (selected_pts_mask [N] bool, selected_faces_idx int64) -- sings_hybrid.py:1026-1088 as a PURE function of its arguments
@@ -207,6 +308,25 @@ class MeshState:
         self.vertex_label = vertex_label.reshape(-1).to(torch.int32)
         if N > n_old:
             self.level_id = torch.cat([self.level_id, self.level_id[-1:].expand(N - n_old)])
+        self.gs_level_mark[-1] = N
+
+    def prune(self, new_faces, keep_mask, edges=None):
+        """The mesh after a simplification (sings_hybrid.py:1243-1252): ``new_faces`` index the kept vertices; the unique edges of the
+        new faces (same kernel; ``edges``: given instead -- a caller that holds them, or a host without the library); the kept
+        vertices' labels.  ``level_id`` is TRUNCATED to the new count, not masked -- the reference's ``_level_id[:n_gs]``: with more
+        than one level a pruned vertex of an early level shifts the later levels' ids; kept as it is there."""
+        keep = keep_mask.reshape(-1).to(torch.bool)
+        if keep.shape[0] != self.num_verts:
+            raise ValueError(f"MeshState.prune: keep_mask has {keep.shape[0]} entries, the mesh {self.num_verts} vertices")
+        self.vertex_label = self.vertex_label[keep]
+        N = int(self.vertex_label.shape[0])
+        if edges is None:
+            self.faces = _faces_i32(new_faces, N)
+            edges, _, _ = unique_edges(self.faces, N)
+        else:
+            self.faces = new_faces.to(torch.int32).contiguous()
+        self.edges = edges
+        self.level_id = self.level_id[:N]
         self.gs_level_mark[-1] = N
 
     def checkpoint_entries(self):

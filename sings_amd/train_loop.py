@@ -8,12 +8,14 @@ number of Gaussians every pre-sized piece of the hot path was built for:
     densify (clone) + prune from the accumulated statistics,
     Adam moments carried over for the survivors                             gs_trainer.py:280-343, sings_hybrid.py:856-932, 968-1004
     densify by selective subdivision of the anchors' mesh                   gs_trainer.py:219-222, 515-521, sings_hybrid.py:1022-1150
+    prune by edge collapse on the anchors' mesh                             gs_trainer.py:495-510, sings_hybrid.py:1153-1257
 
 Two ways to change the set.  ``densify_and_prune`` follows the reference's ``vanilla`` strategy's clone + prune.
 ``densify_and_subdivide`` (a trainer built with ``mesh=MeshState``) is its ``hybrid`` strategy, the one every shipped configuration
 sets: faces picked from the statistics are split 1-to-4 on the device (``sings_amd.topology``, csrc/sg_mesh.hip -- no trimesh, no
-host copy of the mesh), the midpoints become new anchors with interpolated skinning weights, labels and scales.  For the hot path
-what matters is THAT the set changes: P(t) != P(t-1).
+host copy of the mesh), the midpoints become new anchors with interpolated skinning weights, labels and scales; ``prune_and_simplify``
+is the strategy's other half: transparent-and-small or big-and-dead vertices lose their longest edges by collapse, in one launch.
+For the hot path what matters is THAT the set changes: P(t) != P(t-1).
 
 A topology change (or a new SH degree) invalidates everything that was sized or captured for the old set:
 
@@ -94,7 +96,7 @@ class AvatarTrainer:
     fused optimiser refuses parameters without a gradient).  With ``poses=None`` nothing changes.
 
     ``mesh``: a ``sings_amd.topology.MeshState`` over the anchors (faces, unique edges, vertex labels, level ids) -- what
-    ``densify_and_subdivide`` needs and keeps up to date.  With ``mesh=None`` nothing changes."""
+    ``densify_and_subdivide`` and ``prune_and_simplify`` need and keep up to date.  With ``mesh=None`` nothing changes."""
 
     POSE_GROUPS = ("global_orient", "body_pose", "transl")
 
@@ -103,7 +105,7 @@ class AvatarTrainer:
                  mesh=None):
         if mesh is not None and mesh.num_verts != int(module.xyz.shape[0]):
             raise ValueError(f"AvatarTrainer: the mesh has {mesh.num_verts} vertices, the module {int(module.xyz.shape[0])} Gaussians")
-        self.mesh, self.last_subdivision = mesh, None
+        self.mesh, self.last_subdivision, self.last_simplification = mesh, None, None
         learnable = self._pose_params(poses)
         for what, names in (("lrs", lrs), ("lr_schedules", lr_schedules or {})):
             extra = [n for n in self.POSE_GROUPS if n in names and n not in learnable]
@@ -367,3 +369,73 @@ class AvatarTrainer:
             self.last_subdivision = {"interpolated_scales": interpolated, "n_old": n_old}
         self._rebuild()
         return selected, faces_idx, n_old, n_new
+
+    def prune_and_simplify(self, opacity_threshold, scale_threshold, dead_grad=0.0005, large_scale=0.01, prune_max_n_gs_once=5000,
+                           min_n_gs=None, exclude=(6, 7), decision=None):
+        """``SinGS.prune_and_simplify`` (sings_hybrid.py:1153-1257) from the accumulated (and, with ``fp``, reduced) statistics; ->
+        (vert_mask, prune_mask, N_old, N_new).  ``decision``: a (vert_mask, selected_edges) pair to apply instead of
+        ``topology.simplify_decision`` (whose docstring names the reference's quirks that are kept).
+
+        The selected edges of ``mesh`` are collapsed (``topology.collapse_edges`` at the reference's rate 0.5, on ``xyz_canon`` = anchor +
+        offset); the vertices no face is left on are pruned.  The survivors keep their rows of the anchors, the skinning weights, a
+        per-Gaussian ``scaling_multiplier`` and both Adam moments, bit for bit -- and, unlike after clone + prune, their accumulated
+        statistics (``prune_points`` masks them, sings_hybrid.py:887-890; with ``fp`` each rank keeps its OWN sums, the reduced ones
+        only take the decision).  Then ``mesh.prune``, the opacity reset on the new set, the rebuild.
+
+        A skip (``simplify_decision``'s reasons, or a ``decision`` without edges) changes nothing -- no parameter, no statistic, not
+        ``topology_version``, not a captured graph -- and returns ``prune_mask`` all false.  ``self.last_simplification`` records the reason,
+        or the counts of the call."""
+        if self.mesh is None:
+            raise RuntimeError("AvatarTrainer.prune_and_simplify needs mesh=MeshState(...)")
+        m, mesh = self.m, self.mesh
+        stats = ("xyz_gradient_accum", "denom", "max_radii2D")
+        own = None
+        if self.fp is not None:
+            own = [getattr(m, k).clone() for k in stats]
+            self.fp.reduce_densification_stats(m.xyz_gradient_accum, m.denom, m.max_radii2D)
+        with torch.no_grad():
+            attrs = _dec.decode_attributes(m.xyz, m.triplane, m.geometry_dec, m.appearance_dec, m.thickness_factor, m.scaling_multiplier)
+            scales = attrs["scales"] if self.smpl_scale is None else attrs["scales"] * self.smpl_scale.reshape(1, -1)
+            n_old = int(m.xyz.shape[0])
+            if decision is None:
+                vert_mask, edges, reason = _topo.simplify_decision(
+                    m.xyz_gradient_accum, m.denom, attrs["opacity"], scales, mesh.vertex_label, mesh.faces, opacity_threshold,
+                    scale_threshold, dead_grad=dead_grad, large_scale=large_scale, prune_max_n_gs_once=prune_max_n_gs_once,
+                    min_n_gs=min_n_gs, exclude=exclude)
+            else:
+                vert_mask, edges = decision
+                vert_mask, edges = vert_mask.to(self.dev), edges.to(self.dev)
+                reason = None if int(edges.shape[0]) else "no_edges"
+            result = None if reason else _topo.collapse_edges(attrs["xyz_canon"], m.lbs_weights, edges, mesh.faces, return_collapses=True)
+            if own is not None:                                      # (the decision is taken: back to this rank's own sums)
+                for k, t in zip(stats, own):
+                    getattr(m, k).copy_(t)
+            if result is None:
+                self.last_simplification = {"skipped": reason, "selected_edges": int(edges.shape[0])}
+                return vert_mask, torch.zeros(n_old, dtype=torch.bool, device=self.dev), n_old, n_old
+            _, new_faces, _, prune, collapses = result
+            keep = ~prune
+            kept_stats = [getattr(m, k)[keep].clone() for k in stats]
+            sm = m.scaling_multiplier
+            per_gaussian = torch.is_tensor(sm) and sm.dim() > 0 and sm.shape[0] == n_old and n_old != 1
+            group = next(g for g in self.opt.param_groups if g["name"] == "xyz")
+            old = group["params"][0]
+            state = None if self.fused else self.opt.state.pop(old, None)
+            m.set_topology(old.detach()[keep], m.lbs_weights[keep], scaling_multiplier=sm[keep].clone() if per_gaussian else None)
+            if self.fused:
+                self.opt.remap_rows(old, m.xyz, torch.zeros(n_old, dtype=torch.bool, device=self.dev), keep)
+            group["params"][0] = m.xyz
+            if state:
+                for k in ("exp_avg", "exp_avg_sq"):
+                    state[k] = state[k][keep].clone()
+                self.opt.state[m.xyz] = state
+            mesh.prune(new_faces, keep)
+            if not getattr(m.appearance_dec, "fixed_opacity", False):
+                m.appearance_dec.reset_opacity(m.triplane(m.xyz))
+            n_new = int(m.xyz.shape[0])
+            self.last_simplification = {"skipped": None, "selected_edges": int(edges.shape[0]), "collapses": collapses, "n_old": n_old,
+                                        "n_new": n_new}
+        self._rebuild()
+        # (set_topology and the rebuild start the statistics at zero, as after clone + prune: the survivors' rows go back)
+        m.xyz_gradient_accum, m.denom, m.max_radii2D = kept_stats
+        return vert_mask, prune, n_old, n_new
