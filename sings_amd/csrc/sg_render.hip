@@ -16,13 +16,17 @@
 //    saturated pixels drop out; the forward stores the mask byte per sorted entry and the backward reuses it.
 //  * The per-entry body is straight-line predicated code (no exec-mask branches).
 //  * Lists longer than 256 entries: the forward checkpoints (T, colour) every 256 entries and the backward runs one
-//    workgroup per (tile, 256-entry depth segment) instead of one serial walk per tile.
-//  * Backward: the 9 per-pixel partials of an entry are summed across the wave's 64 lanes with a
+//    work item per (tile, 256-entry depth segment) instead of one serial walk per tile.
+//  * Backward: the 9 per-pixel partials of an entry are summed across a wave's 64 lanes with a
 //    multi-value butterfly (v_permlane32_swap / v_permlane16_swap / DPP: 24 ops for 9 values instead of
-//    54), the <= 4 quadrant sums are combined in LDS in a fixed order and stored ONCE per (tile,Gaussian)
-//    as a 36-byte record at the Gaussian-major slot reserved in the forward pass.  No float atomics
-//    (memory-side atomics cap at ~1.3 TB/s on MI355X and scattered single-row adds are 17x slower);
-//    gradients are bitwise reproducible.
+//    54) and stored ONCE per (tile,Gaussian) as a 36-byte record at the Gaussian-major slot reserved in
+//    the forward pass.  No float atomics (memory-side atomics cap at ~1.3 TB/s on MI355X and scattered
+//    single-row adds are 17x slower); gradients are bitwise reproducible.
+//     - Frames of many tiles (the dense kernels): ONE WAVE per work item, four items per workgroup, no workgroup barrier.  A lane
+//       owns one pixel of each quadrant (four pixel states, statically indexed), evaluates an entry in the quadrants of its mask
+//       byte, adds the partials over them in registers (quadrant order 0..3) and runs ONE butterfly per (tile, entry).
+//     - Frames of few tiles (the sparse kernels): a workgroup per work item, a wave per quadrant, one butterfly per (entry,
+//       quadrant), the <= 4 quadrant sums combined in LDS in a fixed order.
 #include "sg_sort.h"
 
 #define SG_FB 256         // forward: list entries staged per batch (one per thread)
@@ -479,12 +483,15 @@ void sg_launch_render_fwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, 
 // total of value sg_red_idx(lane); lane 63 additionally gets the total of v[8] in *v8tot.
 // v_permlane{32,16}_swap are issued from inline asm: hipcc (ROCm 7.2) folds "r[0] + r[1]" of the builtins' result
 // into r[0] + r[0]; the swaps of one level are independent, so one pair of wait states serves all of them.
-__device__ __forceinline__ float sg_reduce9(const float v[9], int lane, float *v8tot)
+// v[0..7] are left as the first swaps left them (finite where the inputs were): a caller that keeps `v` alive -- the dense backward's
+// accumulators -- pays no copies for it, and for one that does not the stores are dead.
+__device__ __forceinline__ float sg_reduce9(float v[9], int lane, float *v8tot)
 {
     float a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3], a4 = v[4], a5 = v[5], a6 = v[6], a7 = v[7];
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3\n\t"
                  "v_permlane32_swap_b32 %4, %5\n\tv_permlane32_swap_b32 %6, %7\n\ts_nop 1"
                  : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7));
+    v[0] = a0; v[1] = a1; v[2] = a2; v[3] = a3; v[4] = a4; v[5] = a5; v[6] = a6; v[7] = a7;
     float s01 = a0 + a1, s23 = a2 + a3, s45 = a4 + a5, s67 = a6 + a7;   // (x_lo + x_hi | y_lo + y_hi)
     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3\n\ts_nop 1"
                  : "+v"(s01), "+v"(s23), "+v"(s45), "+v"(s67));
@@ -524,19 +531,23 @@ __device__ __forceinline__ int sg_red_idx(int lane)
 }
 
 // One (entry, quadrant) pass of the backward composite: `ga, gb, gc` the staged record, KPOS the entry's position in the batch
-// (compared with the pixel's contributor count inside the batch, `ncq_b`), KSLOT its row in sG.  `continue` skips entries that
-// touch no pixel of the quadrant.  Shared by sg_render_bwd_kernel and sg_render_bwd_sparse_kernel.
+// (compared with the pixel's contributor count inside the batch, `ncq_b`), KSLOT its row in sG.  SKIP is what to do with an entry that
+// touches no pixel of the quadrant.  Three pieces: SG_BWD_EVAL moves the quadrant's 64 pixels in front of the entry and leaves each
+// pixel's `w`, `dchan`, `dx`, `dy`; SG_BWD_PARTIALS forms the nine per-lane partials from them; SG_BWD_FILE sums nine (AUX: ten)
+// per-lane values over the wave and files the sums in row KSLOT.  The sparse kernels run all three per (entry, quadrant) --
+// SG_BWD_PASS, their arithmetic since round 5 -- and the dense kernels, where one wave owns the whole tile, run the first two per
+// quadrant and SG_BWD_FILE once per entry (sg_render_bwd.inc).
 // AUX (the depth / alpha maps): the entry's colour gains a fourth channel z with upstream gradient dD = dL/ddepth (so `Sd` carries
 // <colour, dL/dpixel> + D_behind dD), dL/dalpha enters through `tb` (T_final (<bg, dL/dpixel> - dL/dalpha)), and the tenth
 // partial dchan dD = dL/dz goes to slot 9 (lane 63).
-#define SG_BWD_PASS(KPOS, KSLOT)                                                                                      \
+#define SG_BWD_EVAL(KPOS, SKIP)                                                                                       \
     /* straight-line, predicated (alpha_eff = 0 makes every update an exact no-op) */                                 \
     const float dx = ga.x - pxf, dy = ga.y - pyf;                                                                     \
     const float power = sg_power2(ga.z, ga.w, gb.x, dx, dy);   /* the forward's expression: same decisions */         \
     const float G = __builtin_amdgcn_exp2f(power);                                                                    \
     const float alpha = fminf(0.99f, gb.y * G);                                                                       \
     const bool valid = ((KPOS) < ncq_b) & !(power > 0.0f) & !(alpha < 1.0f / 255.0f);                                 \
-    if (__ballot(valid) == 0ull) continue;          /* touches no pixel of this quadrant: the slot stays unset */     \
+    if (__ballot(valid) == 0ull) SKIP;              /* touches no pixel of this quadrant: the slot stays unset */     \
     const float ae = valid ? alpha : 0.0f;                                                                            \
     const float rinv = __builtin_amdgcn_rcpf(1.0f - ae);      /* rcp(1) == 1 exactly */                               \
     Tr = Tr * rinv;                                  /* T in front of this entry */                                   \
@@ -548,21 +559,31 @@ __device__ __forceinline__ int sg_red_idx(int lane)
     const float w = valid ? G * dLa : 0.0f;          /* = dL/dopacity contribution; dL/dG = o * dLa */                \
     /* first and second moments of w over the pixels: dL/dmean is a per-entry combination of the first moments */     \
     /* (conic . (sum w dx, sum w dy), applied once per record), and so are the factors (-o W/2, -o H/2, -o/2) */      \
+    do { } while (0)
+// the nine per-lane partials of the pass just evaluated, into V[0..8]
+#define SG_BWD_PARTIALS(V)                                                                                            \
     const float wx = w * dx, wy = w * dy;                                                                             \
-    float v[9];                                                                                                       \
-    v[0] = wx; v[1] = wy;                                                                                             \
-    v[2] = wx * dx; v[3] = wx * dy; v[4] = wy * dy;                                                                   \
-    v[5] = w;                                                                                                         \
-    v[6] = dchan * d0; v[7] = dchan * d1; v[8] = dchan * d2;                                                          \
+    V[0] = wx; V[1] = wy;                                                                                             \
+    V[2] = wx * dx; V[3] = wx * dy; V[4] = wy * dy;                                                                   \
+    V[5] = w;                                                                                                         \
+    V[6] = dchan * d0; V[7] = dchan * d1; V[8] = dchan * d2;                                                          \
+    do { } while (0)
+// V: the nine per-lane values, V9 the tenth (AUX: dL/dz)
+#define SG_BWD_FILE(V, V9, KSLOT)                                                                                     \
     float v8;                                                                                                         \
-    const float z = sg_reduce9(v, lane, &v8);                                                                         \
+    const float z = sg_reduce9(V, lane, &v8);                                                                         \
     float v9 = 0.0f;                                                                                                  \
-    if (AUX) v9 = sg_reduce_to63(dchan * dD);                                                                         \
+    if (AUX) v9 = sg_reduce_to63(V9);                                                                                 \
     float *slot = &sG[wave][KSLOT][cslot];               /* lanes 0, 8, .., 56: their value's slot; lane 63: slot 8 */\
     if ((lane & 7) == 0) *slot = z;                                                                                   \
     if (lane == 63) *slot = v8;                                                                                       \
     if (AUX && lane == 63) sG[wave][KSLOT][9] = v9;                                                                   \
     do { } while (0)
+#define SG_BWD_PASS(KPOS, KSLOT)                                                                                      \
+    SG_BWD_EVAL(KPOS, continue);                                                                                      \
+    float v[9];                                                                                                       \
+    SG_BWD_PARTIALS(v);                                                                                               \
+    SG_BWD_FILE(v, dchan * dD, KSLOT)
 
 // frame blockIdx.y of a launch of K frames (see SG_FWD_FRAME_OFFSETS)
 #define SG_BWD_FRAME_OFFSETS                                                                                            \
@@ -584,12 +605,6 @@ __device__ __forceinline__ int sg_red_idx(int lane)
         ax.depth = sg_at(ax.depth, (size_t)blockIdx.y * bt.geom); ax.ckD = sg_at(ax.ckD, fa); ax.dz = sg_at(ax.dz, fa);  \
         ax.dL_ddepth = sg_at(ax.dL_ddepth, fm); ax.dL_dalpha = sg_at(ax.dL_dalpha, fm);                                  \
     }
-// Round 5: the dependent gathers of an item (list id -> record slot -> records) are done in ONE round per chunk of SG_BCH entries, one
-// entry per thread, and the 64-entry batches then run out of LDS -- at cfg3 (lists of ~96 entries) one round per tile instead of one
-// per batch; the quadrant-sum slots are re-armed by the combine step itself (one barrier per batch less).  148.4 -> 145.8 us per
-// cfg3 view, +1.5 % views/s on one box (A / B / A / B).  Requesting the first chunk's ids and slot words in front of the prologue's
-// barrier on top of that: measured, no gain (146.7 us).
-#define SG_BCH 128
 #ifdef SG_RENDER_STAMP
 // diagnostic build only (tools/render_stamps.py): per-workgroup start / end stamps of the shader clock and of the 100 MHz real-time clock
 __device__ unsigned long long sg_render_stamps[65536 * 4];
@@ -683,6 +698,8 @@ sg_order_items_kernel(SgBatch bt, const uint32_t *__restrict__ header, const uin
 // sg_skinned_backward_aux: one frame; sg_rasterize_backward_records_frames_aux: K frames).  One source, included twice, so that the plain kernels stay the round-5 kernels
 // instruction for instruction (as inlined bodies the compiler allocated them differently) and the aux kernels are separate
 // symbols for the profiles.
+// waves per SIMD of the dense kernels (four pixel states per lane): 76 VGPRs, six waves; with the depth / alpha adjoints 83, five
+#define SG_BWD_TW_WAVES (SG_BWD_AUX ? 5 : 6)
 #define SG_BWD_AUX 0
 #include "sg_render_bwd.inc"
 #undef SG_BWD_AUX
@@ -696,6 +713,7 @@ void sg_launch_render_bwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, 
     static_assert(SG_SEG % SG_BB == 0, "segments are whole backward batches");
     const int T = c.gx * c.gy;
     const int grid = sg_render_blocks((int)sg_items_cap((size_t)T, cap));
+    const int grid4 = sg_render_blocks((int)((sg_items_cap((size_t)T, cap) + 3u) / 4u));   // dense kernels: four work items per workgroup
     const unsigned K = (unsigned)bt.K;
     uint32_t cap32 = cap > 0xffffffffull ? 0xffffffffu : (uint32_t)cap;
     sg_prof_begin(SG_K_RENDER_BWD, st);
@@ -714,12 +732,12 @@ void sg_launch_render_bwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, 
                            grec.a, grec.b, cap32, b.header, b.items, b.ck_start, im.ckpt, sg_ckpt_cap(cap), b.pair_mask, sg_mask_plane(cap),
                            sg_split_long(c.gx, c.gy, c.flags) ? 1 : 0, b.item_perm, b.rec_valid);
     } else if (ax)
-    hipLaunchKernelGGL(sg_render_bwd_aux_kernel, dim3(grid, K), dim3(256), 0, st, bt, c.W, c.H, c.gx, T, grid, b.ranges,
+    hipLaunchKernelGGL(sg_render_bwd_aux_kernel, dim3(grid4, K), dim3(256), 0, st, bt, c.W, c.H, c.gx, T, grid4, b.ranges,
                        b.point_list, g.recA, g.recB, g.recC, c.bg, im.final_T, im.n_contrib, dL_dpix,
                        grec.a, grec.b, cap32, b.header, b.items, b.ck_start, im.ckpt, sg_ckpt_cap(cap), b.pair_mask, sg_mask_plane(cap),
                        sg_split_long(c.gx, c.gy, c.flags) ? 1 : 0, *ax);
     else
-    hipLaunchKernelGGL(sg_render_bwd_kernel, dim3(grid, K), dim3(256), 0, st, bt, c.W, c.H, c.gx, T, grid, b.ranges,
+    hipLaunchKernelGGL(sg_render_bwd_kernel, dim3(grid4, K), dim3(256), 0, st, bt, c.W, c.H, c.gx, T, grid4, b.ranges,
                        b.point_list, g.recA, g.recB, g.recC, c.bg, im.final_T, im.n_contrib, dL_dpix,
                        grec.a, grec.b, cap32, b.header, b.items, b.ck_start, im.ckpt, sg_ckpt_cap(cap), b.pair_mask, sg_mask_plane(cap),
                        sg_split_long(c.gx, c.gy, c.flags) ? 1 : 0);

@@ -4,7 +4,35 @@
 // kernels every AUX branch is dead.
 // (no include guard: included once per variant)
 
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+// Quadrant Q of the current entry in the dense kernels: SG_BWD_EVAL on the quadrant's pixel state, then the per-lane partials go into the
+// entry's accumulators as acc = acc * keep + v, `keep` 0 for the entry's first evaluated quadrant (acc = v exactly: what the registers
+// held, the previous entry's sums, drops out) and 1 behind it (one rounding of acc + v: a plain add).  One instruction per value and
+// no branch: as `first ? v : acc + v` the compiler emits a select per value, as a branch its two sides meet in 18 register copies per
+// quadrant.  (Written as the instruction, in place: from fmaf() the result lands in the product's register and is copied.)
+// The price: the registers must hold finite values -- zero at the start, sums of finite partials afterwards.  An entry whose sums
+// overflow (a gradient that is infinite anyway) turns the sums of the wave's later entries into NaN.
+#define SG_BWD_ACC(J, X) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(acc[J]) : "v"(keep), "v"(X))
+#define SG_BWD_QUAD(Q)                                                                                                \
+    do {                                                                                                              \
+        const float pxf = ((Q) & 1) ? pxf0 + 8.0f : pxf0, pyf = ((Q) >> 1) ? pyf0 + 8.0f : pyf0;                      \
+        const float d0 = d04[Q], d1 = d14[Q], d2 = d24[Q], dD = dD4[Q], tb = tb4[Q];                                  \
+        const uint32_t ncq_b = ncq4[Q];                                                                               \
+        float &Tr = Tr4[Q], &Sd = Sd4[Q];                                                                             \
+        SG_BWD_EVAL((uint32_t)pos, break);                                                                            \
+        float v[9];                                                                                                   \
+        SG_BWD_PARTIALS(v);                                                                                           \
+        for (int j = 0; j < 9; j++) SG_BWD_ACC(j, v[j]);                                                              \
+        if (AUX) SG_BWD_ACC(9, dchan * dD);                                                                           \
+        asm volatile("v_mov_b32 %0, 1.0" : "=v"(keep));                                                               \
+        some = true;                                                                                                  \
+    } while (0)
+// Dense backward (frames of many tiles): ONE WAVE per work item (tile, depth segment), four consecutive items per workgroup.  Lane l
+// owns pixel (l & 7, l >> 3) of EACH of the tile's four 8x8 quadrants and keeps that pixel's state four times, statically indexed.
+// An entry is evaluated in the quadrants the forward composited it in (its mask bits: wave-uniform branches, the quadrant loop fully
+// unrolled), its per-lane partials are added over those quadrants in registers -- the first assigns (SG_BWD_QUAD), the others add, in
+// the order 0, 1, 2, 3 -- and ONE lane butterfly per (tile, entry) sums them; with a wave per quadrant an entry that reached q quadrants paid q
+// butterflies and an LDS combine behind two workgroup barriers.  The waves of a workgroup share nothing: no __syncthreads at all.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SG_BWD_TW_WAVES, SG_BWD_TW_WAVES)))
 #if SG_BWD_AUX
 sg_render_bwd_aux_kernel(SG_BWD_PARAMS, SgAuxBwd ax)
 #else
@@ -15,149 +43,164 @@ sg_render_bwd_kernel(SG_BWD_PARAMS)
 #if !SG_BWD_AUX
     const SgAuxBwd ax = { };
 #endif
-    __shared__ float4 sR[SG_BCH][3];           // staged entry: (mean x, mean y, A', B') (C', opacity, colour 0, 1) (colour 2, z [AUX], -, -)
-    __shared__ uint32_t sM[SG_BCH];
-    __shared__ uint16_t sList[4][SG_BB];
-    __shared__ float sG[4][SG_BB][9 + AUX];    // per-quadrant reduced partials of the batch; [8] = SG_UNSET: quadrant w wrote nothing
-    __shared__ uint32_t smax[4];
+    // per wave: its staged batch -- (mean x, mean y, A', B') (C', opacity, colour 0, 1) (colour 2, z [AUX], quadrant mask, -) and, for the
+    // record store, (A, B, C, record slot): kept here, not in registers, across the walk -- and a row of sums per entry
+    __shared__ float4 sR[4][SG_BB][4];
+    __shared__ float sG[4][SG_BB][9 + AUX];
     SG_STAMP_SCOPE
     SG_BWD_FRAME_OFFSETS;
 #if SG_BWD_AUX
     SG_BWD_AUX_FRAME_OFFSETS;
 #endif
-    // one workgroup per work item (tile, depth segment); the item list is in tile order, so the XCD-aware map
-    // over the ACTUAL item count keeps neighbouring tiles on one L2.  The grid is an upper bound.
+    // the item list is in tile order, so the XCD-aware map over groups of four items keeps neighbouring tiles on one L2.  The grid is
+    // an upper bound; the last workgroup's waves past the item count have nothing to do.
     (void)T; (void)nblocks;
     const int nitems = header[1] ? 0 : (int)header[5];             // nothing to do after a capacity overflow
-    const int it = sg_tile_of_block(blockIdx.x);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int it = 4 * sg_tile_of_block(blockIdx.x) + wave;
     if (it >= nitems) return;
     const uint32_t item = items[it];
     const int tile = (int)(item & 0xfffffu), seg = (int)(item >> 20);
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int tx = tile % gx, ty = tile / gx;
     const int X0 = tx * 16, Y0 = ty * 16;
-    const int px = X0 + 8 * (wave & 1) + (lane & 7), py = Y0 + 8 * (wave >> 1) + (lane >> 3);
-    const bool inside = px < W && py < H;
-    const float pxf = (float)px, pyf = (float)py;
     const uint2 range = ranges[tile];
     const int n = (int)(range.y - range.x);
     const uint32_t cks = ck_start[tile];
     const int lo = seg * SG_SEG;                                   // this item: entries [lo, hi)
     const int hi = cks != 0xffffffffu && lo + SG_SEG < n ? lo + SG_SEG : n;
     if (lo >= n) return;
-    const size_t pid = (size_t)py * W + px, hw = (size_t)H * W;
-    // per-pixel state: running T, colour accumulated BEHIND the current entry, dL/dpixel, T_final <bg, dL/dpixel>
-    const float Tfin = inside ? final_T[pid] : 0.0f;
-    const uint32_t ncq = inside ? n_contrib[pid] : 0u;
-    const float d0 = inside ? dL_dpix[pid] : 0.0f, d1 = inside ? dL_dpix[hw + pid] : 0.0f, d2 = inside ? dL_dpix[2 * hw + pid] : 0.0f;
-    const float dD = AUX && inside && ax.dL_ddepth ? ax.dL_ddepth[pid] : 0.0f, dA = AUX && inside && ax.dL_dalpha ? ax.dL_dalpha[pid] : 0.0f;
-    const float tb = AUX ? Tfin * (bg[0] * d0 + bg[1] * d1 + bg[2] * d2 - dA) : Tfin * (bg[0] * d0 + bg[1] * d1 + bg[2] * d2);
-    // (the colour behind enters the gradient only through <S, dL/dpixel>: ONE running scalar Sd instead of three channels)
-    float Tr = Tfin, Sd = 0.0f;
-    // Not the last segment, and this pixel has contributors behind it: start from the forward checkpoint at `hi`.
-    // T in front of entry hi; S = colour composited behind it, normalised by that T.  (A pixel with ncq <= hi has
-    // nothing behind: final state.  ncq > hi implies the forward reached that boundary with this pixel live.)
-    if (hi < n && ncq > (uint32_t)hi && cks + (uint32_t)(hi / SG_SEG) < ck_cap) {
-        const float4 cb = ckpt[(size_t)(cks + (uint32_t)(hi / SG_SEG)) * 256 + tid];
-        const float4 cf = ckpt[(size_t)cks * 256 + tid];
-        const float rT = 1.0f / cb.x;
-        Tr = cb.x;
-        Sd = fmaf((cf.w - cb.w) * rT, d2, fmaf((cf.z - cb.z) * rT, d1, (cf.y - cb.y) * rT * d0));
-        if (AUX) {                                                     // + D_behind dL/ddepth, normalised like the colour
-            const float Db = ax.ckD[(size_t)(cks + (uint32_t)(hi / SG_SEG)) * 256 + tid], Df = ax.ckD[(size_t)cks * 256 + tid];
-            Sd = fmaf((Df - Db) * rT, dD, Sd);
+    const size_t hw = (size_t)H * W;
+    // per-pixel state, once per quadrant: running T, <colour accumulated BEHIND the current entry, dL/dpixel> (ONE running scalar
+    // instead of three channels), dL/dpixel, T_final <bg, dL/dpixel>, the contributor count
+    const float pxf0 = (float)(X0 + (lane & 7)), pyf0 = (float)(Y0 + (lane >> 3));     // quadrant 0's pixel; the others' are + 8, exactly
+    float Tr4[4], Sd4[4], d04[4], d14[4], d24[4], dD4[4], tb4[4];
+    uint32_t ncq4[4];
+    int maxq4[4];                                                  // the quadrants' deepest contributors (wave-uniform)
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int px = X0 + 8 * (q & 1) + (lane & 7), py = Y0 + 8 * (q >> 1) + (lane >> 3);
+        const bool inside = px < W && py < H;
+        const size_t pid = (size_t)py * W + px;
+        const float Tfin = inside ? final_T[pid] : 0.0f;
+        const uint32_t ncq = inside ? n_contrib[pid] : 0u;
+        const float d0 = inside ? dL_dpix[pid] : 0.0f, d1 = inside ? dL_dpix[hw + pid] : 0.0f, d2 = inside ? dL_dpix[2 * hw + pid] : 0.0f;
+        const float dD = AUX && inside && ax.dL_ddepth ? ax.dL_ddepth[pid] : 0.0f, dA = AUX && inside && ax.dL_dalpha ? ax.dL_dalpha[pid] : 0.0f;
+        tb4[q] = AUX ? Tfin * (bg[0] * d0 + bg[1] * d1 + bg[2] * d2 - dA) : Tfin * (bg[0] * d0 + bg[1] * d1 + bg[2] * d2);
+        float Tr = Tfin, Sd = 0.0f;
+        // Not the last segment, and this pixel has contributors behind it: start from the forward checkpoint at `hi`.
+        // T in front of entry hi; S = colour composited behind it, normalised by that T.  (A pixel with ncq <= hi has
+        // nothing behind: final state.  ncq > hi implies the forward reached that boundary with this pixel live.)
+        if (hi < n && ncq > (uint32_t)hi && cks + (uint32_t)(hi / SG_SEG) < ck_cap) {
+            const float4 cb = ckpt[(size_t)(cks + (uint32_t)(hi / SG_SEG)) * 256 + q * 64 + lane];
+            const float4 cf = ckpt[(size_t)cks * 256 + q * 64 + lane];
+            const float rT = 1.0f / cb.x;
+            Tr = cb.x;
+            Sd = fmaf((cf.w - cb.w) * rT, d2, fmaf((cf.z - cb.z) * rT, d1, (cf.y - cb.y) * rT * d0));
+            if (AUX) {                                                     // + D_behind dL/ddepth, normalised like the colour
+                const float Db = ax.ckD[(size_t)(cks + (uint32_t)(hi / SG_SEG)) * 256 + q * 64 + lane], Df = ax.ckD[(size_t)cks * 256 + q * 64 + lane];
+                Sd = fmaf((Df - Db) * rT, dD, Sd);
+            }
         }
-    }
-    uint32_t m = ncq;
+        Tr4[q] = Tr; Sd4[q] = Sd; d04[q] = d0; d14[q] = d1; d24[q] = d2; dD4[q] = dD; ncq4[q] = ncq;
+        uint32_t m = ncq;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { uint32_t u = __shfl_xor(m, o, 64); m = u > m ? u : m; }
-    const int maxq = (int)__builtin_amdgcn_readfirstlane(m);          // this quadrant's deepest contributor
-    if (lane == 0) smax[wave] = m;
-    if (tid < SG_BB) {
-#pragma unroll
-        for (int w = 0; w < 4; w++) sG[w][tid][8] = __uint_as_float(SG_UNSET);
+        for (int o = 32; o > 0; o >>= 1) { uint32_t u = __shfl_xor(m, o, 64); m = u > m ? u : m; }
+        maxq4[q] = (int)__builtin_amdgcn_readfirstlane(m);
     }
-    __syncthreads();
-    const int max_contrib = (int)max(max(smax[0], smax[1]), max(smax[2], smax[3]));
+    const int max_contrib = max(max(maxq4[0], maxq4[1]), max(maxq4[2], maxq4[3]));
     const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;
-    const unsigned long long lt = (1ull << lane) - 1ull;
     const int cslot = lane == 63 ? 8 : sg_red_idx(lane);
-    for (int ch = (hi - 1) / SG_BCH; ch >= lo / SG_BCH; ch--) {
-        const int cbase = ch * SG_BCH;
-        const int ccnt = hi - cbase < SG_BCH ? hi - cbase : SG_BCH;
-        // ---- stage the chunk (threads 0..SG_BCH-1): records, quadrant mask, gradient-record slot
-        uint32_t rslot = 0xffffffffu;
-        float opac = 0.0f, cA = 0.0f, cB = 0.0f, cC = 0.0f;
-        if (tid < ccnt) {
-            const int e = cbase + tid;
+    float acc[10] = { };                                           // the current entry's partials, summed over its quadrants ([9]: AUX, dL/dz)
+    // ---- the segment in batches of 64 entries, one entry per lane, back to front
+    for (int base = lo + (hi - 1 - lo) / SG_BB * SG_BB; base >= lo; base -= SG_BB) {
+        const int cnt = hi - base < SG_BB ? hi - base : SG_BB;
+        // ---- stage the batch: list id -> record C -> record slot; the quadrant mask; records A and B of entries composited somewhere
+        uint32_t mk = 0u;
+        if (lane < cnt) {
+            const int e = base + lane;
             const uint32_t gid = point_list[range.x + e];
             // quadrants the forward composited this entry in: nothing else can carry a gradient, so neither the
             // rectangle tests nor the two record gathers are repeated for the rest
-            // (a long tile of a few-tile frame was composited by four workgroups, one mask plane each: sg_render_fwd_body)
-            uint32_t mk = 0u;
             if (e < max_contrib) {
                 mk = pair_mask[range.x + e];
                 if (split_long && n > SG_WSORT_MAX)
                     mk = (mk & 1u) | (pair_mask[(size_t)mask_plane + range.x + e] & 2u) | (pair_mask[2 * (size_t)mask_plane + range.x + e] & 4u) |
                          (pair_mask[3 * (size_t)mask_plane + range.x + e] & 8u);
+                mk &= 15u;
             }
             const float4 c4 = recC[SG_REC_STRIDE * (size_t)gid];
             if (mk) {
                 const float4 a = recA[SG_REC_STRIDE * (size_t)gid], b = recB[SG_REC_STRIDE * (size_t)gid];
-                opac = b.y; cA = a.z; cB = a.w; cC = b.x;
-                sR[tid][0] = make_float4(a.x, a.y, SG_KA * a.z, SG_KB * a.w);
-                sR[tid][1] = make_float4(SG_KA * b.x, b.y, b.z, b.w);
-                sR[tid][2].x = c4.x;
-                if (AUX) sR[tid][2].y = ax.depth[gid];
+                sR[wave][lane][0] = make_float4(a.x, a.y, SG_KA * a.z, SG_KB * a.w);
+                sR[wave][lane][1] = make_float4(SG_KA * b.x, b.y, b.z, b.w);
+                sR[wave][lane][2] = make_float4(c4.x, AUX ? ax.depth[gid] : 0.0f, __uint_as_float(mk), 0.0f);
+                sR[wave][lane][3] = make_float4(a.z, a.w, b.x, 0.0f);
             }
             const uint32_t goff = __float_as_uint(c4.y), mn = __float_as_uint(c4.z), wh = __float_as_uint(c4.w);
             const int x0 = mn & 0xffff, y0 = mn >> 16, rw = wh & 0xffff;
-            rslot = goff + (uint32_t)((ty - y0) * rw + (tx - x0));
-            sM[tid] = mk;
+            sR[wave][lane][3].w = __uint_as_float(goff + (uint32_t)((ty - y0) * rw + (tx - x0)));
         }
-        __syncthreads();
-        for (int kb = (ccnt - 1) / SG_BB; kb >= 0; kb--) {
-            const int b0 = kb * SG_BB, base = cbase + b0;                  // the batch inside the chunk / inside the list
-            const int cnt = ccnt - b0 < SG_BB ? ccnt - b0 : SG_BB;
-            // ---- each wave: the entries that can reach its quadrant, back to front
-            if (base < maxq) {
-                uint16_t *list = sList[wave];
-                const int lim = maxq - base < cnt ? maxq - base : cnt;         // entries >= maxq touch no pixel here
-                const int nl = sg_compact_quadrant<1>(sM + b0, lim, wave, lane, lt, list, SG_BB);
-                const uint32_t ncq_b = ncq > (uint32_t)base ? ncq - (uint32_t)base : 0u;   // contributors of this pixel inside the batch
-                for (int i = nl - 1; i >= 0; i--) {
-                    const uint32_t k = list[i];
-                    const float4 ga = sR[b0 + k][0], gb = sR[b0 + k][1];
-                    const float gc = sR[b0 + k][2].x;
-                    const float gz = AUX ? sR[b0 + k][2].y : 0.0f;
-                    SG_BWD_PASS(k, k);
-                }
+        unsigned long long todo = __ballot(mk != 0u);                  // entries still to walk
+        unsigned long long filed = 0ull;                               // entries whose row of sums was written
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_wave_barrier();
+        while (todo) {
+            const int k = 63 - __builtin_clzll(todo);
+            todo &= ~(1ull << k);
+            const int pos = base + k;                                   // the entry's position in the tile's list
+            const float4 ga = sR[wave][k][0], gb = sR[wave][k][1], gm = sR[wave][k][2];
+            const float gc = gm.x, gz = gm.y;
+            uint32_t mke = __builtin_amdgcn_readfirstlane(__float_as_uint(gm.z));
+            // the quadrants to evaluate: composited there by the forward, and not behind the quadrant's deepest contributor
+            if (pos >= maxq4[0]) mke &= ~1u;
+            if (pos >= maxq4[1]) mke &= ~2u;
+            if (pos >= maxq4[2]) mke &= ~4u;
+            if (pos >= maxq4[3]) mke &= ~8u;
+            // the entry's partials, added over those quadrants in the order 0, 1, 2, 3
+            float keep;
+            asm volatile("v_mov_b32 %0, 0" : "=v"(keep));              // (a vector register: a scalar operand halves the issue rate)
+            bool some = false;                                          // some pixel of the tile took a gradient from this entry
+            if (mke & 1u) SG_BWD_QUAD(0);
+            if (mke & 2u) SG_BWD_QUAD(1);
+            if (mke & 4u) SG_BWD_QUAD(2);
+            if (mke & 8u) SG_BWD_QUAD(3);
+            __builtin_amdgcn_wave_barrier();                           // (no instruction: keeps the paths above from being threaded into the tail, with copies)
+            if (some) {                                                // (else no pixel of the tile: the row reads as zero)
+                SG_BWD_FILE(acc, acc[9], k);
+                filed |= 1ull << k;
             }
-            __syncthreads();
-            // ---- combine the quadrants in a fixed order, store the record, re-arm the slots (the thread that staged the entry)
-            if (tid >= b0 && tid < b0 + cnt) {
-                const int q0 = tid - b0;
-                float s[9 + AUX] = { };
-#pragma unroll
-                for (int w = 0; w < 4; w++)
-                    if (__float_as_uint(sG[w][q0][8]) != SG_UNSET) {
-#pragma unroll
-                        for (int q = 0; q < 9 + AUX; q++) s[q] += sG[w][q0][q];
-                        sG[w][q0][8] = __uint_as_float(SG_UNSET);
-                    }
-                if (rslot < cap) {
-                    const float no = -opac, nh = 0.5f * no;              // -opacity, -opacity / 2
-                    const float m0 = fmaf(cA, s[0], cB * s[1]), m1 = fmaf(cB, s[0], cC * s[1]);   // conic . first moments
-                    grec_a[2 * (size_t)rslot] = make_float4(no * ddelx_dx * m0, no * ddely_dy * m1, nh * s[2], nh * s[3]);
-                    grec_a[2 * (size_t)rslot + 1] = make_float4(nh * s[4], s[5], s[6], s[7]);
-                    grec_b[rslot] = s[8];
-                    if (AUX) ax.dz[rslot] = s[9];
-                }
-            }
-            __syncthreads();
         }
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_wave_barrier();
+        // ---- store the record (the lane that staged the entry): every entry of the segment gets one, zero where nothing was filed
+        const float4 cn = sR[wave][lane][3];
+        const uint32_t rslot = lane < cnt ? __float_as_uint(cn.w) : 0xffffffffu;
+        if (rslot < cap) {
+            float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0;
+            float r2 = 0.0f, r3 = 0.0f;
+            if ((filed >> lane) & 1ull) {                         // (an entry nobody filed has no staged record either)
+                float s[9 + AUX];
+#pragma unroll
+                for (int q = 0; q < 9 + AUX; q++) s[q] = sG[wave][lane][q];
+                const float no = -sR[wave][lane][1].y, nh = 0.5f * no;              // -opacity, -opacity / 2
+                const float m0 = fmaf(cn.x, s[0], cn.y * s[1]), m1 = fmaf(cn.y, s[0], cn.z * s[1]);   // conic . first moments
+                r0 = make_float4(no * ddelx_dx * m0, no * ddely_dy * m1, nh * s[2], nh * s[3]);
+                r1 = make_float4(nh * s[4], s[5], s[6], s[7]);
+                r2 = s[8];
+                if (AUX) r3 = s[9];
+            }
+            grec_a[2 * (size_t)rslot] = r0;
+            grec_a[2 * (size_t)rslot + 1] = r1;
+            grec_b[rslot] = r2;
+            if (AUX) ax.dz[rslot] = r3;
+        }
+        __builtin_amdgcn_wave_barrier();
     }
 }
+
+#undef SG_BWD_QUAD
+#undef SG_BWD_ACC
 
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6)))
 #if SG_BWD_AUX
