@@ -5,7 +5,11 @@
 //
 // Both kernels are VALU-issue bound (not HBM): ~2e8 pixel x Gaussian evaluations per direction at
 // cfg3.  wave64 design:
-//  * One 256-thread workgroup per 16x16 tile; wave w owns the 8x8 pixel QUADRANT w (lane = pixel).
+//  * Few-tile frames and single-frame launches (sg_render_fwd_body): one 256-thread workgroup per 16x16 tile; wave w owns the 8x8
+//    pixel QUADRANT w (lane = pixel).  K-frame launches of many tiles (sg_render_fwd.inc): ONE WAVE per tile, four tiles per
+//    workgroup, a lane owns one pixel of each quadrant; the wave sorts, stages (64 entries per batch) and walks its tile alone --
+//    an entry's record is read once, its mask bits select the quadrants under wave-uniform branches, no workgroup barrier.  The
+//    bullets below describe what both forms compute; the bits they leave are the same.
 //  * The tile's depth-sorted list is staged cooperatively through LDS (three aligned 16-B gathers out of ONE 64-B record per
 //    entry, one entry per thread).  While staging, each thread computes for ITS entry which quadrants the
 //    alpha >= 1/255 ellipse can reach (exact ellipse-vs-rectangle test with safety margins); every wave
@@ -378,7 +382,11 @@ __device__ __forceinline__ void sg_render_fwd_body(SG_FWD_PARAMS, SgAuxFwd ax = 
     }
 }
 
-// The plain loop at eight waves per SIMD: frames of many tiles (cfg3: 8 160 tiles, lists of ~100 entries, every SIMD busy).
+#include "sg_render_fwd.inc"
+
+// The plain loop at eight waves per SIMD: ONE frame of many tiles per launch (cfg3: 8 160 tiles, lists of ~100 entries, every SIMD busy).
+// (On the cooperative body, deliberately: with one frame on the chip the tile-wave body is 4 us slower, 69.7 -> 73.7 us at cfg3 -- the
+// longest tiles are walked by one wave instead of four and nothing else is left to run beside them; LAB.md, "Dense forward composite".)
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
 sg_render_fwd_kernel(SG_FWD_PARAMS) { sg_render_fwd_body<false, false>(SG_FWD_ARGS); }
 // The pipelined loop: ONE frame of few tiles with lists of thousands of entries (an avatar in front of a background: T <= 4096, the
@@ -398,8 +406,11 @@ sg_render_fwd_deep_aux_kernel(SG_FWD_PARAMS, SgAuxFwd ax) { sg_render_fwd_body<t
 // the 8 frames of an avatar step, same box).  The single-frame kernels above are the round-3 kernels, untouched: the offsets'
 // scalar registers and the weight branch cost the cfg3 forward 1.9 of its 71 us (same-box A/B against the round-3 tree).
 // (gridDim.x is a multiple of 8, so blockIdx.x % 8 is the XCD of a workgroup in every frame: sg_tile_of_block.)
+// Frames of many tiles (WEIGHTS = false): the tile-wave body of sg_render_fwd.inc, a wave per tile and four tiles per workgroup -- with
+// K frames on the chip there is always another tile to run beside a long one.  58 VGPRs (63 with the maps), no scratch, eight waves per
+// SIMD; the register budget is asked for at seven, where hipcc also keeps every scalar in a register (at (8, 8) it spills four).
 template <bool WEIGHTS>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WEIGHTS ? 8 : 7, 8)))
 sg_render_fwd_frames_kernel(SgBatch bt, SG_FWD_PARAMS)
 {
     const size_t fb = (size_t)blockIdx.y * bt.bin, fg = (size_t)blockIdx.y * bt.geom, fi = (size_t)blockIdx.y * bt.img;
@@ -410,13 +421,14 @@ sg_render_fwd_frames_kernel(SgBatch bt, SG_FWD_PARAMS)
     recA = sg_at(recA, fg); recB = sg_at(recB, fg); recC = sg_at(recC, fg);
     final_T = sg_at(final_T, fi); n_contrib = sg_at(n_contrib, fi); ckpt = sg_at(ckpt, fi);
     out_color += (size_t)blockIdx.y * bt.image;
-    sg_render_fwd_body<false, WEIGHTS>(SG_FWD_ARGS);
+    if constexpr (WEIGHTS) sg_render_fwd_body<false, true>(SG_FWD_ARGS);
+    else sg_render_fwd_tile_wave<false>(SG_FWD_ARGS);
 }
 // The kernel above with the depth / alpha maps: K-frame calls of sg_skinned_forward_frames_aux (and its THROUGHPUT frames, K = 1
 // included).  A separate symbol, so that the plain frames kernel keeps its instructions; the frame's z is in its geometry workspace,
 // its D checkpoints in its aux workspace (+ frame x ax.ws), its maps at + frame x H W.
 template <bool WEIGHTS>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WEIGHTS ? 8 : 7, 8)))
 sg_render_fwd_frames_aux_kernel(SgBatch bt, SG_FWD_PARAMS, SgAuxFwd ax)
 {
     const size_t fb = (size_t)blockIdx.y * bt.bin, fg = (size_t)blockIdx.y * bt.geom, fi = (size_t)blockIdx.y * bt.img;
@@ -430,7 +442,8 @@ sg_render_fwd_frames_aux_kernel(SgBatch bt, SG_FWD_PARAMS, SgAuxFwd ax)
     const size_t fm = (size_t)blockIdx.y * ax.map;
     ax.depth = sg_at(ax.depth, fg); ax.ckD = sg_at(ax.ckD, (size_t)blockIdx.y * ax.ws);
     ax.out_depth += fm; ax.out_alpha += fm;
-    sg_render_fwd_body<false, WEIGHTS, true>(SG_FWD_ARGS, ax);
+    if constexpr (WEIGHTS) sg_render_fwd_body<false, true, true>(SG_FWD_ARGS, ax);
+    else sg_render_fwd_tile_wave<true>(SG_FWD_ARGS, ax);
 }
 
 static inline int sg_render_blocks(int T) { return ((T + 8 * SG_XCD_RUN - 1) / (8 * SG_XCD_RUN)) * (8 * SG_XCD_RUN); }
@@ -441,6 +454,7 @@ void sg_launch_render_fwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, 
     static_assert(SG_FB == SG_SEG, "forward batches are the checkpoint granularity");
     const int T = c.gx * c.gy;
     const int grid = sg_render_blocks(T);
+    const int grid4 = sg_render_blocks((T + 3) / 4);               // the tile-wave kernels: four tiles per workgroup
     const unsigned K = (unsigned)bt.K;
     const bool few = sg_lds_hist(c.gx, c.gy);
     uint64_t *pk = write_keys ? b.point_keys : (uint64_t *)nullptr;
@@ -453,7 +467,7 @@ void sg_launch_render_fwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, 
     if (ax && (K > 1 || (few && (c.flags & SG_FLAG_THROUGHPUT)))) {
         // depth / alpha maps of K frames, or of a few-tile frame that shares the chip: the frames kernel's regime, as below
         if (few) hipLaunchKernelGGL(sg_render_fwd_frames_aux_kernel<true>, dim3(grid, K), dim3(256), 0, st, bt, SG_RF_ARGS(grid), *ax);
-        else hipLaunchKernelGGL(sg_render_fwd_frames_aux_kernel<false>, dim3(grid, K), dim3(256), 0, st, bt, SG_RF_ARGS(grid), *ax);
+        else hipLaunchKernelGGL(sg_render_fwd_frames_aux_kernel<false>, dim3(grid4, K), dim3(256), 0, st, bt, SG_RF_ARGS(grid4), *ax);
     } else if (ax) {
         // depth / alpha maps of one frame: the single-frame kernels' regimes (the single-frame entry points refuse SG_FLAG_THROUGHPUT)
         if (few) {
@@ -464,7 +478,7 @@ void sg_launch_render_fwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, 
     } else if (K > 1 || (few && (c.flags & SG_FLAG_THROUGHPUT))) {
         // K frames per launch, or a few-tile frame that shares the chip with other views: the plain loop (see the kernel)
         if (few) hipLaunchKernelGGL(sg_render_fwd_frames_kernel<true>, dim3(grid, K), dim3(256), 0, st, bt, SG_RF_ARGS(grid));
-        else hipLaunchKernelGGL(sg_render_fwd_frames_kernel<false>, dim3(grid, K), dim3(256), 0, st, bt, SG_RF_ARGS(grid));
+        else hipLaunchKernelGGL(sg_render_fwd_frames_kernel<false>, dim3(grid4, K), dim3(256), 0, st, bt, SG_RF_ARGS(grid4));
     } else if (few) {
         // ONE few-tile frame alone on the chip: the deep kernel.  Upper bound of its extra blocks: quadrants 1..3 of every long
         // tile (most exit at once)

@@ -24,6 +24,47 @@ __device__ __forceinline__ void sg_bitonic_wave(uint64_t *__restrict__ s, int n2
         }
 }
 
+// One WAVE sorts the n <= 512 keys at `src` into s[0, n) (LDS of its own, 512 entries) -- no workgroup barriers; n is wave-uniform.
+//  * n <= 128: the rank sort below on one wave.  A lane counts for its (up to) two keys, lane and lane + 64, out of the same
+//    broadcast reads; the unsorted copy lives behind the sorted one (s + SG_RANKSORT_MAX);
+//  * beyond: the one-wave bitonic network.
+__device__ __forceinline__ void sg_sort_short_list_wave(const uint64_t *__restrict__ src, int n, uint64_t *__restrict__ s, int lane)
+{
+    if (n <= SG_RANKSORT_MAX) {
+        uint64_t *tmp = s + SG_RANKSORT_MAX;
+        uint64_t key0 = 0, key1 = 0;
+        if (lane < n) { key0 = src[lane]; tmp[lane] = key0; }
+        if (lane + 64 < n) { key1 = src[lane + 64]; tmp[lane + 64] = key1; }
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_wave_barrier();
+        int rank0 = 0, rank1 = 0, j = 0;
+        if (n <= 64) {
+            for (; j + 2 <= n; j += 2) {
+                const ulonglong2 kk = *(const ulonglong2 *)(tmp + j);          // one 16-B broadcast read, two keys
+                rank0 += (kk.x < key0) + (kk.y < key0);
+            }
+            if (j < n) rank0 += tmp[j] < key0;
+        } else {
+            for (; j + 2 <= n; j += 2) {
+                const ulonglong2 kk = *(const ulonglong2 *)(tmp + j);
+                rank0 += (kk.x < key0) + (kk.y < key0);
+                rank1 += (kk.x < key1) + (kk.y < key1);
+            }
+            if (j < n) { const uint64_t k = tmp[j]; rank0 += k < key0; rank1 += k < key1; }
+        }
+        if (lane < n) s[rank0] = key0;
+        if (lane + 64 < n) s[rank1] = key1;
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_wave_barrier();
+        return;
+    }
+    int n2 = 1; while (n2 < n) n2 <<= 1;
+    for (int i = lane; i < n2; i += 64) s[i] = i < n ? src[i] : ~0ull;
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_wave_barrier();
+    sg_bitonic_wave(s, n2, lane);
+}
+
 // A 256-thread workgroup sorts the n <= SG_WSORT_MAX keys at `src` into s[0, n) (LDS, >= SG_WSORT_MAX entries;
 // `tmp`: another SG_RANKSORT_MAX entries).  Contains workgroup barriers: every thread must call it; n is uniform.
 //  * n <= 128: rank sort.  Thread e < n counts the keys smaller than its own by walking the (broadcast-read) list: n
