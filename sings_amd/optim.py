@@ -83,6 +83,23 @@ def build_tables(addresses, numels, groups, chunk=None):
     return seg, np.ascontiguousarray(chunks.astype(np.int32))
 
 
+# ---- the row map of a change of the set ------------------------------------------------------------------------------------------
+def take_rows(t, src):
+    """``t`` [n, ...] through the row map ``src`` (int64 [n_new], entries -1 .. n-1) -> a fresh contiguous [n_new, ...] tensor: row i is
+    a bit copy of ``t[src[i]]``, or +0.0 where ``src[i] == -1`` (a row that starts its life).  Every change of the set of Gaussians is
+    this one operation on whatever is kept per row: clone + prune, rows appended by a subdivision, a plain ``t[keep]``.  CPU or GPU
+    tensors; an index outside -1 .. n-1 is a ValueError (a host check: this runs between steps)."""
+    n = int(t.shape[0])
+    if src.dtype != torch.int64 or src.dim() != 1:
+        raise ValueError(f"take_rows: src must be a 1-D int64 tensor (got {src.dtype}, {src.dim()}-D)")
+    if src.numel() and (int(src.min()) < -1 or int(src.max()) >= n):
+        raise ValueError(f"take_rows: src has entries outside -1 .. {n - 1}")
+    out = torch.zeros((int(src.shape[0]),) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    kept = torch.nonzero(src >= 0).reshape(-1)
+    out.index_copy_(0, kept, t.index_select(0, src[kept]))
+    return out
+
+
 class FusedAdam:
     """``torch.optim.Adam`` (no weight decay, no amsgrad, not maximize) for GPU fp32 parameters whose gradients live in a flat arena.
 
@@ -267,31 +284,31 @@ class FusedAdam:
                     g[key] = saved[key]
 
     # ---- a densify / prune of one parameter's rows
-    def append_rows(self, old, new):
-        """Parameter ``old`` [n, ...] becomes ``new`` [n + k, ...] whose first n rows are the old ones (a subdivision): the old rows'
-        moments are kept, the k new rows start at zero.  ``remap_rows`` with k appended rows and nothing dropped."""
-        k = int(new.shape[0]) - int(old.shape[0])
-        if k < 0:
-            raise ValueError(f"FusedAdam.append_rows: `new` has {int(new.shape[0])} rows, `old` {int(old.shape[0])}")
-        self.remap_rows(old, new, torch.zeros(k, dtype=torch.int64, device=self.dev),
-                        torch.ones(int(new.shape[0]), dtype=torch.bool, device=self.dev))
-
     def remap_rows(self, old, new, clone_mask, keep_mask):
         """Parameter ``old`` becomes ``new`` = ``cat([old, old[clone_mask]])[keep_mask]``: its moments become
         ``cat([m, zeros_like(m[clone_mask])])[keep_mask]`` (cat_tensors_to_optimizer / _prune_optimizer), every other parameter's are
+        copied, the step counts stay.  The arena is unbound: ``bind_arena`` with the new parameters' arena before the next step.
+        (``reindex_rows`` with the masks written as a row map.)"""
+        n, n_clones = int(old.shape[0]), int(old.detach()[clone_mask].shape[0])
+        src = torch.cat([torch.arange(n, device=self.dev), torch.full((n_clones,), -1, dtype=torch.int64, device=self.dev)])[keep_mask]
+        self.reindex_rows(old, new, src)
+
+    def reindex_rows(self, old, new, src):
+        """Parameter ``old`` [n, ...] becomes ``new`` [n_new, ...] whose row i is old row ``src[i]`` or, where ``src[i] == -1``, a new
+        one: both moments go through ``take_rows`` (kept rows bit for bit, zeros for the new ones), every other parameter's are
         copied, the step counts stay.  The arena is unbound: ``bind_arena`` with the new parameters' arena before the next step."""
         params = self._params()
         at = [i for i, p in enumerate(params) if p is old]
         if len(at) != 1:
-            raise ValueError("FusedAdam.remap_rows: `old` is not a registered parameter")
+            raise ValueError("FusedAdam.reindex_rows: `old` is not a registered parameter")
         at = at[0]
         if not new.is_cuda or new.dtype != torch.float32:
-            raise RuntimeError("FusedAdam.remap_rows: `new` must be a float32 GPU tensor (no CPU fallback)")
+            raise RuntimeError("FusedAdam.reindex_rows: `new` must be a float32 GPU tensor (no CPU fallback)")
         with torch.no_grad():
             old_m, old_v = self._moment_views(self.exp_avg), self._moment_views(self.exp_avg_sq)
-            new_mv = [torch.cat([x[at], torch.zeros_like(x[at][clone_mask])])[keep_mask] for x in (old_m, old_v)]
+            new_mv = [take_rows(x[at], src) for x in (old_m, old_v)]
             if tuple(new_mv[0].shape) != tuple(new.shape):
-                raise ValueError(f"FusedAdam.remap_rows: the masks give {tuple(new_mv[0].shape)}, `new` is {tuple(new.shape)}")
+                raise ValueError(f"FusedAdam.reindex_rows: `src` gives {tuple(new_mv[0].shape)}, `new` is {tuple(new.shape)}")
             k = 0
             for g in self.param_groups:
                 for i in range(len(g["params"])):

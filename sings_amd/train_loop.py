@@ -22,8 +22,8 @@ A topology change (or a new SH degree) invalidates everything that was sized or 
     the captured HIP graph          ``CapturedStep.replay`` raises until ``AvatarTrainer`` has captured the step again
     the gradient arena              ``decode.arena_sync`` raises for a stale registration; the trainer registers the new parameters
     the pair-capacity hint          re-measured with synchronous steps before the overflow check is deferred again
-    Adam's moments, the statistics  re-indexed (kept rows, zeros for the clones) / reset, as the reference does (``FusedAdam.remap_rows``
-                                    rebuilds its flat moment buffers and tables for the new sizes)
+    Adam's moments, the statistics  ONE row map ``src`` per change (``_replace_set``): new row i takes its moments (``prune_and_simplify``: its
+                                    statistics too) from old row ``src[i]`` or, at -1, starts at zero (``optim.take_rows``), as the reference does
     the frame-parallel collective   sized by the new flat buffer; the statistics are reduced (sum, sum, max) BEFORE the decision, so every
                                     rank takes the same one (``densify_decision`` is a pure function of the reduced statistics)
 
@@ -35,7 +35,7 @@ import torch
 from . import decode as _dec
 from . import overflow
 from . import topology as _topo
-from .optim import FusedAdam
+from .optim import FusedAdam, take_rows
 from .train_step import capture_step
 
 
@@ -99,6 +99,7 @@ class AvatarTrainer:
     ``densify_and_subdivide`` and ``prune_and_simplify`` need and keep up to date.  With ``mesh=None`` nothing changes."""
 
     POSE_GROUPS = ("global_orient", "body_pose", "transl")
+    STATS = ("xyz_gradient_accum", "denom", "max_radii2D")      # the module's densification statistics, one row per Gaussian
 
     def __init__(self, module, settings_fn, bg_color, lrs, smpl_scale=None, transl=None, use_graph=False, fp=None,
                  sh_degree=0, max_sh_degree=3, betas=(0.9, 0.999), eps=1e-15, optimizer="torch", lr_schedules=None, poses=None,
@@ -194,6 +195,21 @@ class AvatarTrainer:
             self.opt.apply()                                     # (the Adam launch: part of the body, and so of a captured step)
         return {k: v.detach().reshape(()).clone() for k, v in ld.items()}
 
+    def _capture(self):
+        overflow.set_deferred_overflow_check(True, capacity_pairs=overflow.capacity_pairs(self.dev))
+        # (the capture's warm-up runs execute the body -- statistics included -- without being steps: put the statistics back;
+        # with the fused optimiser in the body they update parameters and moments too: those go back as well)
+        live = [self.m.xyz_gradient_accum, self.m.denom, self.m.max_radii2D]
+        if self.fused and self.fp is None:
+            live += [p.detach() for p in self.params] + [self.opt.exp_avg, self.opt.exp_avg_sq]
+        keep, steps = [x.clone() for x in live], (list(self.opt.steps) if self.fused else None)
+        self.captured = CapturedStep(self.m, self._body, warmup=2, device=self.dev)
+        for dst, src in zip(live, keep):
+            dst.copy_(src)
+        if self.fused:
+            self.opt.steps[:] = steps
+        overflow.check_deferred_overflow(self.dev)
+
     def step(self, A, gt_rgb, mask, lpips_origins=None, lpips_bg=None):
         """``lpips_origins`` / ``lpips_bg``: the step's LPIPS patch corners and random background (``AvatarStep.forward``), copied
         in like the frame's inputs, so that a replayed graph reads this step's patches."""
@@ -243,19 +259,7 @@ class AvatarTrainer:
             self.opt.advance()                                   # host half: this step's rows are on their way before the body runs
         if self.use_graph and self._sizing == 0:
             if self.captured is None:
-                overflow.set_deferred_overflow_check(True, capacity_pairs=overflow.capacity_pairs(self.dev))
-                # (the capture's warm-up runs execute the body -- statistics included -- without being steps: put the statistics back;
-                # with the fused optimiser in the body they update parameters and moments too: those go back as well)
-                live = [self.m.xyz_gradient_accum, self.m.denom, self.m.max_radii2D]
-                if self.fused and self.fp is None:
-                    live += [p.detach() for p in self.params] + [self.opt.exp_avg, self.opt.exp_avg_sq]
-                keep, steps = [x.clone() for x in live], (list(self.opt.steps) if self.fused else None)
-                self.captured = CapturedStep(self.m, self._body, warmup=2, device=self.dev)
-                for dst, src in zip(live, keep):
-                    dst.copy_(src)
-                if self.fused:
-                    self.opt.steps[:] = steps
-                overflow.check_deferred_overflow(self.dev)
+                self._capture()
             ld = self.captured.replay()
         else:
             ld = self._body()                                    # eager (and the synchronous sizing steps in front of a capture)
@@ -280,35 +284,61 @@ class AvatarTrainer:
             self.rs = self.settings_fn(self.sh_degree)
             self.captured = None
 
+    def _reduce_stats(self):
+        """With ``fp``: the statistics summed / maximised over the ranks, in place, so that every rank takes the same decision."""
+        if self.fp is not None:
+            self.fp.reduce_densification_stats(self.m.xyz_gradient_accum, self.m.denom, self.m.max_radii2D)
+
+    def _scales_canon(self, attrs):
+        """human_gs_out['scales_canon']: the decoded scales, times smpl_scale when the step has one (sings_hybrid.py:411-413, 455)."""
+        return attrs["scales"] if self.smpl_scale is None else attrs["scales"] * self.smpl_scale.reshape(1, -1)
+
+    def _reset_opacity(self):
+        if not getattr(self.m.appearance_dec, "fixed_opacity", False):
+            self.m.appearance_dec.reset_opacity(self.m.triplane(self.m.xyz))
+
+    @torch.no_grad()
+    def _replace_set(self, new_xyz, new_lbs_weights, src, scaling_multiplier=None, keep_stats=False, then=None):
+        """The ONE place that replaces the set of Gaussians.  ``src`` (int64 [N_new]) is the row map: new row i carries on from old row
+        ``src[i]``, or is new where ``src[i] == -1``.  Adam's moments go through ``take_rows`` (cat_tensors_to_optimizer /
+        _prune_optimizer: kept rows bit for bit, zeros for the new ones, the step counts stay); with ``keep_stats`` the statistics too,
+        otherwise they start at zero.  ``then()``: the caller's work on the new set (opacity reset) before the rebuild."""
+        m = self.m
+        group = next(g for g in self.opt.param_groups if g["name"] == "xyz")
+        old = group["params"][0]
+        state = None if self.fused else self.opt.state.pop(old, None)
+        stats = [take_rows(getattr(m, k), src) for k in self.STATS] if keep_stats else None
+        m.set_topology(new_xyz, new_lbs_weights, scaling_multiplier=scaling_multiplier)
+        if self.fused:
+            self.opt.reindex_rows(old, m.xyz, src)
+        elif state:                                              # (torch creates a parameter's state at its first step)
+            for k in ("exp_avg", "exp_avg_sq"):
+                state[k] = take_rows(state[k], src)
+            self.opt.state[m.xyz] = state
+        group["params"][0] = m.xyz
+        if then is not None:
+            then()
+        self._rebuild()
+        if keep_stats:                                           # (set_topology and the rebuild start the statistics at zero)
+            m.xyz_gradient_accum, m.denom, m.max_radii2D = stats
+
+    def _appended(self, n_old, n_new):                           # the row map of n_new new rows behind n_old kept ones
+        return torch.cat([torch.arange(n_old, device=self.dev), torch.full((n_new,), -1, dtype=torch.int64, device=self.dev)])
+
     def densify_and_prune(self, max_grad, scale_threshold, min_opacity, big_scale, decision=None):
         """Clone + prune from the accumulated (and, with ``fp``, reduced) statistics; -> (clone_mask, prune_mask, N_old, N_new).
         ``decision``: a (clone_mask, prune_mask) pair to apply instead (tests drive a reference with the decision of the run)."""
         m = self.m
-        if self.fp is not None:
-            self.fp.reduce_densification_stats(m.xyz_gradient_accum, m.denom, m.max_radii2D)
+        self._reduce_stats()
         with torch.no_grad():
             if decision is None:
-                attrs = _dec.decode_attributes(m.xyz, m.triplane, m.geometry_dec, m.appearance_dec, m.thickness_factor, m.scaling_multiplier)
+                attrs = m.decode()
                 decision = densify_decision(m.xyz_gradient_accum, m.denom, attrs["scales"], attrs["opacity"], max_grad, scale_threshold,
                                             min_opacity, big_scale)
             clone, prune = decision
-            n_old = int(m.xyz.shape[0])
-            keep = ~prune
-            # Adam moments: kept rows for the survivors, zeros for the clones (cat_tensors_to_optimizer, _prune_optimizer)
-            group = next(g for g in self.opt.param_groups if g["name"] == "xyz")
-            old = group["params"][0]
-            state = None if self.fused else self.opt.state.pop(old, None)
-            new_xyz = torch.cat([old.detach(), old.detach()[clone]])[keep].clone()
-            new_w = torch.cat([m.lbs_weights, m.lbs_weights[clone]])[keep].clone()
-            m.set_topology(new_xyz, new_w)
-            if self.fused:
-                self.opt.remap_rows(old, m.xyz, clone, keep)
-            group["params"][0] = m.xyz
-            if state is not None:
-                for k in ("exp_avg", "exp_avg_sq"):
-                    state[k] = torch.cat([state[k], torch.zeros_like(state[k][clone])])[keep].clone()
-                self.opt.state[m.xyz] = state
-        self._rebuild()
+            n_old, keep = int(m.xyz.shape[0]), ~prune
+            extended = lambda t: torch.cat([t, t[clone]])[keep].clone()       # (densification_postfix, then prune_points)
+            self._replace_set(extended(m.xyz.detach()), extended(m.lbs_weights), self._appended(n_old, int(clone.sum()))[keep])
         return clone, prune, n_old, int(m.xyz.shape[0])
 
     def densify_and_subdivide(self, grad_threshold, scale_threshold, max_screen_size=None, max_n_gs=None, exclude=(6, 7), decision=None):
@@ -325,49 +355,32 @@ class AvatarTrainer:
         if self.mesh is None:
             raise RuntimeError("AvatarTrainer.densify_and_subdivide needs mesh=MeshState(...)")
         m, mesh = self.m, self.mesh
-        if self.fp is not None:
-            self.fp.reduce_densification_stats(m.xyz_gradient_accum, m.denom, m.max_radii2D)
+        self._reduce_stats()
         with torch.no_grad():
-            decode = lambda: _dec.decode_attributes(m.xyz, m.triplane, m.geometry_dec, m.appearance_dec, m.thickness_factor,
-                                                    m.scaling_multiplier)
-            attrs = decode()
-            # human_gs_out['scales_canon']: the decoded scales, times smpl_scale when the step has one (sings_hybrid.py:411-413, 455)
-            scales_canon = attrs["scales"] if self.smpl_scale is None else attrs["scales"] * self.smpl_scale.reshape(1, -1)
+            attrs = m.decode()
+            scales_canon = self._scales_canon(attrs)
             if decision is None:
                 decision = _topo.subdivide_decision(m.xyz_gradient_accum, m.denom, scales_canon, m.max_radii2D, mesh.vertex_label,
                                                     mesh.faces, grad_threshold, scale_threshold, max_screen_size=max_screen_size,
                                                     max_n_gs=max_n_gs, exclude=exclude)
-            selected, faces_idx = decision
-            selected, faces_idx = selected.to(self.dev), faces_idx.to(self.dev)
-            n_old = int(m.xyz.shape[0])
-            scales = scales_canon[:, :1]
+            selected, faces_idx = (t.to(self.dev) for t in decision)
             sub_vertices, sub_faces, attr = _topo.subdivide_meshes(
-                attrs["xyz_canon"], mesh.faces, faces_idx,
-                {"vertex_label": mesh.vertex_label, "lbs_weights": m.lbs_weights, "scales": torch.clip(scales.mean(-1), max=0.008)})
-            n_new = int(sub_vertices.shape[0])
+                attrs["xyz_canon"], mesh.faces, faces_idx, {"vertex_label": mesh.vertex_label, "lbs_weights": m.lbs_weights,
+                                                            "scales": torch.clip(scales_canon[:, :1].mean(-1), max=0.008)})
+            n_old, n_new = int(m.xyz.shape[0]), int(sub_vertices.shape[0])
             # new multipliers: selected old rows to the mean scale, ones for the new rows (:1127-1131)
             sm = torch.cat([_topo.rescaled_multiplier(m.scaling_multiplier, scales_canon, selected),
                             torch.ones((n_new - n_old, 1), dtype=torch.float32, device=self.dev)])
-            group = next(g for g in self.opt.param_groups if g["name"] == "xyz")
-            old = group["params"][0]
-            state = None if self.fused else self.opt.state.pop(old, None)
-            m.set_topology(torch.cat([old.detach(), sub_vertices[n_old:]]), attr["lbs_weights"], scaling_multiplier=sm)
-            mesh.replace(sub_faces, attr["vertex_label"])
-            if self.fused:
-                self.opt.append_rows(old, m.xyz)
-            group["params"][0] = m.xyz
-            if state:
-                for k in ("exp_avg", "exp_avg_sq"):
-                    state[k] = torch.cat([state[k], torch.zeros((n_new - n_old, 3), dtype=state[k].dtype, device=self.dev)])
-                self.opt.state[m.xyz] = state
-            # post process (:1136-1147): opacity reset on the new set, then the new rows' decoded mean scale := the interpolated one
-            if not getattr(m.appearance_dec, "fixed_opacity", False):
-                m.appearance_dec.reset_opacity(m.triplane(m.xyz))
             interpolated = attr["scales"][n_old:]
-            new_scales = decode()["scales"][n_old:]
-            sm[n_old:] *= (interpolated / new_scales.mean(-1)).unsqueeze(1)
+
+            def post_process():                                  # (:1136-1147) on the new set, before the rebuild
+                self._reset_opacity()
+                sm[n_old:] *= (interpolated / m.decode()["scales"][n_old:].mean(-1)).unsqueeze(1)     # decoded mean scale := interpolated
+
+            mesh.replace(sub_faces, attr["vertex_label"])
+            self._replace_set(torch.cat([m.xyz.detach(), sub_vertices[n_old:]]), attr["lbs_weights"],
+                              self._appended(n_old, n_new - n_old), scaling_multiplier=sm, then=post_process)
             self.last_subdivision = {"interpolated_scales": interpolated, "n_old": n_old}
-        self._rebuild()
         return selected, faces_idx, n_old, n_new
 
     def prune_and_simplify(self, opacity_threshold, scale_threshold, dead_grad=0.0005, large_scale=0.01, prune_max_n_gs_once=5000,
@@ -388,54 +401,34 @@ class AvatarTrainer:
         if self.mesh is None:
             raise RuntimeError("AvatarTrainer.prune_and_simplify needs mesh=MeshState(...)")
         m, mesh = self.m, self.mesh
-        stats = ("xyz_gradient_accum", "denom", "max_radii2D")
-        own = None
-        if self.fp is not None:
-            own = [getattr(m, k).clone() for k in stats]
-            self.fp.reduce_densification_stats(m.xyz_gradient_accum, m.denom, m.max_radii2D)
+        own = [getattr(m, k).clone() for k in self.STATS] if self.fp is not None else None
+        self._reduce_stats()
         with torch.no_grad():
-            attrs = _dec.decode_attributes(m.xyz, m.triplane, m.geometry_dec, m.appearance_dec, m.thickness_factor, m.scaling_multiplier)
-            scales = attrs["scales"] if self.smpl_scale is None else attrs["scales"] * self.smpl_scale.reshape(1, -1)
+            attrs = m.decode()
             n_old = int(m.xyz.shape[0])
             if decision is None:
                 vert_mask, edges, reason = _topo.simplify_decision(
-                    m.xyz_gradient_accum, m.denom, attrs["opacity"], scales, mesh.vertex_label, mesh.faces, opacity_threshold,
-                    scale_threshold, dead_grad=dead_grad, large_scale=large_scale, prune_max_n_gs_once=prune_max_n_gs_once,
-                    min_n_gs=min_n_gs, exclude=exclude)
+                    m.xyz_gradient_accum, m.denom, attrs["opacity"], self._scales_canon(attrs), mesh.vertex_label, mesh.faces,
+                    opacity_threshold, scale_threshold, dead_grad=dead_grad, large_scale=large_scale,
+                    prune_max_n_gs_once=prune_max_n_gs_once, min_n_gs=min_n_gs, exclude=exclude)
             else:
-                vert_mask, edges = decision
-                vert_mask, edges = vert_mask.to(self.dev), edges.to(self.dev)
+                vert_mask, edges = (t.to(self.dev) for t in decision)
                 reason = None if int(edges.shape[0]) else "no_edges"
             result = None if reason else _topo.collapse_edges(attrs["xyz_canon"], m.lbs_weights, edges, mesh.faces, return_collapses=True)
             if own is not None:                                      # (the decision is taken: back to this rank's own sums)
-                for k, t in zip(stats, own):
+                for k, t in zip(self.STATS, own):
                     getattr(m, k).copy_(t)
             if result is None:
                 self.last_simplification = {"skipped": reason, "selected_edges": int(edges.shape[0])}
                 return vert_mask, torch.zeros(n_old, dtype=torch.bool, device=self.dev), n_old, n_old
             _, new_faces, _, prune, collapses = result
             keep = ~prune
-            kept_stats = [getattr(m, k)[keep].clone() for k in stats]
             sm = m.scaling_multiplier
             per_gaussian = torch.is_tensor(sm) and sm.dim() > 0 and sm.shape[0] == n_old and n_old != 1
-            group = next(g for g in self.opt.param_groups if g["name"] == "xyz")
-            old = group["params"][0]
-            state = None if self.fused else self.opt.state.pop(old, None)
-            m.set_topology(old.detach()[keep], m.lbs_weights[keep], scaling_multiplier=sm[keep].clone() if per_gaussian else None)
-            if self.fused:
-                self.opt.remap_rows(old, m.xyz, torch.zeros(n_old, dtype=torch.bool, device=self.dev), keep)
-            group["params"][0] = m.xyz
-            if state:
-                for k in ("exp_avg", "exp_avg_sq"):
-                    state[k] = state[k][keep].clone()
-                self.opt.state[m.xyz] = state
             mesh.prune(new_faces, keep)
-            if not getattr(m.appearance_dec, "fixed_opacity", False):
-                m.appearance_dec.reset_opacity(m.triplane(m.xyz))
+            self._replace_set(m.xyz.detach()[keep], m.lbs_weights[keep], torch.arange(n_old, device=self.dev)[keep],
+                              scaling_multiplier=sm[keep].clone() if per_gaussian else None, keep_stats=True, then=self._reset_opacity)
             n_new = int(m.xyz.shape[0])
             self.last_simplification = {"skipped": None, "selected_edges": int(edges.shape[0]), "collapses": collapses, "n_old": n_old,
                                         "n_new": n_new}
-        self._rebuild()
-        # (set_topology and the rebuild start the statistics at zero, as after clone + prune: the survivors' rows go back)
-        m.xyz_gradient_accum, m.denom, m.max_radii2D = kept_stats
         return vert_mask, prune, n_old, n_new

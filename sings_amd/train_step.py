@@ -48,6 +48,16 @@ class _AddScalars(torch.autograd.Function):
         return g, g
 
 
+def _sum_terms(loss_dict):
+    """The sum of a step's photometric terms: l1 + ssim first, under ONE node that hands both the same upstream tensor (the loss
+    kernel's backward is then a multiplication: sings_amd.photo_loss), the rest added behind."""
+    vals = [v.reshape(()) for v in loss_dict.values()]
+    total = _AddScalars.apply(vals[0], vals[1]) if len(vals) >= 2 else vals[0]
+    for v in vals[2:]:
+        total = total + v
+    return total
+
+
 class _SumFrames(torch.autograd.Function):
     """(l1[K].sum(), ssim[K].sum()) in one node whose backward hands BOTH per-frame terms the SAME upstream tensor when the two sums got
     the same one (they do under ``_AddScalars``): the photometric loss then returns the gradient it computed in the forward, times
@@ -214,8 +224,8 @@ class AvatarStep(torch.nn.Module):
         Inside a HIP-graph capture: use ``sings_amd.train_step.capture_step`` (it refuses, with an error instead of a dead
         process, a captured callable that returns tensors still carrying their autograd graph), and keep the regularisers on
         the ONE side stream this module owns (``GaussiansEdgeLoss.finish`` refuses any other stream while capturing)."""
-        has_reg = self.l2_norm is not None or (self.gaussian_connect is not None and self.gaussian_connect_w > 0)
         has_knn = self.gaussian_connect is not None and self.gaussian_connect_w > 0
+        has_reg = self.l2_norm is not None or has_knn
         overlap = has_reg and self.overlap_regularisers and self.xyz.is_cuda
         defer = (overlap and self.defer_regulariser_join and torch.is_grad_enabled() and has_knn
                  and hasattr(self.gaussian_connect, "prepare"))
@@ -228,8 +238,7 @@ class AvatarStep(torch.nn.Module):
         _dec._TP["late"] = bool(defer)
         del _dec._TP_PENDING[:]                                  # (a preparation left behind by a forward that raised)
         try:
-            attrs = decode_attributes(self.xyz, self.triplane, self.geometry_dec, self.appearance_dec, self.thickness_factor,
-                                      self.scaling_multiplier, geometry_hook=hook)
+            attrs = self.decode(geometry_hook=hook)
         finally:
             _dec._TP["late"] = late_prev
         # Two roots (defer): the render and the regularisers read DETACHED views of the decoded attributes (`use`), so that the
@@ -239,22 +248,16 @@ class AvatarStep(torch.nn.Module):
         use = attrs
         if defer:
             use = {k: (v.detach().requires_grad_(v.requires_grad) if torch.is_tensor(v) else v) for k, v in attrs.items()}
-        # anisotropic: the decoder's 6-D rotations go to the fused kernels as they are (rotation_6d_to_matrix of
-        # sings_hybrid.py:356-357 runs inside them); isotropic: None
-        rot = use["rot6d_canon"]
         reg = {}
 
-        def l2():
-            if self.l2_norm is not None:
-                reg["l2"] = self.l2_norm({"xyz_offsets": use["xyz_offsets"], "scales": use["scales"], "opacity": use["opacity"]})
-
         def regularisers():
-            l2()
+            if self.l2_norm is not None:
+                reg["l2"] = self._l2(use)
             if has_knn:
                 reg["gaussian_connect_loss"] = self.gaussian_connect_w * self.gaussian_connect(
                     {"xyz_canon": use["xyz_canon"], "scales": use["scales"]})
 
-        side = None
+        side = cur = decoded = rendered = None
         if overlap:
             dev = attrs["xyz_canon"].device
             if self._side is None or self._side.device != dev:
@@ -273,16 +276,13 @@ class AvatarStep(torch.nn.Module):
         if self.xyz_gradient_accum is not None and torch.is_grad_enabled():
             shape = (int(A_cano2pose.shape[0]), int(self.xyz.shape[0]), 3) if frames else (int(self.xyz.shape[0]), 3)
             m2d = torch.zeros(shape, dtype=torch.float32, device=self.xyz.device, requires_grad=True)
-        if frames:
-            # one decode, K frames rendered and differentiated in one call per direction: the attribute decode -- 3/4 of a
-            # one-frame step -- is paid once per step, not once per frame (gt_rgb / mask: [K,...] or one for all frames)
-            color, radii = rasterize_skinned_frames(use["xyz_canon"], rot, use["scales"], use["opacity"], use["shs"],
-                                                    self.lbs_weights, A_cano2pose, raster_settings, smpl_scale=smpl_scale,
-                                                    transl=transl, means2D=m2d)
-        else:
-            color, radii = rasterize_skinned_gaussians(use["xyz_canon"], rot, use["scales"], use["opacity"], use["shs"],
-                                                       self.lbs_weights, A_cano2pose, raster_settings, smpl_scale=smpl_scale,
-                                                       transl=transl, means2D=m2d)
+        # frames: one decode, K frames rendered and differentiated in one call per direction: the attribute decode -- 3/4 of a
+        # one-frame step -- is paid once per step, not once per frame (gt_rgb / mask: [K,...] or one for all frames).
+        # anisotropic: the decoder's 6-D rotations go to the fused kernels as they are (rotation_6d_to_matrix of
+        # sings_hybrid.py:356-357 runs inside them); isotropic: None
+        rasterize = rasterize_skinned_frames if frames else rasterize_skinned_gaussians
+        color, radii = rasterize(use["xyz_canon"], use["rot6d_canon"], use["scales"], use["opacity"], use["shs"], self.lbs_weights,
+                                 A_cano2pose, raster_settings, smpl_scale=smpl_scale, transl=transl, means2D=m2d)
         if defer:
             rendered = torch.cuda.Event()
             rendered.record(cur)
@@ -304,67 +304,73 @@ class AvatarStep(torch.nn.Module):
             if frames:
                 extras["per_frame"] = dict(extras["per_frame"], lpips_patch=lp)
         if defer:
-            # two roots, no join: the regularisers' gradients are waited for where they are consumed (AvatarStep.backward)
-            vals = [v.reshape(()) for v in loss_dict.values()]
-            photo_root = _AddScalars.apply(vals[0], vals[1]) if len(vals) >= 2 else torch.stack(vals).sum()
-            for v in vals[2:]:
-                photo_root = photo_root + v
-            # the regularisers, ISSUED last (the main chain keeps its queue in the graph executor, sings_amd/decode.py "capture
-            # order") but waiting only for what they read: L2Norm and the k-NN grids for the decode, the k-NN QUERY -- 9 waves per
-            # SIMD on every CU for 0.23 ms -- for the raster forward.  (Measured, profiles/r05_graph_queues.log: the executor starts
-            # a second queue's chain 60-160 us after its dependency is met, so part of the query is still exposed behind the
-            # backward composite; issued FIRST, as in round 4, the chain starts at once and the raster forward is what waits.)
-            # No autograd on the side stream: both regularisers' kernels compute their gradients with the value (`last_grads`), and the
-            # engine's stream bookkeeping around an autograd call put a wait for THIS stream's newest kernel in front of them.
-            side.wait_event(decoded)
-            l2_grads = None
-            det = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in use.items()}
-            with torch.cuda.stream(side):
-                if self.l2_norm is not None:
-                    # in front of the k-NN query on this stream: the appearance decoder's backward needs the opacity term
-                    reg["l2"] = self.l2_norm({"xyz_offsets": det["xyz_offsets"], "scales": det["scales"], "opacity": det["opacity"]})
-                    l2_grads = (dict(self.l2_norm.last_grads), torch.cuda.Event())
-                    l2_grads[1].record(side)
-                edge = self.gaussian_connect.prepare({"xyz_canon": det["xyz_canon"], "scales": det["scales"]})
-                side.wait_event(rendered)
-                try:
-                    self.gaussian_connect.finish()
-                except BaseException:
-                    self.gaussian_connect.abort()
-                    raise
-                g_edge = self.gaussian_connect.last_grads["scales"]
-                if self.gaussian_connect_w != 1.0:
-                    edge, g_edge = self.gaussian_connect_w * edge, self.gaussian_connect_w * g_edge
-                reg["gaussian_connect_loss"] = edge
-                if use["scales"].requires_grad:
-                    inject["scales"] = g_edge                    # reaches the decoders' backward through the _Inject node
-                reg_root = edge.reshape(())
-                inject["ready"] = torch.cuda.Event()
-                inject["ready"].record(side)
-                _dec.flush_triplane_prepare(side)                # (same stream, behind the query: executed in this order)
-            loss_dict.update(reg)
-            extras["loss_roots"] = (photo_root, reg_root)
-            extras["staged"] = (attrs, use, inject, l2_grads)
+            self._finish_deferred(loss_dict, extras, attrs, use, inject, side, decoded, rendered)
             # a pose that is itself learned (sings_amd.pose.PoseTable): the staged backward hands its gradients on
             extras["pose_inputs"] = [t for t in (A_cano2pose, transl) if torch.is_tensor(t) and t.requires_grad]
-            return None, loss_dict, {"render_raw": color, "radii": radii, "attrs": attrs, "viewspace_points": m2d, **extras}
+        loss = None if defer else self._finish_joined(loss_dict, reg, regularisers, side)
+        return loss, loss_dict, {"render_raw": color, "radii": radii, "attrs": attrs, "viewspace_points": m2d, **extras}
+
+    def decode(self, geometry_hook=None):
+        """The decoded attributes of the current set (``decode.decode_attributes`` of this module's anchors, tri-plane and decoders)."""
+        return decode_attributes(self.xyz, self.triplane, self.geometry_dec, self.appearance_dec, self.thickness_factor,
+                                 self.scaling_multiplier, geometry_hook=geometry_hook)
+
+    def _l2(self, a):                                            # (`a`: the decoded attributes, or their detached copy)
+        return self.l2_norm({k: a[k] for k in ("xyz_offsets", "scales", "opacity")})
+
+    def _finish_deferred(self, loss_dict, extras, attrs, use, inject, side, decoded, rendered):
+        """The two-roots tail of ``forward``, no join: the regularisers' gradients are waited for where they are consumed
+        (``AvatarStep.backward``).  ``decoded`` / ``rendered``: the main stream's events behind the decode and the raster forward."""
+        photo_root = _sum_terms(loss_dict)
+        # the regularisers, ISSUED last (the main chain keeps its queue in the graph executor, sings_amd/decode.py "capture
+        # order") but waiting only for what they read: L2Norm and the k-NN grids for the decode, the k-NN QUERY -- 9 waves per
+        # SIMD on every CU for 0.23 ms -- for the raster forward.  (Measured, profiles/r05_graph_queues.log: the executor starts
+        # a second queue's chain 60-160 us after its dependency is met, so part of the query is still exposed behind the
+        # backward composite; issued FIRST, as in round 4, the chain starts at once and the raster forward is what waits.)
+        # No autograd on the side stream: both regularisers' kernels compute their gradients with the value (`last_grads`), and the
+        # engine's stream bookkeeping around an autograd call put a wait for THIS stream's newest kernel in front of them.
+        side.wait_event(decoded)
+        reg, l2_grads = {}, None
+        det = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in use.items()}
+        with torch.cuda.stream(side):
+            if self.l2_norm is not None:
+                # in front of the k-NN query on this stream: the appearance decoder's backward needs the opacity term
+                reg["l2"] = self._l2(det)
+                l2_grads = (dict(self.l2_norm.last_grads), torch.cuda.Event())
+                l2_grads[1].record(side)
+            edge = self.gaussian_connect.prepare({"xyz_canon": det["xyz_canon"], "scales": det["scales"]})
+            side.wait_event(rendered)
+            try:
+                self.gaussian_connect.finish()
+            except BaseException:
+                self.gaussian_connect.abort()
+                raise
+            g_edge = self.gaussian_connect.last_grads["scales"]
+            if self.gaussian_connect_w != 1.0:
+                edge, g_edge = self.gaussian_connect_w * edge, self.gaussian_connect_w * g_edge
+            reg["gaussian_connect_loss"] = edge
+            if use["scales"].requires_grad:
+                inject["scales"] = g_edge                    # reaches the decoders' backward through the _Inject node
+            reg_root = edge.reshape(())
+            inject["ready"] = torch.cuda.Event()
+            inject["ready"].record(side)
+            _dec.flush_triplane_prepare(side)                # (same stream, behind the query: executed in this order)
+        loss_dict.update(reg)
+        extras["loss_roots"] = (photo_root, reg_root)
+        extras["staged"] = (attrs, use, inject, l2_grads)
+
+    def _finish_joined(self, loss_dict, reg, regularisers, side):
+        """The one-root tail of ``forward``: the regularisers joined (or, without a side stream, run here), -> the loss."""
         if side is not None:
-            cur.wait_stream(side)                                # join before the loss terms meet
-            for v in reg.values():
-                v.record_stream(cur)
-        elif has_reg:
+            self.join_regularisers(reg)                          # join before the loss terms meet
+        else:
             regularisers()
-        # l1 + ssim first, under ONE node that hands both the same upstream tensor (the loss kernel's backward is then a multiplication:
-        # sings_amd.photo_loss), the regularisers added behind
-        vals = [v.reshape(()) for v in loss_dict.values()]
-        loss = _AddScalars.apply(vals[0], vals[1]) if len(vals) >= 2 else vals[0]
-        for v in vals[2:]:
-            loss = loss + v
+        loss = _sum_terms(loss_dict)
         for v in reg.values():
             loss = loss + v.reshape(())
         loss_dict.update(reg)
         loss_dict["loss"] = loss
-        return loss, loss_dict, {"render_raw": color, "radii": radii, "attrs": attrs, "viewspace_points": m2d, **extras}
+        return loss
 
     def join_regularisers(self, loss_dict=None):
         """Make the current stream wait for the regularisers' side stream (a ``defer_regulariser_join`` forward leaves it
