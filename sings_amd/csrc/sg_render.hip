@@ -28,7 +28,9 @@
 //    single-row adds are 17x slower); gradients are bitwise reproducible.
 //     - Frames of many tiles (the dense kernels): ONE WAVE per work item, four items per workgroup, no workgroup barrier.  A lane
 //       owns one pixel of each quadrant (four pixel states, statically indexed), evaluates an entry in the quadrants of its mask
-//       byte, adds the partials over them in registers (quadrant order 0..3) and runs ONE butterfly per (tile, entry).
+//       byte, adds the partials over them in registers (quadrant order 0..3) and runs ONE butterfly per (tile, entry).  The entry's
+//       first accumulating quadrant assigns the nine partials (9 vector instructions), every later one adds them (11: one rounding
+//       per v_fmac); 32-36 vector instructions per evaluated quadrant in all (sg_render_bwd.inc: SG_BWD_QUAD).
 //     - Frames of few tiles (the sparse kernels): a workgroup per work item, a wave per quadrant, one butterfly per (entry,
 //       quadrant), the <= 4 quadrant sums combined in LDS in a fixed order.
 #include "sg_sort.h"
@@ -497,8 +499,8 @@ void sg_launch_render_fwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, 
 // total of value sg_red_idx(lane); lane 63 additionally gets the total of v[8] in *v8tot.
 // v_permlane{32,16}_swap are issued from inline asm: hipcc (ROCm 7.2) folds "r[0] + r[1]" of the builtins' result
 // into r[0] + r[0]; the swaps of one level are independent, so one pair of wait states serves all of them.
-// v[0..7] are left as the first swaps left them (finite where the inputs were): a caller that keeps `v` alive -- the dense backward's
-// accumulators -- pays no copies for it, and for one that does not the stores are dead.
+// v[0..7] are left as the first swaps left them: a caller that keeps `v` alive -- the dense backward's accumulators, which the next
+// entry's first quadrant overwrites without reading -- pays no copies for it, and for one that does not the stores are dead.
 __device__ __forceinline__ float sg_reduce9(float v[9], int lane, float *v8tot)
 {
     float a0 = v[0], a1 = v[1], a2 = v[2], a3 = v[3], a4 = v[4], a5 = v[5], a6 = v[6], a7 = v[7];
@@ -712,7 +714,7 @@ sg_order_items_kernel(SgBatch bt, const uint32_t *__restrict__ header, const uin
 // sg_skinned_backward_aux: one frame; sg_rasterize_backward_records_frames_aux: K frames).  One source, included twice, so that the plain kernels stay the round-5 kernels
 // instruction for instruction (as inlined bodies the compiler allocated them differently) and the aux kernels are separate
 // symbols for the profiles.
-// waves per SIMD of the dense kernels (four pixel states per lane): 76 VGPRs, six waves; with the depth / alpha adjoints 83, five
+// waves per SIMD of the dense kernels (four pixel states per lane): 73 VGPRs, six waves; with the depth / alpha adjoints 79, five
 #define SG_BWD_TW_WAVES (SG_BWD_AUX ? 5 : 6)
 #define SG_BWD_AUX 0
 #include "sg_render_bwd.inc"

@@ -5,26 +5,68 @@
 // (no include guard: included once per variant)
 
 // Quadrant Q of the current entry in the dense kernels: SG_BWD_EVAL on the quadrant's pixel state, then the per-lane partials go into the
-// entry's accumulators as acc = acc * keep + v, `keep` 0 for the entry's first evaluated quadrant (acc = v exactly: what the registers
-// held, the previous entry's sums, drops out) and 1 behind it (one rounding of acc + v: a plain add).  One instruction per value and
-// no branch: as `first ? v : acc + v` the compiler emits a select per value, as a branch its two sides meet in 18 register copies per
-// quadrant.  (Written as the instruction, in place: from fmaf() the result lands in the product's register and is copied.)
-// The price: the registers must hold finite values -- zero at the start, sums of finite partials afterwards.  An entry whose sums
-// overflow (a gradient that is infinite anyway) turns the sums of the wave's later entries into NaN.
-#define SG_BWD_ACC(J, X) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(acc[J]) : "v"(keep), "v"(X))
+// entry's accumulators.  The entry's first accumulating quadrant ASSIGNS them -- nine instructions (SG_BWD_FIRST): the two first moments,
+// the three second moments from them, a move of `w`, the three colour products; what the registers held, the previous entry's
+// sums, is never read -- and every later one ADDS -- eleven (SG_BWD_LATER): `wx`, `wy`, an add for each of them and for `w`, one
+// v_fmac per second moment and colour (ONE rounding of acc + a b; the three adds round the sum of a rounded product, as ever).
+// Quadrant 0, when it accumulates, is always the first: the assigning form, statically.  Quadrants 1-3 hold BOTH forms in one asm
+// statement behind a scalar branch on `some` (wave-uniform, a scalar register): in C++ every form of that choice costs copies or
+// selects -- as `first ? v : acc + v` a select per value, as a branch 18 register copies where its sides meet -- and inside the
+// statement the compiler sees one instruction that updates the accumulators in place.  Every instruction in the strings is a plain
+// VALU operation on interlocked registers and their first reads `w` (a v_cndmask result) and `dchan` (a v_mul result): no wait state.
+#define SG_BWD_FIRST(A0, A1, A2, A3, A4, A5, A6, A7, A8, Wv, DX, DY, DC, C0, C1, C2)                                   \
+    "v_mul_f32 " A0 ", " Wv ", " DX "\n\tv_mul_f32 " A1 ", " Wv ", " DY "\n\t"                                          \
+    "v_mul_f32 " A2 ", " A0 ", " DX "\n\tv_mul_f32 " A3 ", " A0 ", " DY "\n\tv_mul_f32 " A4 ", " A1 ", " DY "\n\t"       \
+    "v_mov_b32 " A5 ", " Wv "\n\t"                                                                                    \
+    "v_mul_f32 " A6 ", " DC ", " C0 "\n\tv_mul_f32 " A7 ", " DC ", " C1 "\n\tv_mul_f32 " A8 ", " DC ", " C2 "\n\t"
+#define SG_BWD_LATER(A0, A1, A2, A3, A4, A5, A6, A7, A8, T0, T1, Wv, DX, DY, DC, C0, C1, C2)                           \
+    "v_mul_f32 " T0 ", " Wv ", " DX "\n\tv_mul_f32 " T1 ", " Wv ", " DY "\n\t"                                          \
+    "v_add_f32 " A0 ", " A0 ", " T0 "\n\tv_add_f32 " A1 ", " A1 ", " T1 "\n\t"                                          \
+    "v_fmac_f32 " A2 ", " T0 ", " DX "\n\tv_fmac_f32 " A3 ", " T0 ", " DY "\n\tv_fmac_f32 " A4 ", " T1 ", " DY "\n\t"    \
+    "v_add_f32 " A5 ", " A5 ", " Wv "\n\t"                                                                            \
+    "v_fmac_f32 " A6 ", " DC ", " C0 "\n\tv_fmac_f32 " A7 ", " DC ", " C1 "\n\tv_fmac_f32 " A8 ", " DC ", " C2 "\n\t"
+#define SG_BWD_ACC9 "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]), "+v"(acc[6]), "+v"(acc[7]), "+v"(acc[8])
+// quadrant 0.  Operands: %0-%8 acc (AUX: %9 acc[9]), then w, dx, dy, dchan, d0, d1, d2 (AUX: dD)
+#define SG_BWD_ASSIGN()                                                                                               \
+    do {                                                                                                              \
+        if (AUX)                                                                                                      \
+            asm volatile(SG_BWD_FIRST("%0", "%1", "%2", "%3", "%4", "%5", "%6", "%7", "%8", "%10", "%11", "%12", "%13", "%14", "%15", "%16") \
+                         "v_mul_f32 %9, %13, %17"                                                                     \
+                         : SG_BWD_ACC9, "+v"(acc[9]) : "v"(w), "v"(dx), "v"(dy), "v"(dchan), "v"(d0), "v"(d1), "v"(d2), "v"(dD)); \
+        else                                                                                                          \
+            asm volatile(SG_BWD_FIRST("%0", "%1", "%2", "%3", "%4", "%5", "%6", "%7", "%8", "%9", "%10", "%11", "%12", "%13", "%14", "%15") \
+                         : SG_BWD_ACC9 : "v"(w), "v"(dx), "v"(dy), "v"(dchan), "v"(d0), "v"(d1), "v"(d2));             \
+    } while (0)
+// quadrants 1-3.  Operands: %0-%8 acc, two temporaries, w, dx, dy, dchan, d0, d1, d2, `some` (AUX: acc[9] behind acc[8], dD behind d2)
+#define SG_BWD_ASSIGN_OR_ADD()                                                                                        \
+    do {                                                                                                              \
+        float t0, t1;                                                                                                 \
+        if (AUX)                                                                                                      \
+            asm volatile("s_cmp_lg_u32 %20, 0\n\ts_cbranch_scc0 1f\n\t"                                              \
+                         SG_BWD_LATER("%0", "%1", "%2", "%3", "%4", "%5", "%6", "%7", "%8", "%10", "%11", "%12", "%13", "%14", "%15", "%16", "%17", "%18") \
+                         "v_fmac_f32 %9, %15, %19\n\ts_branch 2f\n1:\n\t"                                            \
+                         SG_BWD_FIRST("%0", "%1", "%2", "%3", "%4", "%5", "%6", "%7", "%8", "%12", "%13", "%14", "%15", "%16", "%17", "%18") \
+                         "v_mul_f32 %9, %15, %19\n2:"                                                                  \
+                         : SG_BWD_ACC9, "+v"(acc[9]), "=&v"(t0), "=&v"(t1)                                             \
+                         : "v"(w), "v"(dx), "v"(dy), "v"(dchan), "v"(d0), "v"(d1), "v"(d2), "v"(dD), "s"(some) : "scc"); \
+        else                                                                                                          \
+            asm volatile("s_cmp_lg_u32 %18, 0\n\ts_cbranch_scc0 1f\n\t"                                              \
+                         SG_BWD_LATER("%0", "%1", "%2", "%3", "%4", "%5", "%6", "%7", "%8", "%9", "%10", "%11", "%12", "%13", "%14", "%15", "%16", "%17") \
+                         "s_branch 2f\n1:\n\t"                                                                        \
+                         SG_BWD_FIRST("%0", "%1", "%2", "%3", "%4", "%5", "%6", "%7", "%8", "%11", "%12", "%13", "%14", "%15", "%16", "%17") \
+                         "\n2:"                                                                                       \
+                         : SG_BWD_ACC9, "=&v"(t0), "=&v"(t1)                                                          \
+                         : "v"(w), "v"(dx), "v"(dy), "v"(dchan), "v"(d0), "v"(d1), "v"(d2), "s"(some) : "scc");        \
+    } while (0)
 #define SG_BWD_QUAD(Q)                                                                                                \
     do {                                                                                                              \
         const float pxf = ((Q) & 1) ? pxf0 + 8.0f : pxf0, pyf = ((Q) >> 1) ? pyf0 + 8.0f : pyf0;                      \
         const float d0 = d04[Q], d1 = d14[Q], d2 = d24[Q], dD = dD4[Q], tb = tb4[Q];                                  \
         const uint32_t ncq_b = ncq4[Q];                                                                               \
         float &Tr = Tr4[Q], &Sd = Sd4[Q];                                                                             \
-        SG_BWD_EVAL((uint32_t)pos, break);                                                                            \
-        float v[9];                                                                                                   \
-        SG_BWD_PARTIALS(v);                                                                                           \
-        for (int j = 0; j < 9; j++) SG_BWD_ACC(j, v[j]);                                                              \
-        if (AUX) SG_BWD_ACC(9, dchan * dD);                                                                           \
-        asm volatile("v_mov_b32 %0, 1.0" : "=v"(keep));                                                               \
-        some = true;                                                                                                  \
+        SG_BWD_EVAL((uint32_t)pos, break);          /* (no pixel valid: `some` stays what it was) */                  \
+        if ((Q) == 0) SG_BWD_ASSIGN(); else SG_BWD_ASSIGN_OR_ADD();                                                   \
+        some = 1u;                                                                                                    \
     } while (0)
 // Dense backward (frames of many tiles): ONE WAVE per work item (tile, depth segment), four consecutive items per workgroup.  Lane l
 // owns pixel (l & 7, l >> 3) of EACH of the tile's four 8x8 quadrants and keeps that pixel's state four times, statically indexed.
@@ -158,9 +200,7 @@ sg_render_bwd_kernel(SG_BWD_PARAMS)
             if (pos >= maxq4[2]) mke &= ~4u;
             if (pos >= maxq4[3]) mke &= ~8u;
             // the entry's partials, added over those quadrants in the order 0, 1, 2, 3
-            float keep;
-            asm volatile("v_mov_b32 %0, 0" : "=v"(keep));              // (a vector register: a scalar operand halves the issue rate)
-            bool some = false;                                          // some pixel of the tile took a gradient from this entry
+            uint32_t some = 0u;                                         // some pixel of the tile took a gradient from this entry (a scalar register)
             if (mke & 1u) SG_BWD_QUAD(0);
             if (mke & 2u) SG_BWD_QUAD(1);
             if (mke & 4u) SG_BWD_QUAD(2);
@@ -200,7 +240,11 @@ sg_render_bwd_kernel(SG_BWD_PARAMS)
 }
 
 #undef SG_BWD_QUAD
-#undef SG_BWD_ACC
+#undef SG_BWD_ASSIGN_OR_ADD
+#undef SG_BWD_ASSIGN
+#undef SG_BWD_ACC9
+#undef SG_BWD_LATER
+#undef SG_BWD_FIRST
 
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6)))
 #if SG_BWD_AUX
