@@ -96,7 +96,8 @@ typedef struct SgLayout {
  * sg_skinned_backward_gaussians_frames_aux (depth and alpha maps of K frames); sg_lpips_weights_layout, sg_lpips_ws_bytes,
  * sg_lpips_forward, sg_lpips_backward, sg_lpips_patch_gather, sg_lpips_patch_scatter (the LPIPS-VGG patch loss),
  * sg_lpips_ws_layout (its workspace pieces); sg_frames_to_u8 (8-bit HWC frames); sg_adam_chunk_elements, sg_adam_step (the fused Adam
- * step); sg_pose_transforms, sg_pose_transforms_backward (learned per-frame pose tables).  Also since 8: SgFrameBatch.reserved became
+ * step); sg_pose_transforms, sg_pose_transforms_backward (learned per-frame pose tables); sg_init_ws_bytes, sg_init_attributes,
+ * sg_attr_mse_ws_bytes, sg_attr_mse, sg_plateau_step (initial values and the decoder pre-fit).  Also since 8: SgFrameBatch.reserved became
  * SgFrameBatch.placement (per-frame ext_tfs / smpl_scale in the skinned K-frame forward); 0, what every ABI-8 caller passes, keeps
  * the earlier meaning. */
 #define SG_ABI_VERSION 8
@@ -804,6 +805,55 @@ int sg_mesh_collapse_build(int V, int F, int Es, const float *verts, const int32
                            const double *collapse_rate, void *ws, int32_t *info, void *stream);
 int sg_mesh_collapse_emit(int V, int F, int Fn, int Vn, const int32_t *faces, const void *ws, int32_t *new_faces, uint8_t *prune_mask,
                           int32_t *survivors, void *stream);
+
+/* ---- initial values and the decoder pre-fit (sings_amd/csrc/sg_init.hip; entry points added to ABI 8) -----------------------------
+ * Replaces, on the device, `SinGS.initialize` (sings_hybrid.py:674-741) and the loss and scheduler of `SinGS.init_attrs` (:608-671).
+ *
+ * sg_init_attributes.  verts [V][3] fp32; faces [F][3] and edges [E][2] int32, edges as sings_amd.topology holds them (unique rows
+ * a < b, lexicographic).  Outputs, one row per vertex:
+ *   first, second [V]  int32  the two smallest row indices of `edges` that contain the vertex (INT_MAX where there is none)
+ *   scales        [V][3]      with (a0, b0) = edges[first], (a1, b1) = edges[second] (sings_hybrid.py:687-702, as written):
+ *                             len = init_scale_multiplier * max(|x[a0] - x[a1]|, |x[b0] - x[b1]|);  log-scale (l, l, l * thickness_factor),
+ *                             l = log(len);  scales = exp(.)
+ *   scales_aux    [V][3]      log(exp(scales) - 1)
+ *   normals       [V][3]      the normalised sum over the vertex' faces of (unit face normal) * (corner angle at the vertex); zero
+ *                             for a vertex no non-degenerate face holds
+ *   rotmat        [V][9]      the rotation that takes (0,0,1) to the normal: I + K + K^2 / (1 + c), K the cross-product matrix of
+ *                             (0,0,1) x n, c = n.z (rotations.py:606-627 with (1 - c) / s^2 written as 1 / (1 + c)); 1 + c <= 0: the
+ *                             half-turn about x, diag(1, -1, -1); no normal: the identity
+ * Arithmetic in fp64 from the fp32 inputs, each output rounded once; the normals' sum is 64-bit fixed point with integer atomics, the
+ * incident rows integer minima: every output is a pure function of the inputs, two calls give the same bits.
+ * info[4] (device): [0] != 0: an edge row is not 0 <= a < b < V (skipped, never dereferenced); [1] != 0: a vertex has fewer than two
+ * incident rows (its scales are zero); [2] != 0: a face corner is outside [0, V) (the face is skipped).  ws: sg_init_ws_bytes(V)
+ * bytes of scratch, 8-byte aligned, initialised by the call.  Refused (status 1, sg_last_error) before anything is launched: V < 1 or
+ * beyond 2^30, F < 0 or beyond (2^31 - 1) / 3, E < 0, NULL pointers.  sg_init_ws_bytes returns 0 for a V it refuses.
+ *
+ * sg_attr_mse.  Up to six pairs (output, target) of flat fp32 arrays with N rows of 3, 3, 3, 6, 48 and 1 floats (xyz_offsets, scales,
+ * scales_aux, rot6d_canon, shs, opacity).  outputs, targets, grads: HOST arrays of six device pointers; outputs[k] == targets[k] ==
+ * NULL: the pair is absent.  terms[8] (device): terms[k] = mean((out_k - tgt_k)^2) (0 for an absent pair), terms[6] = their sum in the
+ * order k = 0 .. 5 (fp32), terms[7] = 0.  grads (or grads[k]) NULL: no gradient; else grads[k][i] = (2 * (out_k[i] - tgt_k[i])) / numel_k
+ * in fp32, written in the same march.  Deterministic: per-workgroup partial sums in `ws` (sg_attr_mse_ws_bytes() bytes of scratch),
+ * then one wave adds them in a fixed order, in double.  No floating-point atomics.
+ *
+ * sg_plateau_step.  torch.optim.lr_scheduler.ReduceLROnPlateau (mode min, relative threshold, cooldown 0, min_lr 0) with its state in
+ * device memory, one launch of one wave per step.  state (double): [0] best, [1] bad steps, [2] losses digested, [3] steps begun,
+ * [4 .. 4 + G) the multiplier of each group, [4 + G .. 4 + 2 G) its base learning rate.  A fresh state: best = +inf, zeros, multipliers 1.
+ * The launch first, if more steps were begun than losses digested, digests the loss at `loss` (it belongs to the previous step):
+ *   better = loss < best * (1 - threshold): best = loss, bad = 0; else bad += 1;  bad > patience: for every group, with
+ *   old = base * multiplier, new = old * factor: multiplier *= factor if old - new > eps;  bad = 0
+ * and writes row (losses digested) of `log` [log_rows][n_copy + G], doubles: n_copy (<= 64) floats from `terms`, then the G multipliers
+ * the digested step ran with (log NULL, or the row outside: not written).  Then, with begin != 0, it counts a step as begun and multiplies column 5 (neg_step) of every group's row of
+ * `hyper` [G][8] (sg_adam_step's table, freshly written from the base rates by the caller) by the group's multiplier.
+ * settings: HOST pointer to three doubles: factor (0 < factor < 1), threshold, eps.  1 <= n_groups <= 64. */
+size_t sg_init_ws_bytes(int V);
+int sg_init_attributes(int V, int F, int E, float init_scale_multiplier, float thickness_factor, const float *verts,
+                       const int32_t *faces, const int32_t *edges, void *ws, int32_t *first, int32_t *second, float *scales,
+                       float *scales_aux, float *normals, float *rotmat, int32_t *info, void *stream);
+size_t sg_attr_mse_ws_bytes(void);
+int sg_attr_mse(int N, const float *const *outputs, const float *const *targets, float *const *grads, void *ws, float *terms,
+                void *stream);
+int sg_plateau_step(int n_groups, int begin, int patience, const double *settings, const float *loss, double *state, float *hyper,
+                    const float *terms, int n_copy, double *log, int log_rows, void *stream);
 
 /* ---- optional per-kernel timing (bench / profiling only; process-global, not thread-safe).
  * When enabled, every kernel launch of forward/backward is bracketed by hipEvents on the

@@ -162,6 +162,11 @@ _PROTOTYPES = {
     "sg_mesh_collapse_ws_bytes": "z: i2",
     "sg_mesh_collapse_build": "i: i3 p3 d p3",
     "sg_mesh_collapse_emit": "i: i4 p6",
+    "sg_init_ws_bytes": "z: i",
+    "sg_init_attributes": "i: i3 f2 p12",
+    "sg_attr_mse_ws_bytes": "z:",
+    "sg_attr_mse": "i: i V3 p3",
+    "sg_plateau_step": "i: i3 d p4 i p i p",
     "sg_profile_enable": "i: i",
     "sg_copy_probe": "i: p2 z i p",
     "sg_profile_collect": "i: d n i",

@@ -254,3 +254,86 @@ def mesh_collapse(verts, selected_edges, faces, collapse_rate):
         _lib.check(lib.sg_mesh_collapse_emit(V, F, Fn, Vn, _ptr(faces), _ptr(ws), _ptr(new_faces), _ptr(prune_mask), _ptr(survivors),
                                              _stream(dev)), "sg_mesh_collapse_emit")
     return new_faces, prune_mask, survivors, done
+
+
+# ---- initial values and the decoder pre-fit (csrc/sg_init.hip)
+ATTR_MSE_WIDTHS = (3, 3, 3, 6, 48, 1)             # floats per row of xyz_offsets, scales, scales_aux, rot6d_canon, shs, opacity
+
+
+def init_attributes(verts, faces, edges, init_scale_multiplier, thickness_factor):
+    """``sg_init_attributes`` on torch's current stream: ``verts`` [V,3] fp32, ``faces`` [F,3] and ``edges`` [E,2] int32 -> (dict of
+    ``first`` / ``second`` [V] int32, ``scales`` / ``scales_aux`` / ``normals`` [V,3] and ``rotmat`` [V,3,3] fp32, info [4] int32 on the
+    device: the caller reads it)."""
+    dev = verts.device if torch.is_tensor(verts) else None
+    verts = _mesh_arg(verts, "verts", torch.float32, dev, (3,))
+    faces = _mesh_arg(faces, "faces", torch.int32, dev, (3,))
+    edges = _mesh_arg(edges, "edges", torch.int32, dev, (2,))
+    V, F, E = int(verts.shape[0]), int(faces.shape[0]), int(edges.shape[0])
+    lib = _lib.load()
+    nbytes = int(lib.sg_init_ws_bytes(V))
+    if V < 1 or nbytes == 0:
+        raise ValueError(f"init_attributes: {V} vertices are outside what the kernels cover (1 <= V <= 2^30)")
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+        out = {"first": torch.empty(V, dtype=torch.int32, device=dev), "second": torch.empty(V, dtype=torch.int32, device=dev)}
+        for k in ("scales", "scales_aux", "normals"):
+            out[k] = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        out["rotmat"] = torch.empty((V, 3, 3), dtype=torch.float32, device=dev)
+        info = torch.empty(4, dtype=torch.int32, device=dev)
+        _lib.check(lib.sg_init_attributes(V, F, E, float(init_scale_multiplier), float(thickness_factor), _ptr(verts), _ptr(faces),
+                                          _ptr(edges), _ptr(ws), _ptr(out["first"]), _ptr(out["second"]), _ptr(out["scales"]),
+                                          _ptr(out["scales_aux"]), _ptr(out["normals"]), _ptr(out["rotmat"]), _ptr(info), _stream(dev)),
+                   "sg_init_attributes")
+    return out, info
+
+
+def attr_mse_ws_bytes():
+    return int(_lib.load().sg_attr_mse_ws_bytes())
+
+
+def _pointer_row(tensors):
+    """Six tensors (or None) -> the host array of six device pointers ``sg_attr_mse`` takes."""
+    return (C.c_void_p * 6)(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def attr_mse(N, outputs, targets, grads, ws, terms):
+    """``sg_attr_mse`` on torch's current stream.  ``outputs`` / ``targets`` / ``grads``: six entries each in the order of
+    ``ATTR_MSE_WIDTHS``, a contiguous fp32 GPU tensor of N rows or None (``grads``: None for no gradient at all); ``ws``:
+    ``attr_mse_ws_bytes()`` bytes; ``terms``: 8 floats.  Nothing is allocated here."""
+    dev = terms.device
+    if not terms.is_cuda or terms.dtype != torch.float32 or terms.numel() < 8 or not ws.is_cuda or ws.numel() * ws.element_size() < attr_mse_ws_bytes():
+        raise RuntimeError("attr_mse: terms must be 8 fp32 values and ws attr_mse_ws_bytes() bytes on the GPU (no CPU fallback)")
+    rows = [outputs, targets] + ([grads] if grads is not None else [])
+    for row in rows:
+        if len(row) != 6:
+            raise ValueError("attr_mse: six entries per row (None for an absent pair)")
+        for t, w in zip(row, ATTR_MSE_WIDTHS):
+            if t is None:
+                continue
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise RuntimeError("attr_mse: tensors must live on the GPU (no CPU fallback)")
+            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != int(N) * w:
+                raise ValueError(f"attr_mse: every tensor must be contiguous fp32 on {dev} with {int(N)} rows of its width ({w})")
+    for k in range(6):
+        if (outputs[k] is None) != (targets[k] is None) or (grads is not None and grads[k] is not None and outputs[k] is None):
+            raise ValueError("attr_mse: a pair needs both its output and its target")
+    _lib.check(_lib.load().sg_attr_mse(int(N), _pointer_row(outputs), _pointer_row(targets),
+                                       None if grads is None else _pointer_row(grads), _ptr(ws), _ptr(terms), _stream(dev)), "sg_attr_mse")
+
+
+def plateau_step(n_groups, begin, patience, settings, loss, state, hyper, terms, n_copy, log, log_rows):
+    """``sg_plateau_step`` on torch's current stream.  ``settings``: a ``ctypes.c_double * 3`` (factor, threshold, eps); ``loss``: a
+    view of one fp32 value; ``state`` / ``log``: fp64 device tensors (``log`` may be None); ``hyper``: ``FusedAdam.hyper`` or None."""
+    dev = state.device
+    for name, t, dt in (("loss", loss, torch.float32), ("state", state, torch.float64), ("hyper", hyper, torch.float32),
+                        ("terms", terms, torch.float32), ("log", log, torch.float64)):
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.device != dev or t.dtype != dt or not t.is_contiguous()):
+            raise RuntimeError(f"plateau_step: {name} must be a contiguous {dt} tensor on {dev} (no CPU fallback)")
+    if state.numel() < 4 + 2 * int(n_groups) or (hyper is not None and tuple(hyper.shape) != (int(n_groups), 8)):
+        raise ValueError("plateau_step: state must hold 4 + 2 G doubles and hyper be [G,8]")
+    if log is not None and log.numel() < int(log_rows) * (int(n_copy) + int(n_groups)):
+        raise ValueError("plateau_step: log must hold log_rows rows of n_copy + G doubles")
+    if terms is not None and terms.numel() < int(n_copy):
+        raise ValueError("plateau_step: terms must hold n_copy floats")
+    _lib.check(_lib.load().sg_plateau_step(int(n_groups), int(bool(begin)), int(patience), settings, _ptr(loss), _ptr(state), _ptr(hyper),
+                                           _ptr(terms), int(n_copy), _ptr(log), int(log_rows), _stream(dev)), "sg_plateau_step")
