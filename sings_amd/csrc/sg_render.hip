@@ -547,8 +547,8 @@ __device__ __forceinline__ int sg_red_idx(int lane)
 }
 
 // One (entry, quadrant) pass of the backward composite: `ga, gb, gc` the staged record, KPOS the entry's position in the batch
-// (compared with the pixel's contributor count inside the batch, `ncq_b`), KSLOT its row in sG.  SKIP is what to do with an entry that
-// touches no pixel of the quadrant.  Three pieces: SG_BWD_EVAL moves the quadrant's 64 pixels in front of the entry and leaves each
+// (compared with the pixel's contributor count inside the batch, `ncq_b`), KSLOT its row in sG (in the dense kernels a view of the
+// staged rows themselves).  SKIP is what to do with an entry that touches no pixel of the quadrant.  Three pieces: SG_BWD_EVAL moves the quadrant's 64 pixels in front of the entry and leaves each
 // pixel's `w`, `dchan`, `dx`, `dy`; SG_BWD_PARTIALS forms the nine per-lane partials from them; SG_BWD_FILE sums nine (AUX: ten)
 // per-lane values over the wave and files the sums in row KSLOT.  The sparse kernels run all three per (entry, quadrant) --
 // SG_BWD_PASS, their arithmetic since round 5 -- and the dense kernels, where one wave owns the whole tile, run the first two per
@@ -714,8 +714,10 @@ sg_order_items_kernel(SgBatch bt, const uint32_t *__restrict__ header, const uin
 // sg_skinned_backward_aux: one frame; sg_rasterize_backward_records_frames_aux: K frames).  One source, included twice, so that the plain kernels stay the round-5 kernels
 // instruction for instruction (as inlined bodies the compiler allocated them differently) and the aux kernels are separate
 // symbols for the profiles.
-// waves per SIMD of the dense kernels (four pixel states per lane): 73 VGPRs, six waves; with the depth / alpha adjoints 79, five
-#define SG_BWD_TW_WAVES (SG_BWD_AUX ? 5 : 6)
+// waves per SIMD of the dense kernels (four pixel states per lane): 64 VGPRs, eight waves; with the depth / alpha adjoints 75, six.
+// No scratch in either.  16 384 B of LDS per workgroup (the entries' sums live in their staged rows) allow ten workgroups per CU, so
+// the registers alone set the count.
+#define SG_BWD_TW_WAVES (SG_BWD_AUX ? 6 : 8)
 #define SG_BWD_AUX 0
 #include "sg_render_bwd.inc"
 #undef SG_BWD_AUX

@@ -85,10 +85,14 @@ sg_render_bwd_kernel(SG_BWD_PARAMS)
 #if !SG_BWD_AUX
     const SgAuxBwd ax = { };
 #endif
-    // per wave: its staged batch -- (mean x, mean y, A', B') (C', opacity, colour 0, 1) (colour 2, z [AUX], quadrant mask, -) and, for the
-    // record store, (A, B, C, record slot): kept here, not in registers, across the walk -- and a row of sums per entry
+    // per wave: its staged batch -- (mean x, mean y, A', B') (C', opacity, colour 0, 1) (colour 2, z [AUX], quadrant mask, opacity) and, for the
+    // record store, (A, B, C, record slot): kept here, not in registers, across the walk.  Row as 16 floats: 0-3 `ga`, 4-7 `gb`, 8 `gc`,
+    // 9 `gz`, 10 the mask, 11 the opacity once more, 12-15 (A, B, C, slot).  An entry's nine (AUX: ten) sums are filed over floats 0-8
+    // (9) of its OWN row (SG_BWD_FILE through `sG`): the walk has read them by then and every other entry reads only its own row.
+    // Floats 10-15 are never overwritten; the record store takes the opacity from float 11.  A row nobody filed still holds staged
+    // floats (or an earlier batch's): `filed` keeps the store from reading it.
     __shared__ float4 sR[4][SG_BB][4];
-    __shared__ float sG[4][SG_BB][9 + AUX];
+    float (*sG)[SG_BB][16] = (float (*)[SG_BB][16])sR;
     SG_STAMP_SCOPE
     SG_BWD_FRAME_OFFSETS;
 #if SG_BWD_AUX
@@ -151,7 +155,12 @@ sg_render_bwd_kernel(SG_BWD_PARAMS)
         maxq4[q] = (int)__builtin_amdgcn_readfirstlane(m);
     }
     const int max_contrib = max(max(maxq4[0], maxq4[1]), max(maxq4[2], maxq4[3]));
-    const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;
+    // Wave-uniform and read only at the record store: scalar registers, not two vector registers held across the walk.  (As an asm
+    // statement: hipcc folds the builtin away on a value it knows to be uniform and keeps the v_cvt's result where it is.  The
+    // s_nop is the wait state between a VALU write of a vector register and a lane read of it.)
+    float ddelx_dx, ddely_dy;
+    asm volatile("s_nop 0\n\tv_readfirstlane_b32 %0, %2\n\tv_readfirstlane_b32 %1, %3"
+                 : "=&s"(ddelx_dx), "=s"(ddely_dy) : "v"(0.5f * (float)W), "v"(0.5f * (float)H));
     const int cslot = lane == 63 ? 8 : sg_red_idx(lane);
     float acc[10] = { };                                           // the current entry's partials, summed over its quadrants ([9]: AUX, dL/dz)
     // ---- the segment in batches of 64 entries, one entry per lane, back to front
@@ -176,7 +185,7 @@ sg_render_bwd_kernel(SG_BWD_PARAMS)
                 const float4 a = recA[SG_REC_STRIDE * (size_t)gid], b = recB[SG_REC_STRIDE * (size_t)gid];
                 sR[wave][lane][0] = make_float4(a.x, a.y, SG_KA * a.z, SG_KB * a.w);
                 sR[wave][lane][1] = make_float4(SG_KA * b.x, b.y, b.z, b.w);
-                sR[wave][lane][2] = make_float4(c4.x, AUX ? ax.depth[gid] : 0.0f, __uint_as_float(mk), 0.0f);
+                sR[wave][lane][2] = make_float4(c4.x, AUX ? ax.depth[gid] : 0.0f, __uint_as_float(mk), b.y);
                 sR[wave][lane][3] = make_float4(a.z, a.w, b.x, 0.0f);
             }
             const uint32_t goff = __float_as_uint(c4.y), mn = __float_as_uint(c4.z), wh = __float_as_uint(c4.w);
@@ -220,10 +229,9 @@ sg_render_bwd_kernel(SG_BWD_PARAMS)
             float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0;
             float r2 = 0.0f, r3 = 0.0f;
             if ((filed >> lane) & 1ull) {                         // (an entry nobody filed has no staged record either)
-                float s[9 + AUX];
-#pragma unroll
-                for (int q = 0; q < 9 + AUX; q++) s[q] = sG[wave][lane][q];
-                const float no = -sR[wave][lane][1].y, nh = 0.5f * no;              // -opacity, -opacity / 2
+                const float4 s03 = sR[wave][lane][0], s47 = sR[wave][lane][1], s8o = sR[wave][lane][2];    // the sums, (8, 9 [AUX], mask, opacity)
+                const float s[10] = { s03.x, s03.y, s03.z, s03.w, s47.x, s47.y, s47.z, s47.w, s8o.x, s8o.y };
+                const float no = -s8o.w, nh = 0.5f * no;                            // -opacity, -opacity / 2
                 const float m0 = fmaf(cn.x, s[0], cn.y * s[1]), m1 = fmaf(cn.y, s[0], cn.z * s[1]);   // conic . first moments
                 r0 = make_float4(no * ddelx_dx * m0, no * ddely_dy * m1, nh * s[2], nh * s[3]);
                 r1 = make_float4(nh * s[4], s[5], s[6], s[7]);
