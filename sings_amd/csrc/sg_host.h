@@ -1,0 +1,45 @@
+// Host side of the extern "C" boundary: what every entry point shares (the formatted refusal, the launch epilogue) and the
+// launcher prototypes that sg_common.h does not carry.  Host only; included by the translation units that define entry points.
+#pragma once
+#include "sg_common.h"
+
+#include <stdarg.h>
+#include <stdio.h>
+
+// sg_set_error of an argument error whose text is formatted (the entry point's name first: "%s: ...", who)
+static inline int sg_failf(const char *fmt, ...)
+{
+    char msg[256];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(msg, sizeof msg, fmt, ap);
+    va_end(ap);
+    return sg_set_error(msg, hipSuccess);
+}
+
+// the end of an entry point that launches and returns: 0, or the launch error under `what`
+static inline int sg_launched(const char *what)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : sg_set_error(what, e);
+}
+
+// between the launches of one entry point: return on a launch error; SgRasterSettings.debug also waits for the kernel
+#define SG_CHECK_LAST(what, s, st)                                           \
+    do {                                                                     \
+        hipError_t e_ = hipGetLastError();                                   \
+        if (e_ != hipSuccess) return sg_set_error(what, e_);                 \
+        if ((s)->debug) {                                                    \
+            e_ = hipStreamSynchronize(st);                                   \
+            if (e_ != hipSuccess) return sg_set_error(what, e_);             \
+        }                                                                    \
+    } while (0)
+
+// (declared here, not in sg_common.h: that header is one of the sources the committed PMC profiles are keyed on)
+int sg_launch_linear_bwd_fan(int N, int Cin, int Cout, int act, const float *z, const float *dh, const float *W, float *dz_out,
+                             float *dx_out, const SgLinearSide *side, hipStream_t st);
+void sg_launch_scales_head(int N, const float *z, float *scales, float *aux, const float *dscales, const float *daux, float *dz,
+                           hipStream_t st);
+void sg_launch_rows_laplacian(int R, int V, int C, const float *x, const int *row_ptr, const int *col, const float *val,
+                              const float *rscale, const int *t_row_ptr, const int *t_row, const float *t_val, void *ws, float *g_ws,
+                              float *loss, const float *upstream, float *dL_dx, hipStream_t st);

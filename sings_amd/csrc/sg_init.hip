@@ -17,7 +17,7 @@
 //
 // Every row index and corner is range-checked BEFORE it is used: a row that is not 0 <= a < b < V, or a face with a corner outside
 // [0, V), sets a bit of info[] and is skipped, never dereferenced.
-#include "sg_common.h"
+#include "sg_host.h"
 #include <climits>
 
 #define SG_INIT_THREADS 256
@@ -186,8 +186,7 @@ extern "C" int sg_init_attributes(int V, int F, int E, float init_scale_multipli
                            info);
     hipLaunchKernelGGL(sg_init_vertex_kernel, dim3(sg_init_blocks(V)), dim3(SG_INIT_THREADS), 0, st, V, init_scale_multiplier,
                        thickness_factor, verts, edges, first, second, acc, scales, scales_aux, normals, rotmat, info);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error("sg_init_attributes", e);
+    return sg_launched("sg_init_attributes");
 }
 
 // ---- the pre-fit's loss: up to six MSE terms, value and gradient in one march -------------------------------------------------------
@@ -280,8 +279,7 @@ extern "C" int sg_attr_mse(int N, const float *const *outputs, const float *cons
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(sg_attr_mse_kernel, dim3((unsigned)blocks), dim3(SG_MSE_THREADS), 0, st, P, (float *)ws);
     hipLaunchKernelGGL(sg_attr_mse_final_kernel, dim3(1), dim3(SG_WAVE), 0, st, P, (int)blocks, (const float *)ws, terms);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error("sg_attr_mse", e);
+    return sg_launched("sg_attr_mse");
 }
 
 // ---- ReduceLROnPlateau (mode min, relative threshold, cooldown 0, min_lr 0) in device memory ------------------------------------------
@@ -336,6 +334,5 @@ extern "C" int sg_plateau_step(int n_groups, int begin, int patience, const doub
         return sg_set_error("sg_plateau_step: 0 < factor < 1, threshold >= 0, eps >= 0", hipSuccess);
     hipLaunchKernelGGL(sg_plateau_kernel, dim3(1), dim3(SG_WAVE), 0, (hipStream_t)stream, n_groups, begin, factor, patience, threshold, eps,
                        loss, state, hyper, terms, n_copy, log, log_rows);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error("sg_plateau_step", e);
+    return sg_launched("sg_plateau_step");
 }

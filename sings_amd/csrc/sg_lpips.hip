@@ -16,7 +16,7 @@
 // host), and the ReLU select of the layer's own output (y > 0 ? g : 0) fused into the operand load.
 // Determinism: every sum runs in a fixed order, no atomics; no tile spans two images, so a patch's value does not depend on what
 // else is in the batch.
-#include "sg_common.h"
+#include "sg_host.h"
 
 typedef float sg_v16f __attribute__((ext_vector_type(16)));
 
@@ -503,8 +503,7 @@ extern "C" int sg_lpips_forward(int B, int height, int width, int normalize, con
         s.dpix[k] = d; s.hw[k] = hw;
     }
     hipLaunchKernelGGL(lp_head_reduce, dim3(B), dim3(256), 0, st, s, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error("sg_lpips_forward", e);
+    return sg_launched("sg_lpips_forward");
 }
 
 extern "C" int sg_lpips_backward(int B, int height, int width, int normalize, const float *packed, const void *ws_c,
@@ -541,8 +540,7 @@ extern "C" int sg_lpips_backward(int B, int height, int width, int normalize, co
     }
     hipLaunchKernelGGL(lp_conv1_bwd, dim3(lp_blocks((size_t)B * 3 * height * width)), dim3(256), 0, st, B, height, width, normalize,
                        Y(0), gbuf[cur], packed + w.off[0], packed + w.off[3 * LP_NCONV + 6], dL_din0);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error("sg_lpips_backward", e);
+    return sg_launched("sg_lpips_backward");
 }
 
 extern "C" int sg_lpips_patch_gather(int K, int n, int patch, int height, int width, const float *raw, const float *gt_rgb,
@@ -556,8 +554,7 @@ extern "C" int sg_lpips_patch_gather(int K, int n, int patch, int height, int wi
         return sg_set_error("sg_lpips_patch_gather: null pointer");
     hipLaunchKernelGGL(lp_patch_gather, dim3(lp_blocks((size_t)K * n * 3 * patch * patch)), dim3(256), 0, (hipStream_t)stream, K, n,
                        patch, height, width, raw, gt_rgb, mask, bg, bg_rand, origins, pred_patches, gt_patches);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error("sg_lpips_patch_gather", e);
+    return sg_launched("sg_lpips_patch_gather");
 }
 
 extern "C" int sg_lpips_patch_scatter(int K, int n, int patch, int height, int width, const float *raw, const float *mask,
@@ -570,6 +567,5 @@ extern "C" int sg_lpips_patch_scatter(int K, int n, int patch, int height, int w
     if (!raw || !mask || !bg_rand || !origins || !dL_dpred_patches || !dL_draw) return sg_set_error("sg_lpips_patch_scatter: null pointer");
     hipLaunchKernelGGL(lp_patch_scatter, dim3(lp_blocks((size_t)K * 3 * height * width)), dim3(256), 0, (hipStream_t)stream, K, n,
                        patch, height, width, raw, mask, bg_rand, origins, dL_dpred_patches, dL_draw);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error("sg_lpips_patch_scatter", e);
+    return sg_launched("sg_lpips_patch_scatter");
 }

@@ -20,7 +20,7 @@
 //   unique counts       heads per row (integer atomics again), scanned -> the first edge of every row; edge (a, b) = that + rank.
 //
 // The host reads info[] once between sg_mesh_edges_build and sg_mesh_edges_emit: E sizes the outputs.
-#include "sg_common.h"
+#include "sg_host.h"
 
 #define SG_MESH_THREADS 256
 #define SG_MESH_MAX_V (1 << 30)                  // the scan's block table and the 32-bit row offsets cover this many vertices
@@ -254,8 +254,7 @@ extern "C" int sg_mesh_edges_build(int V, int F, const int32_t *faces, const uin
     hipLaunchKernelGGL(sg_mesh_heads_kernel, dim3(ib), dim3(SG_MESH_THREADS), 0, st, info, w);
     const SgScanJob uniq = {w.ucount, nullptr, w.ebase, w.bsum_u, info, V};
     sg_mesh_scan(uniq, nullptr, st);
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error("sg_mesh_edges_build", e);
+    return sg_launched("sg_mesh_edges_build");
 }
 
 extern "C" int sg_mesh_edges_emit(int V, int F, int E, const int32_t *faces, const uint8_t *flags, const void *ws, int32_t *edges,
@@ -273,8 +272,7 @@ extern "C" int sg_mesh_edges_emit(int V, int F, int E, const int32_t *faces, con
     const unsigned ib = (unsigned)((3 * (size_t)F + SG_MESH_THREADS - 1) / SG_MESH_THREADS);
     hipLaunchKernelGGL(sg_mesh_emit_kernel, dim3(ib), dim3(SG_MESH_THREADS), 0, (hipStream_t)stream, V, F, E, faces, flags, w, edges,
                        edge_faces, face_edges);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error("sg_mesh_edges_emit", e);
+    return sg_launched("sg_mesh_edges_emit");
 }
 
 // ---- selective subdivision (geometry_ops.py:41-58): the unflagged faces in their order, then four children per flagged face
@@ -318,8 +316,7 @@ extern "C" int sg_mesh_subdivide(int V, int F, int Fs, const int32_t *faces, con
     const unsigned fb = ((unsigned)F + SG_MESH_THREADS - 1) / SG_MESH_THREADS;
     hipLaunchKernelGGL(sg_mesh_subdivide_kernel, dim3(fb), dim3(SG_MESH_THREADS), 0, st, V, F, Fs, faces, flags, face_edges, w.frank,
                        w.bsum_f, new_faces);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error("sg_mesh_subdivide", e);
+    return sg_launched("sg_mesh_subdivide");
 }
 
 // ---- midpoint rows: dst[e] = (src[a] + src[b]) * 0.5f (one add, one exact scaling: the bits of `values[rows].mean(axis=1)`), or
@@ -358,8 +355,7 @@ static int sg_mesh_midpoints_launch(const char *what, int V, int E, int C, const
                            (const S4 *)src, (S4 *)dst);
     else
         hipLaunchKernelGGL((sg_mesh_midpoints_kernel<S, MEAN>), dim3(blocks), dim3(SG_MESH_THREADS), 0, st, V, n, width, edges, src, dst);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error(what, e);
+    return sg_launched(what);
 }
 extern "C" int sg_mesh_midpoints(int V, int E, int C, const int32_t *edges, const float *src, float *dst, void *stream)
 {
@@ -697,8 +693,7 @@ extern "C" int sg_mesh_collapse_build(int V, int F, int Es, const float *verts, 
         const SgScanJob used = {nullptr, w.used, w.vrank, w.bsum_v, info + 1, V};
         sg_mesh_scan(kept, &used, st);
     }
-    e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error("sg_mesh_collapse_build", e);
+    return sg_launched("sg_mesh_collapse_build");
 }
 
 extern "C" int sg_mesh_collapse_emit(int V, int F, int Fn, int Vn, const int32_t *faces, const void *ws, int32_t *new_faces,
@@ -713,6 +708,5 @@ extern "C" int sg_mesh_collapse_emit(int V, int F, int Fn, int Vn, const int32_t
     const unsigned n = (unsigned)(V > F ? V : F);
     hipLaunchKernelGGL(sg_mesh_collapse_emit_kernel, dim3((n + SG_MESH_THREADS - 1) / SG_MESH_THREADS), dim3(SG_MESH_THREADS), 0,
                        (hipStream_t)stream, V, F, Fn, Vn, faces, w, new_faces, prune_mask, survivors);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error("sg_mesh_collapse_emit", e);
+    return sg_launched("sg_mesh_collapse_emit");
 }

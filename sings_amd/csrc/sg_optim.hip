@@ -13,7 +13,7 @@
 //
 // The arithmetic is the contract (include/sings_hip.h), fp32, in this order, nothing contracted (-ffp-contract=off), division and
 // square root correctly rounded, denormals kept.
-#include "sg_common.h"
+#include "sg_host.h"
 
 #define SG_ADAM_THREADS 256
 #define SG_ADAM_CHUNK 4096                       // elements: 4 quads per lane
@@ -118,6 +118,5 @@ extern "C" int sg_adam_step(int n_segments, int n_chunks, int n_groups, const in
     const unsigned blocks = n_chunks < SG_ADAM_MAX_BLOCKS ? (unsigned)n_chunks : SG_ADAM_MAX_BLOCKS;
     hipLaunchKernelGGL(sg_adam_step_kernel, dim3(blocks), dim3(SG_ADAM_THREADS), 0, (hipStream_t)stream, n_chunks, segments, chunks,
                        hyper, grad_flat, exp_avg, exp_avg_sq);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error("sg_adam_step", e);
+    return sg_launched("sg_adam_step");
 }

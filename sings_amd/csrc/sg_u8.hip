@@ -5,7 +5,7 @@
 // of the three planes (a wave reads three contiguous 1-KB runs) and three 4-byte stores of the 12 interleaved bytes (a contiguous
 // 768-B run per wave).  When the plane size is not a multiple of 4 pixels (or a pointer is not aligned for that) the same thread
 // shape reads scalars and writes single bytes.
-#include "sg_common.h"
+#include "sg_host.h"
 
 #define SG_U8_THREADS 256
 
@@ -44,8 +44,6 @@ sg_frames_to_u8_kernel(size_t HW, const float *__restrict__ rgb, int bgr, uint8_
     }
 }
 
-int sg_set_error(const char *what, hipError_t e);
-
 extern "C" int sg_frames_to_u8(int K, int width, int height, const float *rgb, int bgr, uint8_t *out, void *stream)
 {
     if (K < 1 || K > 65535) return sg_set_error("sg_frames_to_u8: K must be 1..65535", hipSuccess);
@@ -58,6 +56,5 @@ extern "C" int sg_frames_to_u8(int K, int width, int height, const float *rgb, i
     hipStream_t st = (hipStream_t)stream;
     if (vec) hipLaunchKernelGGL(sg_frames_to_u8_kernel<true>, grid, block, 0, st, HW, rgb, bgr ? 1 : 0, out);
     else hipLaunchKernelGGL(sg_frames_to_u8_kernel<false>, grid, block, 0, st, HW, rgb, bgr ? 1 : 0, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : sg_set_error("sg_frames_to_u8", e);
+    return sg_launched("sg_frames_to_u8");
 }
