@@ -172,6 +172,12 @@ _PROTOTYPES = {
     "sg_profile_collect": "i: d n i",
     "sg_kernel_name": "s: i",
 }
+# The evaluation entry points of include/sings_eval.h, in the same mini-language: a second header and a second table, so that
+# include/sings_hip.h, EXPORTS and SG_ABI_VERSION stay what callers of the render path built against.  load() binds both tables.
+_PROTOTYPES_EVAL = {
+    "sg_image_metrics_ws_bytes": "z: i3",
+    "sg_image_metrics_frames": "i: i4 p2 z p z p3",
+}
 _P = C.POINTER
 _CTYPE = {"i": C.c_int, "z": C.c_size_t, "f": C.c_float, "s": C.c_char_p,
           "p": C.c_void_p,                        # a raw device pointer (or NULL), and the stream
@@ -186,6 +192,10 @@ LPIPS_WS_NUM_PIECES = 28             # SG_LPIPS_WS_NUM_PIECES
 LPIPS_MIN_SIZE = 16                  # SG_LPIPS_MIN_SIZE
 NUM_KERNELS = 8
 ABI_VERSION = 8                      # SG_ABI_VERSION
+METRICS_CLAMP = 1                    # SG_METRICS_CLAMP
+METRICS_FLOATS = 8                   # SG_METRICS_FLOATS
+METRICS_STRIP_COLS = 64              # SG_METRICS_STRIP_COLS
+METRICS_CHUNK_ROWS = 32              # SG_METRICS_CHUNK_ROWS
 FLAG_SHORT_LISTS = 1                 # SG_FLAG_SHORT_LISTS
 COUNT_FLAG_HALF_ROWS = 4             # SG_COUNT_FLAG_HALF_ROWS
 COUNT_FLAG_HALF_LONG_ROWS = 8        # SG_COUNT_FLAG_HALF_LONG_ROWS
@@ -224,7 +234,7 @@ def load():
     if lib.sg_abi_version() != ABI_VERSION:
         raise RuntimeError(f"sings_amd: {LIB_PATH} speaks ABI {lib.sg_abi_version()}, this host code ABI {ABI_VERSION} "
                            "(include/sings_hip.h SG_ABI_VERSION): rebuild with `make -C sings_amd/csrc`")
-    for name, signature in _PROTOTYPES.items():
+    for name, signature in (*_PROTOTYPES.items(), *_PROTOTYPES_EVAL.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = _ctypes_of(signature)
     _lib = lib
