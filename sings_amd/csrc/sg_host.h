@@ -3,6 +3,7 @@
 #pragma once
 #include "sg_common.h"
 
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -22,6 +23,20 @@ static inline int sg_launched(const char *what)
 {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : sg_set_error(what, e);
+}
+
+// The reference's 11-tap SSIM window (losses/utils.py:28-30): the fp32 values exp(-(x-5)^2 / (2 * 1.5^2)) divided by their sum AS
+// torch.Tensor.sum() GIVES IT -- the correctly rounded sum (0x1.e12e8ap+1: summed in fp64, rounded once), not the left-to-right fp32 sum
+// (one ulp less: nine weights one ulp larger, the window's sum 1 + 8.9e-8 instead of 1 - 6.2e-8 -- on a smooth frame, where
+// 2 sigma12 + C2 is a small difference of window sums, that moves the SSIM mean by 5e-6 to 1e-5: LAB.md "Validation on the device",
+// "Photometric loss on smooth frames").  The one copy: the training loss (sg_loss.hip) and the validation metrics (sg_metrics.hip)
+// weigh a frame with the same bits, those of tests/golden/photo_loss_golden.npz `window_1d`.
+static inline void sg_ssim_window(float w[11])
+{
+    float g[11];
+    double s = 0.0;
+    for (int x = 0; x < 11; x++) { g[x] = (float)exp(-(double)((x - 5) * (x - 5)) / (2.0 * 1.5 * 1.5)); s += (double)g[x]; }
+    for (int x = 0; x < 11; x++) w[x] = g[x] / (float)s;
 }
 
 // between the launches of one entry point: return on a launch error; SgRasterSettings.debug also waits for the kernel

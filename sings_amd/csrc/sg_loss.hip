@@ -25,7 +25,7 @@
 // + mask 4 = 40; the halo re-reads (x 1.19 columns, x (R + 20) / R rows) and the second read of the centre row are L2 / Infinity
 // Cache hits.  Every pixel's sums run in the same order over its own 21 x 21 neighbourhood, so pixels with identical
 // neighbourhoods get identical bits wherever they lie in a strip (tests: flat background of an avatar frame).
-#include "sg_common.h"
+#include "sg_host.h"
 
 #define SG_LN 64                  // lanes of a strip = columns whose window statistics it holds
 #define SG_NP 256                 // mask partial sums per frame
@@ -695,12 +695,7 @@ static SgLossArgs sg_loss_args(int K, bool grad, int W, int H, float l1_w, float
     SgLossArgs a;
     a.W = W; a.H = H; a.l1_w = l1_w; a.ssim_w = ssim_w; a.up_stride = up_stride;
     a.gt_stride = gt_stride; a.mask_stride = mask_stride; a.ws_stride = sg_photo_loss_ws_bytes_impl(W, H);
-    {   // losses/utils.py:28-30 in fp32, like torch.Tensor([...]) / sum()
-        float g[11], s = 0.0f;
-        for (int x = 0; x < 11; x++) { g[x] = (float)exp(-(double)((x - 5) * (x - 5)) / (2.0 * 1.5 * 1.5)); }
-        for (int x = 0; x < 11; x++) s += g[x];
-        for (int x = 0; x < 11; x++) a.w[x] = g[x] / s;
-    }
+    sg_ssim_window(a.w);                                      // (sg_host.h: the reference's fp32 window, bit for bit)
     {   // strips x chunks: at most SG_LOSS_UNITS units per launch (one round of workgroups), chunks of at least 16 rows
         const int nout = grad ? SgLossGeo<true>::NOUT : SgLossGeo<false>::NOUT;
         a.nstrips = (W + nout - 1) / nout;

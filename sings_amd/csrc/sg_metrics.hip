@@ -272,15 +272,7 @@ static bool sg_metrics_args(int W, int H, size_t gt_stride, size_t mask_stride, 
 {
     if (W < 1 || H < 1 || (size_t)W * (size_t)H >= ((size_t)1 << 30)) return false;
     a.W = W; a.H = H; a.gt_stride = gt_stride; a.mask_stride = mask_stride;
-    {   // losses/utils.py:28-30: fp32 values, divided by their sum AS torch.Tensor.sum() GIVES IT -- the correctly rounded sum
-        // (0x1.e12e8ap+1), not the left-to-right fp32 sum (one ulp less: nine weights one ulp larger, the window's sum 1 + 8.9e-8
-        // instead of 1 - 6.2e-8 -- on a smooth frame, where 2 sigma12 + C2 is a small difference of window sums, that moves the SSIM
-        // mean by 1e-5: LAB.md "Validation on the device")
-        float g[11];
-        double s = 0.0;
-        for (int x = 0; x < 11; x++) { g[x] = (float)exp(-(double)((x - 5) * (x - 5)) / (2.0 * 1.5 * 1.5)); s += (double)g[x]; }
-        for (int x = 0; x < 11; x++) a.w[x] = g[x] / (float)s;
-    }
+    sg_ssim_window(a.w);                                      // (sg_host.h: the reference's fp32 window, bit for bit)
     a.nstrips = (W + SGM_LN - 1) / SGM_LN;
     const int most = (H + SG_METRICS_CHUNK_ROWS - 1) / SG_METRICS_CHUNK_ROWS;
     int nch = SGM_UNITS / (3 * a.nstrips);

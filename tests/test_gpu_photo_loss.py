@@ -88,11 +88,14 @@ def test_full_hd_deterministic_and_flat_image_properties():
 
 
 def test_flat_tiles_take_the_short_path_with_the_same_bits():
-    """An avatar frame: the body covers part of the image, the rest is background on both sides (render = bg, mask = 0).  Workgroups
-    whose whole 42 x 42 halo tile holds ONE value evaluate one 11-tap chain per quantity instead of the tile's (sg_tile_is_flat).
+    """An avatar frame: the body covers part of the image, the rest is background on both sides (render = bg, mask = 0).  The first
+    wave of the marching gradient kernel hands on the window sums of the row above when the 74 staged (x, y) pairs of a row are all
+    equal and equal to that row's (REPEATED ROWS in csrc/sg_loss.hip), instead of the LDS round trip and the 11-tap chains.
     (i) the result agrees with the oracle like any other image; (ii) a pixel's gradient depends on its 21 x 21 neighbourhood only
-    (two 11-tap windows), so every pixel with a flat neighbourhood -- whether its tile went the short way (far from the body) or
-    the long way (tiles that also hold part of the body, tiles at the image border) -- must carry the SAME gradient bits."""
+    (two 11-tap windows), so every pixel with a flat neighbourhood -- whether its rows went the short way (strips far from the body)
+    or the long way (strips that also hold part of the body, rows at the image border) -- must carry the SAME gradient bits.  (The
+    32 x 32 tiles below are those of the older tiled kernel; they still split the flat pixels into ones near the body or the border
+    and ones far from both, which is all the two counts need.)"""
     from sings_amd.photo_loss import photometric_loss
     dev = _dev()
     W, H = 352, 288
