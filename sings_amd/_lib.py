@@ -173,10 +173,15 @@ _PROTOTYPES = {
     "sg_kernel_name": "s: i",
 }
 # The evaluation entry points of include/sings_eval.h, in the same mini-language: a second header and a second table, so that
-# include/sings_hip.h, EXPORTS and SG_ABI_VERSION stay what callers of the render path built against.  load() binds both tables.
+# include/sings_hip.h, EXPORTS and SG_ABI_VERSION stay what callers of the render path built against.  load() binds every table.
 _PROTOTYPES_EVAL = {
     "sg_image_metrics_ws_bytes": "z: i3",
     "sg_image_metrics_frames": "i: i4 p2 z p z p3",
+}
+# The mesh terms of the training step, include/sings_mesh_terms.h: a third header and a third table, for the same reason.
+_PROTOTYPES_MESH_TERMS = {
+    "sg_mesh_terms_build": "i: i3 p13",
+    "sg_mesh_terms": "i: i p4 i p13",
 }
 _P = C.POINTER
 _CTYPE = {"i": C.c_int, "z": C.c_size_t, "f": C.c_float, "s": C.c_char_p,
@@ -196,6 +201,9 @@ METRICS_CLAMP = 1                    # SG_METRICS_CLAMP
 METRICS_FLOATS = 8                   # SG_METRICS_FLOATS
 METRICS_STRIP_COLS = 64              # SG_METRICS_STRIP_COLS
 METRICS_CHUNK_ROWS = 32              # SG_METRICS_CHUNK_ROWS
+MESH_TERMS_INFO_INTS = 2             # SG_MESH_TERMS_INFO_INTS
+MESH_TERMS_BAD_LABEL = 1             # SG_MESH_TERMS_BAD_LABEL
+MESH_TERMS_BAD_EDGE = 2              # SG_MESH_TERMS_BAD_EDGE
 FLAG_SHORT_LISTS = 1                 # SG_FLAG_SHORT_LISTS
 COUNT_FLAG_HALF_ROWS = 4             # SG_COUNT_FLAG_HALF_ROWS
 COUNT_FLAG_HALF_LONG_ROWS = 8        # SG_COUNT_FLAG_HALF_LONG_ROWS
@@ -234,7 +242,7 @@ def load():
     if lib.sg_abi_version() != ABI_VERSION:
         raise RuntimeError(f"sings_amd: {LIB_PATH} speaks ABI {lib.sg_abi_version()}, this host code ABI {ABI_VERSION} "
                            "(include/sings_hip.h SG_ABI_VERSION): rebuild with `make -C sings_amd/csrc`")
-    for name, signature in (*_PROTOTYPES.items(), *_PROTOTYPES_EVAL.items()):
+    for name, signature in (*_PROTOTYPES.items(), *_PROTOTYPES_EVAL.items(), *_PROTOTYPES_MESH_TERMS.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = _ctypes_of(signature)
     _lib = lib

@@ -24,6 +24,7 @@ A topology change (or a new SH degree) invalidates everything that was sized or 
     the pair-capacity hint          re-measured with synchronous steps before the overflow check is deferred again
     Adam's moments, the statistics  ONE row map ``src`` per change (``_replace_set``): new row i takes its moments (``prune_and_simplify``: its
                                     statistics too) from old row ``src[i]`` or, at -1, starts at zero (``optim.take_rows``), as the reference does
+    the mesh terms                  ``MeshTerms.reset``: the CSR of the new edges, built on the device; a holder of the old set refuses
     the frame-parallel collective   sized by the new flat buffer; the statistics are reduced (sum, sum, max) BEFORE the decision, so every
                                     rank takes the same one (``densify_decision`` is a pure function of the reduced statistics)
 
@@ -96,14 +97,26 @@ class AvatarTrainer:
     fused optimiser refuses parameters without a gradient).  With ``poses=None`` nothing changes.
 
     ``mesh``: a ``sings_amd.topology.MeshState`` over the anchors (faces, unique edges, vertex labels, level ids) -- what
-    ``densify_and_subdivide`` and ``prune_and_simplify`` need and keep up to date.  With ``mesh=None`` nothing changes."""
+    ``densify_and_subdivide`` and ``prune_and_simplify`` need and keep up to date.  With ``mesh=None`` nothing changes.
+
+    ``mesh_terms``: a ``sings_amd.mesh_terms.MeshTerms`` -- the region Laplacians of the anchor positions and of the DC colours, the hand
+    Laplacian and the mesh edge term of gs_trainer.py:366-399.  Needs ``mesh=``.  The trainer hands it to the module, calls its ``reset``
+    whenever the set changes (the mesh's current edges and labels; vertex normals from ``avatar_init.initial_attributes``, which is
+    parity-unpinned, INTEGRATION.md 13: of the anchors at construction, of the vertices a densify / prune produced afterwards; the
+    same vertices for the constant edge term) and ``set_iteration(self.iteration)`` before every step: a captured step replays with the
+    iteration's own weights.  With ``mesh_terms=None`` nothing changes."""
 
     POSE_GROUPS = ("global_orient", "body_pose", "transl")
     STATS = ("xyz_gradient_accum", "denom", "max_radii2D")      # the module's densification statistics, one row per Gaussian
 
     def __init__(self, module, settings_fn, bg_color, lrs, smpl_scale=None, transl=None, use_graph=False, fp=None,
                  sh_degree=0, max_sh_degree=3, betas=(0.9, 0.999), eps=1e-15, optimizer="torch", lr_schedules=None, poses=None,
-                 mesh=None):
+                 mesh=None, mesh_terms=None):
+        if mesh_terms is not None and mesh is None:
+            raise ValueError("AvatarTrainer: mesh_terms needs mesh=MeshState(...) (the edges and labels the terms are built from)")
+        self.mesh_terms, self._mesh_verts = mesh_terms, None
+        if mesh_terms is not None:
+            module.mesh_terms = mesh_terms
         if mesh is not None and mesh.num_verts != int(module.xyz.shape[0]):
             raise ValueError(f"AvatarTrainer: the mesh has {mesh.num_verts} vertices, the module {int(module.xyz.shape[0])} Gaussians")
         self.mesh, self.last_subdivision, self.last_simplification = mesh, None, None
@@ -170,10 +183,24 @@ class AvatarTrainer:
             self.views = _dec.set_gradient_arena(self.params, self.flat)
         if self.fused:
             self.opt.bind_arena(self.flat, self.views)
+        if self.mesh_terms is not None:
+            self._reset_mesh_terms()
         if self.dev.type == "cuda":
             overflow.set_overflow_check("sync")                  # the next steps size the pair capacity for the new set
             overflow.reset_overflow_state()
         self._sizing = 2 if self.use_graph else 0
+
+    def _reset_mesh_terms(self):
+        """The mesh terms for the current mesh: the vertices the last topology call produced (the anchors before the first), their normals."""
+        from .avatar_init import initial_attributes
+        verts = self.m.xyz.detach() if self._mesh_verts is None else self._mesh_verts
+        if self.mesh.num_verts != int(verts.shape[0]):
+            raise RuntimeError(f"AvatarTrainer: the mesh has {self.mesh.num_verts} vertices, the new set {int(verts.shape[0])} Gaussians: "
+                               "with mesh_terms the set changes through densify_and_subdivide / prune_and_simplify only")
+        self._mesh_verts = None
+        with torch.no_grad():
+            normals = initial_attributes(verts.contiguous(), self.mesh.faces, self.mesh.edges)["normals"]
+        self.mesh_terms.reset(self.mesh, normals, verts)
 
     def _body(self):
         for p in self.params:
@@ -255,6 +282,8 @@ class AvatarTrainer:
         for g in self.opt.param_groups:
             if g["name"] in self.lr_schedules:
                 g["lr"] = self.lr_schedules[g["name"]](self.iteration)
+        if self.mesh_terms is not None:
+            self.mesh_terms.set_iteration(self.iteration)        # (device weights: a captured step replays with this iteration's)
         if self.fused:
             self.opt.advance()                                   # host half: this step's rows are on their way before the body runs
         if self.use_graph and self._sizing == 0:
@@ -378,6 +407,7 @@ class AvatarTrainer:
                 sm[n_old:] *= (interpolated / m.decode()["scales"][n_old:].mean(-1)).unsqueeze(1)     # decoded mean scale := interpolated
 
             mesh.replace(sub_faces, attr["vertex_label"])
+            self._mesh_verts = sub_vertices if self.mesh_terms is not None else None
             self._replace_set(torch.cat([m.xyz.detach(), sub_vertices[n_old:]]), attr["lbs_weights"],
                               self._appended(n_old, n_new - n_old), scaling_multiplier=sm, then=post_process)
             self.last_subdivision = {"interpolated_scales": interpolated, "n_old": n_old}
@@ -426,6 +456,7 @@ class AvatarTrainer:
             sm = m.scaling_multiplier
             per_gaussian = torch.is_tensor(sm) and sm.dim() > 0 and sm.shape[0] == n_old and n_old != 1
             mesh.prune(new_faces, keep)
+            self._mesh_verts = result[0] if self.mesh_terms is not None else None
             self._replace_set(m.xyz.detach()[keep], m.lbs_weights[keep], torch.arange(n_old, device=self.dev)[keep],
                               scaling_multiplier=sm[keep].clone() if per_gaussian else None, keep_stats=True, then=self._reset_opacity)
             n_new = int(m.xyz.shape[0])

@@ -6,6 +6,7 @@
     clamp + L1 + SSIM                                 losses/loss.py:55-69         sings_amd/photo_loss.py
     LPIPS-VGG patch term (optional)                   losses/loss.py:71-80         sings_amd/lpips.py
     regularisers (optional)                           gs_trainer.py:355-399        sings_amd/regularizers.py
+    mesh terms (optional)                             gs_trainer.py:366-399        sings_amd/mesh_terms.py
     backward through all of it
 
 Everything between the parameters and the scalar loss runs in HIP kernels (library GEMMs for the decoders' forward /
@@ -151,8 +152,11 @@ def capture_step(fn, warmup=3, device=None):
 class AvatarStep(torch.nn.Module):
     def __init__(self, xyz_anchor, lbs_weights, triplane, geometry_dec, appearance_dec, l1_w=0.8, ssim_w=0.2,
                  thickness_factor=1.0, scaling_multiplier=None, l2_norm=None, gaussian_connect=None, gaussian_connect_w=0.0,
-                 overlap_regularisers=True, defer_regulariser_join=False, lpips=None, lpips_w=0.0, lpips_patch_size=128):
+                 overlap_regularisers=True, defer_regulariser_join=False, lpips=None, lpips_w=0.0, lpips_patch_size=128,
+                 mesh_terms=None):
         super().__init__()
+        # the mesh terms (gs_trainer.py:366-399): a sings_amd.mesh_terms.MeshTerms that has been reset() for these anchors' mesh, or None
+        self.mesh_terms = mesh_terms
         # the LPIPS patch term (loss.py:71-80): a sings_amd.lpips.LPIPS, its weight (human.loss.lpips_w) and patch size
         self.lpips, self.lpips_w, self.lpips_patch_size = lpips, float(lpips_w), int(lpips_patch_size)
         self.overlap_regularisers, self._side = bool(overlap_regularisers), None
@@ -225,7 +229,7 @@ class AvatarStep(torch.nn.Module):
         process, a captured callable that returns tensors still carrying their autograd graph), and keep the regularisers on
         the ONE side stream this module owns (``GaussiansEdgeLoss.finish`` refuses any other stream while capturing)."""
         has_knn = self.gaussian_connect is not None and self.gaussian_connect_w > 0
-        has_reg = self.l2_norm is not None or has_knn
+        has_reg = self.l2_norm is not None or has_knn or self.mesh_terms is not None
         overlap = has_reg and self.overlap_regularisers and self.xyz.is_cuda
         defer = (overlap and self.defer_regulariser_join and torch.is_grad_enabled() and has_knn
                  and hasattr(self.gaussian_connect, "prepare"))
@@ -253,6 +257,8 @@ class AvatarStep(torch.nn.Module):
         def regularisers():
             if self.l2_norm is not None:
                 reg["l2"] = self._l2(use)
+            if self.mesh_terms is not None:
+                reg.update(self.mesh_terms(use))
             if has_knn:
                 reg["gaussian_connect_loss"] = self.gaussian_connect_w * self.gaussian_connect(
                     {"xyz_canon": use["xyz_canon"], "scales": use["scales"]})
@@ -330,9 +336,15 @@ class AvatarStep(torch.nn.Module):
         # No autograd on the side stream: both regularisers' kernels compute their gradients with the value (`last_grads`), and the
         # engine's stream bookkeeping around an autograd call put a wait for THIS stream's newest kernel in front of them.
         side.wait_event(decoded)
-        reg, l2_grads = {}, None
+        reg, l2_grads, mt_grads = {}, None, None
         det = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in use.items()}
         with torch.cuda.stream(side):
+            if self.mesh_terms is not None:
+                # in front of the k-NN preparation: three launches whose gradients (`last_grads`, buffers the module owns) join the
+                # photometric ones in step 2 of the staged backward
+                reg.update(self.mesh_terms(det))
+                mt_grads = (self.mesh_terms.last_grads, torch.cuda.Event())
+                mt_grads[1].record(side)
             if self.l2_norm is not None:
                 # in front of the k-NN query on this stream: the appearance decoder's backward needs the opacity term
                 reg["l2"] = self._l2(det)
@@ -358,6 +370,7 @@ class AvatarStep(torch.nn.Module):
         loss_dict.update(reg)
         extras["loss_roots"] = (photo_root, reg_root)
         extras["staged"] = (attrs, use, inject, l2_grads)
+        extras["staged_mesh_terms"] = mt_grads
 
     def _finish_joined(self, loss_dict, reg, regularisers, side):
         """The one-root tail of ``forward``: the regularisers joined (or, without a side stream, run here), -> the loss."""
@@ -429,6 +442,18 @@ class AvatarStep(torch.nn.Module):
             #  for it -- 1.867-1.875 ms either way, same box: its length is the work of BOTH queues, LAB 6.8)
             for x, y in zip(both_a, both_b):
                 x.add_(y)
+        #    the mesh terms' gradients, next to them; the colour gradient goes into the DC rows of the photometric `shs` gradient in
+        #    place (no [N,16,3] temporary)
+        mt_grads = extras.get("staged_mesh_terms")
+        if mt_grads is not None:
+            cur.wait_event(mt_grads[1])
+            for k in ("xyz_canon", "scales"):
+                if k in g:
+                    g[k] = mt_grads[0][k].clone() if g[k] is None else g[k].add_(mt_grads[0][k])
+            if "shs" in g:
+                if g["shs"] is None:
+                    g["shs"] = torch.zeros_like(use["shs"])
+                (g["shs"][:, 0] if g["shs"].dim() == 3 else g["shs"]).add_(mt_grads[0]["shs_dc"])
         # 3. the decoders' backward: appearance decoder first (its nodes are the youngest), then the _Inject node waits for the side stream
         #    (behind them the learned pose's dL/dA and dL/dtransl, if any: the oldest node of the step, one launch, reached last)
         roots = [(attrs[k], g[k]) for k in names if g.get(k) is not None] + pose_roots
@@ -439,5 +464,8 @@ class AvatarStep(torch.nn.Module):
         total = photo_root.detach() + reg_root.detach()
         if l2_grads is not None:
             total = total + loss_dict["l2"].reshape(())
+        if mt_grads is not None:
+            for k in self.mesh_terms.KEYS:
+                total = total + loss_dict[k].reshape(())
         loss_dict["loss"] = total
         return loss_dict["loss"]
