@@ -482,7 +482,10 @@ int sg_l2norm_reg(int N, const float *xyz_offsets, const float *scales, const fl
 /* GaussiansEdgeLoss.forward (:57-90): mean_edge_i = mean Euclidean distance to the K-1 nearest other points
  * (K = 9 in the reference, K in {5, 9, 17} supported, N >= K), exact, uniform-grid search instead of the brute-force
  * pytorch3d.ops.knn_points; loss = mean((scales[:,0] - mean_edge)^2), gradient to scales only (edge lengths are
- * detached in the reference).  mean_edge_out [N] optional; scales NULL = neighbour search only. */
+ * detached in the reference).  mean_edge_out [N] optional; scales NULL = neighbour search only.
+ * Every coordinate of xyz must be FINITE (no NaN, no Inf; not checked).  Any finite cloud is accepted -- flat, thin,
+ * colinear, coincident, N barely above K: both search grids are sized to at most the cells the workspace holds
+ * (csrc/sg_knn_grid.h), and the result does not depend on the grid. */
 size_t sg_knn_ws_bytes(int N);
 int sg_gaussian_edge_loss(int N, int K, const float *xyz, const float *scales, void *ws, float *mean_edge_out,
                           float *loss, const float *upstream, float *d_scales, void *stream);

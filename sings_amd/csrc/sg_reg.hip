@@ -10,6 +10,7 @@
 // All HBM / latency-bound graph work: CSR gathers (no scatter, no float atomics -> deterministic), a uniform-grid
 // exact k-nearest-neighbour search instead of the O(N^2) brute force, fixed-order two-stage reductions.
 #include "sg_common.h"
+#include "sg_knn_grid.h"
 
 #define SG_RED_MAXQ 8
 // block partial sums -> partial[blockIdx.x][q]; every thread passes its NQ values
@@ -244,10 +245,6 @@ sg_l2norm_grad_kernel(SgL2Args a, const float *__restrict__ off, const float *__
 
 // ---------------------------------------------------------------------------------------------------------
 // Exact k nearest neighbours on a uniform grid.  grid params live in device memory (computed on the device):
-struct SgGrid {
-    float lo[3], inv_h, h;
-    int dim[3], ncells;
-};
 __global__ void __launch_bounds__(256)
 sg_bbox_partial_kernel(int N, const float *__restrict__ xyz, float *__restrict__ partial /* [nb][8]: min xyz, max xyz */)
 {
@@ -274,7 +271,7 @@ sg_bbox_partial_kernel(int N, const float *__restrict__ xyz, float *__restrict__
         partial[(size_t)blockIdx.x * 8 + 3 + c] = fmaxf(fmaxf(sMx[0][c], sMx[1][c]), fmaxf(sMx[2][c], sMx[3][c]));
     }
 }
-// one workgroup: bounding box -> cell edge h with ~max_cells cells in the box, dims clamped
+// one workgroup: bounding box -> grid (sg_knn_grid.h: cell edge h with ~max_cells cells in the box, never more)
 __device__ __forceinline__ void sg_grid_setup_body(const float *__restrict__ partial, int nblocks, int N, int max_cells, SgGrid *__restrict__ grid)
 {
     __shared__ float sMn[256][3], sMx[256][3];
@@ -291,23 +288,7 @@ __device__ __forceinline__ void sg_grid_setup_body(const float *__restrict__ par
             }
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        float ext[3], vol = 1.0f, emax = 0.0f;
-        for (int c = 0; c < 3; c++) { ext[c] = sMx[0][c] - sMn[0][c]; emax = fmaxf(emax, ext[c]); }
-        if (!(emax > 0.0f)) emax = 1.0f;
-        for (int c = 0; c < 3; c++) { ext[c] = fmaxf(ext[c], 1e-3f * emax); vol *= ext[c]; }
-        float h = cbrtf(vol / (float)max_cells);
-        int dim[3];
-        for (int it = 0; it < 8; it++) {                       // grow h until the cell count fits
-            long long n = 1;
-            for (int c = 0; c < 3; c++) { dim[c] = (int)(ext[c] / h) + 1; n *= dim[c]; }
-            if (n <= (long long)max_cells) break;
-            h *= 1.1f;
-        }
-        grid->h = h; grid->inv_h = 1.0f / h;
-        for (int c = 0; c < 3; c++) { grid->lo[c] = sMn[0][c]; grid->dim[c] = dim[c]; }
-        grid->ncells = dim[0] * dim[1] * dim[2];
-    }
+    if (threadIdx.x == 0) sg_knn_grid_size(sMn[0], sMx[0], max_cells, grid);
 }
 __device__ __forceinline__ void sg_cell_of(const SgGrid &g, float x, float y, float z, int c[3])
 {
@@ -693,8 +674,6 @@ void sg_launch_l2norm(int N, const float *off, const float *scales, const float 
 
 // workspace of the k-NN search: partials, then per grid (coarse, fine): grid struct, per-point cell / rank, sorted points,
 // cell counters + starts + block sums + (start, count) pairs
-static inline int sg_knn_max_cells(int N) { long long c = 4LL * N; if (c < 4096) c = 4096; if (c > (1 << 23)) c = 1 << 23; return (int)c; }
-static inline int sg_knn_max_cells_fine(int N) { long long c = 32LL * N; if (c < 4096) c = 4096; if (c > (1 << 25)) c = 1 << 25; return (int)c; }
 static size_t sg_knn_grid_bytes(size_t n, size_t mc)
 {
     return 256 + 2 * sg_align(n * 4) + sg_align(n * 16) + 2 * sg_align(mc * 4) + sg_align(((mc + 1023) / 1024) * 4) + sg_align(mc * 8);
