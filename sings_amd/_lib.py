@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SINGS_HIP_LIB: another build of the SAME library (kernel experiments: tools/build_variants.sh); never a fallback
 LIB_PATH = os.environ.get("SINGS_HIP_LIB") or os.path.join(_HERE, "libsings_hip.so")
 _lib = None
+HAS_ORDER = False                    # set by load(): the library exports the table of include/sings_order.h
 
 
 class SgRasterSettings(C.Structure):
@@ -183,6 +184,11 @@ _PROTOTYPES_MESH_TERMS = {
     "sg_mesh_terms_build": "i: i3 p13",
     "sg_mesh_terms": "i: i p4 i p13",
 }
+# The work order of a K-camera launch, include/sings_order.h: a fourth header and a fourth table, for the same reason.
+_PROTOTYPES_ORDER = {
+    "sg_rasterize_forward_frames_ordered": "i: S F i p9 z p3 n p i p",
+    "sg_work_order_codes": "i: i p4",
+}
 _P = C.POINTER
 _CTYPE = {"i": C.c_int, "z": C.c_size_t, "f": C.c_float, "s": C.c_char_p,
           "p": C.c_void_p,                        # a raw device pointer (or NULL), and the stream
@@ -201,6 +207,11 @@ METRICS_CLAMP = 1                    # SG_METRICS_CLAMP
 METRICS_FLOATS = 8                   # SG_METRICS_FLOATS
 METRICS_STRIP_COLS = 64              # SG_METRICS_STRIP_COLS
 METRICS_CHUNK_ROWS = 32              # SG_METRICS_CHUNK_ROWS
+ORDER_WINDOW_TILES = 1536            # SG_ORDER_WINDOW_TILES
+ORDER_BLOCK = 256                    # SG_ORDER_BLOCK
+ORDER_CODE_BITS = 10                 # SG_ORDER_CODE_BITS
+ORDER_WS_BYTES = 32                  # SG_ORDER_WS_BYTES
+HIST_TILES_MAX = 4096                # SG_HIST_TILES_MAX (sings_amd/csrc/sg_common.h): tile counters up to which a frame has "few tiles"
 MESH_TERMS_INFO_INTS = 2             # SG_MESH_TERMS_INFO_INTS
 MESH_TERMS_BAD_LABEL = 1             # SG_MESH_TERMS_BAD_LABEL
 MESH_TERMS_BAD_EDGE = 2              # SG_MESH_TERMS_BAD_EDGE
@@ -242,7 +253,14 @@ def load():
     if lib.sg_abi_version() != ABI_VERSION:
         raise RuntimeError(f"sings_amd: {LIB_PATH} speaks ABI {lib.sg_abi_version()}, this host code ABI {ABI_VERSION} "
                            "(include/sings_hip.h SG_ABI_VERSION): rebuild with `make -C sings_amd/csrc`")
-    for name, signature in (*_PROTOTYPES.items(), *_PROTOTYPES_EVAL.items(), *_PROTOTYPES_MESH_TERMS.items()):
+    # (SINGS_HIP_LIB may name a library that predates include/sings_order.h -- an A/B run against a parent build: it exports none of
+    # that table, HAS_ORDER says so, and the engines then make the unordered calls that library knows)
+    global HAS_ORDER
+    HAS_ORDER = all(hasattr(lib, name) for name in _PROTOTYPES_ORDER)
+    if not HAS_ORDER and LIB_PATH == os.path.join(_HERE, "libsings_hip.so"):
+        raise RuntimeError(f"sings_amd: {LIB_PATH} lacks the entry points of include/sings_order.h: rebuild with `make -C sings_amd/csrc`")
+    for name, signature in (*_PROTOTYPES.items(), *_PROTOTYPES_EVAL.items(), *_PROTOTYPES_MESH_TERMS.items(),
+                            *(_PROTOTYPES_ORDER.items() if HAS_ORDER else ())):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = _ctypes_of(signature)
     _lib = lib

@@ -1,6 +1,7 @@
 // extern "C" boundary of the rasterizer (see include/sings_hip.h): settings -> camera, the frame batch, the early pair count,
 // and the forward / backward entry points of the plain and the skinned paths, with and without the depth / alpha maps.
 #include "sg_host.h"
+#include "../../include/sings_order.h"
 
 #include <chrono>
 #include <stdlib.h>
@@ -149,15 +150,25 @@ static int sg_aux_flags(const char *who, int flags, bool frames)
     return 0;
 }
 
+// A work order (include/sings_order.h) is P entries or none; the kernels never dereference an entry >= P.
+static int sg_check_order(const char *who, const uint32_t *order, int order_len, int P)
+{
+    if (!order) return order_len ? sg_failf("%s: order_len %d without an order", who, order_len) : 0;
+    if (order_len != P) return sg_failf("%s: the order has %d entries, the call %d Gaussians", who, order_len, P);
+    return 0;
+}
+
 static int sg_forward_impl(const char *who, const SgRasterSettings *s, const SgFrameBatch *fb, int P, const SgSkinInputs *skin,
                            const float *means3D, const float *shs, const float *colors_precomp, const float *opacities,
                            const float *scales, const float *rotations, const float *cov3D_precomp, void *geom_ws, void *binning_ws,
                            size_t cap, void *image_ws, float *out_color, int32_t *radii, float *posed_xyz, float *posed_rotq,
                            float *posed_scales, int write_point_keys, int64_t *num_rendered_host, void *stream,
-                           SgAux aux = SG_AUX_NONE, void *aux_ws = nullptr, float *out_depth = nullptr, float *out_alpha = nullptr)
+                           SgAux aux = SG_AUX_NONE, void *aux_ws = nullptr, float *out_depth = nullptr, float *out_alpha = nullptr,
+                           const uint32_t *order = nullptr, int order_len = 0)
 {
     hipStream_t st = (hipStream_t)stream;
     SgCam c;
+    if (sg_check_order(who, order, order_len, P)) return 1;
     if (aux && !aux_ws) return sg_failf("%s: null pointer (aux_ws)", who);
     if (sg_make_cam(s, &c)) return sg_failf("%s: bad settings", who);
     if (aux) {
@@ -197,7 +208,8 @@ static int sg_forward_impl(const char *who, const SgRasterSettings *s, const SgF
             for (int f = 0; f < bt.K; f++) sg_zero_async((char *)b.header + (size_t)f * bt.bin, zb, st);
         }
         if (skin) sg_launch_skin_fwd(c, bt, P, skin, shs, opacities, scales, g, b, cap, radii, posed_xyz, posed_rotq, posed_scales, st);
-        else sg_launch_preprocess_fwd(c, bt, P, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, g, b, cap, radii, st);
+        else sg_launch_preprocess_fwd_ordered(c, bt, P, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, g, b, cap,
+                                              radii, order, st);
         SG_CHECK_LAST("preprocess_fwd", s, st);
         sg_launch_binning(c, bt, P, radii, g, b, cap, write_point_keys, st);
         SG_CHECK_LAST("binning", s, st);
@@ -612,4 +624,26 @@ extern "C" int sg_skinned_backward_gaussians_frames_aux(const SgRasterSettings *
     return sg_skin_gaussians_impl("sg_skinned_backward_gaussians_frames_aux", s, fb, P, skin, shs, scales, radii, geom_ws, binning_ws,
                                   cap, bwd_ws, skin_ws, accumulate, dL_dposed_xyz_in, dL_dposed_rotq_in, dL_dxyz_canon, dL_drot_canon,
                                   dL_dscales, dL_dopacity, dL_dsh, dL_dmeans2D, dL_dA, dL_dtransl, stream, SG_AUX_FRAMES, aux_ws);
+}
+
+// ---- work order (include/sings_order.h) ------------------------------------------------------------------------------------------
+extern "C" int sg_rasterize_forward_frames_ordered(const SgRasterSettings *s, const SgFrameBatch *fb, int P, const float *means3D,
+                                                   const float *shs, const float *colors_precomp, const float *opacities,
+                                                   const float *scales, const float *rotations, const float *cov3D_precomp,
+                                                   void *geom_ws, void *binning_ws, size_t cap, void *image_ws, float *out_color,
+                                                   int32_t *radii, int64_t *num_rendered_host, const uint32_t *order, int order_len,
+                                                   void *stream)
+{
+    return sg_forward_impl("sg_rasterize_forward_frames_ordered", s, fb, P, nullptr, means3D, shs, colors_precomp, opacities, scales,
+                           rotations, cov3D_precomp, geom_ws, binning_ws, cap, image_ws, out_color, radii, nullptr, nullptr, nullptr,
+                           0, num_rendered_host, stream, SG_AUX_NONE, nullptr, nullptr, nullptr, order, order_len);
+}
+
+extern "C" int sg_work_order_codes(int P, const float *means3D, void *ws, uint32_t *codes, void *stream)
+{
+    if (P < 0) return sg_failf("sg_work_order_codes: P = %d", P);
+    if (P == 0) return 0;
+    if (!means3D || !ws || !codes) return sg_failf("sg_work_order_codes: null pointer");
+    sg_launch_morton_codes(P, means3D, (float *)ws, codes, (hipStream_t)stream);
+    return sg_launched("sg_work_order_codes");
 }

@@ -58,3 +58,13 @@ void sg_launch_scales_head(int N, const float *z, float *scales, float *aux, con
 void sg_launch_rows_laplacian(int R, int V, int C, const float *x, const int *row_ptr, const int *col, const float *val,
                               const float *rscale, const int *t_row_ptr, const int *t_row, const float *t_val, void *ws, float *g_ws,
                               float *loss, const float *upstream, float *dL_dx, hipStream_t st);
+
+// ---- work order (include/sings_order.h) ----
+// Where a work order takes effect: many-tile frames binned directly (SG_FLAG_SHORT_LISTS, no whole-image histogram).  Elsewhere the
+// launch is the unordered one -- any order is correct, so is none.
+static inline bool sg_order_applies(const SgCam &c) { return !sg_lds_hist(c.gx, c.gy) && sg_key_pitch_of(false, c.flags) != 0u; }
+void sg_launch_preprocess_fwd_ordered(const SgCam &c, const SgBatch &bt, int P, const float *means3D, const float *shs,
+                                      const float *colors_precomp, const float *opacities, const float *scales,
+                                      const float *rotations, const float *cov3D_precomp, SgGeom g, SgBin b,
+                                      size_t cap, int32_t *radii, const uint32_t *order, hipStream_t st);
+void sg_launch_morton_codes(int P, const float *means3D, float *box, uint32_t *codes, hipStream_t st);

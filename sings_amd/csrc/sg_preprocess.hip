@@ -6,8 +6,11 @@
 // HBM-bound streaming kernels: forward reads `in` bytes per Gaussian and writes a 56-B projected
 // record; backward re-reads the inputs, sums the Gaussian's gradient records and writes 248 B.
 #include "sg_project.h"
+#include "sg_host.h"
 
-template <int D>
+// NOBIN (include/sings_order.h): everything but the pair expansion, which sg_bin_ordered_kernel does in work order behind this kernel.
+// (A compile-time switch: the instantiation that bins keeps its code.)
+template <int D, bool NOBIN>
 __global__ void __launch_bounds__(256)
 sg_preprocess_fwd_kernel(SgCam c, SgBatch bt, int P, const float *__restrict__ means3D,
                          const float *__restrict__ shs, const float *__restrict__ colors_precomp,
@@ -16,7 +19,7 @@ sg_preprocess_fwd_kernel(SgCam c, SgBatch bt, int P, const float *__restrict__ m
                          SgGeom g, SgBin bn, uint32_t cap, int32_t *__restrict__ radii, int hist_tiles, int nblocks)
 {
     extern __shared__ uint32_t sg_hist_lds[];               // hist_tiles words (0: per-pair global atomics)
-    __shared__ uint32_t scratch_all[4][256];
+    __shared__ uint32_t scratch_all[4][NOBIN ? 1 : 256];
     // (Gaussian block, camera) of this workgroup: the K cameras of one block run back to back on ONE XCD (sg_block_frame)
     int gblock, frame;
     if (!sg_block_frame((int)blockIdx.x, bt.K, nblocks, gblock, frame)) return;
@@ -58,8 +61,31 @@ sg_preprocess_fwd_kernel(SgCam c, SgBatch bt, int P, const float *__restrict__ m
                           colors_precomp ? colors_precomp + 3 * (size_t)idx : nullptr, sh, o);
         opac = opacities[idx];
     }
+    if constexpr (NOBIN)
+        sg_store_proj_nobin(live, idx, o, opac, g, bn, radii);
+    else
     sg_store_proj(live, idx, o, opac, g, bn, c.gx, cap, radii, scratch_all[wave], hist_tiles ? sg_hist_lds : nullptr, hist_tiles,
                   sg_key_pitch_of(hist_tiles != 0, c.flags));
+}
+
+// The pair expansion of a NOBIN launch, in work order: lane i reads the rectangle (recC) and the depth of Gaussian order[i] -- what
+// the kernel above stored -- and bins it (sg_bin_ordered).  Grid: Gaussian blocks x frames.  An entry >= P is never dereferenced:
+// its lane is idle.
+__global__ void __launch_bounds__(256)
+sg_bin_ordered_kernel(SgBatch bt, int P, SgGeom g, SgBin bn, int gx, uint32_t key_pitch, const uint32_t *__restrict__ order)
+{
+    __shared__ uint32_t scratch_all[4][320];
+    const int frame = blockIdx.y;
+    g = sg_frame(g, (size_t)frame * bt.geom); bn = sg_frame(bn, (size_t)frame * bt.bin);
+    const int pos = blockIdx.x * 256 + (int)threadIdx.x, wave = threadIdx.x >> 6;
+    uint32_t gid = pos < P ? order[pos] : 0xffffffffu;
+    uint32_t rmin = 0u, rwh = 0u, dep = 0u;
+    if (gid < (uint32_t)P) {
+        const float4 rc = g.recC[SG_REC_STRIDE * (size_t)gid];
+        rmin = __float_as_uint(rc.z); rwh = __float_as_uint(rc.w);
+        dep = __float_as_uint(g.depth[gid]);
+    } else gid = 0u;
+    sg_bin_ordered(gid, rmin, rwh, dep, bn, gx, scratch_all[wave], scratch_all[wave] + 256, key_pitch);
 }
 
 void sg_launch_preprocess_fwd(const SgCam &c, const SgBatch &bt, int P, const float *means3D, const float *shs,
@@ -67,17 +93,32 @@ void sg_launch_preprocess_fwd(const SgCam &c, const SgBatch &bt, int P, const fl
                               const float *rotations, const float *cov3D_precomp, SgGeom g, SgBin b,
                               size_t cap, int32_t *radii, hipStream_t st)
 {
+    sg_launch_preprocess_fwd_ordered(c, bt, P, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, g, b, cap,
+                                     radii, nullptr, st);
+}
+
+// order != null (P entries) takes effect where sg_order_applies says so; elsewhere the launch is the unordered one
+void sg_launch_preprocess_fwd_ordered(const SgCam &c, const SgBatch &bt, int P, const float *means3D, const float *shs,
+                                      const float *colors_precomp, const float *opacities, const float *scales,
+                                      const float *rotations, const float *cov3D_precomp, SgGeom g, SgBin b,
+                                      size_t cap, int32_t *radii, const uint32_t *order, hipStream_t st)
+{
     if (P <= 0) return;
     const int nblocks = (P + 255) / 256;
     dim3 grid(sg_frame_grid(nblocks, bt.K)), block(256);
     const int ht = sg_lds_hist(c.gx, c.gy) ? (int)sg_ctr_count((uint32_t)c.gx, (uint32_t)c.gy) : 0;     // histogram words (= tile counters)
-#define SG_PP(DD) hipLaunchKernelGGL(sg_preprocess_fwd_kernel<DD>, grid, block, (size_t)ht * 4, st, c, bt, P, means3D, shs, \
+    const bool ord = order && sg_order_applies(c);
+#define SG_PPO(DD, OO) hipLaunchKernelGGL((sg_preprocess_fwd_kernel<DD, OO>), grid, block, (size_t)ht * 4, st, c, bt, P, means3D, shs, \
                                      colors_precomp, opacities, scales, rotations, cov3D_precomp, g, b, sg_cap32(cap), radii, ht, nblocks)
+#define SG_PP(DD) do { if (ord) SG_PPO(DD, true); else SG_PPO(DD, false); } while (0)
     int D = colors_precomp ? 0 : c.D;
     sg_prof_begin(SG_K_PREPROCESS_FWD, st);
     switch (D) { case 0: SG_PP(0); break; case 1: SG_PP(1); break; case 2: SG_PP(2); break; default: SG_PP(3); break; }
+    if (ord)
+        hipLaunchKernelGGL(sg_bin_ordered_kernel, dim3(nblocks, bt.K), block, 0, st, bt, P, g, b, c.gx, sg_key_pitch_of(false, c.flags), order);
     sg_prof_end(SG_K_PREPROCESS_FWD, st);
 #undef SG_PP
+#undef SG_PPO
 }
 
 // ------------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 // sings/rec/renderer/gs_renderer_single.py:87-95).  Exact operation order -- see sg_math.h.
 #pragma once
 #include "sg_math.h"
+#include "../../include/sings_order.h"
 
 template <int D>
 __device__ __forceinline__ void sg_eval_sh(const float *__restrict__ sh, const float dir[3],
@@ -268,6 +269,197 @@ __device__ __forceinline__ void sg_store_proj(bool live, int idx, const SgProj &
         }
     }
     __builtin_amdgcn_wave_barrier();
+}
+
+// ---- work order (include/sings_order.h) -------------------------------------------------------------------------------------------
+// Direct binning of a many-tile frame in two kernels.  The per-Gaussian kernel stays in id order -- coalesced loads and stores, slots
+// contiguous per wave -- and does everything of sg_store_proj but the pair expansion (sg_store_proj_nobin).  The pairs are then
+// expanded by sg_bin_ordered_kernel, whose lane i works on Gaussian order[i]: in a spatially coherent order the rectangles of a
+// workgroup's 256 Gaussians cover a small WINDOW of tiles (their bounding box, reduced in LDS).  A window of at most
+// SG_ORDER_WINDOW_TILES tiles is counted in LDS:
+//   1. every pair adds 1 to its window cell (row-major inside the window; no result is needed);
+//   2. one barrier later the touched cells are rebased: ONE global returning atomic per (workgroup, tile), walked in the 4x4 blocks
+//      of sg_ctr_index so that the 64 lanes of an instruction touch 4 counter lines, a round of four per thread in flight together;
+//   3. one barrier later every pair takes its final rank with a returning LDS add on the rebased cell and stores its key.  The
+//      ranks a workgroup takes in a tile's row are consecutive: its keys of that tile share a line of the row.
+// The first round's pairs (4 per lane) wait in registers between 1 and 3, later rounds are expanded again.  A workgroup whose
+// window is larger (one splat covering the screen inside an otherwise compact block; any block of an unordered cloud) takes the
+// per-pair path of sg_store_proj.  The branch is workgroup-uniform.  Ranks are arbitrary slots -- the composite sorts a row by
+// (depth, id) -- so the frame is bit for bit the one of the single-kernel launch.
+// (The single-kernel form -- the per-Gaussian kernel itself in work order, every record, radius, depth, flag word and slot stored at
+// order[i] -- lost: 167.6 -> 191.9 us per launch of 8 cfg3 cameras, and the record sums walking the slots in that order 62.4 -> 98.6:
+// what the atomics gave back went into 4- to 64-byte stores scattered over the id-indexed arrays.  LAB "Work order".)
+// MUST be reached by every thread of a 256-thread workgroup.
+__device__ __forceinline__ void sg_store_proj_nobin(bool live, int idx, const SgProj &o, float opac, SgGeom g, SgBin bn,
+                                                    int32_t *__restrict__ radii)
+{
+    __shared__ uint32_t sWaveTot[4];
+    __shared__ uint32_t sBlockBase;
+    const int lane = threadIdx.x & 63, wave_ = (threadIdx.x >> 6) & 3;
+    uint32_t incl = o.tt;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        uint32_t v = __shfl_up(incl, s, 64);
+        if (lane >= s) incl += v;
+    }
+    if (lane == 63) sWaveTot[wave_] = incl;
+    const uint32_t rmin = (uint32_t)o.x0 | ((uint32_t)o.y0 << 16);
+    const uint32_t rwh = (uint32_t)(o.x1 - o.x0) | ((uint32_t)(o.y1 - o.y0) << 16);
+    if (live) {
+        radii[idx] = o.mr;
+        g.recA[SG_REC_STRIDE * (size_t)idx] = make_float4(o.pix[0], o.pix[1], o.conic[0], o.conic[1]);
+        g.recB[SG_REC_STRIDE * (size_t)idx] = make_float4(o.conic[2], o.mr ? opac : 0.0f, o.rgb[0], o.rgb[1]);
+        g.depth[idx] = o.depth;
+        g.flags[idx] = o.clampbits;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                   // ONE allocator atomic per workgroup (see sg_store_proj)
+        uint32_t t = sWaveTot[0] + sWaveTot[1] + sWaveTot[2] + sWaveTot[3];
+        sBlockBase = t ? atomicAdd(&bn.header[2], t) : 0u;
+    }
+    __syncthreads();
+    uint32_t base = sBlockBase;
+    for (int w = 0; w < wave_; w++) base += sWaveTot[w];
+    if (live) {
+        g.recC[SG_REC_STRIDE * (size_t)idx] = make_float4(o.rgb[2], __uint_as_float(base + incl - o.tt), __uint_as_float(rmin), __uint_as_float(rwh));
+        g.slot[idx] = make_uint2(base + incl - o.tt, rwh);
+    }
+}
+
+// The pairs of this lane's Gaussian `gid` -- rectangle (rmin, rwh) as recC carries it, rwh = 0: none -- counted and their keys stored.
+// `scratch`: 256 words, `sGid`: 64 words of LDS private to this wave.
+#define SG_ORDER_WINDOW_MAX SG_ORDER_WINDOW_TILES
+__device__ __forceinline__ void sg_bin_ordered(uint32_t gid, uint32_t rmin, uint32_t rwh, uint32_t depthbits, SgBin bn, int gx,
+                                               uint32_t *__restrict__ scratch, uint32_t *__restrict__ sGid, uint32_t key_pitch)
+{
+    uint32_t *sIncl = scratch, *sMin = scratch + 64, *sWid = scratch + 128, *sDep = scratch + 192;
+    __shared__ uint32_t sWindow[SG_ORDER_WINDOW_MAX];
+    __shared__ uint32_t sWaveWin[4][4];
+    const int lane = threadIdx.x & 63, wave_ = (threadIdx.x >> 6) & 3;
+    const uint32_t rw = rwh & 0xffffu, rh = rwh >> 16, tt = rw * rh;
+    uint32_t incl = tt;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        uint32_t v = __shfl_up(incl, s, 64);
+        if (lane >= s) incl += v;
+    }
+    const uint32_t total = __shfl(incl, 63, 64);
+    // the wave's tile window (a lane without tiles is neutral)
+    uint32_t wx0 = tt ? (rmin & 0xffffu) : 0xffffu, wy0 = tt ? (rmin >> 16) : 0xffffu;
+    uint32_t wx1 = tt ? (rmin & 0xffffu) + rw : 0u, wy1 = tt ? (rmin >> 16) + rh : 0u;
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const uint32_t a = __shfl_xor(wx0, s, 64), b = __shfl_xor(wy0, s, 64), c = __shfl_xor(wx1, s, 64), d = __shfl_xor(wy1, s, 64);
+        wx0 = a < wx0 ? a : wx0; wy0 = b < wy0 ? b : wy0; wx1 = c > wx1 ? c : wx1; wy1 = d > wy1 ? d : wy1;
+    }
+    if (lane == 63) { sWaveWin[wave_][0] = wx0; sWaveWin[wave_][1] = wy0; sWaveWin[wave_][2] = wx1; sWaveWin[wave_][3] = wy1; }
+    for (int t = threadIdx.x; t < SG_ORDER_WINDOW_MAX; t += 256) sWindow[t] = 0u;
+    sIncl[lane] = incl; sMin[lane] = rmin; sWid[lane] = rw; sDep[lane] = depthbits; sGid[lane] = gid;
+    __syncthreads();
+    uint32_t X0 = sWaveWin[0][0], Y0 = sWaveWin[0][1], X1 = sWaveWin[0][2], Y1 = sWaveWin[0][3];
+#pragma unroll
+    for (int w = 1; w < 4; w++) {
+        X0 = sWaveWin[w][0] < X0 ? sWaveWin[w][0] : X0; Y0 = sWaveWin[w][1] < Y0 ? sWaveWin[w][1] : Y0;
+        X1 = sWaveWin[w][2] > X1 ? sWaveWin[w][2] : X1; Y1 = sWaveWin[w][3] > Y1 ? sWaveWin[w][3] : Y1;
+    }
+    const bool any = X1 > X0 && Y1 > Y0;                      // (workgroup-uniform) somebody has a pair
+    if (!any) return;
+    const uint32_t ww = X1 - X0, wh = Y1 - Y0;
+    const bool windowed = ww * wh <= (uint32_t)SG_ORDER_WINDOW_MAX;      // (ww, wh < 2^16: the product fits the word)
+    // pairs p0 + 64 u + lane of the wave: tile, Gaussian, depth bits and the counter the pair counts in -- its window cell
+    // (windowed) or its word of bn.tile_count
+    uint32_t tile[4], gj[4], dep[4], cell[4];
+    auto expand = [&](uint32_t p0) {
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const uint32_t p = p0 + 64 * u + lane;
+            tile[u] = 0; gj[u] = 0; dep[u] = 0; cell[u] = 0;
+            if (p < total) {
+                int lo = 0, hi = 63;                  // smallest j with incl[j] > p
+#pragma unroll
+                for (int it = 0; it < 6; it++) {
+                    int mid = (lo + hi) >> 1;
+                    if (sIncl[mid] > p) hi = mid; else lo = mid + 1;
+                }
+                const int j = lo;
+                const uint32_t excl = j ? sIncl[j - 1] : 0u;
+                const uint32_t t = p - excl, w = sWid[j], mn = sMin[j];
+                const uint32_t ty = (uint32_t)(((float)t + 0.5f) / (float)w);      // exact floor: t, w < 2^16
+                const uint32_t tx = t - ty * w;
+                const uint32_t ax = (mn & 0xffffu) + tx, ay = (mn >> 16) + ty;
+                tile[u] = ay * (uint32_t)gx + ax;
+                gj[u] = sGid[j];
+                dep[u] = sDep[j];
+                cell[u] = windowed ? (ay - Y0) * ww + (ax - X0) : sg_ctr_index(ax, ay, (uint32_t)gx);
+            }
+        }
+    };
+    auto store_key = [&](uint32_t tl, uint32_t rank, uint32_t d, uint32_t gi) {
+        if (rank < key_pitch) SG_KEY_STORE(&bn.tile_keys[(size_t)tl * key_pitch + rank], ((uint64_t)d << 32) | gi);
+        else bn.header[8] = 1u;                     // a list longer than its row: sticky until the scan has seen it
+    };
+    if (!windowed) {
+        // the per-pair path: a returning atomic on the tile's counter, the key at the rank it returns
+        for (uint32_t p0 = 0; p0 < total; p0 += 256) {
+            expand(p0);
+            uint32_t rank[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) rank[u] = p0 + 64 * u + lane < total ? atomicAdd(&bn.tile_count[cell[u]], 1u) : 0u;
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (p0 + 64 * u + lane < total) store_key(tile[u], rank[u], dep[u], gj[u]);
+        }
+        return;
+    }
+    // 1. count (round 0 stays in registers)
+    uint32_t tile0[4], gj0[4], dep0[4], cell0[4];
+    expand(0u);
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        tile0[u] = tile[u]; gj0[u] = gj[u]; dep0[u] = dep[u]; cell0[u] = cell[u];
+        if (64 * u + lane < total) atomicAdd(&sWindow[cell[u]], 1u);
+    }
+    for (uint32_t p0 = 256; p0 < total; p0 += 256) {
+        expand(p0);
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+            if (p0 + 64 * u + lane < total) atomicAdd(&sWindow[cell[u]], 1u);
+    }
+    __syncthreads();
+    {
+        // 2. rebase the touched cells, walked in the counters' 4x4 blocks (the blocks that the window overlaps)
+        const uint32_t bx0 = X0 >> 2, by0 = Y0 >> 2, bxn = ((X1 - 1u) >> 2) - bx0 + 1u, byn = ((Y1 - 1u) >> 2) - by0 + 1u;
+        const uint32_t cover = bxn * byn * 16u, cbx = sg_ctr_blocks_x((uint32_t)gx);
+        for (uint32_t c0 = threadIdx.x; c0 < cover; c0 += 4 * 256) {
+            uint32_t cnt[4], lc[4], ctr[4], ans[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const uint32_t c = c0 + 256u * u, b = c >> 4, i = c & 15u;
+                const uint32_t bby = (uint32_t)(((float)b + 0.5f) / (float)bxn), bbx = b - bby * bxn;      // exact floor: b, bxn < 2^16
+                const uint32_t ax = ((bx0 + bbx) << 2) + (i & 3u), ay = ((by0 + bby) << 2) + (i >> 2);
+                const bool in = c < cover && ax >= X0 && ax < X1 && ay >= Y0 && ay < Y1;
+                lc[u] = in ? (ay - Y0) * ww + (ax - X0) : 0u;
+                ctr[u] = ((by0 + bby) * cbx + bx0 + bbx) * 16u + i;
+                cnt[u] = in ? sWindow[lc[u]] : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) ans[u] = cnt[u] ? atomicAdd(&bn.tile_count[ctr[u]], cnt[u]) : 0u;
+#pragma unroll
+            for (int u = 0; u < 4; u++)
+                if (cnt[u]) sWindow[lc[u]] = ans[u];
+        }
+    }
+    __syncthreads();
+    // 3. final ranks and keys
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+        if (64 * u + lane < total) store_key(tile0[u], atomicAdd(&sWindow[cell0[u]], 1u), dep0[u], gj0[u]);
+    for (uint32_t p0 = 256; p0 < total; p0 += 256) {
+        expand(p0);
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+            if (p0 + 64 * u + lane < total) store_key(tile[u], atomicAdd(&sWindow[cell[u]], 1u), dep[u], gj[u]);
+    }
 }
 
 // ---- coalesced staging of 48-float rows ([P,16,3] SH coefficients / their gradients) through LDS:

@@ -8,12 +8,18 @@ all-reduce them with a single RCCL call (see sings_amd/dp.py).  The engines fill
 sings_amd/_marshal.py, the same functions the autograd ops use.
 """
 import ctypes as C
+import os
 
 import torch
 
 from . import _lib
+from . import work_order as _work_order
 from ._marshal import _camera_stride, _frame_batch, _frame_rows, _ptr, _settings_struct, _skin_frames, _skin_struct
 from ._marshal import _stream as _current_stream
+
+
+# RasterFramesEngine(order=None): build and keep the Morton work order (SINGS_WORK_ORDER=0: no order unless the caller passes one)
+_ORDER_BY_DEFAULT = os.environ.get("SINGS_WORK_ORDER", "1") != "0"
 
 
 def _raster_fields(M):
@@ -534,27 +540,63 @@ class SkinnedFramesEngine(_FramesEngine):
 
 class RasterFramesEngine(_FramesEngine):
     """Un-skinned path: K cameras of the same Gaussians per call (``sg_rasterize_*_frames``).  Flat gradient layout as
-    ``RasterEngine`` (``sh_planar``: dL/dsh coefficient-major [M,P,3]); ``color`` [K,3,H,W], ``radii`` [K,P], ``d_means2D`` [K,P,3]."""
+    ``RasterEngine`` (``sh_planar``: dL/dsh coefficient-major [M,P,3]); ``color`` [K,3,H,W], ``radii`` [K,P], ``d_means2D`` [K,P,3].
 
-    def __init__(self, P, W, H, sh_coeffs, K, device, capacity_pairs, grad_flat=None, sh_planar=False):
+    ``order`` (include/sings_order.h, sings_amd/work_order.py): the work order the forward bins its pairs in.  None: the Morton order
+    of the positions, built on the first ``forward`` whose frame is in the direct many-tile regime and kept until
+    ``refresh_order()`` (call it when the Gaussians have moved far, or after a densification that keeps P) -- a stale order is
+    still correct, only slower; an int32 tensor [P]: that permutation; False: no order (the unordered entry points).  The results
+    are the same bits whichever is used."""
+
+    def __init__(self, P, W, H, sh_coeffs, K, device, capacity_pairs, grad_flat=None, sh_planar=False, order=None):
         super().__init__(P, W, H, sh_coeffs, device, capacity_pairs, K)
         self._gradients(_raster_fields(self.M), grad_flat, sh_planar)
+        self.set_order(order)
+
+    def set_order(self, order):
+        """``order`` as in the constructor: None (build and keep the Morton order), an int32 tensor [P], or False."""
+        if order is None and not _ORDER_BY_DEFAULT:
+            order = False
+        self._order_auto = order is None
+        self._order = None if order is None or order is False else _work_order.check_order(order, self.P, self.geom.device)
 
     def set_camera(self, raster_settings, short_lists=False, long_rows=False):
         """As ``RasterEngine.set_camera``, with one camera or K."""
         self._camera(raster_settings, (_lib.FLAG_SHORT_LISTS if short_lists else 0) | (_lib.FLAG_LONG_ROWS if long_rows else 0))
         self._fb = _frame_batch(self.K, self._cam_stride, 0)
 
+    def refresh_order(self):
+        """Drop the built order: the next ``forward`` builds it again from the positions it is given."""
+        if self._order_auto:
+            self._order = None
+
+    def _order_for(self, means3D):
+        """The order of this call (None: the unordered launch).  Built here once, outside any graph capture."""
+        if self._order is not None and not _lib.HAS_ORDER:
+            raise RuntimeError("RasterFramesEngine: this library predates include/sings_order.h and takes no work order")
+        if (self._order is None and self._order_auto and _lib.HAS_ORDER and self.P > 0
+                and _work_order.order_applies(self.W, self.H, self._rows)):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("RasterFramesEngine: the work order is built on the first forward, which cannot be inside a graph "
+                                   "capture (run one forward first, or pass order=False / order=<tensor>)")
+            self._order = _work_order.build_order(means3D)
+        return self._order
+
     def forward(self, means3D, shs, opacities, scales, rotations, sync_num_rendered=False):
         if self._s is None or self._fb is None:
             raise RuntimeError("RasterFramesEngine: set_camera() first")
+        order = self._order_for(means3D)
         nr = (C.c_int64 * self.K)()
         self._s.flags = self._flags()
         self._clean = False
-        _lib.check(self.lib.sg_rasterize_forward_frames(
-            C.byref(self._s), C.byref(self._fb), self.P, _ptr(means3D), _ptr(shs), None, _ptr(opacities), _ptr(scales),
-            _ptr(rotations), None, _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.img), _ptr(self.color),
-            _ptr(self.radii), nr if sync_num_rendered else None, self._stream()), "forward (frames)")
+        args = (C.byref(self._s), C.byref(self._fb), self.P, _ptr(means3D), _ptr(shs), None, _ptr(opacities), _ptr(scales),
+                _ptr(rotations), None, _ptr(self.geom), _ptr(self.binning), self.cap, _ptr(self.img), _ptr(self.color),
+                _ptr(self.radii), nr if sync_num_rendered else None)
+        if order is None:
+            _lib.check(self.lib.sg_rasterize_forward_frames(*args, self._stream()), "forward (frames)")
+        else:
+            _lib.check(self.lib.sg_rasterize_forward_frames_ordered(*args, _ptr(order), order.numel(), self._stream()),
+                       "forward (frames, ordered)")
         self._clean = True
         return [int(v) for v in nr] if sync_num_rendered else None
 
