@@ -1,4 +1,5 @@
-"""Pair capacity and learned list-length hints of the three autograd rasterizer ops (rasterizer.py, skinned.py).
+"""Pair capacity and list-length hints: of the three autograd rasterizer ops (rasterizer.py, skinned.py) and, in a section of its
+own (``EngineCapacity``), of the forward-only animator's pre-allocated engines (posed.py).
 
 The workspaces of a call hold `cap` (tile, Gaussian) pairs; the forward reports the count R it produced.  The mode decides when R is read:
   "sync"     (default; the drop-in guarantee) every forward knows R before it returns and re-runs with a larger workspace if needed:
@@ -15,7 +16,7 @@ A "sync" forward's count word also says whether every tile list held <= 512 entr
 hinted frame that meets a longer list reports NUM_RENDERED_LONG_LIST and is rendered again without the hint before the call returns;
 where R is not read (the fused LBS ops pass the long-rows hint in every mode), that is a background frame reported like an overflow.
 
-The decision layer (``plan`` .. ``set_deferred_overflow_check``) works on plain ints and bools; the I/O layer below it feeds it from
+The decision layer (``plan`` .. ``EngineCapacity``) works on plain ints and bools; the I/O layer below it feeds it from
 the early-count words, the pinned ring of "async" results and the "deferred" accumulator, and ``run_forward`` is the forward loop.
 """
 import atexit
@@ -158,8 +159,58 @@ def set_deferred_overflow_check(on=True, capacity_pairs=None, device=None):
     set_overflow_check("deferred" if on else "sync", capacity_pairs=capacity_pairs, device=device)
 
 
+# ---- decision layer: the pre-allocated engines of the forward-only animator (posed.FrameAnimator) ---------------------------------
+class EngineCapacity:
+    """Pair capacity and long-rows hint of a set of engines that render frames nobody differentiates.  The workspaces are held for a
+    whole animation and every count is read before its frame is handed out, so the policy is 8 pairs per Gaussian and 1.25x growth:
+    deliberately not the 4 P / 2x of the autograd ops above, whose workspaces live for one call."""
+
+    def __init__(self):
+        # SG_FLAG_LONG_ROWS (direct binning of few-tile frames: no tile list beyond 16384 entries) is passed optimistically; a frame
+        # that reports a longer list is rendered again without the hint, which then stays off
+        self.long_rows = True
+
+    @staticmethod
+    def floor(cap, P, W, H):
+        """The capacity of a first set of engines: what is held already, 8 pairs per Gaussian + 1 per tile, at least 2^16."""
+        return max(cap, 8 * P + ((W + 15) // 16) * ((H + 15) // 16), 1 << 16)
+
+    @staticmethod
+    def grown(need):
+        """The capacity a count of ``need`` pairs asks for."""
+        return need + need // 4 + 1024
+
+    def settle(self, counts, cap, flags=0):
+        """Frames rendered with capacity ``cap`` have reported their pair counts (``num_rendered()``, or the header's count and
+        flag word of a frame whose count was not read): drops the long-rows hint for good if a list outgrew its row.  Returns None
+        if the frames stand, else the capacity to render them again with: ``cap`` after a NUM_RENDERED_LONG_LIST count (it hides
+        the frame's R: the plain path counts it), ``grown(R)`` if R exceeded ``cap``."""
+        if min(counts) == _lib.NUM_RENDERED_LONG_LIST:           # (also of a frame launched before an earlier one dropped the hint)
+            self.long_rows = False
+            return cap
+        long_list = bool(flags & _lib.HDR_FLAG_LONG_LIST)        # (the header's R is the frame's: it may also have overflowed)
+        if long_list:
+            self.long_rows = False
+        need = max(counts)
+        if need > cap:
+            return self.grown(need)
+        return cap if long_list else None
+
+    def redo(self, cap, render):
+        """A unit failed ``settle``, which asked for ``cap``: ``render(cap)`` renders it again with at least that capacity and reads
+        its counts -> (result, counts, the capacity it ran with).  Returns the result that stands.  The plain path reports the
+        exact R and ``grown(R) >= R``, so two renders are enough (hint dropped, then grown); a third failure is an error."""
+        for _ in range(2):
+            result, counts, ran_with = render(cap)
+            cap = self.settle(counts, ran_with)
+            if cap is None:
+                return result
+        raise RuntimeError(f"sings_amd: a frame reported the pair counts {list(counts)} for a capacity of {ran_with} after two "
+                           f"re-renders (hint dropped, capacity grown): the counts of one frame do not repeat")
+
+
 # ---- I/O layer: early-count words ------------------------------------------------------------------------------------------------
-_signal = {}                           # device index -> [host address, device address, next slot] of the early-count words
+_signal = {}                          # device index -> [host address, device address, next slot] of the early-count words
 _SIGNAL_SLOTS = 64
 _signal_lock = threading.Lock()
 

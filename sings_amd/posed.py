@@ -13,12 +13,15 @@
    ``frames_per_launch = K`` (round 4): K consecutive frames of the chunk per DISPATCH through ``SkinnedFramesEngine`` -- what
    ``SinGS.forward_chunk`` + the render loop of gs_trainer.py:684-714 do for a chunk of 16 frames, in one pass over the kernels.
 """
+from collections import deque
+
 import numpy as np
 import torch
 
 from . import _lib
 from ._marshal import _ptr, _stream
 from .body import SMPL_PARENTS, rodrigues
+from .overflow import EngineCapacity
 from .renderer import _settings, get_render_pkg_fused
 
 # sings/rec/defaults/constants.py:13-18: SMPL-H (52 joints, AMASS order) -> the 24 SMPL joints
@@ -150,18 +153,32 @@ def _batch_rows(ts, K, width):
     return torch.stack([t.reshape(width) for t in ts] + [ts[-1].reshape(width)] * (K - len(ts))).contiguous()
 
 
-def _capacity_floor(cap, P, W, H):                   # the FrameAnimator's engines: 8 pairs per Gaussian + 1 per tile, at least
-    return max(cap, 8 * P + ((W + 15) // 16) * ((H + 15) // 16), 1 << 16)
+_capacity_floor, _grown = EngineCapacity.floor, EngineCapacity.grown      # (the names the two rules had in this module)
 
 
-def _grown(need):                                    # ... and what a count of `need` pairs asks for
-    return need + need // 4 + 1024
+def _batches(jobs, K):
+    """The job stream as (index of the first job, batch): at most K consecutive jobs per batch, and a new batch where
+    ``(smpl_scale is None, ext_tfs is None)`` changes (frames with and without scale / placement cannot share a launch)."""
+    kind = lambda job: (job[3] is None, job[4] is None)
+    batch, i0 = [], 0
+    for i, job in enumerate(jobs):
+        if batch and kind(job) != kind(batch[0]):
+            yield i0, batch
+            batch = []
+        if not batch:
+            i0 = i
+        batch.append(job)
+        if len(batch) == K:
+            yield i0, batch
+            batch = []
+    if batch:
+        yield i0, batch
 
 
 class FrameAnimator:
-    """Forward-only rendering of posed frames, ``streams`` frames in flight: one pre-allocated SkinnedEngine (workspaces)
-    per stream, nothing allocated or synchronised per frame except one read of the pair counts per round (a frame whose
-    (tile, Gaussian) pairs exceed the capacity is re-rendered after the engines have grown)."""
+    """Forward-only rendering of posed frames, ``streams`` launches in flight: one pre-allocated engine (workspaces) per stream,
+    nothing allocated or synchronised per frame except the read of its pair counts (``overflow.EngineCapacity``: a unit whose
+    (tile, Gaussian) pairs exceed the capacity, or whose long-rows hint failed, is rendered again before it is handed out)."""
 
     def __init__(self, canon, streams=3):
         self.canon = canon
@@ -170,142 +187,120 @@ class FrameAnimator:
             raise RuntimeError("sings_amd.posed.FrameAnimator runs on the MI355X only; there is no CPU fallback")
         self.n = max(1, int(streams))
         self.streams = [torch.cuda.Stream(self.dev) for _ in range(self.n)]
-        self.engs, self.shape, self.cap = [], None, 0
-        self._fengs, self._fshape, self._fcap = [], None, 0             # (the K-frame engines: _frame_engines)
-        # SG_FLAG_LONG_ROWS (direct binning of few-tile frames: no tile list beyond 16384 entries), passed optimistically: every path
-        # below reads the frames' counts before it hands an image out, and a frame that reports NUM_RENDERED_LONG_LIST is rendered
-        # again without the hint -- which then stays off
-        self.long_rows = True
+        self.engs, self.key, self.cap = [], None, 0
+        self.policy = EngineCapacity()
 
-    def _engines(self, J, W, H, cap):
-        from .engine import SkinnedEngine
-        c = self.canon
-        P, M = int(c['xyz_canon'].shape[0]), int(c['shs'].shape[1])
-        if self.shape != (P, J, W, H, M) or cap > self.cap:
+    long_rows = property(lambda self: self.policy.long_rows)
+
+    def _engines(self, key, cap):
+        """The ``n`` engines of ``key`` = (P, J, W, H, M, K, rot width | None, aux) that hold at least ``cap`` pairs: SkinnedEngine
+        (K None) or SkinnedFramesEngine.  A set of another key or a smaller capacity is replaced."""
+        if key != self.key or cap > self.cap:
+            from .engine import SkinnedEngine, SkinnedFramesEngine
+            P, J, W, H, M, K, rw, aux = key
+            if self.engs:
+                torch.cuda.synchronize(self.dev)                 # (engines in flight are about to be replaced)
             self.engs = []                                       # (drop the old workspaces before the new ones are sized)
-            self.engs = [SkinnedEngine(P, J, W, H, M, self.dev, capacity_pairs=cap) for _ in range(self.n)]
-            self.shape, self.cap = (P, J, W, H, M), cap
+            if K is None:
+                self.engs = [SkinnedEngine(P, J, W, H, M, self.dev, capacity_pairs=cap) for _ in range(self.n)]
+            else:
+                self.engs = [SkinnedFramesEngine(P, J, W, H, M, K, self.dev, capacity_pairs=cap, with_rot=rw is not None,
+                                                 rot_width=9 if rw is None else rw, aux=aux) for _ in range(self.n)]
+            self.key, self.cap = key, cap
         return self.engs
 
-    def _settle(self, counts, cap, flags=0):
-        """Frames rendered with capacity ``cap`` have reported their pair counts (``num_rendered()``, or the header's count and
-        flag word of a frame whose count was not read): drops the long-rows hint for good if a list outgrew its row.  Returns None
-        if the frames stand, else the capacity to render them again with: ``cap`` after a NUM_RENDERED_LONG_LIST count (it hides
-        the frame's R: the plain path counts it), ``_grown(R)`` if R exceeded ``cap``."""
-        if self.long_rows and min(counts) == _lib.NUM_RENDERED_LONG_LIST:
-            self.long_rows = False
-            return cap
-        long_list = bool(flags & _lib.HDR_FLAG_LONG_LIST)        # (the header's R is the frame's: it may also have overflowed)
-        if long_list:
-            self.long_rows = False
-        need = max(counts)
-        if need > cap:
-            return _grown(need)
-        return cap if long_list else None
+    def _pipeline(self, units, launch, K=None, aux=False, depth=None):
+        """What the three public methods go through.  ``units``: an iterable of (index of the first job, unit); a unit is a list of
+        one job for a single-frame engine (``K`` None), of at most K jobs for a K-frame engine.  ``launch(e, unit)`` renders the
+        unit through engine ``e`` on the current stream -> a tuple of new tensors.  Unit number s goes to engine and stream s % n,
+        forked from the caller's stream.  Yields (index, unit, tensors) in order, each once ITS launch has finished and its
+        pair counts have been settled (``EngineCapacity.settle``; a unit that fails is rendered again: ``EngineCapacity.redo``).
+        ``depth`` None: one unit per engine in flight, whose counts ``num_rendered()`` reads at the hand-out.  ``depth`` = d: up to
+        d + 1 units in flight, several per engine, so every launch is followed by a non-blocking copy of its header words 0 and 1
+        (pair count R, flags) to pinned memory, and nothing but the unit's event is waited for."""
+        cur = torch.cuda.current_stream(self.dev)
+        bound = self.n if depth is None else depth + 1
+        slots = None if depth is None else [torch.empty(2, dtype=torch.int32).pin_memory() for _ in range(bound)]
+        q = deque()
 
-    def _launch(self, e, job, bg_color, scaling_modifier, cur):
-        """One frame on the current stream: ``job`` (a tuple of ``render_round``) through engine ``e`` -> the clamped image, for
-        use on stream ``cur``."""
+        def render(s, unit, cap, slot=None):
+            """Unit number s on engine and stream s % n of a set that holds at least ``cap`` pairs -> (engine, stream, tensors)."""
+            cam, A = unit[0][0], unit[0][1]
+            c = self.canon
+            P, rot = int(c['xyz_canon'].shape[0]), c.get('rotmat_canon')
+            key = (P, int(A.reshape(-1, 16).shape[0]), int(cam['image_width']), int(cam['image_height']), int(c['shs'].shape[1]), K,
+                   None if rot is None else int(rot.reshape(P, -1).shape[1]), bool(aux))
+            e = self._engines(key, EngineCapacity.floor(max(cap, self.cap), P, key[2], key[3]))[s % self.n]
+            st = self.streams[s % self.n]
+            st.wait_stream(cur)                                  # the jobs' tensors were produced on the caller's stream
+            with torch.cuda.stream(st):
+                out = launch(e, unit)
+                for t in out:
+                    t.record_stream(cur)                         # ... and the images are used there
+                if slot is not None:
+                    slot.copy_(e.binning[:8].view(torch.int32), non_blocking=True)
+            return e, st, out
+
+        def again(s, unit, cap):
+            torch.cuda.synchronize(self.dev)                     # rare: the engines are idle, a grown set may replace them
+            e, st, out = render(s, unit, cap)
+            with torch.cuda.stream(st):
+                Rs = e.num_rendered()                            # (waits for the render)
+            return out, [Rs] if K is None else Rs[:len(unit)], e.cap
+
+        def pop():
+            s, i0, unit, e, st, out, ev, slot = q.popleft()
+            ev.synchronize()
+            # compared with the capacity of the engine that rendered it: an earlier pop may have grown the set while this unit
+            # was queued, and a count between the two capacities means a background-only image
+            if slot is None:
+                with torch.cuda.stream(st):
+                    Rs = e.num_rendered()                        # (this engine has nothing else queued)
+                cap = self.policy.settle([Rs] if K is None else Rs[:len(unit)], e.cap)
+            else:
+                cap = self.policy.settle([int(slot[0])], e.cap, int(slot[1]))
+            if cap is not None:
+                # on engine s % n again: its own counts have been read, the queued units' are in their slots or on other engines
+                out = self.policy.redo(cap, lambda cap: again(s, unit, cap))
+            return i0, unit, out
+
+        for s, (i0, unit) in enumerate(units):
+            while len(q) >= bound:
+                yield pop()
+            slot = None if slots is None else slots[s % bound]
+            e, st, out = render(s, unit, 0, slot)
+            ev = torch.cuda.Event()
+            ev.record(st)
+            q.append((s, i0, unit, e, st, out, ev, slot))
+        while q:
+            yield pop()
+
+    def _launch(self, e, job, bg_color, scaling_modifier):
+        """One frame on the current stream: ``job`` (a tuple of ``render_round``) through engine ``e`` -> the clamped image (a new
+        tensor: the engine's image buffer is reused)."""
         cam, A, transl, smpl_scale, ext = job
         c = self.canon
-        e.color = torch.empty((3, e.H, e.W), dtype=torch.float32, device=self.dev)    # handed to the caller
         e.set_camera(_settings(cam, bg_color, scaling_modifier, c['active_sh_degree']), long_rows=self.long_rows)
         e.set_frame(c['xyz_canon'], c.get('rotmat_canon'), c['lbs_weights'], A, smpl_scale, transl, ext)
         e.forward(c['shs'], c['opacity'], c['scales'])
-        img = torch.clamp(e.color, 0.0, 1.0)
-        img.record_stream(cur)
-        return img
+        return (torch.clamp(e.color, 0.0, 1.0),)
 
     def render_round(self, jobs, bg_color, scaling_modifier=1.0):
         """jobs: up to ``streams`` tuples (camera dict, A_cano2pose [J,4,4], transl | None, smpl_scale | None,
         ext_tfs | None) -> list of clamped images [3,H,W] (the keys 'render' of get_render_pkg_fused)."""
-        c = self.canon
         assert 0 < len(jobs) <= self.n
-        J = int(jobs[0][1].reshape(-1, 16).shape[0])
-        W, H = int(jobs[0][0]['image_width']), int(jobs[0][0]['image_height'])
-        P = int(c['xyz_canon'].shape[0])
-        cap = _capacity_floor(self.cap, P, W, H)
-        cur = torch.cuda.current_stream(self.dev)
-        while True:
-            engs = self._engines(J, W, H, cap)
-            outs = []
-            for st in self.streams[:len(jobs)]:
-                st.wait_stream(cur)
-            for job, e, st in zip(jobs, engs, self.streams):
-                with torch.cuda.stream(st):
-                    outs.append(self._launch(e, job, bg_color, scaling_modifier, cur))
-            for st in self.streams[:len(jobs)]:
-                cur.wait_stream(st)
-            cap = self._settle([e.num_rendered() for e in engs[:len(jobs)]], self.cap)
-            if cap is None:
-                return outs
-
+        launch = lambda e, unit: self._launch(e, unit[0], bg_color, scaling_modifier)
+        return [out[0] for _, _, out in self._pipeline(((i, [job]) for i, job in enumerate(jobs)), launch)]
 
     def render_frames(self, jobs, bg_color, scaling_modifier=1.0, depth=None):
         """Pipelined variant: ``jobs`` is an iterable of the tuples ``render_round`` takes; frame i goes to stream
         i % streams and NOTHING waits between frames -- a frame is handed out (in order) once ITS forward has finished
         (its pair count comes back with an asynchronous copy, checked then), while up to ``depth`` later frames are
         already queued.  Yields (index, clamped image)."""
-        from collections import deque
-        c = self.canon
         depth = 2 * self.n if depth is None else max(1, int(depth))
-        cur = torch.cuda.current_stream(self.dev)
-        P = int(c['xyz_canon'].shape[0])
-        slots = [torch.empty(2, dtype=torch.int32).pin_memory() for _ in range(depth + self.n + 1)]
-        q = deque()
-
-        def submit(i, job):
-            cam, A = job[0], job[1]
-            J = int(A.reshape(-1, 16).shape[0])
-            W, H = int(cam['image_width']), int(cam['image_height'])
-            cap = _capacity_floor(self.cap, P, W, H)
-            if self.shape != (P, J, W, H, int(c['shs'].shape[1])) or cap > self.cap:
-                torch.cuda.synchronize(self.dev)                 # (engines in flight are about to be replaced)
-            e, st = self._engines(J, W, H, cap)[i % self.n], self.streams[i % self.n]
-            st.wait_stream(cur)                                  # the job's tensors were produced on the caller's stream
-            with torch.cuda.stream(st):
-                img = self._launch(e, job, bg_color, scaling_modifier, cur)
-                slot = slots[i % len(slots)]
-                slot.copy_(e.binning[:8].view(torch.int32), non_blocking=True)      # header words 0, 1 = pair count R, flags
-                ev = torch.cuda.Event()
-                ev.record(st)
-            q.append((i, job, img, ev, slot, e.cap))          # (the capacity THIS frame was rendered with)
-
-        def pop():
-            i, job, img, ev, slot, cap_used = q.popleft()
-            ev.synchronize()
-            # compared with the capacity of the engine that rendered it: an earlier pop may have grown self.cap while this
-            # frame was still queued, and a count between the two capacities means a background-only image
-            cap = self._settle([int(slot[0])], cap_used, int(slot[1]))
-            if cap is not None:                                  # rare: grow the workspaces / drop the hint, render this frame again
-                torch.cuda.synchronize(self.dev)
-                if cap > cap_used:
-                    self._engines(self.shape[1], self.shape[2], self.shape[3], cap)
-                img = self.render_round([job], bg_color, scaling_modifier)[0]
-                torch.cuda.synchronize(self.dev)
-            return i, img
-
-        for i, job in enumerate(jobs):
-            submit(i, job)
-            while len(q) > depth:
-                yield pop()
-        while q:
-            yield pop()
-
-
-    # ---- K frames of the same Gaussians per dispatch (round 4: sings_amd.engine.SkinnedFramesEngine) -------------------------
-    def _frame_engines(self, J, W, H, K, cap, aux=False):
-        from .engine import SkinnedFramesEngine
-        c = self.canon
-        P, M = int(c['xyz_canon'].shape[0]), int(c['shs'].shape[1])
-        rot = c.get('rotmat_canon')
-        key = (P, J, W, H, M, K, None if rot is None else int(rot.reshape(P, -1).shape[1]), bool(aux))
-        if self._fshape != key or cap > self._fcap:
-            self._fengs = []
-            self._fengs = [SkinnedFramesEngine(P, J, W, H, M, K, self.dev, capacity_pairs=cap, with_rot=rot is not None,
-                                               rot_width=9 if rot is None else key[6], aux=aux) for _ in range(self.n)]
-            self._fshape, self._fcap = key, cap
-        return self._fengs
+        launch = lambda e, unit: self._launch(e, unit[0], bg_color, scaling_modifier)
+        for i, _, out in self._pipeline(((i, [job]) for i, job in enumerate(jobs)), launch, depth=depth):
+            yield i, out[0]
 
     def render_frames_batched(self, jobs, bg_color, frames_per_launch=8, scaling_modifier=1.0, out="float32", return_aux=False):
         """``render_frames`` with K = ``frames_per_launch`` consecutive frames per DISPATCH: the reference's chunk
@@ -318,16 +313,11 @@ class FrameAnimator:
         ``out``: "float32" (the clamped [3,H,W] image), "rgb8" / "bgr8" (uint8 [H,W,3], ``frames_to_u8``: one conversion launch
         per batch).  ``return_aux``: yields (index, image, depth [1,H,W], alpha [1,H,W]) -- the maps of
         ``get_render_pkg_fused(return_aux=True)``, re-rendered fallbacks included; the maps stay fp32."""
-        from collections import deque
         c = self.canon
         bgr = _out_bgr(out)
         K = max(1, min(int(frames_per_launch), 16))
-        cur = torch.cuda.current_stream(self.dev)
-        P = int(c['xyz_canon'].shape[0])
-        q = deque()
-        state = dict(b=0)
 
-        def launch(i0, batch, e, st):
+        def launch(e, batch):
             k = len(batch)
             cams = [j[0] for j in batch]
             A = torch.stack([j[1].reshape(-1, 16) for j in batch] + [batch[-1][1].reshape(-1, 16)] * (K - k)).contiguous()
@@ -338,85 +328,22 @@ class FrameAnimator:
             ext = None
             if batch[0][4] is not None:
                 ext = tuple(_batch_rows([j[4][n] for j in batch], K, w) for n, w in enumerate((3, 9, 1)))
-            st.wait_stream(cur)                                  # the jobs' tensors were produced on the caller's stream
-            with torch.cuda.stream(st):
-                rs = _settings(cams[0], bg_color, scaling_modifier, c['active_sh_degree'])
-                if any(cm is not cams[0] for cm in cams):        # per-frame cameras: stacked [K,4,4] / [K,3]
-                    pad = cams + [cams[-1]] * (K - k)
-                    rs = rs._replace(viewmatrix=torch.stack([cm['world_view_transform'] for cm in pad]).contiguous(),
-                                     projmatrix=torch.stack([cm['full_proj_transform'] for cm in pad]).contiguous(),
-                                     campos=torch.stack([cm['camera_center'] for cm in pad]).contiguous())
-                e.set_camera(rs, long_rows=self.long_rows)
-                e.set_frames(c['xyz_canon'], c.get('rotmat_canon'), c['lbs_weights'], A, sc, tr, ext)
-                e.forward(c['shs'], c['opacity'], c['scales'])
-                # [K,3,H,W] (or [K,H,W,3] uint8): a new tensor, the engine's image buffer is reused
-                img = torch.clamp(e.color, 0.0, 1.0) if bgr is None else frames_to_u8(e.color, bgr)
-                maps = (e.depth.clone(), e.alpha.clone()) if return_aux else None      # (so are its map buffers)
-                ev = torch.cuda.Event(); ev.record(st)
-            img.record_stream(cur)
-            if maps is not None:
-                for m in maps:
-                    m.record_stream(cur)
-            return (img, maps), ev
+            rs = _settings(cams[0], bg_color, scaling_modifier, c['active_sh_degree'])
+            if any(cm is not cams[0] for cm in cams):            # per-frame cameras: stacked [K,4,4] / [K,3]
+                pad = cams + [cams[-1]] * (K - k)
+                rs = rs._replace(viewmatrix=torch.stack([cm['world_view_transform'] for cm in pad]).contiguous(),
+                                 projmatrix=torch.stack([cm['full_proj_transform'] for cm in pad]).contiguous(),
+                                 campos=torch.stack([cm['camera_center'] for cm in pad]).contiguous())
+            e.set_camera(rs, long_rows=self.long_rows)
+            e.set_frames(c['xyz_canon'], c.get('rotmat_canon'), c['lbs_weights'], A, sc, tr, ext)
+            e.forward(c['shs'], c['opacity'], c['scales'])
+            # [K,3,H,W] (or [K,H,W,3] uint8): a new tensor, the engine's image buffer is reused (so are its map buffers)
+            img = torch.clamp(e.color, 0.0, 1.0) if bgr is None else frames_to_u8(e.color, bgr)
+            return (img, e.depth.clone(), e.alpha.clone()) if return_aux else (img,)
 
-        def submit(i0, batch):
-            J = int(batch[0][1].reshape(-1, 16).shape[0])
-            W, H = int(batch[0][0]['image_width']), int(batch[0][0]['image_height'])
-            cap = _capacity_floor(self._fcap, P, W, H)
-            engs = self._frame_engines(J, W, H, K, cap, return_aux)
-            e, st = engs[state['b'] % self.n], self.streams[state['b'] % self.n]
-            state['b'] += 1
-            img, ev = launch(i0, batch, e, st)
-            q.append((i0, batch, img, ev, e, st))
-
-        def pop():
-            i0, batch, img, ev, e, st = q.popleft()
-            ev.synchronize()
-            with torch.cuda.stream(st):
-                Rs = e.num_rendered()                            # (this engine has nothing else queued: one launch per engine)
-            if self._settle(Rs[:len(batch)], e.cap) is not None:    # rare: grow the workspaces / drop the hint, render this batch again
-                torch.cuda.synchronize(self.dev)
-                # (a NEW set of engines either way: the queued batches keep theirs, whose counts are still to be read)
-                need = max(max(Rs[:len(batch)]), self._fcap - self._fcap // 5)
-                J, W, H = self._fshape[1], self._fshape[2], self._fshape[3]
-                e2 = self._frame_engines(J, W, H, K, _grown(need), return_aux)[0]
-                img, ev = launch(i0, batch, e2, self.streams[0])
-                torch.cuda.synchronize(self.dev)
-                Rs2 = e2.num_rendered()
-                if max(Rs2[:len(batch)]) > e2.cap:               # (both at once: the plain path has now counted the batch)
-                    need = max(Rs2[:len(batch)])
-                    e2 = self._frame_engines(J, W, H, K, _grown(need), return_aux)[0]
-                    img, ev = launch(i0, batch, e2, self.streams[0])
-                    torch.cuda.synchronize(self.dev)
-            img, maps = img
+        for i0, batch, outs in self._pipeline(_batches(jobs, K), launch, K=K, aux=return_aux):
             for k in range(len(batch)):
-                if maps is not None:
-                    yield i0 + k, img[k], maps[0][k], maps[1][k]
-                else:
-                    yield i0 + k, img[k]
-
-        kind = lambda job: (job[3] is None, job[4] is None)     # (frames with and without scale / placement: separate batches)
-        batch, i0, i = [], 0, 0
-        for i, job in enumerate(jobs):
-            if batch and kind(job) != kind(batch[0]):
-                while len(q) >= self.n:
-                    yield from pop()
-                submit(i0, batch)
-                batch = []
-            if not batch:
-                i0 = i
-            batch.append(job)
-            if len(batch) == K:
-                while len(q) >= self.n:
-                    yield from pop()
-                submit(i0, batch)
-                batch = []
-        if batch:
-            while len(q) >= self.n:
-                yield from pop()
-            submit(i0, batch)
-        while q:
-            yield from pop()
+                yield (i0 + k,) + tuple(t[k] for t in outs)
 
 
 @torch.no_grad()

@@ -271,27 +271,49 @@ def test_long_rows_fallback_keeps_the_placement():
         assert torch.equal(got[f], want[f]), f
 
 
-def test_capacity_overflow_fallback_keeps_the_placement():
-    """Gaussians large enough that a frame's pairs exceed the animator's first capacity (8 per Gaussian): the batch is rendered
-    again on grown workspaces, with the same per-frame placements and scales; a short tail batch (5 = 4 + 1) is padded with its
-    last frame's placement."""
-    from sings_amd.posed import FrameAnimator, _capacity_floor
-    dev = _dev()
-    N, J, W, H, F = 20000, 52, 160, 288, 5
-    s, ins, A, transl, one, stacked, _ = _avatar(N, J, W, H, 6, F, False, True)
-    ext = _placements(F, _center(s), 9)
-    sc = torch.from_numpy(np.linspace(0.95, 1.05, F, dtype=np.float32)[:, None]).to(dev)
-    canon = dict(xyz_canon=ins["xyz"], rotmat_canon=None, scales=ins["sc"] * 15.0, opacity=ins["op"], shs=ins["sh"],
-                 lbs_weights=ins["w"], active_sh_degree=0)
-    camd = {k_: (torch.from_numpy(np.ascontiguousarray(v)).to(dev) if isinstance(v, np.ndarray) else v) for k_, v in s["cam"].items()}
-    bg = torch.from_numpy(s["bg"]).to(dev)
-    want = _single_frame_refs(canon, camd, A.reshape(F, J, 4, 4), bg, sc, transl, ext)
-    jobs = [(camd, A[f].reshape(J, 4, 4), transl[f], sc[f], tuple(x[f] for x in ext)) for f in range(F)]
+_overflow_scene_cache = []
+
+
+def _overflow_scene():
+    """The scene of the capacity-overflow test and its single-frame references, rendered once for the three paths."""
+    if not _overflow_scene_cache:
+        dev = _dev()
+        N, J, W, H, F = 20000, 52, 160, 288, 5
+        s, ins, A, transl, one, stacked, _ = _avatar(N, J, W, H, 6, F, False, True)
+        ext = _placements(F, _center(s), 9)
+        sc = torch.from_numpy(np.linspace(0.95, 1.05, F, dtype=np.float32)[:, None]).to(dev)
+        canon = dict(xyz_canon=ins["xyz"], rotmat_canon=None, scales=ins["sc"] * 15.0, opacity=ins["op"], shs=ins["sh"],
+                     lbs_weights=ins["w"], active_sh_degree=0)
+        camd = {k_: (torch.from_numpy(np.ascontiguousarray(v)).to(dev) if isinstance(v, np.ndarray) else v)
+                for k_, v in s["cam"].items()}
+        bg = torch.from_numpy(s["bg"]).to(dev)
+        want = _single_frame_refs(canon, camd, A.reshape(F, J, 4, 4), bg, sc, transl, ext)
+        jobs = [(camd, A[f].reshape(J, 4, 4), transl[f], sc[f], tuple(x[f] for x in ext)) for f in range(F)]
+        _overflow_scene_cache.append((canon, bg, jobs, want, (N, W, H)))
+    return _overflow_scene_cache[0]
+
+
+@pytest.mark.parametrize("path", ["render_round", "render_frames", "render_frames_batched"])
+def test_capacity_overflow_fallback_keeps_the_placement(path):
+    """Gaussians large enough that a frame's pairs exceed the animator's first capacity (8 per Gaussian): the frame (or the batch) is
+    rendered again on grown workspaces, with the same per-frame placements and scales, on each of the three paths -- rounds of 2, 2
+    and 1 jobs, the pipelined per-frame path, and K = 4 frames per launch, whose short tail batch (5 = 4 + 1) is padded with its
+    last frame's placement.  Scales x 15: the largest frame produces R = 1 167 541 pairs against a floor of 160 180, so a single
+    frame overflows as the batch does and each path ends with the capacity 1 460 450 (measured on the MI355X)."""
+    from sings_amd.overflow import EngineCapacity
+    from sings_amd.posed import FrameAnimator
+    canon, bg, jobs, want, (N, W, H) = _overflow_scene()
+    F = len(jobs)
     fa = FrameAnimator(canon, streams=2)
-    floor = _capacity_floor(0, N, W, H)
-    got = dict(fa.render_frames_batched(iter(jobs), bg, frames_per_launch=4))
+    floor = EngineCapacity.floor(0, N, W, H)
+    if path == "render_round":
+        got = {f0 + k: img for f0 in range(0, F, 2) for k, img in enumerate(fa.render_round(jobs[f0:f0 + 2], bg))}
+    elif path == "render_frames":
+        got = dict(fa.render_frames(iter(jobs), bg))
+    else:
+        got = dict(fa.render_frames_batched(iter(jobs), bg, frames_per_launch=4))
     torch.cuda.synchronize()
-    assert fa._fcap > floor, (fa._fcap, floor)                            # (the overflow re-render ran)
+    assert fa.cap > floor, (fa.cap, floor)                                # (the overflow re-render ran)
     assert sorted(got) == list(range(F))
     for f in range(F):
         assert torch.equal(got[f], want[f]), f

@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from sings_amd import _lib, overflow as ov
-from sings_amd.posed import FrameAnimator, _capacity_floor, _grown
+from sings_amd.overflow import EngineCapacity
 
 SHORT, ROWS = _lib.FLAG_SHORT_LISTS, _lib.FLAG_LONG_ROWS
 ARRIVED = 1 << 63
@@ -175,20 +175,21 @@ def test_rasterizer_reexports_the_policy():
 
 
 def test_frame_animator_capacity_rules():
-    assert _capacity_floor(0, 1000, 64, 64) == 1 << 16
-    assert _capacity_floor(0, 100000, 512, 896) == 800000 + 32 * 56
-    assert _capacity_floor(10 ** 7, 100000, 512, 896) == 10 ** 7
-    assert _grown(400000) == 501024
-    fa = FrameAnimator.__new__(FrameAnimator)                            # (the decisions only: no engines, no streams)
-    fa.long_rows = True
-    assert fa._settle([1000, 3000], 4000) is None
-    assert fa._settle([1000, 5000], 4000) == _grown(5000) and fa.long_rows
+    floor, grown = EngineCapacity.floor, EngineCapacity.grown
+    assert floor(0, 1000, 64, 64) == 1 << 16
+    assert floor(0, 100000, 512, 896) == 800000 + 32 * 56
+    assert floor(10 ** 7, 100000, 512, 896) == 10 ** 7
+    assert grown(400000) == 501024
+    fa = EngineCapacity()                                                # (the decisions only: no engines, no streams)
+    assert fa.long_rows is True
+    assert fa.settle([1000, 3000], 4000) is None
+    assert fa.settle([1000, 5000], 4000) == grown(5000) and fa.long_rows
     # a count that hides R: the same capacity, the plain path counts the frame
-    assert fa._settle([5000, _lib.NUM_RENDERED_LONG_LIST], 4000) == 4000 and fa.long_rows is False
-    assert fa._settle([1000, 3000], 4000) is None
+    assert fa.settle([5000, _lib.NUM_RENDERED_LONG_LIST], 4000) == 4000 and fa.long_rows is False
+    assert fa.settle([1000, 3000], 4000) is None
     # an unread header: its R is the frame's, so a long list and an overflow are settled at once
     fa.long_rows = True
-    assert fa._settle([3000], 4000, _lib.HDR_FLAG_LONG_LIST) == 4000 and fa.long_rows is False
+    assert fa.settle([3000], 4000, _lib.HDR_FLAG_LONG_LIST) == 4000 and fa.long_rows is False
     fa.long_rows = True
-    assert fa._settle([5000], 4000, _lib.HDR_FLAG_LONG_LIST | _lib.HDR_FLAG_OVERFLOW) == _grown(5000) and fa.long_rows is False
-    assert fa._settle([5000], 4000, _lib.HDR_FLAG_OVERFLOW) == _grown(5000)
+    assert fa.settle([5000], 4000, _lib.HDR_FLAG_LONG_LIST | _lib.HDR_FLAG_OVERFLOW) == grown(5000) and fa.long_rows is False
+    assert fa.settle([5000], 4000, _lib.HDR_FLAG_OVERFLOW) == grown(5000)
