@@ -74,7 +74,7 @@ extern "C" int sg_frames_layout(int P, int width, int height, size_t cap, int K,
     if (geom_bytes) *geom_bytes = L.geom_bytes * K;
     if (binning_bytes) *binning_bytes = L.bin_bytes * K;
     if (image_bytes) *image_bytes = L.img_bytes * K;
-    if (bwd_bytes) *bwd_bytes = L.bwd_bytes * K + sg_a9_bytes(P, K);      // (+ the record sums [K][P][12] of the K-camera backward)
+    if (bwd_bytes) *bwd_bytes = L.bwd_bytes * K + sg_a9_bytes(P, K);      // (+ the per-frame rows of the K-camera backward)
     return 0;
 }
 

@@ -141,227 +141,287 @@ void sg_launch_preprocess_fwd_ordered(const SgCam &c, const SgBatch &bt, int P, 
 #include "sg_preprocess_bwd.inc"
 #undef SG_PBWD_AUX
 
-// ---- K cameras per launch (round 4) -------------------------------------------------------------------------------------------
-// K cameras (bt.K frames) of the SAME Gaussians: the kernel walks the frames -- chain rule with camera f on the record sums of frame
-// f -- and sums the K gradients of a Gaussian in frame order (frame 0 assigns, frame f > 0 adds: bit for bit what K single-camera
-// calls leave behind when the first writes the gradient buffer and the others run with accumulate = 1), then writes the 248-byte
-// gradient row ONCE: K - 1 read-modify-write passes over the buffer less (at cfg3 2 x 47 MB per view), and the Gaussian's position,
-// scale and rotation are read once for the K cameras.  dL_dmeans2D (the densifier's per-view statistic) is per frame.
+// ---- K cameras per launch (round 4; two kernels since round 12) ---------------------------------------------------------------
+// K cameras (bt.K frames) of the SAME Gaussians: the K gradients of a Gaussian are summed in frame order (frame 0 assigns, frame
+// f > 0 adds: bit for bit what K single-camera calls leave behind when the first writes the gradient buffer and the others run with
+// accumulate = 1) and the 248-byte gradient row is written ONCE: K - 1 read-modify-write passes over the buffer less (at cfg3
+// 2 x 47 MB per view).  dL_dmeans2D (the densifier's per-view statistic) is per frame.
 //
-// What a frame needs is kept OUT of the loop-carried registers (the first form of this kernel held 48 SH coefficients, 48 dL/dsh
-// sums and the record-chunk staging across the loop: 316 registers at degree 3, one wave per SIMD, 45.8 us per view against the
-// single-camera kernel's 30):
-//  * the record sums of all frames come from sg_record_sums_kernel (a9 [K][P][12]: a kernel of ~40 registers at full occupancy
-//    does the dependent chunk loop); the loop reads 48 contiguous bytes per Gaussian and frame, requested one frame ahead;
-//  * the dL/dsh sums live in LDS ([coefficient][thread], pitch 257: conflict-free for the sums and for the transposed read of the
-//    row store) -- 48 KiB per workgroup at degree 3: three workgroups per CU, which is what 168 registers allow anyway;
-//  * the SH coefficients are re-read per frame (192 B per Gaussian out of L2: frame 0 brought them in).
-#define SG_ACC_PITCH 257
-template <int D, bool ACC>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, D >= 2 ? 2 : 3)))
-sg_preprocess_bwd_frames_kernel(SgCam c0, SgBatch bt, int P, const float *__restrict__ means3D, const float *__restrict__ shs,
-                         const float *__restrict__ colors_precomp, const float *__restrict__ scales,
-                         const float *__restrict__ rotations, const float *__restrict__ cov3D_precomp,
-                         const int32_t *__restrict__ radii0, SgGeom g0_, const uint32_t *__restrict__ header0,
-                         const float4 *__restrict__ a9in, float *__restrict__ dL_dmeans3D, float *__restrict__ dL_dmeans2D,
-                         float *__restrict__ dL_dsh, float *__restrict__ dL_dcolors,
-                         float *__restrict__ dL_dopacity, float *__restrict__ dL_dscales,
-                         float *__restrict__ dL_drots, float *__restrict__ dL_dcov3D)
+// Only the ADDITIONS are ordered; what a frame contributes depends on that frame alone.  So the work is two kernels:
+//  1. sg_gauss_frame_bwd_kernel: one (Gaussian, frame) per lane at full grid, in the (block, frame) order of the forward
+//     (sg_block_frame: the K frames of a block back to back on one XCD -- positions, scales, rotations and SH rows come from HBM
+//     once and from L2 K - 1 times).  Steps 0-2 of the single-camera kernel -- visibility, sg_sum_records_coop, sg_project_bwd --
+//     without forming dL/dsh: it writes the frame's dL_dmeans2D row and one 64-byte row per VISIBLE (frame, Gaussian) into the
+//     block behind the K record buffers (sg_a9_bytes):
+//         vector 0: dmean.xyz, dop      vector 1: dsc.xyz, -      vector 2: drot.xyzw      vector 3: dRGB.xyz, -
+//     dRGB: the colour gradient after the clamp mask (no SH rows: the plain colour gradient); with cov3D_precomp the six g6 values
+//     take vectors 1-2 instead (g6[0..3] | g6[4], g6[5], -, -).
+//  2. sg_gauss_sum_frames_kernel: one Gaussian per lane, the ordered part and nothing else.  It walks the K rows of its Gaussian
+//     (the next one requested ahead), adds the geometry values as the single-camera accumulate does (new + old) and forms
+//     dL/dsh = basis(dir_f) * dRGB_f from the position and the frame's camera centre -- the expressions of sg_project_bwd --
+//     in 48 registers: no SH coefficient, record, slot or flag word is read here.
+// (The one-kernel form this replaces held the chain rule INSIDE the frame loop: 168 registers and 48 KiB of LDS per workgroup,
+//  two waves per SIMD, the 192-byte SH row re-read per trip: 119 us + 63 us of record sums at cfg3, K = 8 -- LAB.md.)
+#define SG_GROW_VEC 4                                       // 16-byte vectors per (frame, Gaussian) row
+template <int D>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
+sg_gauss_frame_bwd_kernel(SgCam c, SgBatch bt, int P, const float *__restrict__ means3D, const float *__restrict__ shs,
+                          const float *__restrict__ scales, const float *__restrict__ rotations,
+                          const float *__restrict__ cov3D_precomp, const int32_t *__restrict__ radii, SgGeom g, SgRec grec,
+                          size_t cap, const uint32_t *__restrict__ header, const uint8_t *__restrict__ rec_valid,
+                          float4 *__restrict__ rows, float *__restrict__ dL_dmeans2D, int nblocks)
 {
-    constexpr bool accumulate = ACC;
-    extern __shared__ float sAcc[];                         // dL/dsh sums [nc * 3][SG_ACC_PITCH]; afterwards the staging rows of the store
-    const int idx_all = blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane_all = threadIdx.x & 63, wave_all = threadIdx.x >> 6;
-    const int g0 = idx_all - lane_all;
-    const bool live = idx_all < P;
+    __shared__ float lds_all[4][32 * SG_ROW_LDS];          // 6.5 KiB per wave: the record chunks
+    int gblock, frame;
+    if (!sg_block_frame((int)blockIdx.x, bt.K, nblocks, gblock, frame)) return;
+    c = sg_frame(c, frame, bt.cam_stride); g = sg_frame(g, (size_t)frame * bt.geom); grec = sg_frame(grec, (size_t)frame * bt.rec);
+    header = sg_at(header, (size_t)frame * bt.bin); rec_valid = sg_at(rec_valid, (size_t)frame * bt.bin);
+    radii += (size_t)frame * bt.P;
+    const int idx = gblock * 256 + (int)threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (idx - lane >= P) return;                            // whole wave out of range
+    const bool live = idx < P;
+    // after a forward that overflowed (header[1] != 0) the backward composite wrote no records: the frame contributes nothing
+    const bool vis = live && radii[idx] > 0 && header[1] == 0u;
+    const int Mrows = c.M;
+    constexpr int nc = (D + 1) * (D + 1);
+    const bool want_sh = shs != nullptr;
+    // 0. every load that does not depend on another one up front
+    float4 rc = make_float4(0, 0, 0, 0);
+    float p[3] = { 0, 0, 0 }, s3[3] = { 0, 0, 0 }, q[4] = { 0, 0, 0, 0 }, sh[nc * 3];
+    uint32_t flags = 0;
+    if (vis) {
+        { const uint2 sl = g.slot[idx]; rc.y = __uint_as_float(sl.x); rc.w = __uint_as_float(sl.y); }
+        flags = g.flags[idx];
+        p[0] = means3D[3 * idx]; p[1] = means3D[3 * idx + 1]; p[2] = means3D[3 * idx + 2];
+        if (!cov3D_precomp) {
+            s3[0] = scales[3 * idx]; s3[1] = scales[3 * idx + 1]; s3[2] = scales[3 * idx + 2];
+            q[0] = rotations[4 * idx]; q[1] = rotations[4 * idx + 1]; q[2] = rotations[4 * idx + 2]; q[3] = rotations[4 * idx + 3];
+        }
+    }
+    // 1. this Gaussian's gradient records of this frame (wave-cooperative, coalesced)
+    float a9[9];
+    sg_sum_records_coop(grec, cap, vis, rc, lane, lds_all[wave], a9, rec_valid);
+    if (!live) return;
+    // the screen-space gradient is per VIEW (the densifier's statistic): zeros for a Gaussian this frame does not see
+    float *m2 = dL_dmeans2D + 3 * ((size_t)frame * bt.P + idx);
+    if (!vis) { m2[0] = 0.0f; m2[1] = 0.0f; m2[2] = 0.0f; return; }
+    // 2. the chain rule without its SH block (dL/dsh is NOT formed: the rows below carry dRGB, the sum kernel multiplies by the basis)
+    SgGaussGrad G;
+    sg_project_bwd<D>(c, p, s3, q, cov3D_precomp ? cov3D_precomp + 6 * (size_t)idx : nullptr, nullptr, flags, a9, false, nullptr, G);
+    m2[0] = G.g2[0]; m2[1] = G.g2[1]; m2[2] = 0.0f;
+    float dRGB[3] = { G.dcol[0], G.dcol[1], G.dcol[2] };
+    if (want_sh) {
+        // the SH block of sg_project_bwd, its expressions in its order: dL/ddir and its share of dL/dmean.  The coefficient row is
+        // requested HERE (opaque index: not in front of the record loop or the cov2D / cov3D chain, where its 48 registers would be
+        // live across both) and consumed in order by the dL/ddir sums.
+        int ish = idx;
+        asm volatile("" : "+v"(ish), "+v"(G.dmean[2]), "+v"(G.drot[3]));
+        const float *src = shs + (size_t)ish * Mrows * 3;
+        if (D == 3 && Mrows == 16) {
+#pragma unroll
+            for (int k = 0; k < nc * 3 / 4; k++) {
+                const float4 v = ((const float4 *)src)[k];
+                sh[4 * k] = v.x; sh[4 * k + 1] = v.y; sh[4 * k + 2] = v.z; sh[4 * k + 3] = v.w;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < nc * 3; k++) sh[k] = src[k];
+        }
+        float dorig[3] = { p[0] - c.campos[0], p[1] - c.campos[1], p[2] - c.campos[2] };
+        float sum2 = dorig[0] * dorig[0] + dorig[1] * dorig[1] + dorig[2] * dorig[2];
+        float len = sqrtf(sum2);
+        float dir[3] = { dorig[0] / len, dorig[1] / len, dorig[2] / len };
+        float db[48];
+        sg_sh_basis_grad<D>(dir, db);
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) dRGB[ch] = (flags >> ch) & 1u ? 0.0f : G.dcol[ch];
+        float ddir[3] = { 0, 0, 0 };
+#pragma unroll
+        for (int k = 1; k < nc; k++)
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) {
+                float sv = sh[3 * k + ch] * dRGB[ch];
+                ddir[0] += db[3 * k] * sv; ddir[1] += db[3 * k + 1] * sv; ddir[2] += db[3 * k + 2] * sv;
+            }
+        float inv32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
+        float vx = dorig[0], vy = dorig[1], vz = dorig[2];
+        G.dmean[0] += ((sum2 - vx * vx) * ddir[0] - vy * vx * ddir[1] - vz * vx * ddir[2]) * inv32;
+        G.dmean[1] += (-vx * vy * ddir[0] + (sum2 - vy * vy) * ddir[1] - vz * vy * ddir[2]) * inv32;
+        G.dmean[2] += (-vx * vz * ddir[0] - vy * vz * ddir[1] + (sum2 - vz * vz) * ddir[2]) * inv32;
+    }
+    float4 *o = rows + SG_GROW_VEC * ((size_t)frame * bt.P + idx);
+    o[0] = make_float4(G.dmean[0], G.dmean[1], G.dmean[2], G.dop);
+    if (cov3D_precomp) {
+        o[1] = make_float4(G.g6[0], G.g6[1], G.g6[2], G.g6[3]);
+        o[2] = make_float4(G.g6[4], G.g6[5], 0.0f, 0.0f);
+    } else {
+        o[1] = make_float4(G.dsc[0], G.dsc[1], G.dsc[2], 0.0f);
+        o[2] = make_float4(G.drot[0], G.drot[1], G.drot[2], G.drot[3]);
+    }
+    o[3] = make_float4(dRGB[0], dRGB[1], dRGB[2], 0.0f);
+}
+
+// ACC: the sums START from what the gradient buffer holds (read once, here), so that the K frames are added in the order K
+// single-camera calls with accumulate = 1 would add them: ((old + g0) + g1) + ...; otherwise frame 0 ASSIGNS (a -0 survives).
+// A frame that does not see the Gaussian enters the geometry sums as +0 -- what the single-camera kernel adds for it -- and
+// leaves the dL/dsh sums alone.
+template <int D, bool ACC>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
+sg_gauss_sum_frames_kernel(SgCam c0, SgBatch bt, int P, const float *__restrict__ means3D, const int32_t *__restrict__ radii0,
+                           const uint32_t *__restrict__ header0, const float4 *__restrict__ rows, int g6rows,
+                           float *__restrict__ dL_dmeans3D, float *__restrict__ dL_dsh, float *__restrict__ dL_dcolors,
+                           float *__restrict__ dL_dopacity, float *__restrict__ dL_dscales, float *__restrict__ dL_drots,
+                           float *__restrict__ dL_dcov3D)
+{
+    __shared__ float lds_all[4][32 * SG_ROW_LDS];          // the staging rows of the dL/dsh store
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g0 = idx - lane;
+    if (g0 >= P) return;                                    // whole wave out of range
+    const bool live = idx < P;
     const int Mrows = c0.M;
     const int nframes = bt.K;
     constexpr int nc = (D + 1) * (D + 1);
     const bool want_sh = dL_dsh != nullptr;
     const bool planar = c0.flags & SG_FLAG_SH_PLANAR;
-    const bool vec_rows = D == 3 && Mrows == 16 && shs != nullptr;            // 16-byte loads of the coefficient row
-    const bool staged = vec_rows && want_sh && !planar;
-    // the Gaussian's position / scale / rotation: read ONCE for all frames
-    float p[3] = { 0, 0, 0 }, s3[3] = { 0, 0, 0 }, q[4] = { 0, 0, 0, 0 };
-    // frame f + 1's (visible, clamp flags, record sums) are requested while frame f is worked on; frame 0's go out with the inputs
-    bool vis_n = live && radii0[idx_all] > 0 && header0[1] == 0u;
-    uint32_t fl_n = 0u;
-    float4 n0 = make_float4(0, 0, 0, 0), n1 = n0, n2 = n0;
+    const bool staged = D == 3 && Mrows == 16 && want_sh && !planar;
+    // frame f + 1's (visible, row) are requested while frame f is added; frame 0's go out with the position
+    bool vis_n = live && radii0[idx] > 0 && header0[1] == 0u;
+    const float4 z4 = make_float4(0, 0, 0, 0);
+    float4 n[SG_GROW_VEC] = { z4, z4, z4, z4 };
     if (vis_n) {
-        fl_n = g0_.flags[idx_all];
-        const float4 *src = a9in + 3 * (size_t)idx_all;
-        n0 = src[0]; n1 = src[1]; n2 = src[2];
+        const float4 *src = rows + SG_GROW_VEC * (size_t)idx;
+#pragma unroll
+        for (int v = 0; v < SG_GROW_VEC; v++) n[v] = src[v];
     }
-    if (live) {
-        p[0] = means3D[3 * idx_all]; p[1] = means3D[3 * idx_all + 1]; p[2] = means3D[3 * idx_all + 2];
-        if (!cov3D_precomp) {
-            s3[0] = scales[3 * idx_all]; s3[1] = scales[3 * idx_all + 1]; s3[2] = scales[3 * idx_all + 2];
-            q[0] = rotations[4 * idx_all]; q[1] = rotations[4 * idx_all + 1]; q[2] = rotations[4 * idx_all + 2]; q[3] = rotations[4 * idx_all + 3];
-        }
-    }
-    SgGaussGrad A;                                          // the sum over the frames
+    float p[3] = { 0, 0, 0 };
+    if (live) { p[0] = means3D[3 * idx]; p[1] = means3D[3 * idx + 1]; p[2] = means3D[3 * idx + 2]; }
+    // the sums over the frames.  Geometry, in the rows' layout: A[0..3] = dmean.xyz, dop; A[4..11] = dsc.xyz, -, drot.xyzw (g6rows:
+    // the six g6, -, -); A[12..14] = the colour gradient -- kept in the wave's LDS block while the frames are walked ([value][lane]:
+    // conflict-free; the dL/dsh sums, the requested row and the basis take the 128 registers of four waves per SIMD)
+    constexpr int NA = 4 * SG_GROW_VEC - 1;
+    static_assert(NA * 64 <= 32 * SG_ROW_LDS, "the geometry sums fit the wave's staging block");
+    float *sA = lds_all[wave] + lane;
+    float A[NA];
 #pragma unroll
-    for (int k = 0; k < 3; k++) { A.dmean[k] = 0; A.dcol[k] = 0; A.dsc[k] = 0; }
+    for (int k = 0; k < NA; k++) A[k] = 0.0f;
+    float acc[nc * 3];
 #pragma unroll
-    for (int k = 0; k < 4; k++) A.drot[k] = 0;
+    for (int k = 0; k < nc * 3; k++) acc[k] = 0.0f;
+    if (ACC && live) {
 #pragma unroll
-    for (int k = 0; k < 6; k++) A.g6[k] = 0;
-    A.g2[0] = A.g2[1] = 0; A.dop = 0;
-    // K > 1 and accumulate: the sums START from what the gradient buffer holds (read once, here), so that the K frames are added
-    // in the order K single-camera calls with accumulate = 1 would add them: ((old + g0) + g1) + ...
-    constexpr bool preload = ACC;
-    if (preload && live) {
+        for (int k = 0; k < 3; k++) A[k] = dL_dmeans3D[3 * idx + k];
+        A[3] = dL_dopacity[idx];
+        if (g6rows) {
 #pragma unroll
-        for (int k = 0; k < 3; k++) A.dmean[k] = dL_dmeans3D[3 * idx_all + k];
-        A.dop = dL_dopacity[idx_all];
-#pragma unroll
-        for (int k = 0; k < 3; k++) { A.dcol[k] = dL_dcolors ? dL_dcolors[3 * idx_all + k] : 0.0f; A.dsc[k] = dL_dscales ? dL_dscales[3 * idx_all + k] : 0.0f; }
-#pragma unroll
-        for (int k = 0; k < 4; k++) A.drot[k] = dL_drots ? dL_drots[4 * idx_all + k] : 0.0f;
-#pragma unroll
-        for (int k = 0; k < 6; k++) A.g6[k] = dL_dcov3D ? dL_dcov3D[6 * idx_all + k] : 0.0f;
-    }
-    if (want_sh) {
-        float *acc = sAcc + threadIdx.x;
-        if (preload && live) {
-            const float *row = dL_dsh + (size_t)idx_all * Mrows * 3;
-#pragma unroll
-            for (int k = 0; k < nc * 3; k++) acc[k * SG_ACC_PITCH] = planar ? dL_dsh[((size_t)(k / 3) * P + idx_all) * 3 + k % 3] : row[k];
+            for (int k = 0; k < 6; k++) A[4 + k] = dL_dcov3D ? dL_dcov3D[6 * idx + k] : 0.0f;
         } else {
 #pragma unroll
-            for (int k = 0; k < nc * 3; k++) acc[k * SG_ACC_PITCH] = 0.0f;
+            for (int k = 0; k < 3; k++) A[4 + k] = dL_dscales ? dL_dscales[3 * idx + k] : 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4; k++) A[8 + k] = dL_drots ? dL_drots[4 * idx + k] : 0.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; k++) A[12 + k] = dL_dcolors ? dL_dcolors[3 * idx + k] : 0.0f;
+        if (want_sh) {
+            const float *row = dL_dsh + (size_t)idx * Mrows * 3;
+#pragma unroll
+            for (int k = 0; k < nc * 3; k++) acc[k] = planar ? dL_dsh[((size_t)(k / 3) * P + idx) * 3 + k % 3] : row[k];
         }
     }
+#pragma unroll
+    for (int k = 0; k < NA; k++) sA[64 * k] = A[k];
 #pragma unroll 1
     for (int f = 0; f < nframes; f++) {
-        // (opaque per trip: keeps hipcc from hoisting what depends on the thread's index only -- the SH row, LDS addresses, the
-        //  per-frame arrays' addresses -- in front of the loop, where it would stay live across it: see sg_skin_bwd_frames_kernel)
-        int idx = idx_all, tid = (int)threadIdx.x;
-        asm volatile("" : "+v"(idx), "+v"(tid));
-        const SgCam c = sg_frame(c0, f, bt.cam_stride);
-        SgGaussGrad G;
-#pragma unroll
-        for (int k = 0; k < 3; k++) { G.dmean[k] = 0; G.dcol[k] = 0; G.dsc[k] = 0; }
-#pragma unroll
-        for (int k = 0; k < 4; k++) G.drot[k] = 0;
-#pragma unroll
-        for (int k = 0; k < 6; k++) G.g6[k] = 0;
-        G.g2[0] = G.g2[1] = 0; G.dop = 0;
-        // after a forward that overflowed (header[1] != 0) the backward composite wrote no records: every gradient is ZERO, the
-        // stale contents of the record buffer are never summed (asynchronous overflow check: rasterizer.py)
         const bool vis = vis_n;
-        const uint32_t flags = fl_n;
-        const float a9[9] = { n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w, n2.x };
+        const bool first = !ACC && f == 0;
+        // (opaque per trip: keeps hipcc from promoting the LDS sums to registers across the loop)
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        float *sAf = lds_all[wave] + ln;
+        // (operand order of the single-camera accumulate: new + old)
+#pragma unroll
+        for (int v = 0; v < SG_GROW_VEC; v++) {
+            const float r[4] = { n[v].x, n[v].y, n[v].z, n[v].w };
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (4 * v + k < NA) sAf[64 * (4 * v + k)] = first ? r[k] : r[k] + sAf[64 * (4 * v + k)];
+        }
+        const float dRGB[3] = { n[3].x, n[3].y, n[3].z };
         if (f + 1 < nframes) {
-            const SgGeom gn = sg_frame(g0_, (size_t)(f + 1) * bt.geom);
             vis_n = live && radii0[(size_t)(f + 1) * bt.P + idx] > 0 && sg_at(header0, (size_t)(f + 1) * bt.bin)[1] == 0u;
-            fl_n = 0u;
+#pragma unroll
+            for (int v = 0; v < SG_GROW_VEC; v++) n[v] = z4;
             if (vis_n) {
-                fl_n = gn.flags[idx];
-                const float4 *src = a9in + 3 * ((size_t)(f + 1) * bt.P + idx);
-                n0 = src[0]; n1 = src[1]; n2 = src[2];
+                const float4 *src = rows + SG_GROW_VEC * ((size_t)(f + 1) * bt.P + idx);
+#pragma unroll
+                for (int v = 0; v < SG_GROW_VEC; v++) n[v] = src[v];
             }
         }
-        // the chain rule; dL/dsh rows: frame 0 assigns, later frames add
-        if (vis) {
-            float sh[nc * 3], dshf[nc * 3];
+        if (want_sh && vis) {
+            // the view direction and the basis: sg_project_bwd's expressions
+            const float *campos = c0.campos + 3 * (size_t)f * (size_t)bt.cam_stride;
+            float dorig[3] = { p[0] - campos[0], p[1] - campos[1], p[2] - campos[2] };
+            float sum2 = dorig[0] * dorig[0] + dorig[1] * dorig[1] + dorig[2] * dorig[2];
+            float len = sqrtf(sum2);
+            float dir[3] = { dorig[0] / len, dorig[1] / len, dorig[2] / len };
+            float bas[16];
+            sg_sh_basis<D>(dir, bas);
 #pragma unroll
-            for (int k = 0; k < nc * 3; k++) { sh[k] = 0.0f; dshf[k] = 0.0f; }
-            if (shs) {
-                const float *src = shs + (size_t)idx * Mrows * 3;
-                if (vec_rows) {
+            for (int k = 0; k < nc; k++)
 #pragma unroll
-                    for (int k = 0; k < nc * 3 / 4; k++) {
-                        float4 v = ((const float4 *)src)[k];
-                        sh[4 * k] = v.x; sh[4 * k + 1] = v.y; sh[4 * k + 2] = v.z; sh[4 * k + 3] = v.w;
-                    }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < nc * 3; k++) sh[k] = src[k];
-                }
-            }
-            sg_project_bwd<D>(c, p, s3, q, cov3D_precomp ? cov3D_precomp + 6 * (size_t)idx : nullptr, sh, flags, a9,
-                              want_sh, dshf, G);
-            if (want_sh) {
-                float *acc = sAcc + tid;
-                if (!preload && f == 0) {
-#pragma unroll
-                    for (int k = 0; k < nc * 3; k++) acc[k * SG_ACC_PITCH] = dshf[k];
-                } else {
-#pragma unroll
-                    for (int k = 0; k < nc * 3; k++) acc[k * SG_ACC_PITCH] = acc[k * SG_ACC_PITCH] + dshf[k];
-                }
-            }
-        }
-        // the screen-space gradient is per VIEW (the densifier's statistic): never accumulated
-        if (live) {
-            float *m2 = dL_dmeans2D + 3 * ((size_t)f * bt.P + idx);
-            m2[0] = G.g2[0]; m2[1] = G.g2[1]; m2[2] = 0.0f;
-        }
-        if (!preload && f == 0) {
-            A = G;
-        } else {
-            // (operand order of the single-camera accumulate: new + old)
-#pragma unroll
-            for (int k = 0; k < 3; k++) { A.dmean[k] = G.dmean[k] + A.dmean[k]; A.dcol[k] = G.dcol[k] + A.dcol[k]; A.dsc[k] = G.dsc[k] + A.dsc[k]; }
-#pragma unroll
-            for (int k = 0; k < 4; k++) A.drot[k] = G.drot[k] + A.drot[k];
-#pragma unroll
-            for (int k = 0; k < 6; k++) A.g6[k] = G.g6[k] + A.g6[k];
-            A.dop = G.dop + A.dop;
+                for (int ch = 0; ch < 3; ch++)
+                    acc[3 * k + ch] = first ? bas[k] * dRGB[ch] : acc[3 * k + ch] + bas[k] * dRGB[ch];
         }
     }
-    SgGaussGrad &G = A;
-    const int idx = idx_all, lane = lane_all;
+#pragma unroll
+    for (int k = 0; k < NA; k++) A[k] = sA[64 * k];
+    __builtin_amdgcn_s_waitcnt(0xC07F);                     // every lane holds its sums: the block is free for the staging rows
+    __builtin_amdgcn_wave_barrier();
     // dL/dsh out: coefficient-major planes [M][P][3], only the (D+1)^2 in use (SG_FLAG_SH_PLANAR); or the reference's rows
-    // (every one of the M rows is written; coalesced through LDS when staged).  (accumulate: the sums already hold old + frames)
+    // (every one of the M rows is written; coalesced through LDS when staged).  (ACC: the sums already hold old + frames)
     if (want_sh && planar) {
         if (live) {
-            const float *acc = sAcc + threadIdx.x;
 #pragma unroll
-            for (int k = 0; k < nc * 3; k++) dL_dsh[((size_t)(k / 3) * P + idx) * 3 + k % 3] = acc[k * SG_ACC_PITCH];
+            for (int k = 0; k < nc * 3; k++) dL_dsh[((size_t)(k / 3) * P + idx) * 3 + k % 3] = acc[k];
         }
     } else if (want_sh) {
-        float dsh[nc * 3];
-        {
-            const float *acc = sAcc + threadIdx.x;
-#pragma unroll
-            for (int k = 0; k < nc * 3; k++) dsh[k] = acc[k * SG_ACC_PITCH];
-        }
         if (staged) {
-            __syncthreads();                                 // every thread holds its sums: the LDS is free for the staging rows
-            float *L = sAcc + wave_all * (32 * SG_ROW_LDS);
-            static_assert(4 * 32 * SG_ROW_LDS <= 48 * SG_ACC_PITCH, "staging rows fit the accumulator block");
+            float *L = lds_all[wave];
 #pragma unroll
             for (int h = 0; h < 2; h++) {                    // 32 rows at a time
                 if ((lane >> 5) == h) {
 #pragma unroll
-                    for (int k = 0; k < 12; k++)
-                        *(float4 *)(L + (lane & 31) * SG_ROW_LDS + 4 * k) = make_float4(dsh[4 * k], dsh[4 * k + 1], dsh[4 * k + 2], dsh[4 * k + 3]);
+                    for (int k = 0; k < nc * 3 / 4; k++)
+                        *(float4 *)(L + (lane & 31) * SG_ROW_LDS + 4 * k) = make_float4(acc[4 * k], acc[4 * k + 1], acc[4 * k + 2], acc[4 * k + 3]);
                 }
                 __builtin_amdgcn_s_waitcnt(0xC07F);
                 __builtin_amdgcn_wave_barrier();
-                if (g0 < P) sg_rows48_store(dL_dsh, g0 + 32 * h, P, lane, L, 32, false);
+                sg_rows48_store(dL_dsh, g0 + 32 * h, P, lane, L, 32, false);
                 __builtin_amdgcn_s_waitcnt(0xC07F);
                 __builtin_amdgcn_wave_barrier();
             }
         } else if (live) {
             float *dsh_row = dL_dsh + (size_t)idx * Mrows * 3;
 #pragma unroll
-            for (int k = 0; k < nc * 3; k++) dsh_row[k] = dsh[k];
-            if (!accumulate)
+            for (int k = 0; k < nc * 3; k++) dsh_row[k] = acc[k];
+            if (!ACC)
                 for (int k = nc * 3; k < Mrows * 3; k++) dsh_row[k] = 0.0f;
         }
     }
     if (!live) return;
-    dL_dmeans3D[3 * idx] = G.dmean[0]; dL_dmeans3D[3 * idx + 1] = G.dmean[1]; dL_dmeans3D[3 * idx + 2] = G.dmean[2];
-    dL_dopacity[idx] = G.dop;
-    if (dL_dcolors) { dL_dcolors[3 * idx] = G.dcol[0]; dL_dcolors[3 * idx + 1] = G.dcol[1]; dL_dcolors[3 * idx + 2] = G.dcol[2]; }
-    if (dL_dscales) { dL_dscales[3 * idx] = G.dsc[0]; dL_dscales[3 * idx + 1] = G.dsc[1]; dL_dscales[3 * idx + 2] = G.dsc[2]; }
-    if (dL_drots) { dL_drots[4 * idx] = G.drot[0]; dL_drots[4 * idx + 1] = G.drot[1]; dL_drots[4 * idx + 2] = G.drot[2]; dL_drots[4 * idx + 3] = G.drot[3]; }
-    if (dL_dcov3D) {
+    dL_dmeans3D[3 * idx] = A[0]; dL_dmeans3D[3 * idx + 1] = A[1]; dL_dmeans3D[3 * idx + 2] = A[2];
+    dL_dopacity[idx] = A[3];
+    if (dL_dcolors) { dL_dcolors[3 * idx] = A[12]; dL_dcolors[3 * idx + 1] = A[13]; dL_dcolors[3 * idx + 2] = A[14]; }
+    if (g6rows) {
+        if (dL_dcov3D) {
 #pragma unroll
-        for (int k = 0; k < 6; k++) dL_dcov3D[6 * idx + k] = G.g6[k];
+            for (int k = 0; k < 6; k++) dL_dcov3D[6 * idx + k] = A[4 + k];
+        }
+    } else {
+        if (dL_dscales) { dL_dscales[3 * idx] = A[4]; dL_dscales[3 * idx + 1] = A[5]; dL_dscales[3 * idx + 2] = A[6]; }
+        if (dL_drots) { dL_drots[4 * idx] = A[8]; dL_drots[4 * idx + 1] = A[9]; dL_drots[4 * idx + 2] = A[10]; dL_drots[4 * idx + 3] = A[11]; }
     }
 }
 
@@ -375,23 +435,38 @@ void sg_launch_preprocess_bwd(const SgCam &c, const SgBatch &bt, int P, const fl
 {
     (void)opacities;
     if (P <= 0) return;
-    dim3 grid((P + 255) / 256), block(256);
+    const int nblocks = (P + 255) / 256;
+    dim3 grid(nblocks), block(256);
     int D = shs ? c.D : 0;
-    // K > 1: dL/dsh sums in LDS ([coefficient][thread]); the staged row store reuses the block
-    const size_t dyn = dL_dsh ? (size_t)(D + 1) * (D + 1) * 3 * SG_ACC_PITCH * sizeof(float) : 0;
+    // K > 1 with an output the 64-byte rows have no room for (dL_dcolors beside SH rows; dL_dcov3D without cov3D_precomp -- no
+    // caller of the project asks for either): the chain of K single-camera launches the two kernels are defined by
+    if (bt.K > 1 && ((shs && dL_dcolors) || (!cov3D_precomp && dL_dcov3D))) {
+        SgBatch one = bt;
+        one.K = 1;
+        for (int f = 0; f < bt.K; f++)
+            sg_launch_preprocess_bwd(sg_frame(c, f, bt.cam_stride), one, P, means3D, shs, colors_precomp, opacities, scales, rotations,
+                                     cov3D_precomp, radii + (size_t)f * bt.P, sg_frame(g, (size_t)f * bt.geom),
+                                     sg_frame(grec, (size_t)f * bt.rec), cap, sg_at(header, (size_t)f * bt.bin),
+                                     sg_at(rec_valid, (size_t)f * bt.bin), nullptr, dL_dmeans3D, dL_dmeans2D + 3 * (size_t)f * bt.P,
+                                     dL_dsh, dL_dcolors, dL_dopacity, dL_dscales, dL_drots, dL_dcov3D, accumulate || f > 0, st, nullptr);
+        return;
+    }
 #define SG_PB1(DD, AA) hipLaunchKernelGGL((sg_preprocess_bwd_kernel<DD, AA>), grid, block, 0, st, c, P, means3D, shs, \
                                      colors_precomp, scales, rotations, cov3D_precomp, radii, g,            \
                                      grec, cap, header, rec_valid, dL_dmeans3D, dL_dmeans2D, dL_dsh, dL_dcolors, \
                                      dL_dopacity, dL_dscales, dL_drots, dL_dcov3D)
-#define SG_PBK(DD, AA) hipLaunchKernelGGL((sg_preprocess_bwd_frames_kernel<DD, AA>), grid, block, dyn, st, c, bt, P, means3D, shs, \
-                                     colors_precomp, scales, rotations, cov3D_precomp, radii, g,            \
-                                     header, a9buf, dL_dmeans3D, dL_dmeans2D, dL_dsh, dL_dcolors, \
-                                     dL_dopacity, dL_dscales, dL_drots, dL_dcov3D)
+// K > 1: the per-(Gaussian, frame) chain rule at full grid (rows [K][P][4] vectors behind the K record buffers), then the ordered sums
+#define SG_PBK(DD, AA) do {                                                                                                        \
+        hipLaunchKernelGGL((sg_gauss_frame_bwd_kernel<DD>), dim3(sg_frame_grid(nblocks, bt.K)), block, 0, st, c, bt, P, means3D,   \
+                           shs, scales, rotations, cov3D_precomp, radii, g, grec, cap, header, rec_valid, a9buf, dL_dmeans2D,      \
+                           nblocks);                                                                                               \
+        hipLaunchKernelGGL((sg_gauss_sum_frames_kernel<DD, AA>), grid, block, 0, st, c, bt, P, means3D, radii, header, a9buf,      \
+                           cov3D_precomp != nullptr, dL_dmeans3D, dL_dsh, dL_dcolors, dL_dopacity, dL_dscales, dL_drots,           \
+                           dL_dcov3D);                                                                                             \
+    } while (0)
 #define SG_PB2(DD, AA) do { if (bt.K == 1) SG_PB1(DD, AA); else SG_PBK(DD, AA); } while (0)      // (K = 1: the round-3 kernel, untouched)
 #define SG_PB(DD) do { if (accumulate) SG_PB2(DD, true); else SG_PB2(DD, false); } while (0)
     sg_prof_begin(SG_K_PREPROCESS_BWD, st);
-    // K > 1: the record sums of all frames first, as a kernel of their own (a9 [K][P][12] behind the K record buffers)
-    if (bt.K > 1) sg_launch_record_sums(bt, P, radii, g, grec, cap, header, rec_valid, a9buf, st);
 #define SG_PBA(DD) hipLaunchKernelGGL((sg_preprocess_bwd_aux_kernel<DD>), grid, block, 0, st, c, P, means3D, shs,            \
                                      colors_precomp, scales, rotations, cov3D_precomp, radii, g,            \
                                      grec, cap, header, rec_valid, dL_dmeans3D, dL_dmeans2D, dL_dsh, dL_dcolors, \
