@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SINGS_HIP_LIB") or os.path.join(_HERE, "libsings_hip.so")
 _lib = None
 HAS_ORDER = False                    # set by load(): the library exports the table of include/sings_order.h
+HAS_SAMPLER = False                  # set by load(): the library exports the table of include/sings_sampler.h
 
 
 class SgRasterSettings(C.Structure):
@@ -189,6 +190,11 @@ _PROTOTYPES_ORDER = {
     "sg_rasterize_forward_frames_ordered": "i: S F i p9 z p3 n p i p",
     "sg_work_order_codes": "i: i p4",
 }
+# The patch sampler of the LPIPS term, include/sings_sampler.h: a fifth header and a fifth table, for the same reason.
+_PROTOTYPES_SAMPLER = {
+    "sg_patch_sampler_ws_bytes": "z: i4",
+    "sg_patch_origins": "i: i6 f p6",
+}
 _P = C.POINTER
 _CTYPE = {"i": C.c_int, "z": C.c_size_t, "f": C.c_float, "s": C.c_char_p,
           "p": C.c_void_p,                        # a raw device pointer (or NULL), and the stream
@@ -212,6 +218,10 @@ ORDER_BLOCK = 256                    # SG_ORDER_BLOCK
 ORDER_CODE_BITS = 10                 # SG_ORDER_CODE_BITS
 ORDER_WS_BYTES = 32                  # SG_ORDER_WS_BYTES
 HIST_TILES_MAX = 4096                # SG_HIST_TILES_MAX (sings_amd/csrc/sg_common.h): tile counters up to which a frame has "few tiles"
+PATCH_MAX_N = 16                     # SG_PATCH_MAX_N
+PATCH_CHUNK = 4096                   # SG_PATCH_CHUNK
+PATCH_STATE_WORDS = 4                # SG_PATCH_STATE_WORDS
+PATCH_BRANCH_MASKED, PATCH_BRANCH_UNIFORM, PATCH_BRANCH_FORCED = 0, 1, 2         # SG_PATCH_BRANCH_*
 MESH_TERMS_INFO_INTS = 2             # SG_MESH_TERMS_INFO_INTS
 MESH_TERMS_BAD_LABEL = 1             # SG_MESH_TERMS_BAD_LABEL
 MESH_TERMS_BAD_EDGE = 2              # SG_MESH_TERMS_BAD_EDGE
@@ -255,12 +265,14 @@ def load():
                            "(include/sings_hip.h SG_ABI_VERSION): rebuild with `make -C sings_amd/csrc`")
     # (SINGS_HIP_LIB may name a library that predates include/sings_order.h -- an A/B run against a parent build: it exports none of
     # that table, HAS_ORDER says so, and the engines then make the unordered calls that library knows)
-    global HAS_ORDER
+    global HAS_ORDER, HAS_SAMPLER
     HAS_ORDER = all(hasattr(lib, name) for name in _PROTOTYPES_ORDER)
-    if not HAS_ORDER and LIB_PATH == os.path.join(_HERE, "libsings_hip.so"):
-        raise RuntimeError(f"sings_amd: {LIB_PATH} lacks the entry points of include/sings_order.h: rebuild with `make -C sings_amd/csrc`")
+    HAS_SAMPLER = all(hasattr(lib, name) for name in _PROTOTYPES_SAMPLER)    # (the same, for include/sings_sampler.h)
+    for has, header in ((HAS_ORDER, "sings_order.h"), (HAS_SAMPLER, "sings_sampler.h")):
+        if not has and LIB_PATH == os.path.join(_HERE, "libsings_hip.so"):
+            raise RuntimeError(f"sings_amd: {LIB_PATH} lacks the entry points of include/{header}: rebuild with `make -C sings_amd/csrc`")
     for name, signature in (*_PROTOTYPES.items(), *_PROTOTYPES_EVAL.items(), *_PROTOTYPES_MESH_TERMS.items(),
-                            *(_PROTOTYPES_ORDER.items() if HAS_ORDER else ())):
+                            *(_PROTOTYPES_ORDER.items() if HAS_ORDER else ()), *(_PROTOTYPES_SAMPLER.items() if HAS_SAMPLER else ())):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = _ctypes_of(signature)
     _lib = lib

@@ -6,7 +6,8 @@ autograd to ``in0``.  The network is frozen: no weight gradients, and ``in1`` mu
 
 ``lpips_patch_loss`` is the whole term of loss.py:71-80 -- clamp, the two compositions over the random background, the patch crop,
 ``.clip(max=1)``, LPIPS, ``.mean()`` and the weight -- with the patch origins as a device tensor (no host round trip, so the step
-can be captured as a graph).  ``PatchSampler`` draws the origins as utils/image/sampler.py does, with the same numpy RNG calls.
+can be captured as a graph).  ``PatchSampler`` draws the origins as utils/image/sampler.py does, with the same numpy RNG calls
+-- on the host, from a copy of the mask; ``sings_amd.patch_sampler.DevicePatchSampler`` draws them on the device, inside a captured step.
 No CPU fallback: the HIP library must be present.
 """
 import ctypes as C

@@ -104,14 +104,28 @@ class AvatarTrainer:
     whenever the set changes (the mesh's current edges and labels; vertex normals from ``avatar_init.initial_attributes``, which is
     parity-unpinned, INTEGRATION.md 13: of the anchors at construction, of the vertices a densify / prune produced afterwards; the
     same vertices for the constant edge term) and ``set_iteration(self.iteration)`` before every step: a captured step replays with the
-    iteration's own weights.  With ``mesh_terms=None`` nothing changes."""
+    iteration's own weights.  With ``mesh_terms=None`` nothing changes.
+
+    ``lpips_sampler``: a ``sings_amd.patch_sampler.DevicePatchSampler`` -- the step draws its own LPIPS patch corners from the step's
+    mask, on the device, in front of the module's forward: the draw is part of a captured step, and every replay draws the next
+    patches of the sampler's sequence (an eager and a captured trainer with the same seed see the same patches at the same
+    iteration: the capture's warm-up runs are not steps, the sampler's state is put back after them).  The module must carry the
+    term (``lpips=``, ``lpips_w`` > 0) with the sampler's patch size; ``lpips_origins=`` of ``step`` / ``step_frames`` is then refused.
+    The corners a step used: ``lpips_sampler.last_origins``.  With ``lpips_sampler=None`` nothing changes."""
 
     POSE_GROUPS = ("global_orient", "body_pose", "transl")
     STATS = ("xyz_gradient_accum", "denom", "max_radii2D")      # the module's densification statistics, one row per Gaussian
 
     def __init__(self, module, settings_fn, bg_color, lrs, smpl_scale=None, transl=None, use_graph=False, fp=None,
                  sh_degree=0, max_sh_degree=3, betas=(0.9, 0.999), eps=1e-15, optimizer="torch", lr_schedules=None, poses=None,
-                 mesh=None, mesh_terms=None):
+                 mesh=None, mesh_terms=None, lpips_sampler=None):
+        if lpips_sampler is not None:
+            if getattr(module, "lpips", None) is None or not module.lpips_w > 0.0:
+                raise ValueError("AvatarTrainer: lpips_sampler needs the module's LPIPS term (AvatarStep(lpips=..., lpips_w > 0))")
+            if lpips_sampler.patch_size != module.lpips_patch_size:
+                raise ValueError(f"AvatarTrainer: lpips_sampler draws corners for patches of {lpips_sampler.patch_size}, the module "
+                                 f"crops patches of {module.lpips_patch_size}")
+        self.lpips_sampler = lpips_sampler
         if mesh_terms is not None and mesh is None:
             raise ValueError("AvatarTrainer: mesh_terms needs mesh=MeshState(...) (the edges and labels the terms are built from)")
         self.mesh_terms, self._mesh_verts = mesh_terms, None
@@ -211,8 +225,14 @@ class AvatarTrainer:
             A, transl = self.poses(s["idx"])
             if s["single"]:
                 A, transl = A[0], transl[0]
+        origins = s.get("lp_origins")
+        if self.lpips_sampler is not None:                       # this step's corners, drawn from its mask: two launches, no host read
+            frames = A.dim() == 4
+            origins = self.lpips_sampler.origins(s["mask"], frames=int(A.shape[0]) if frames else None)
+            if not frames:
+                origins = origins.reshape(-1, 2)
         loss, ld, ex = self.m(A, self.rs, s["gt"], s["mask"], self.bg, smpl_scale=self.smpl_scale, transl=transl,
-                              lpips_origins=s.get("lp_origins"), lpips_bg=s.get("lp_bg"))
+                              lpips_origins=origins, lpips_bg=s.get("lp_bg"))
         if loss is None:
             self.m.backward(ld, ex)
         else:
@@ -227,6 +247,8 @@ class AvatarTrainer:
         # (the capture's warm-up runs execute the body -- statistics included -- without being steps: put the statistics back;
         # with the fused optimiser in the body they update parameters and moments too: those go back as well)
         live = [self.m.xyz_gradient_accum, self.m.denom, self.m.max_radii2D]
+        if self.lpips_sampler is not None:
+            live.append(self.lpips_sampler.state)                # (the counter: the warm-up runs draw patches too)
         if self.fused and self.fp is None:
             live += [p.detach() for p in self.params] + [self.opt.exp_avg, self.opt.exp_avg_sq]
         keep, steps = [x.clone() for x in live], (list(self.opt.steps) if self.fused else None)
@@ -263,13 +285,18 @@ class AvatarTrainer:
         s = self._static
         key = "idx" if "idx" in pose_in else "A"
         A = pose_in[key]
+        if self.lpips_sampler is not None and lpips_origins is not None:
+            raise ValueError("AvatarTrainer: the trainer draws the patch corners itself (lpips_sampler=): lpips_origins= cannot be passed too")
         lp = {"lp_origins": lpips_origins, "lp_bg": lpips_bg}
         lp = {k: (None if v is None else torch.as_tensor(v).to(self.dev)) for k, v in lp.items()}
         if lp["lp_origins"] is not None:
             lp["lp_origins"] = lp["lp_origins"].to(torch.int32)
-        shapes = lambda d: tuple(None if d.get(k) is None else tuple(d[k].shape) for k in ("lp_origins", "lp_bg"))
+        # (with a sampler the corners' shape follows the mask's: a mask of another shape is a new set of static inputs, as new corners are)
+        keys = ("lp_origins", "lp_bg") + (("mask",) if self.lpips_sampler is not None else ())
+        shapes = lambda d: tuple(None if d.get(k) is None else tuple(d[k].shape) for k in keys)
+        lp_shape = dict(lp, mask=mask)
         if (not s or s.get(key) is None or s[key].shape != A.shape or s.get("single") != pose_in.get("single")
-                or shapes(s) != shapes(lp)):
+                or shapes(s) != shapes(lp_shape)):
             s.update(A=None, idx=None, single=pose_in.get("single"))      # (the step reads A, or the tables' rows at idx: not both)
             s.update({key: A.clone(), "gt": gt_rgb.clone(), "mask": mask.clone()})
             s.update({k: (None if v is None else v.clone()) for k, v in lp.items()})
