@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("SINGS_HIP_LIB") or os.path.join(_HERE, "libsings_hip.
 _lib = None
 HAS_ORDER = False                    # set by load(): the library exports the table of include/sings_order.h
 HAS_SAMPLER = False                  # set by load(): the library exports the table of include/sings_sampler.h
+HAS_FROZEN = False                   # set by load(): the library exports the table of include/sings_frozen.h
 
 
 class SgRasterSettings(C.Structure):
@@ -195,6 +196,11 @@ _PROTOTYPES_SAMPLER = {
     "sg_patch_sampler_ws_bytes": "z: i4",
     "sg_patch_origins": "i: i6 f p6",
 }
+# The decoders without a gradient, include/sings_frozen.h: a sixth header and a sixth table, for the same reason.
+_PROTOTYPES_FROZEN = {
+    "sg_frozen_geometry": "i: i4 p18",
+    "sg_frozen_appearance": "i: i3 p13",
+}
 _P = C.POINTER
 _CTYPE = {"i": C.c_int, "z": C.c_size_t, "f": C.c_float, "s": C.c_char_p,
           "p": C.c_void_p,                        # a raw device pointer (or NULL), and the stream
@@ -222,6 +228,8 @@ PATCH_MAX_N = 16                     # SG_PATCH_MAX_N
 PATCH_CHUNK = 4096                   # SG_PATCH_CHUNK
 PATCH_STATE_WORDS = 4                # SG_PATCH_STATE_WORDS
 PATCH_BRANCH_MASKED, PATCH_BRANCH_UNIFORM, PATCH_BRANCH_FORCED = 0, 1, 2         # SG_PATCH_BRANCH_*
+FROZEN_BLOCK = 128                   # SG_FROZEN_BLOCK: points per workgroup of the fused no-gradient decode
+FROZEN_SHS = 48                      # SG_FROZEN_SHS
 MESH_TERMS_INFO_INTS = 2             # SG_MESH_TERMS_INFO_INTS
 MESH_TERMS_BAD_LABEL = 1             # SG_MESH_TERMS_BAD_LABEL
 MESH_TERMS_BAD_EDGE = 2              # SG_MESH_TERMS_BAD_EDGE
@@ -265,14 +273,16 @@ def load():
                            "(include/sings_hip.h SG_ABI_VERSION): rebuild with `make -C sings_amd/csrc`")
     # (SINGS_HIP_LIB may name a library that predates include/sings_order.h -- an A/B run against a parent build: it exports none of
     # that table, HAS_ORDER says so, and the engines then make the unordered calls that library knows)
-    global HAS_ORDER, HAS_SAMPLER
+    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN
     HAS_ORDER = all(hasattr(lib, name) for name in _PROTOTYPES_ORDER)
     HAS_SAMPLER = all(hasattr(lib, name) for name in _PROTOTYPES_SAMPLER)    # (the same, for include/sings_sampler.h)
-    for has, header in ((HAS_ORDER, "sings_order.h"), (HAS_SAMPLER, "sings_sampler.h")):
+    HAS_FROZEN = all(hasattr(lib, name) for name in _PROTOTYPES_FROZEN)      # (the same, for include/sings_frozen.h)
+    for has, header in ((HAS_ORDER, "sings_order.h"), (HAS_SAMPLER, "sings_sampler.h"), (HAS_FROZEN, "sings_frozen.h")):
         if not has and LIB_PATH == os.path.join(_HERE, "libsings_hip.so"):
             raise RuntimeError(f"sings_amd: {LIB_PATH} lacks the entry points of include/{header}: rebuild with `make -C sings_amd/csrc`")
     for name, signature in (*_PROTOTYPES.items(), *_PROTOTYPES_EVAL.items(), *_PROTOTYPES_MESH_TERMS.items(),
-                            *(_PROTOTYPES_ORDER.items() if HAS_ORDER else ()), *(_PROTOTYPES_SAMPLER.items() if HAS_SAMPLER else ())):
+                            *(_PROTOTYPES_ORDER.items() if HAS_ORDER else ()), *(_PROTOTYPES_SAMPLER.items() if HAS_SAMPLER else ()),
+                            *(_PROTOTYPES_FROZEN.items() if HAS_FROZEN else ())):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = _ctypes_of(signature)
     _lib = lib

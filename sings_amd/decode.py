@@ -219,21 +219,36 @@ def arena_sync(params, views, to_arena=True):
     return len(pairs)
 
 
+def _tp_lookup(pts, aabb, n_scales, planes):
+    """the tri-plane features of ``pts`` (sg_triplane_forward) -> (feats, x, tp, lib): the lookup alone, nothing kept for a backward."""
+    if not pts.is_cuda:
+        raise RuntimeError("sings_amd.decode: tensors must live on the GPU (no CPU fallback)")
+    lib = _lib.load()
+    grids = [planes[3 * s:3 * s + 3] for s in range(n_scales)]
+    keep = []
+    tp = _tp_struct(grids, aabb, keep)
+    x = pts.detach().contiguous().float()
+    dev, N = x.device, int(x.shape[0])
+    ws = torch.empty(int(lib.sg_triplane_ws_bytes(C.byref(tp))), dtype=torch.uint8, device=dev)
+    feats = torch.empty((N, tp.n_scales * tp.feat), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.sg_triplane_forward(C.byref(tp), N, _ptr(x), _ptr(ws), _ptr(feats), _stream(dev)), "triplane forward")
+    return feats, x, tp, lib
+
+
+def triplane_features_nograd(triplane, pts):
+    """``triplane(pts)`` for a caller that will never differentiate it: no autograd node, nothing saved, and none of the backward's
+    preparation (the point sorts of ``_Triplane.forward``) is launched or queued -- under ``torch.no_grad()`` the autograd function
+    would still see parameters that require a gradient and prepare for one."""
+    planes = [p for gp in triplane.grids for p in gp]
+    return _tp_lookup(pts.reshape(-1, 3), triplane.aabb, len(triplane.grids), planes)[0]
+
+
 class _Triplane(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pts, aabb, n_scales, *planes):
-        if not pts.is_cuda:
-            raise RuntimeError("sings_amd.decode: tensors must live on the GPU (no CPU fallback)")
-        lib = _lib.load()
-        grids = [planes[3 * s:3 * s + 3] for s in range(n_scales)]
-        keep = []
-        tp = _tp_struct(grids, aabb, keep)
-        x = pts.detach().contiguous().float()
+        feats, x, tp, lib = _tp_lookup(pts, aabb, n_scales, planes)
         dev, N = x.device, int(x.shape[0])
-        ws = torch.empty(int(lib.sg_triplane_ws_bytes(C.byref(tp))), dtype=torch.uint8, device=dev)
-        feats = torch.empty((N, tp.n_scales * tp.feat), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.sg_triplane_forward(C.byref(tp), N, _ptr(x), _ptr(ws), _ptr(feats), _stream(dev)), "triplane forward")
         ctx.save_for_backward(x, aabb, *planes)
         ctx.n_scales = n_scales
         ctx.early = None
@@ -795,12 +810,141 @@ class _Act(torch.autograd.Function):
         return dz, None
 
 
+# ---- decoders without a gradient ---------------------------------------------------------------------------------------------
+# The reference's first opt_geo_from / opt_app_from iterations run a decoder under torch.no_grad() (sings_hybrid.py:265-277): nothing
+# of it is ever differentiated, so nothing of it needs saving.  One launch per decoder (include/sings_frozen.h: the hidden layers stay
+# in LDS); where the library lacks that table or refuses the widths, the per-layer kernels under no_grad -- the same values up to the
+# summation order.
+def _fz_param(t):
+    t = t.detach()
+    return t if (t.dtype == torch.float32 and t.is_contiguous()) else t.contiguous().float()
+
+
+def _fz_usable(feats, hidden, wide):
+    """the fused kernels take these features and weights: the table is there, the widths are theirs, the 16-byte loads are aligned."""
+    cin = int(feats.shape[1])
+    return (_lib.HAS_FROZEN and feats.is_cuda and feats.shape[0] >= 1 and cin % 4 == 0 and 4 <= cin <= 128 and hidden in (64, 128)
+            and all(t.data_ptr() % 16 == 0 for t in wide))
+
+
+def frozen_geometry(feats, dec, fused=True, out=None):
+    """GeometryDecoder.forward without autograd: {'xyz_offsets', 'rotations' | None, 'scales', 'scales_aux'}.  ``fused=False``: the
+    per-layer kernels under no_grad.  ``out``: buffers (xyz_offsets, scales, scales_aux, rotations | None) of at least N rows the
+    fused kernel writes its N rows into."""
+    _lib.load()
+    feats = feats.detach()
+    if feats.dtype != torch.float32 or not feats.is_contiguous():
+        feats = feats.contiguous().float()
+    lins = [dec.net[0], dec.net[2], dec.scales[0], dec.scales[2], dec.xyz_offsets] + ([] if dec.isotropic else [dec.rotations[0]])
+    W = [_fz_param(l.weight) for l in lins]
+    hidden = int(W[0].shape[0])
+    if not (fused and _fz_usable(feats, hidden, W)):
+        if out is not None:
+            raise RuntimeError("sings_amd.decode: the fused no-gradient decode does not take these widths")
+        with torch.no_grad():
+            return dec(feats)
+    b = [_fz_param(l.bias) for l in lins]
+    dev, N = feats.device, int(feats.shape[0])
+    if out is None:
+        out = [torch.empty((N, 3), dtype=torch.float32, device=dev) for _ in range(3)]
+        out.append(None if dec.isotropic else torch.empty((N, 6), dtype=torch.float32, device=dev))
+    xyz_offsets, scales, scales_aux, rotations = out
+    rot = (W[5], b[5]) if not dec.isotropic else (None, None)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().sg_frozen_geometry(
+            N, int(feats.shape[1]), hidden, 0 if dec.isotropic else 1, _ptr(feats), _ptr(W[0]), _ptr(b[0]), _ptr(W[1]), _ptr(b[1]),
+            _ptr(W[2]), _ptr(b[2]), _ptr(W[3]), _ptr(b[3]), _ptr(W[4]), _ptr(b[4]), _ptr(rot[0]), _ptr(rot[1]), _ptr(xyz_offsets),
+            _ptr(scales), _ptr(scales_aux), _ptr(rotations), _stream(dev)), "frozen geometry decode")
+    return {'xyz_offsets': xyz_offsets, 'rotations': rotations, 'scales': scales, 'scales_aux': scales_aux}
+
+
+def frozen_appearance(feats, dec, fused=True, out=None):
+    """AppearanceDecoder.forward without autograd: {'shs' [N,16,3], 'opacity' [N,1]}.  ``out``: (shs [>=N,48], opacity [>=N,1] |
+    None) for the fused kernel."""
+    _lib.load()
+    feats = feats.detach()
+    if feats.dtype != torch.float32 or not feats.is_contiguous():
+        feats = feats.contiguous().float()
+    lins = [dec.net[0], dec.net[2], dec.shs] + ([] if dec.fixed_opacity else [dec.opacity])
+    W = [_fz_param(l.weight) for l in lins]
+    b = [_fz_param(l.bias) for l in lins]
+    hidden = int(W[0].shape[0])
+    if not (fused and _fz_usable(feats, hidden, W + [b[2]]) and int(W[2].shape[0]) == _lib.FROZEN_SHS):
+        if out is not None:
+            raise RuntimeError("sings_amd.decode: the fused no-gradient decode does not take these widths")
+        with torch.no_grad():
+            return dec(feats)
+    dev, N = feats.device, int(feats.shape[0])
+    if out is None:
+        out = (torch.empty((N, _lib.FROZEN_SHS), dtype=torch.float32, device=dev),
+               None if dec.fixed_opacity else torch.empty((N, 1), dtype=torch.float32, device=dev))
+    shs, opacity = out
+    off = None
+    if not dec.fixed_opacity and torch.is_tensor(dec.opacity_offset):
+        off = dec.opacity_offset.detach().contiguous().float().reshape(-1)
+    op = (W[3], b[3]) if not dec.fixed_opacity else (None, None)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().sg_frozen_appearance(
+            N, int(feats.shape[1]), hidden, _ptr(feats), _ptr(W[0]), _ptr(b[0]), _ptr(W[1]), _ptr(b[1]), _ptr(W[2]), _ptr(b[2]),
+            _ptr(op[0]), _ptr(op[1]), _ptr(off), _ptr(shs), _ptr(opacity), _stream(dev)), "frozen appearance decode")
+    if dec.fixed_opacity:
+        opacity = torch.ones((N, 1), device=dev)
+    return {'shs': shs[:N].reshape(-1, 16, 3), 'opacity': opacity}
+
+
+def _assemble(xyz, g, a_fn, thickness_factor, scaling_multiplier, geometry_hook):
+    """the tail of SinGS.get_gs_attrs (sings_hybrid.py:280-313) on a geometry decoder's outputs; ``a_fn()``: the appearance decoder's,
+    issued after the geometry hook."""
+    scales = g['scales']
+    if thickness_factor != 1.0:
+        scales = torch.cat([scales[:, :-1], scales[:, -1:] * thickness_factor], dim=1)
+    if scaling_multiplier is not None:
+        scales = scales * scaling_multiplier
+    xyz_canon = xyz + g['xyz_offsets']
+    if geometry_hook is not None:
+        xyz_canon, scales = geometry_hook(xyz_canon, scales)
+    a = a_fn()
+    return {"xyz_canon": xyz_canon, "xyz_offsets": g['xyz_offsets'], "rot6d_canon": g['rotations'],
+            "scales_aux": g['scales_aux'], "scales": scales, "opacity": a['opacity'], "shs": a['shs']}
+
+
+def decode_frozen(xyz, triplane, geometry_dec, appearance_dec, thickness_factor=1.0, scaling_multiplier=None, geometry_hook=None,
+                  fused=True):
+    """``decode_attributes`` with both decoders frozen: the tri-plane lookup saves nothing, no backward preparation is queued, each
+    decoder is one launch and its outputs carry no autograd history.  ``xyz_canon = xyz + xyz_offsets`` keeps the gradient to ``xyz``
+    (and is the only output that does).  ``fused=False``: the per-layer kernels under no_grad."""
+    tri_feats = triplane_features_nograd(triplane, xyz)
+    g = frozen_geometry(tri_feats, geometry_dec, fused)
+    return _assemble(xyz, g, lambda: frozen_appearance(tri_feats, appearance_dec, fused), thickness_factor, scaling_multiplier,
+                     geometry_hook)
+
+
 def decode_attributes(xyz, triplane, geometry_dec, appearance_dec, thickness_factor=1.0, scaling_multiplier=None,
-                      geometry_hook=None):
+                      geometry_hook=None, opt_geo=True, opt_app=True, fused_frozen=True):
     """SinGS.get_gs_attrs for one level (sings_hybrid.py:249-313): the dict the LBS/render path consumes.
     ``geometry_hook(xyz_canon, scales) -> (xyz_canon, scales)``: applied to the geometry decoder's outputs BEFORE the appearance
     decoder is issued -- autograd nodes the hook creates are visited after the appearance decoder's in the backward pass
-    (sings_amd.train_step uses it to add the k-NN regulariser's gradient as late as possible)."""
+    (sings_amd.train_step uses it to add the k-NN regulariser's gradient as late as possible).
+    ``opt_geo`` / ``opt_app`` (gs_trainer.py:225-226): False freezes that decoder as the reference's torch.no_grad() does -- its
+    outputs carry no autograd history and its parameters receive no gradient; with both False the tri-plane receives none either.
+    ``fused_frozen=False``: a frozen decoder runs through the per-layer kernels under no_grad instead of the fused launch."""
+    if not (opt_geo or opt_app):
+        return decode_frozen(xyz, triplane, geometry_dec, appearance_dec, thickness_factor, scaling_multiplier, geometry_hook,
+                             fused_frozen)
+    if not (opt_geo and opt_app):
+        # one decoder live: the features feed it through today's layers (the shared-input slot sees one consumer) and the frozen
+        # one, detached, through the fused launch
+        tri_feats = triplane(xyz)
+        live = geometry_dec if opt_geo else appearance_dec
+        if tri_feats.is_cuda and torch.is_grad_enabled() and (int(tri_feats.shape[1]) & 31) == 0:
+            first = linear_act_shared(tri_feats, live.net[0], ACT_GELU, {})
+        else:
+            first = linear_act(tri_feats, live.net[0], ACT_GELU)
+        if opt_geo:
+            return _assemble(xyz, geometry_dec(tri_feats, first=first), lambda: frozen_appearance(tri_feats, appearance_dec, fused_frozen),
+                             thickness_factor, scaling_multiplier, geometry_hook)
+        return _assemble(xyz, frozen_geometry(tri_feats, geometry_dec, fused_frozen), lambda: appearance_dec(tri_feats, first=first),
+                         thickness_factor, scaling_multiplier, geometry_hook)
     tri_feats = triplane(xyz)
     # both decoders' first layers read the tri-plane features: ONE feature gradient (the second layer to run its backward adds into
     # the first one's), but two autograd nodes -- the appearance decoder's backward does not wait for the geometry decoder's

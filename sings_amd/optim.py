@@ -64,10 +64,12 @@ def hyper_row(lr, beta1, beta2, eps, step):
     return row.astype(np.float32)
 
 
-def build_tables(addresses, numels, groups, chunk=None):
+def build_tables(addresses, numels, groups, chunk=None, active_groups=None):
     """-> (segments [S,4] int64, chunks [C,2] int32) of ``sg_adam_step`` for parameter tensors at ``addresses`` with ``numels``
     elements that lie one behind the other in the arena.  Pure host arithmetic: every element of every segment is in exactly one
-    chunk, and a chunk never crosses a segment."""
+    chunk, and a chunk never crosses a segment.
+    ``active_groups`` (group indices; None: all): the chunk table lists the segments of these groups only -- the launch never touches
+    the others -- while the segment table, and with it every offset into the arena and the moments, keeps the full layout."""
     chunk = int(_lib.load().sg_adam_chunk_elements()) if chunk is None else int(chunk)
     seg = np.zeros((len(numels), 4), np.int64)
     rows, off = [], 0
@@ -76,7 +78,7 @@ def build_tables(addresses, numels, groups, chunk=None):
         if n < 0 or n >= 2 ** 31:
             raise ValueError(f"FusedAdam: a parameter of {n} elements (must be 0 .. 2^31 - 1)")
         seg[s] = (int(a), off, n, int(g))
-        first = np.arange(0, n, chunk, dtype=np.int64)
+        first = np.arange(0, n if active_groups is None or int(g) in active_groups else 0, chunk, dtype=np.int64)
         rows.append(np.stack([np.full_like(first, s), first], 1))
         off += n
     chunks = np.concatenate(rows) if rows else np.zeros((0, 2), np.int64)
@@ -143,6 +145,7 @@ class FusedAdam:
         self._pinned = torch.zeros((_RING, G, HYPER_COLUMNS), dtype=torch.float32).pin_memory()
         self._events, self._slot = [None] * _RING, 0
         self.grad_flat = self.grad_views = self._reg = None
+        self._active = None                                       # group names that take part in a step (None: all)
         if grad_flat is not None:
             self.bind_arena(grad_flat, grad_views)
 
@@ -163,6 +166,40 @@ class FusedAdam:
         """Per-parameter views of a flat moment buffer, in each parameter's own shape and memory layout."""
         return [_dec._like_layout(flat[o:o + p.numel()], p) for o, p in zip(self._offsets(), self._params())]
 
+    def _active_groups(self):
+        return None if self._active is None else {gi for gi, g in enumerate(self.param_groups) if g["name"] in self._active}
+
+    def _is_active(self, g):
+        return self._active is None or g["name"] in self._active
+
+    def set_active(self, names=None):
+        """The groups that take part in the following steps (``names``: group names; None: all, the default).  An inactive group is a
+        parameter set the reference's Adam skips because it has no gradient (frozen decoders, gs_trainer.py:225-226): its parameters,
+        moments and step count are never touched, ``advance()`` does not count a step for it, and ``apply()`` asks no gradient of it.
+        The chunk table of the launch lists the active groups only; segment offsets keep the full layout, so nothing is re-indexed."""
+        if names is not None:
+            names = set(names)
+            known = {g["name"] for g in self.param_groups}
+            if not names <= known:
+                raise ValueError(f"FusedAdam.set_active: unknown groups {sorted(names - known)}")
+            if not names:
+                raise ValueError("FusedAdam.set_active: no active group")
+            if names == known:
+                names = None
+        if names == self._active:
+            return
+        self._active = names
+        if self._reg is not None:
+            self._build_tables(self._params())
+        self._grads_checked = False
+
+    def _build_tables(self, params):
+        group_of = [gi for gi, g in enumerate(self.param_groups) for _ in g["params"]]
+        seg, chunks = build_tables([p.data_ptr() for p in params], [p.numel() for p in params], group_of,
+                                   active_groups=self._active_groups())
+        self.segments = torch.from_numpy(seg).to(self.dev)
+        self.chunks = torch.from_numpy(chunks).to(self.dev)
+
     def bind_arena(self, grad_flat, grad_views):
         """(Re)bind the gradient arena of the CURRENT parameters and rebuild the device tables."""
         params = self._params()
@@ -176,10 +213,7 @@ class FusedAdam:
                 raise ValueError(f"FusedAdam: parameter {name} must be contiguous (or a feature-minor tri-plane plane)")
         if self.exp_avg.numel() != n:
             raise RuntimeError("FusedAdam: the moments were not re-indexed for the new sizes (remap_rows)")
-        group_of = [gi for gi, g in enumerate(self.param_groups) for _ in g["params"]]
-        seg, chunks = build_tables([p.data_ptr() for p in params], [p.numel() for p in params], group_of)
-        self.segments = torch.from_numpy(seg).to(self.dev)
-        self.chunks = torch.from_numpy(chunks).to(self.dev)
+        self._build_tables(params)
         self.grad_flat, self.grad_views = grad_flat, list(grad_views)
         self._reg = [(weakref.ref(p), p.data_ptr()) for p in params]
         self._grads_checked = False
@@ -192,7 +226,8 @@ class FusedAdam:
 
     # ---- the step
     def advance(self):
-        """Host half of a step: every group's step count + 1, its row from ITS ``lr`` / ``betas`` / ``eps``, H2D copy enqueued."""
+        """Host half of a step: every ACTIVE group's step count + 1, its row from ITS ``lr`` / ``betas`` / ``eps``, H2D copy enqueued.
+        (An inactive group's count stays; its row, which no chunk of the launch refers to, is zero.)"""
         slot = self._slot
         self._slot = (slot + 1) % _RING
         ev = self._events[slot]
@@ -200,6 +235,9 @@ class FusedAdam:
             ev.synchronize()                                      # (only if the host is a whole ring ahead of the GPU)
         host = self._pinned[slot]
         for gi, g in enumerate(self.param_groups):
+            if not self._is_active(g):
+                host[gi].zero_()
+                continue
             self.steps[gi] += 1
             b1, b2 = g["betas"]
             host[gi] = torch.from_numpy(hyper_row(float(g["lr"]), float(b1), float(b2), float(g["eps"]), self.steps[gi]))
@@ -209,12 +247,14 @@ class FusedAdam:
         ev.record()
 
     def _check(self):
-        """Host checks before anything is enqueued: the registration is current, and (once per binding) every parameter has a gradient."""
+        """Host checks before anything is enqueued: the registration is current, and (once per binding and set of active groups)
+        every parameter of an active group has a gradient."""
         params = self._params()
         self._check_current(params)
         if not self._grads_checked:
-            for name, p in zip(self._names(), params):
-                if p.grad is None:
+            active = [self._is_active(g) for g in self.param_groups for _ in g["params"]]
+            for name, p, on in zip(self._names(), params, active):
+                if on and p.grad is None:
                     raise RuntimeError(f"FusedAdam: parameter {name} has no gradient -- its arena slot would feed the update a stale "
                                        "one; every registered parameter must take part in the backward")
             self._grads_checked = True

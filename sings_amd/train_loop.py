@@ -59,6 +59,24 @@ def densify_decision(xyz_gradient_accum, denom, scales, opacity, max_grad, scale
     return clone, prune
 
 
+class DecoderSchedule:
+    """When the two decoders learn: the reference's ``opt_geo_from`` / ``opt_geo_until`` / ``opt_app_from`` / ``opt_app_until``
+    (config.py:148-151; every shipped configuration: from 1 000, until 14 000 / 15 000).  ``flags(t) -> (opt_geo, opt_app)`` is
+    gs_trainer.py:225-226 as written::
+
+        opt_geo = False if t_iter < opt_geo_from and t_iter < opt_geo_until else True
+
+    i.e. a decoder is frozen while ``t < from_ and t < until``.  ``until`` never freezes anything again: past ``from_`` the flag
+    is True for good, and ``until`` only matters where it lies BEFORE ``from_`` (the decoder then thaws at ``until``)."""
+
+    def __init__(self, opt_geo_from=1000, opt_geo_until=14000, opt_app_from=1000, opt_app_until=15000):
+        self.opt_geo_from, self.opt_geo_until = int(opt_geo_from), int(opt_geo_until)
+        self.opt_app_from, self.opt_app_until = int(opt_app_from), int(opt_app_until)
+
+    def flags(self, t):
+        return (not (t < self.opt_geo_from and t < self.opt_geo_until), not (t < self.opt_app_from and t < self.opt_app_until))
+
+
 class CapturedStep:
     """A HIP graph of one training step, valid for ONE topology version of its ``AvatarStep``: ``replay`` refuses (RuntimeError) once
     the set of Gaussians or the SH degree has changed -- the graph holds the old tensors' addresses and the old sizes."""
@@ -111,14 +129,23 @@ class AvatarTrainer:
     patches of the sampler's sequence (an eager and a captured trainer with the same seed see the same patches at the same
     iteration: the capture's warm-up runs are not steps, the sampler's state is put back after them).  The module must carry the
     term (``lpips=``, ``lpips_w`` > 0) with the sampler's patch size; ``lpips_origins=`` of ``step`` / ``step_frames`` is then refused.
-    The corners a step used: ``lpips_sampler.last_origins``.  With ``lpips_sampler=None`` nothing changes."""
+    The corners a step used: ``lpips_sampler.last_origins``.  With ``lpips_sampler=None`` nothing changes.
+
+    ``decoder_schedule``: a ``DecoderSchedule`` -- before every step the flags of ``self.iteration`` are compared with the module's; on a
+    change the module's ``set_trainable`` is called, the optimiser is told (``FusedAdam.set_active``; ``torch.optim.Adam`` skips a
+    parameter whose ``.grad`` is None by itself, and a frozen parameter ends the backward with none), the captured graph is dropped and,
+    with a gradient arena, the slots of the parameters that no longer receive a gradient are zeroed once (a frame-parallel all-reduce
+    then carries zeros for them).  Groups that learn: ``xyz`` and the pose tables always, ``geometry`` iff ``opt_geo``, ``appearance``
+    iff ``opt_app``, ``triplane`` iff either.  A frozen group's parameters, moments and step count stay as they are, so its bias
+    correction starts at step 1 when it thaws, as the reference's does.  With ``decoder_schedule=None`` nothing changes."""
 
     POSE_GROUPS = ("global_orient", "body_pose", "transl")
     STATS = ("xyz_gradient_accum", "denom", "max_radii2D")      # the module's densification statistics, one row per Gaussian
 
     def __init__(self, module, settings_fn, bg_color, lrs, smpl_scale=None, transl=None, use_graph=False, fp=None,
                  sh_degree=0, max_sh_degree=3, betas=(0.9, 0.999), eps=1e-15, optimizer="torch", lr_schedules=None, poses=None,
-                 mesh=None, mesh_terms=None, lpips_sampler=None):
+                 mesh=None, mesh_terms=None, lpips_sampler=None, decoder_schedule=None):
+        self.decoder_schedule = decoder_schedule
         if lpips_sampler is not None:
             if getattr(module, "lpips", None) is None or not module.lpips_w > 0.0:
                 raise ValueError("AvatarTrainer: lpips_sampler needs the module's LPIPS term (AvatarStep(lpips=..., lpips_w > 0))")
@@ -216,6 +243,34 @@ class AvatarTrainer:
             normals = initial_attributes(verts.contiguous(), self.mesh.faces, self.mesh.edges)["normals"]
         self.mesh_terms.reset(self.mesh, normals, verts)
 
+    def active_groups(self):
+        """Names of the optimiser groups that learn under the module's current ``opt_geo`` / ``opt_app``."""
+        m = self.m
+        frozen = {"geometry": not m.opt_geo, "appearance": not m.opt_app, "triplane": not (m.opt_geo or m.opt_app)}
+        return [g["name"] for g in self.opt.param_groups if not frozen.get(g["name"], False)]
+
+    def _apply_decoder_schedule(self):
+        """The flags of this iteration; on a change: the module, the optimiser's active groups, the captured graph, the arena."""
+        m = self.m
+        flags = self.decoder_schedule.flags(self.iteration)
+        if flags == (m.opt_geo, m.opt_app):
+            return
+        m.set_trainable(*flags)
+        self.captured = None
+        active = set(self.active_groups())
+        if self.fused:
+            self.opt.set_active(active)
+        if self.flat is not None:                                # (slots nothing writes any more: zeros, not the last gradients)
+            with torch.no_grad():
+                for g in self.opt.param_groups:
+                    if g["name"] not in active:
+                        for p in g["params"]:
+                            self.views[next(i for i, q in enumerate(self.params) if q is p)].zero_()
+        for g in self.opt.param_groups:                          # (a frozen parameter carries no gradient into the next step)
+            if g["name"] not in active:
+                for p in g["params"]:
+                    p.grad = None
+
     def _body(self):
         for p in self.params:
             p.grad = None
@@ -306,6 +361,8 @@ class AvatarTrainer:
             for k, v in lp.items():
                 if v is not None:
                     s[k].copy_(v)
+        if self.decoder_schedule is not None:
+            self._apply_decoder_schedule()
         for g in self.opt.param_groups:
             if g["name"] in self.lr_schedules:
                 g["lr"] = self.lr_schedules[g["name"]](self.iteration)

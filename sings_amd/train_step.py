@@ -170,6 +170,8 @@ class AvatarStep(torch.nn.Module):
         # what was captured / sized for this set of Gaussians (sings_amd.train_loop): moves on with every densify / prune / SH-degree change
         self.topology_version = 0
         self.xyz_gradient_accum = self.denom = self.max_radii2D = None
+        # the reference's opt_geo / opt_app of the iteration (gs_trainer.py:225-226): False = that decoder runs without a gradient
+        self.opt_geo = self.opt_app = True
 
     # ---- densification statistics and topology (sings_hybrid.py:1013-1015, 930-932; gs_trainer.py:486-492)
     def enable_densification_stats(self):
@@ -212,6 +214,16 @@ class AvatarStep(torch.nn.Module):
         if self.xyz_gradient_accum is not None:
             self.enable_densification_stats()
 
+    def set_trainable(self, opt_geo=True, opt_app=True):
+        """The decoders that learn from now on (gs_trainer.py:225-226; sings_hybrid.py:265-277: a decoder whose flag is False is decoded
+        under no_grad -- here by ``decode.decode_attributes(opt_geo=, opt_app=)``).  With both False the tri-plane gets no gradient
+        either: only the anchors (and a learned pose) do.  A change moves ``topology_version`` on: the set of tensors that receive a
+        gradient is part of a captured step, which is refused and captured again like after a densify."""
+        flags = (bool(opt_geo), bool(opt_app))
+        if flags != (self.opt_geo, self.opt_app):
+            self.opt_geo, self.opt_app = flags
+            self.topology_version += 1
+
     def forward(self, A_cano2pose, raster_settings, gt_rgb, mask, bg_color, smpl_scale=None, transl=None, lpips_origins=None,
                 lpips_bg=None):
         """-> (loss, loss_dict, extras).  ``A_cano2pose`` [J,4,4]: one frame per step (the reference's step); [K,J,4,4]: a chunk
@@ -242,7 +254,7 @@ class AvatarStep(torch.nn.Module):
         _dec._TP["late"] = bool(defer)
         del _dec._TP_PENDING[:]                                  # (a preparation left behind by a forward that raised)
         try:
-            attrs = self.decode(geometry_hook=hook)
+            attrs = self.decode(geometry_hook=hook, opt_geo=self.opt_geo, opt_app=self.opt_app)
         finally:
             _dec._TP["late"] = late_prev
         # Two roots (defer): the render and the regularisers read DETACHED views of the decoded attributes (`use`), so that the
@@ -316,10 +328,11 @@ class AvatarStep(torch.nn.Module):
         loss = None if defer else self._finish_joined(loss_dict, reg, regularisers, side)
         return loss, loss_dict, {"render_raw": color, "radii": radii, "attrs": attrs, "viewspace_points": m2d, **extras}
 
-    def decode(self, geometry_hook=None):
-        """The decoded attributes of the current set (``decode.decode_attributes`` of this module's anchors, tri-plane and decoders)."""
+    def decode(self, geometry_hook=None, opt_geo=True, opt_app=True):
+        """The decoded attributes of the current set (``decode.decode_attributes`` of this module's anchors, tri-plane and decoders).
+        ``opt_geo`` / ``opt_app``: the training step passes its own flags; every other caller decodes as before."""
         return decode_attributes(self.xyz, self.triplane, self.geometry_dec, self.appearance_dec, self.thickness_factor,
-                                 self.scaling_multiplier, geometry_hook=geometry_hook)
+                                 self.scaling_multiplier, geometry_hook=geometry_hook, opt_geo=opt_geo, opt_app=opt_app)
 
     def _l2(self, a):                                            # (`a`: the decoded attributes, or their detached copy)
         return self.l2_norm({k: a[k] for k in ("xyz_offsets", "scales", "opacity")})
