@@ -4,6 +4,7 @@
 // no spin between workgroups: two calls with the same state give the same bits.
 #include "sg_host.h"
 #include "../../include/sings_sampler.h"
+#include "sg_philox.h"
 
 #define SP_BLOCK 256
 #define SP_WAVES (SP_BLOCK / SG_WAVE)
@@ -60,21 +61,6 @@ sg_patch_count_kernel(int W, int o, uint32_t Wc, uint32_t total, size_t mask_str
     }
 }
 
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11)
-__device__ __forceinline__ void sp_philox(const uint32_t ctr[4], uint32_t k0, uint32_t k1, uint32_t out[4])
-{
-    uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3];
-    for (int r = 0; r < 10; r++) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-__device__ __forceinline__ uint32_t sp_bounded(uint32_t w, uint32_t R) { return (uint32_t)(((uint64_t)w * R) >> 32); }
-
 // One workgroup per frame.  pre: the frame's chunk counts, turned into their exclusive prefix sums in place.
 __global__ void __launch_bounds__(SP_BLOCK)
 sg_patch_pick_kernel(int H, int W, int P, int n, uint32_t nch, uint32_t total, uint64_t thr, size_t mask_stride,
@@ -115,9 +101,9 @@ sg_patch_pick_kernel(int H, int W, int P, int n, uint32_t nch, uint32_t total, u
         const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
         uint32_t ctr[4] = { (uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)k, 0u }, w[4];
         uint32_t block = 0;
-        sp_philox(ctr, k0, k1, w);
+        sg_philox4x32(ctr, k0, k1, w);
         auto word = [&](uint32_t t) {
-            if (t / 4 != block) { block = t / 4; ctr[3] = block; sp_philox(ctr, k0, k1, w); }
+            if (t / 4 != block) { block = t / 4; ctr[3] = block; sg_philox4x32(ctr, k0, k1, w); }
             return w[t % 4];
         };
         // (the draw first, as in the reference: a frame counts as forced only where np.random.choice would have raised)
@@ -125,15 +111,15 @@ sg_patch_pick_kernel(int H, int W, int P, int n, uint32_t nch, uint32_t total, u
         if (branch == SG_PATCH_BRANCH_MASKED) {
             for (int i = 0; i < n; i++) {                                        // Floyd: n distinct ranks of [0, M)
                 const uint32_t j = M - (uint32_t)n + (uint32_t)i;
-                uint32_t t = sp_bounded(word(1u + i), j + 1u);
+                uint32_t t = sg_bounded(word(1u + i), j + 1u);
                 for (int e = 0; e < i; e++)
                     if (sRank[e] == t) { t = j; break; }
                 sRank[i] = t;
             }
         } else {
             for (int i = 0; i < n; i++) {
-                org[2 * i] = (int32_t)sp_bounded(word(1u + 2u * i), (uint32_t)(H - P));
-                org[2 * i + 1] = (int32_t)sp_bounded(word(2u + 2u * i), (uint32_t)(W - P));
+                org[2 * i] = (int32_t)sg_bounded(word(1u + 2u * i), (uint32_t)(H - P));
+                org[2 * i + 1] = (int32_t)sg_bounded(word(2u + 2u * i), (uint32_t)(W - P));
             }
         }
         sBranch = branch;

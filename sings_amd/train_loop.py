@@ -137,15 +137,36 @@ class AvatarTrainer:
     with a gradient arena, the slots of the parameters that no longer receive a gradient are zeroed once (a frame-parallel all-reduce
     then carries zeros for them).  Groups that learn: ``xyz`` and the pose tables always, ``geometry`` iff ``opt_geo``, ``appearance``
     iff ``opt_app``, ``triplane`` iff either.  A frozen group's parameters, moments and step count stay as they are, so its bias
-    correction starts at step 1 when it thaws, as the reference's does.  With ``decoder_schedule=None`` nothing changes."""
+    correction starts at step 1 when it thaws, as the reference's does.  With ``decoder_schedule=None`` nothing changes.
+
+    ``frames``: a ``sings_amd.frame_feed.FrameFeed`` -- ``step_next()`` is the step that takes nothing from outside: its body starts with
+    ``frames.draw()`` (the next K frames of the feed's shuffled epochs and, with ``random_bg``, the step's background colour, expanded
+    from the 8-bit store into the feed's static tensors), reads ``A`` / ``transl`` from ``poses(frames.idx)`` and ``gt`` / ``mask`` from
+    the feed; an ``lpips_sampler`` reads ``frames.mask``.  The draw is part of a captured step: every replay trains on the next frames
+    (an eager and a captured trainer with the same seed visit the same frames: the capture's warm-up runs are not steps, the feed's state
+    is put back after them).  Needs ``poses=`` with one row per frame of the store.  With ``random_bg`` the feed's ``bg`` tensor must be
+    both ``bg_color`` and the ``bg`` of the settings ``settings_fn`` returns -- the render and the loss composite onto the same colour.
+    ``step`` and ``step_frames`` stay what they were.  With ``frames=None`` nothing changes."""
 
     POSE_GROUPS = ("global_orient", "body_pose", "transl")
     STATS = ("xyz_gradient_accum", "denom", "max_radii2D")      # the module's densification statistics, one row per Gaussian
 
     def __init__(self, module, settings_fn, bg_color, lrs, smpl_scale=None, transl=None, use_graph=False, fp=None,
                  sh_degree=0, max_sh_degree=3, betas=(0.9, 0.999), eps=1e-15, optimizer="torch", lr_schedules=None, poses=None,
-                 mesh=None, mesh_terms=None, lpips_sampler=None, decoder_schedule=None):
+                 mesh=None, mesh_terms=None, lpips_sampler=None, decoder_schedule=None, frames=None):
         self.decoder_schedule = decoder_schedule
+        if frames is not None:
+            if poses is None:
+                raise ValueError("AvatarTrainer: frames= needs poses=PoseTable(...) (the drawn frames' rows of the pose tables)")
+            if frames.store.F != int(poses.global_orient.shape[0]):
+                raise ValueError(f"AvatarTrainer: the frame store holds {frames.store.F} frames, the pose tables "
+                                 f"{int(poses.global_orient.shape[0])} rows")
+            same = lambda t: (torch.is_tensor(t) and t.data_ptr() == frames.bg.data_ptr() and t.dtype == frames.bg.dtype
+                              and tuple(t.shape) == tuple(frames.bg.shape))
+            if frames.random_bg and not (same(bg_color) and same(getattr(settings_fn(int(sh_degree)), "bg", None))):
+                raise ValueError("AvatarTrainer: with random_bg the feed's bg tensor must be both bg_color and the bg of the settings "
+                                 "settings_fn returns (the render and the loss composite onto the same colour)")
+        self.frames = frames
         if lpips_sampler is not None:
             if getattr(module, "lpips", None) is None or not module.lpips_w > 0.0:
                 raise ValueError("AvatarTrainer: lpips_sampler needs the module's LPIPS term (AvatarStep(lpips=..., lpips_w > 0))")
@@ -275,6 +296,8 @@ class AvatarTrainer:
         for p in self.params:
             p.grad = None
         s = self._static
+        if s.get("feed"):                                        # this step's frames and background: two launches, no host read
+            self.frames.draw()
         A, transl = s.get("A"), self.transl
         if s.get("idx") is not None:                             # the frames' rows of the pose tables: ONE launch, index on the device
             A, transl = self.poses(s["idx"])
@@ -304,6 +327,8 @@ class AvatarTrainer:
         live = [self.m.xyz_gradient_accum, self.m.denom, self.m.max_radii2D]
         if self.lpips_sampler is not None:
             live.append(self.lpips_sampler.state)                # (the counter: the warm-up runs draw patches too)
+        if self._static.get("feed"):
+            live += self.frames.live_tensors()                   # (the same for the frames: the counter, and the epoch's order)
         if self.fused and self.fp is None:
             live += [p.detach() for p in self.params] + [self.opt.exp_avg, self.opt.exp_avg_sq]
         keep, steps = [x.clone() for x in live], (list(self.opt.steps) if self.fused else None)
@@ -350,9 +375,9 @@ class AvatarTrainer:
         keys = ("lp_origins", "lp_bg") + (("mask",) if self.lpips_sampler is not None else ())
         shapes = lambda d: tuple(None if d.get(k) is None else tuple(d[k].shape) for k in keys)
         lp_shape = dict(lp, mask=mask)
-        if (not s or s.get(key) is None or s[key].shape != A.shape or s.get("single") != pose_in.get("single")
+        if (not s or s.get("feed") or s.get(key) is None or s[key].shape != A.shape or s.get("single") != pose_in.get("single")
                 or shapes(s) != shapes(lp_shape)):
-            s.update(A=None, idx=None, single=pose_in.get("single"))      # (the step reads A, or the tables' rows at idx: not both)
+            s.update(A=None, idx=None, feed=None, single=pose_in.get("single"))      # (the step reads A, or the tables' rows at idx: not both)
             s.update({key: A.clone(), "gt": gt_rgb.clone(), "mask": mask.clone()})
             s.update({k: (None if v is None else v.clone()) for k, v in lp.items()})
             self.captured = None
@@ -361,6 +386,28 @@ class AvatarTrainer:
             for k, v in lp.items():
                 if v is not None:
                     s[k].copy_(v)
+        return self._run()
+
+    def step_next(self, lpips_bg=None):
+        """One step on the next frame(s) of ``frames`` (a ``FrameFeed``): nothing is copied in -- the body draws the frames itself, and
+        the static inputs ARE the feed's tensors.  ``lpips_bg``: as in ``step``."""
+        if self.frames is None:
+            raise RuntimeError("AvatarTrainer.step_next needs frames=FrameFeed(...)")
+        s, fd = self._static, self.frames
+        single = fd.K == 1
+        lp_bg = None if lpips_bg is None else torch.as_tensor(lpips_bg).to(self.dev)
+        shape = lambda t: None if t is None else tuple(t.shape)
+        if not s.get("feed") or shape(s.get("lp_bg")) != shape(lp_bg):
+            s.clear()
+            s.update(feed=True, A=None, idx=fd.idx, single=single, gt=fd.gt[0] if single else fd.gt,
+                     mask=fd.mask[0] if single else fd.mask, lp_origins=None, lp_bg=None if lp_bg is None else lp_bg.clone())
+            self.captured = None
+        elif lp_bg is not None:
+            s["lp_bg"].copy_(lp_bg)
+        return self._run()
+
+    def _run(self):
+        """The step on the static inputs: schedules, the body (eager or replayed), the reduction, the optimiser."""
         if self.decoder_schedule is not None:
             self._apply_decoder_schedule()
         for g in self.opt.param_groups:
