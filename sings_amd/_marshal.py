@@ -337,3 +337,37 @@ def plateau_step(n_groups, begin, patience, settings, loss, state, hyper, terms,
         raise ValueError("plateau_step: terms must hold n_copy floats")
     _lib.check(_lib.load().sg_plateau_step(int(n_groups), int(bool(begin)), int(patience), settings, _ptr(loss), _ptr(state), _ptr(hyper),
                                            _ptr(terms), int(n_copy), _ptr(log), int(log_rows), _stream(dev)), "sg_plateau_step")
+
+
+# ---- densification statistics (csrc/sg_density.hip)
+def density_stats(grad, radii, gate, accum, denom, max_radii):
+    """``sg_density_stats`` on torch's current stream: ``grad`` [N,3] / [K,N,3] fp32 and ``radii`` [N] / [K,N] int32 of one step;
+    ``accum``, ``denom``, ``max_radii``: N contiguous fp32 each ([N] or [N,1]), updated in place; ``gate``: int32 [1] on the device
+    or None."""
+    if not torch.is_tensor(grad) or not grad.is_cuda:
+        raise RuntimeError("density_stats: grad must be a GPU tensor (no CPU fallback)")
+    dev = grad.device
+    if grad.dim() not in (2, 3) or grad.shape[-1] != 3:
+        raise ValueError(f"density_stats: grad must be [N,3] or [K,N,3], got {tuple(grad.shape)}")
+    N, K = int(grad.shape[-2]), (int(grad.shape[0]) if grad.dim() == 3 else 1)
+    if not torch.is_tensor(radii) or tuple(radii.shape) not in ((K, N),) + (((N,),) if K == 1 else ()):
+        raise ValueError(f"density_stats: radii must be [{K},{N}]" + (f" or [{N}]" if K == 1 else "") +
+                         f", got {tuple(radii.shape) if torch.is_tensor(radii) else type(radii).__name__}")
+    for name, t, dt in (("grad", grad, torch.float32), ("radii", radii, torch.int32), ("gate", gate, torch.int32),
+                        ("accum", accum, torch.float32), ("denom", denom, torch.float32), ("max_radii", max_radii, torch.float32)):
+        if t is None and name == "gate":
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != dev or t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError(f"density_stats: {name} must be a contiguous {dt} tensor on {dev} (no CPU fallback)")
+        if name in ("accum", "denom", "max_radii") and t.numel() != N:
+            raise ValueError(f"density_stats: {name} must hold {N} values, got {tuple(t.shape)}")
+    if gate is not None and gate.numel() != 1:
+        raise ValueError(f"density_stats: gate must hold one int32, got {tuple(gate.shape)}")
+    if not 1 <= K <= _lib.DENSITY_MAX_K:
+        raise ValueError(f"density_stats: K = {K} outside 1..{_lib.DENSITY_MAX_K}")
+    lib = _lib.load()
+    if not _lib.HAS_DENSITY:
+        raise RuntimeError("density_stats: the loaded library predates include/sings_density.h (no fallback): rebuild it")
+    with torch.cuda.device(dev):
+        _lib.check(lib.sg_density_stats(K, N, _ptr(grad), _ptr(radii), _ptr(gate), _ptr(accum), _ptr(denom), _ptr(max_radii),
+                                        _stream(dev)), "sg_density_stats")

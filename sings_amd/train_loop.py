@@ -146,7 +146,22 @@ class AvatarTrainer:
     (an eager and a captured trainer with the same seed visit the same frames: the capture's warm-up runs are not steps, the feed's state
     is put back after them).  Needs ``poses=`` with one row per frame of the store.  With ``random_bg`` the feed's ``bg`` tensor must be
     both ``bg_color`` and the ``bg`` of the settings ``settings_fn`` returns -- the render and the loss composite onto the same colour.
-    ``step`` and ``step_frames`` stay what they were.  With ``frames=None`` nothing changes."""
+    ``step`` and ``step_frames`` stay what they were.  With ``frames=None`` nothing changes.
+
+    ``set_density_schedule(schedule)``: a ``sings_amd.density.HybridDensitySchedule`` -- the reference's ``hybrid`` strategy, attached
+    through a method (needs ``mesh=``).  From then on every step -- ``step``, ``step_frames``, ``step_next`` -- (1) accumulates the
+    statistics only on an iteration that takes a decision, from that iteration's frames, as gs_trainer.py:486-492 does: the module makes
+    ONE gated launch (``AvatarStep.stats_gate``) instead of its torch chain, the trainer sets the gate's word to
+    ``schedule.decides_at(iteration)`` in front of the step, stream-ordered, so one captured graph serves both kinds of iteration;
+    (2) hands ``L2Norm`` the keys of ``schedule.l2_keys(iteration)`` (a change drops the captured graph); (3) after the optimiser step of
+    iteration t, in the reference's order (``_periodic_check``, then ``_adjust_density``): ``oneup_sh_degree()`` if ``schedule.sh_up(t)``,
+    then ``prune_and_simplify`` / ``densify_and_subdivide`` with the schedule's thresholds for each of ``schedule.actions(t)``, each
+    recorded in ``density_log`` as ``{t, mode, n_old, n_new, skipped}`` (``skipped``: a prune's ``last_simplification["skipped"]``).
+    One deviation from the reference: on an iteration with a prune AND a densification it accumulates the statistics a second time,
+    with the pre-prune visibility mask on the post-prune arrays (an error as soon as the prune removed a row); here there is one
+    accumulation per iteration, and the densification decides on the statistics the prune kept.  ``set_density_schedule(None)`` goes
+    back to an accumulation per step.  ``run(n_steps)``: ``step_next()`` that many times -- the loop of gs_trainer.py:209-274 without
+    its file output -- -> the list of loss dicts."""
 
     POSE_GROUPS = ("global_orient", "body_pose", "transl")
     STATS = ("xyz_gradient_accum", "denom", "max_radii2D")      # the module's densification statistics, one row per Gaussian
@@ -155,6 +170,8 @@ class AvatarTrainer:
                  sh_degree=0, max_sh_degree=3, betas=(0.9, 0.999), eps=1e-15, optimizer="torch", lr_schedules=None, poses=None,
                  mesh=None, mesh_terms=None, lpips_sampler=None, decoder_schedule=None, frames=None):
         self.decoder_schedule = decoder_schedule
+        # set_density_schedule(): the schedule, the statistics' gate (int32 [1] on the device), the word it holds, what was done
+        self.density_schedule, self._gate, self._gate_value, self.density_log = None, None, None, []
         if frames is not None:
             if poses is None:
                 raise ValueError("AvatarTrainer: frames= needs poses=PoseTable(...) (the drawn frames' rows of the pose tables)")
@@ -292,6 +309,54 @@ class AvatarTrainer:
                 for p in g["params"]:
                     p.grad = None
 
+    def set_density_schedule(self, schedule):
+        """Attach (or, with None, detach) a ``sings_amd.density.HybridDensitySchedule``: the class docstring says what the steps do with
+        it.  The gate is allocated here and handed to the module; the captured graph is dropped either way (the statistics' launch
+        and the L2 term's key list are part of it)."""
+        if schedule is not None and self.mesh is None:
+            raise ValueError("AvatarTrainer.set_density_schedule needs mesh=MeshState(...) (prune_and_simplify / densify_and_subdivide "
+                             "work on the anchors' mesh)")
+        self.density_schedule = schedule
+        if schedule is None:
+            self._gate = self._gate_value = None
+            self.m.l2_keys = ("xyz_offsets", "scales", "opacity")
+        elif self._gate is None:
+            self._gate, self._gate_value = torch.zeros(1, dtype=torch.int32, device=self.dev), 0
+        self.m.stats_gate = self._gate
+        self.captured = None
+
+    def _apply_density_schedule_before(self):
+        """In front of step ``self.iteration``: the gate's word (a stream-ordered fill, only when it changes) and the L2 term's keys."""
+        sch, t = self.density_schedule, self.iteration
+        word = int(sch.decides_at(t))
+        if word != self._gate_value:
+            self._gate.fill_(word)
+            self._gate_value = word
+        keys = tuple(sch.l2_keys(t))
+        if keys != tuple(self.m.l2_keys):
+            self.m.l2_keys = keys
+            self.captured = None
+
+    def _apply_density_schedule_after(self, t):
+        """Behind the optimiser step of iteration ``t``: gs_trainer.py:271-274 (``_periodic_check``'s SH degree, then ``_adjust_density``)."""
+        sch = self.density_schedule
+        if sch.sh_up(t):
+            self.oneup_sh_degree()
+        for mode in sch.actions(t):
+            if mode == "prune":
+                _, _, n_old, n_new = self.prune_and_simplify(**sch.prune_kwargs())
+                skipped = self.last_simplification["skipped"]
+            else:
+                _, _, n_old, n_new = self.densify_and_subdivide(**sch.densify_kwargs())
+                skipped = None
+            self.density_log.append({"t": t, "mode": mode, "n_old": n_old, "n_new": n_new, "skipped": skipped})
+
+    def run(self, n_steps):
+        """``step_next()`` ``n_steps`` times -> the list of the steps' loss dicts (copies: a replayed graph reuses its output tensors)."""
+        if self.frames is None:
+            raise RuntimeError("AvatarTrainer.run needs frames=FrameFeed(...)")
+        return [{k: v.clone() for k, v in self.step_next().items()} for _ in range(int(n_steps))]
+
     def _body(self):
         for p in self.params:
             p.grad = None
@@ -325,6 +390,8 @@ class AvatarTrainer:
         # (the capture's warm-up runs execute the body -- statistics included -- without being steps: put the statistics back;
         # with the fused optimiser in the body they update parameters and moments too: those go back as well)
         live = [self.m.xyz_gradient_accum, self.m.denom, self.m.max_radii2D]
+        if self._gate is not None:
+            live.append(self._gate)                              # (nothing in the body writes it: put back with the statistics it gates)
         if self.lpips_sampler is not None:
             live.append(self.lpips_sampler.state)                # (the counter: the warm-up runs draw patches too)
         if self._static.get("feed"):
@@ -410,6 +477,8 @@ class AvatarTrainer:
         """The step on the static inputs: schedules, the body (eager or replayed), the reduction, the optimiser."""
         if self.decoder_schedule is not None:
             self._apply_decoder_schedule()
+        if self.density_schedule is not None:
+            self._apply_density_schedule_before()
         for g in self.opt.param_groups:
             if g["name"] in self.lr_schedules:
                 g["lr"] = self.lr_schedules[g["name"]](self.iteration)
@@ -432,6 +501,10 @@ class AvatarTrainer:
                 self.opt.apply(sync=False)                       # (the arena holds the reduced gradients)
         if not self.fused:
             self.opt.step()
+        if self.density_schedule is not None:
+            if self._gate_value:                                 # (a change of the set drops the graph whose outputs these may be)
+                ld = {k: v.clone() for k, v in ld.items()}
+            self._apply_density_schedule_after(self.iteration)
         self.iteration += 1
         return ld
 

@@ -172,6 +172,11 @@ class AvatarStep(torch.nn.Module):
         self.xyz_gradient_accum = self.denom = self.max_radii2D = None
         # the reference's opt_geo / opt_app of the iteration (gs_trainer.py:225-226): False = that decoder runs without a gradient
         self.opt_geo = self.opt_app = True
+        # an int32 device tensor [1]: the statistics are ONE gated launch (sings_amd.density.densify_stats) that does nothing while
+        # the word is 0 -- a captured step serves deciding and non-deciding iterations alike; None: the torch chain, every step
+        self.stats_gate = None
+        # the attributes the L2 term reads (gs_trainer.py:356-360 leaves `opacity` out while a density window is open)
+        self.l2_keys = ("xyz_offsets", "scales", "opacity")
 
     # ---- densification statistics and topology (sings_hybrid.py:1013-1015, 930-932; gs_trainer.py:486-492)
     def enable_densification_stats(self):
@@ -186,12 +191,20 @@ class AvatarStep(torch.nn.Module):
     def add_densification_stats(self, extras):
         """``xyz_gradient_accum[vis] += |viewspace_points.grad[vis, :2]|``, ``denom[vis] += 1``, ``max_radii2D[vis] = max(., radii[vis])``
         for every frame of the step.  Masked arithmetic instead of boolean indexing: the same sums without a host round trip, so the
-        call may sit inside a captured step."""
+        call may sit inside a captured step.
+
+        With ``stats_gate`` set the same update is one launch of ``sings_amd.density.densify_stats`` behind that gate: nothing is
+        accumulated while the word is 0, and an invisible frame is skipped instead of multiplied by zero."""
         if self.xyz_gradient_accum is None:
             return
         g, radii = extras["viewspace_points"].grad, extras["radii"]
         if g is None:
             raise RuntimeError("add_densification_stats: call it after the backward pass of the step (viewspace_points.grad is empty)")
+        if self.stats_gate is not None:
+            from .density import densify_stats
+            densify_stats(g.contiguous(), radii.contiguous(), self.xyz_gradient_accum, self.denom, self.max_radii2D,
+                          gate=self.stats_gate)
+            return
         g, radii = g.reshape(-1, g.shape[-2], 3), radii.reshape(-1, radii.shape[-1])
         vis = (radii > 0).to(torch.float32)                                       # [K, N]
         self.xyz_gradient_accum.add_((torch.norm(g[..., :2], dim=-1) * vis).sum(0).unsqueeze(1))
@@ -335,7 +348,7 @@ class AvatarStep(torch.nn.Module):
                                  self.scaling_multiplier, geometry_hook=geometry_hook, opt_geo=opt_geo, opt_app=opt_app)
 
     def _l2(self, a):                                            # (`a`: the decoded attributes, or their detached copy)
-        return self.l2_norm({k: a[k] for k in ("xyz_offsets", "scales", "opacity")})
+        return self.l2_norm({k: a[k] for k in self.l2_keys})     # (without `opacity`: L2Norm leaves its term and its gradient out)
 
     def _finish_deferred(self, loss_dict, extras, attrs, use, inject, side, decoded, rendered):
         """The two-roots tail of ``forward``, no join: the regularisers' gradients are waited for where they are consumed
@@ -443,7 +456,7 @@ class AvatarStep(torch.nn.Module):
             cur.wait_event(l2_grads[1])
             both_a, both_b = [], []
             for k, gr in l2_grads[0].items():
-                if gr is None or k not in g:
+                if gr is None or k not in g:                     # (None: an attribute `l2_keys` leaves out -- no term, no gradient)
                     continue
                 gr.record_stream(cur)
                 if g[k] is None:
