@@ -273,6 +273,12 @@ class FusedAdam:
         self.advance()
         self.apply()
 
+    def live_tensors(self):
+        """What ``apply()`` changes: every parameter's data and both moments.  A caller that runs it without the run being a step (a
+        capture's warm-up, with the launch in the captured body) clones these before and copies them back after -- and ``steps``, the
+        host list, with them."""
+        return [p.detach() for p in self._params()] + [self.exp_avg, self.exp_avg_sq]
+
     def zero_grad(self, set_to_none=True):
         for p in self._params():
             if set_to_none:

@@ -128,6 +128,11 @@ class DevicePatchSampler:
         signed = lambda v: (int(v) & _U64) - (1 << 64) if (int(v) & _U64) >> 63 else int(v) & _U64
         self.state[0], self.state[2] = signed(sd["counter"]), signed(sd["seed"])
 
+    def live_tensors(self):
+        """What a draw changes besides its outputs (the counter): a caller that runs draws which must not count (a capture's warm-up
+        runs draw patches too) clones these before and copies them back after."""
+        return [self.state]
+
     # ---- the draw
     def origins(self, mask, frames=None):
         import torch

@@ -36,7 +36,9 @@ import torch
 from . import decode as _dec
 from . import overflow
 from . import topology as _topo
+from .avatar_init import initial_attributes
 from .optim import FusedAdam, take_rows
+from .step_inputs import StepInputs, preserved
 from .train_step import capture_step
 
 
@@ -99,72 +101,32 @@ class AvatarTrainer:
     captured again after every topology change; Adam and the statistics run outside it.  ``fp``: a ``sings_amd.dp.FrameParallel``
     -- parameter gradients live in one flat arena buffer and are all-reduced, the statistics are reduced before a decision.
 
-    ``optimizer``: ``"torch"`` (``torch.optim.Adam``, outside the graph) or ``"fused"`` (``sings_amd.optim.FusedAdam``: the gradient
-    arena is always created and ONE launch updates every parameter; without ``fp`` that launch is part of the step's body, so a
-    captured step contains it and only the host half -- step counts, the per-group rows -- runs outside; with ``fp`` it follows the
-    all-reduce).  ``lr_schedules``: ``{group name: fn(iteration)}``, applied to the optimiser's groups before every step.
+    The optional parts: what each is, what it needs, where INTEGRATION.md describes it.  With any of them left at None nothing changes.
+    A part's inputs reach the body through ``self.inputs`` (``step_inputs.StepInputs``); its device state that a run which is not a
+    step changes is named by its ``live_tensors()`` and put back behind a capture's warm-up runs ("Trainer components").
 
-    ``poses``: a ``sings_amd.pose.PoseTable`` -- the reference's ``optim_pose`` (sings_hybrid.py:142-150, 761-765).  Its learnable tables
-    join the optimiser as the groups ``"global_orient"`` and ``"body_pose"`` (the reference's ``lr.smpl_pose`` for both) and, if the
-    table was built with ``learn_transl``, ``"transl"`` (``lr.smpl_trans``); ``lrs`` must name each of them.  They are ordinary members
-    of ``params``: the gradient arena, the single ``sg_adam_step`` launch and the frame-parallel all-reduce cover them (each rank's
-    dense table gradient is zero outside its own frames' rows: the sum is the reference's gradient).  Adam is dense over the tables, as in
-    the reference: a row visited earlier keeps moving on its momentum, a row never visited has zero moments and does not move.  The
-    groups are not per-Gaussian: a densify / prune leaves their moments as they are.  ``step_frames(frame_idx, gt_rgb, mask)`` is the
-    step that reads ``A`` and ``transl`` from the tables; ``step(A, ...)`` stays what it was (the tables then take no part, and a
-    fused optimiser refuses parameters without a gradient).  With ``poses=None`` nothing changes.
-
-    ``mesh``: a ``sings_amd.topology.MeshState`` over the anchors (faces, unique edges, vertex labels, level ids) -- what
-    ``densify_and_subdivide`` and ``prune_and_simplify`` need and keep up to date.  With ``mesh=None`` nothing changes.
-
-    ``mesh_terms``: a ``sings_amd.mesh_terms.MeshTerms`` -- the region Laplacians of the anchor positions and of the DC colours, the hand
-    Laplacian and the mesh edge term of gs_trainer.py:366-399.  Needs ``mesh=``.  The trainer hands it to the module, calls its ``reset``
-    whenever the set changes (the mesh's current edges and labels; vertex normals from ``avatar_init.initial_attributes``, which is
-    parity-unpinned, INTEGRATION.md 13: of the anchors at construction, of the vertices a densify / prune produced afterwards; the
-    same vertices for the constant edge term) and ``set_iteration(self.iteration)`` before every step: a captured step replays with the
-    iteration's own weights.  With ``mesh_terms=None`` nothing changes.
-
-    ``lpips_sampler``: a ``sings_amd.patch_sampler.DevicePatchSampler`` -- the step draws its own LPIPS patch corners from the step's
-    mask, on the device, in front of the module's forward: the draw is part of a captured step, and every replay draws the next
-    patches of the sampler's sequence (an eager and a captured trainer with the same seed see the same patches at the same
-    iteration: the capture's warm-up runs are not steps, the sampler's state is put back after them).  The module must carry the
-    term (``lpips=``, ``lpips_w`` > 0) with the sampler's patch size; ``lpips_origins=`` of ``step`` / ``step_frames`` is then refused.
-    The corners a step used: ``lpips_sampler.last_origins``.  With ``lpips_sampler=None`` nothing changes.
-
-    ``decoder_schedule``: a ``DecoderSchedule`` -- before every step the flags of ``self.iteration`` are compared with the module's; on a
-    change the module's ``set_trainable`` is called, the optimiser is told (``FusedAdam.set_active``; ``torch.optim.Adam`` skips a
-    parameter whose ``.grad`` is None by itself, and a frozen parameter ends the backward with none), the captured graph is dropped and,
-    with a gradient arena, the slots of the parameters that no longer receive a gradient are zeroed once (a frame-parallel all-reduce
-    then carries zeros for them).  Groups that learn: ``xyz`` and the pose tables always, ``geometry`` iff ``opt_geo``, ``appearance``
-    iff ``opt_app``, ``triplane`` iff either.  A frozen group's parameters, moments and step count stay as they are, so its bias
-    correction starts at step 1 when it thaws, as the reference's does.  With ``decoder_schedule=None`` nothing changes.
-
-    ``frames``: a ``sings_amd.frame_feed.FrameFeed`` -- ``step_next()`` is the step that takes nothing from outside: its body starts with
-    ``frames.draw()`` (the next K frames of the feed's shuffled epochs and, with ``random_bg``, the step's background colour, expanded
-    from the 8-bit store into the feed's static tensors), reads ``A`` / ``transl`` from ``poses(frames.idx)`` and ``gt`` / ``mask`` from
-    the feed; an ``lpips_sampler`` reads ``frames.mask``.  The draw is part of a captured step: every replay trains on the next frames
-    (an eager and a captured trainer with the same seed visit the same frames: the capture's warm-up runs are not steps, the feed's state
-    is put back after them).  Needs ``poses=`` with one row per frame of the store.  With ``random_bg`` the feed's ``bg`` tensor must be
-    both ``bg_color`` and the ``bg`` of the settings ``settings_fn`` returns -- the render and the loss composite onto the same colour.
-    ``step`` and ``step_frames`` stay what they were.  With ``frames=None`` nothing changes.
-
-    ``set_density_schedule(schedule)``: a ``sings_amd.density.HybridDensitySchedule`` -- the reference's ``hybrid`` strategy, attached
-    through a method (needs ``mesh=``).  From then on every step -- ``step``, ``step_frames``, ``step_next`` -- (1) accumulates the
-    statistics only on an iteration that takes a decision, from that iteration's frames, as gs_trainer.py:486-492 does: the module makes
-    ONE gated launch (``AvatarStep.stats_gate``) instead of its torch chain, the trainer sets the gate's word to
-    ``schedule.decides_at(iteration)`` in front of the step, stream-ordered, so one captured graph serves both kinds of iteration;
-    (2) hands ``L2Norm`` the keys of ``schedule.l2_keys(iteration)`` (a change drops the captured graph); (3) after the optimiser step of
-    iteration t, in the reference's order (``_periodic_check``, then ``_adjust_density``): ``oneup_sh_degree()`` if ``schedule.sh_up(t)``,
-    then ``prune_and_simplify`` / ``densify_and_subdivide`` with the schedule's thresholds for each of ``schedule.actions(t)``, each
-    recorded in ``density_log`` as ``{t, mode, n_old, n_new, skipped}`` (``skipped``: a prune's ``last_simplification["skipped"]``).
-    One deviation from the reference: on an iteration with a prune AND a densification it accumulates the statistics a second time,
-    with the pre-prune visibility mask on the post-prune arrays (an error as soon as the prune removed a row); here there is one
-    accumulation per iteration, and the densification decides on the statistics the prune kept.  ``set_density_schedule(None)`` goes
-    back to an accumulation per step.  ``run(n_steps)``: ``step_next()`` that many times -- the loop of gs_trainer.py:209-274 without
-    its file output -- -> the list of loss dicts."""
+    ``optimizer``         ``"torch"`` (``torch.optim.Adam``, outside the graph) or ``"fused"`` (``sings_amd.optim.FusedAdam``: one launch,
+                          inside the body and so inside a captured step unless ``fp``); ``lr_schedules``: ``{group name:
+                          fn(iteration)}``, applied to the optimiser's groups before every step.  §9.
+    ``poses``             a ``sings_amd.pose.PoseTable`` -- the reference's ``optim_pose`` (sings_hybrid.py:142-150, 761-765): its learnable
+                          tables join the optimiser as the groups of ``POSE_GROUPS``, ``lrs`` must name each; ``step_frames`` reads
+                          ``A`` and ``transl`` from the tables.  §10.
+    ``mesh``              a ``sings_amd.topology.MeshState`` over the anchors: what ``densify_and_subdivide`` and ``prune_and_simplify``
+                          need and keep up to date.  §11, §12.
+    ``mesh_terms``        a ``sings_amd.mesh_terms.MeshTerms`` -- the four mesh terms of gs_trainer.py:366-399, ``reset`` whenever the set
+                          changes, ``set_iteration`` before every step.  Needs ``mesh=``.  §15.
+    ``lpips_sampler``     a ``sings_amd.patch_sampler.DevicePatchSampler`` -- the step draws its own LPIPS patch corners from its mask, on
+                          the device, inside a captured step.  Needs the module's LPIPS term with the sampler's patch size;
+                          ``lpips_origins=`` is then refused.  §8.
+    ``decoder_schedule``  a ``DecoderSchedule`` -- before every step the flags of ``self.iteration`` go to the module, the optimiser's
+                          active groups, the arena; a change drops the captured graph.  §17.
+    ``frames``            a ``sings_amd.frame_feed.FrameFeed`` -- ``step_next()`` takes nothing from outside: the body draws the next K
+                          frames and the background colour.  Needs ``poses=`` with one row per frame of the store.  §18.
+    ``set_density_schedule(schedule)``  a ``sings_amd.density.HybridDensitySchedule`` -- gated statistics, the L2 term's keys, the SH
+                          degree and both changes of the set after the optimiser step, recorded in ``density_log``; ``run(n_steps)``
+                          is ``step_next()`` that many times.  Needs ``mesh=``.  §19."""
 
     POSE_GROUPS = ("global_orient", "body_pose", "transl")
-    STATS = ("xyz_gradient_accum", "denom", "max_radii2D")      # the module's densification statistics, one row per Gaussian
 
     def __init__(self, module, settings_fn, bg_color, lrs, smpl_scale=None, transl=None, use_graph=False, fp=None,
                  sh_degree=0, max_sh_degree=3, betas=(0.9, 0.999), eps=1e-15, optimizer="torch", lr_schedules=None, poses=None,
@@ -184,6 +146,8 @@ class AvatarTrainer:
                 raise ValueError("AvatarTrainer: with random_bg the feed's bg tensor must be both bg_color and the bg of the settings "
                                  "settings_fn returns (the render and the loss composite onto the same colour)")
         self.frames = frames
+        # what step_next adopts of the feed: the SAME objects every call (one frame: [0] views, the step is handed [3,H,W] and [H,W])
+        self._feed_views = None if frames is None else (frames.gt[0], frames.mask[0]) if frames.K == 1 else (frames.gt, frames.mask)
         if lpips_sampler is not None:
             if getattr(module, "lpips", None) is None or not module.lpips_w > 0.0:
                 raise ValueError("AvatarTrainer: lpips_sampler needs the module's LPIPS term (AvatarStep(lpips=..., lpips_w > 0))")
@@ -228,7 +192,7 @@ class AvatarTrainer:
             self.opt = torch.optim.Adam(self._groups(), betas=betas, eps=eps)
         self.captured = self.flat = self.views = None
         self.iteration = 0
-        self._static = {}
+        self.inputs = StepInputs()
         self._rebuild()
 
     @classmethod
@@ -255,7 +219,7 @@ class AvatarTrainer:
         self.rs = self.settings_fn(self.sh_degree)
         self.params = [p for g in self.opt.param_groups for p in g["params"]]
         m.enable_densification_stats()
-        self.captured = None
+        self._drop_graph()
         if self.fp is not None or self.fused:
             n = sum(p.numel() for p in self.params)
             self.flat = torch.zeros(n, dtype=torch.float32, device=self.dev)
@@ -271,7 +235,6 @@ class AvatarTrainer:
 
     def _reset_mesh_terms(self):
         """The mesh terms for the current mesh: the vertices the last topology call produced (the anchors before the first), their normals."""
-        from .avatar_init import initial_attributes
         verts = self.m.xyz.detach() if self._mesh_verts is None else self._mesh_verts
         if self.mesh.num_verts != int(verts.shape[0]):
             raise RuntimeError(f"AvatarTrainer: the mesh has {self.mesh.num_verts} vertices, the new set {int(verts.shape[0])} Gaussians: "
@@ -294,23 +257,20 @@ class AvatarTrainer:
         if flags == (m.opt_geo, m.opt_app):
             return
         m.set_trainable(*flags)
-        self.captured = None
+        self._drop_graph()
         active = set(self.active_groups())
         if self.fused:
             self.opt.set_active(active)
-        if self.flat is not None:                                # (slots nothing writes any more: zeros, not the last gradients)
-            with torch.no_grad():
-                for g in self.opt.param_groups:
-                    if g["name"] not in active:
-                        for p in g["params"]:
-                            self.views[next(i for i, q in enumerate(self.params) if q is p)].zero_()
-        for g in self.opt.param_groups:                          # (a frozen parameter carries no gradient into the next step)
-            if g["name"] not in active:
-                for p in g["params"]:
-                    p.grad = None
+        view = {} if self.flat is None else {id(p): v for p, v in zip(self.params, self.views)}
+        with torch.no_grad():
+            for g in self.opt.param_groups:
+                for p in (g["params"] if g["name"] not in active else ()):
+                    if view:
+                        view[id(p)].zero_()                      # (a slot nothing writes any more: zeros, not the last gradients)
+                    p.grad = None                                # (a frozen parameter carries no gradient into the next step)
 
     def set_density_schedule(self, schedule):
-        """Attach (or, with None, detach) a ``sings_amd.density.HybridDensitySchedule``: the class docstring says what the steps do with
+        """Attach (or, with None, detach) a ``sings_amd.density.HybridDensitySchedule``: INTEGRATION.md §19 says what the steps do with
         it.  The gate is allocated here and handed to the module; the captured graph is dropped either way (the statistics' launch
         and the L2 term's key list are part of it)."""
         if schedule is not None and self.mesh is None:
@@ -323,7 +283,7 @@ class AvatarTrainer:
         elif self._gate is None:
             self._gate, self._gate_value = torch.zeros(1, dtype=torch.int32, device=self.dev), 0
         self.m.stats_gate = self._gate
-        self.captured = None
+        self._drop_graph()
 
     def _apply_density_schedule_before(self):
         """In front of step ``self.iteration``: the gate's word (a stream-ordered fill, only when it changes) and the L2 term's keys."""
@@ -335,7 +295,7 @@ class AvatarTrainer:
         keys = tuple(sch.l2_keys(t))
         if keys != tuple(self.m.l2_keys):
             self.m.l2_keys = keys
-            self.captured = None
+            self._drop_graph()
 
     def _apply_density_schedule_after(self, t):
         """Behind the optimiser step of iteration ``t``: gs_trainer.py:271-274 (``_periodic_check``'s SH degree, then ``_adjust_density``)."""
@@ -360,22 +320,22 @@ class AvatarTrainer:
     def _body(self):
         for p in self.params:
             p.grad = None
-        s = self._static
-        if s.get("feed"):                                        # this step's frames and background: two launches, no host read
+        inp = self.inputs
+        if inp.source == "feed":                                 # this step's frames and background: two launches, no host read
             self.frames.draw()
-        A, transl = s.get("A"), self.transl
-        if s.get("idx") is not None:                             # the frames' rows of the pose tables: ONE launch, index on the device
-            A, transl = self.poses(s["idx"])
-            if s["single"]:
+        A, transl = inp.A, self.transl
+        if inp.source != "A":                                    # the frames' rows of the pose tables: ONE launch, index on the device
+            A, transl = self.poses(inp.idx)
+            if inp.single:
                 A, transl = A[0], transl[0]
-        origins = s.get("lp_origins")
+        origins = inp.lp_origins
         if self.lpips_sampler is not None:                       # this step's corners, drawn from its mask: two launches, no host read
             frames = A.dim() == 4
-            origins = self.lpips_sampler.origins(s["mask"], frames=int(A.shape[0]) if frames else None)
+            origins = self.lpips_sampler.origins(inp.mask, frames=int(A.shape[0]) if frames else None)
             if not frames:
                 origins = origins.reshape(-1, 2)
-        loss, ld, ex = self.m(A, self.rs, s["gt"], s["mask"], self.bg, smpl_scale=self.smpl_scale, transl=transl,
-                              lpips_origins=origins, lpips_bg=s.get("lp_bg"))
+        loss, ld, ex = self.m(A, self.rs, inp.gt, inp.mask, self.bg, smpl_scale=self.smpl_scale, transl=transl,
+                              lpips_origins=origins, lpips_bg=inp.lp_bg)
         if loss is None:
             self.m.backward(ld, ex)
         else:
@@ -385,31 +345,33 @@ class AvatarTrainer:
             self.opt.apply()                                     # (the Adam launch: part of the body, and so of a captured step)
         return {k: v.detach().reshape(()).clone() for k, v in ld.items()}
 
+    def _drop_graph(self):
+        """The captured step no longer matches what a step would run: the next graph step captures again."""
+        self.captured = None
+
+    def _live_tensors(self):
+        """The device state a run of ``_body`` changes besides its outputs, stated by each component the trainer has (their
+        ``live_tensors`` say why).  The gate: nothing in the body writes it; put back with the statistics it gates."""
+        live = list(self.m.stats_tensors()) + ([] if self._gate is None else [self._gate])
+        if self.lpips_sampler is not None:
+            live += self.lpips_sampler.live_tensors()
+        if self.frames is not None:
+            live += self.frames.live_tensors()
+        if self.fused and self.fp is None:                       # (the Adam launch is part of the body)
+            live += self.opt.live_tensors()
+        return live
+
     def _capture(self):
         overflow.set_deferred_overflow_check(True, capacity_pairs=overflow.capacity_pairs(self.dev))
-        # (the capture's warm-up runs execute the body -- statistics included -- without being steps: put the statistics back;
-        # with the fused optimiser in the body they update parameters and moments too: those go back as well)
-        live = [self.m.xyz_gradient_accum, self.m.denom, self.m.max_radii2D]
-        if self._gate is not None:
-            live.append(self._gate)                              # (nothing in the body writes it: put back with the statistics it gates)
-        if self.lpips_sampler is not None:
-            live.append(self.lpips_sampler.state)                # (the counter: the warm-up runs draw patches too)
-        if self._static.get("feed"):
-            live += self.frames.live_tensors()                   # (the same for the frames: the counter, and the epoch's order)
-        if self.fused and self.fp is None:
-            live += [p.detach() for p in self.params] + [self.opt.exp_avg, self.opt.exp_avg_sq]
-        keep, steps = [x.clone() for x in live], (list(self.opt.steps) if self.fused else None)
-        self.captured = CapturedStep(self.m, self._body, warmup=2, device=self.dev)
-        for dst, src in zip(live, keep):
-            dst.copy_(src)
-        if self.fused:
-            self.opt.steps[:] = steps
+        # (the capture's warm-up runs execute the body without being steps)
+        with preserved(self._live_tensors(), lists=[self.opt.steps] if self.fused else ()):
+            self.captured = CapturedStep(self.m, self._body, warmup=2, device=self.dev)
         overflow.check_deferred_overflow(self.dev)
 
     def step(self, A, gt_rgb, mask, lpips_origins=None, lpips_bg=None):
         """``lpips_origins`` / ``lpips_bg``: the step's LPIPS patch corners and random background (``AvatarStep.forward``), copied
         in like the frame's inputs, so that a replayed graph reads this step's patches."""
-        return self._step({"A": A}, gt_rgb, mask, lpips_origins, lpips_bg)
+        return self._step("A", A, None, gt_rgb, mask, lpips_origins, lpips_bg)
 
     def step_frames(self, frame_idx, gt_rgb, mask, lpips_origins=None, lpips_bg=None):
         """One step on the frame(s) ``frame_idx`` of the pose tables: an int (one frame, the reference's step) or K indices (a
@@ -426,33 +388,18 @@ class AvatarTrainer:
             F = int(self.poses.global_orient.shape[0])
             if int(idx.min()) < 0 or int(idx.max()) >= F:
                 raise IndexError(f"AvatarTrainer.step_frames: frame index outside the table's {F} rows")
-        return self._step({"idx": idx.to(self.dev, torch.int32), "single": single}, gt_rgb, mask, lpips_origins, lpips_bg)
+        return self._step("idx", idx.to(self.dev, torch.int32), single, gt_rgb, mask, lpips_origins, lpips_bg)
 
-    def _step(self, pose_in, gt_rgb, mask, lpips_origins, lpips_bg):
-        s = self._static
-        key = "idx" if "idx" in pose_in else "A"
-        A = pose_in[key]
+    def _step(self, source, pose, single, gt_rgb, mask, lpips_origins, lpips_bg):
         if self.lpips_sampler is not None and lpips_origins is not None:
             raise ValueError("AvatarTrainer: the trainer draws the patch corners itself (lpips_sampler=): lpips_origins= cannot be passed too")
-        lp = {"lp_origins": lpips_origins, "lp_bg": lpips_bg}
-        lp = {k: (None if v is None else torch.as_tensor(v).to(self.dev)) for k, v in lp.items()}
-        if lp["lp_origins"] is not None:
-            lp["lp_origins"] = lp["lp_origins"].to(torch.int32)
-        # (with a sampler the corners' shape follows the mask's: a mask of another shape is a new set of static inputs, as new corners are)
-        keys = ("lp_origins", "lp_bg") + (("mask",) if self.lpips_sampler is not None else ())
-        shapes = lambda d: tuple(None if d.get(k) is None else tuple(d[k].shape) for k in keys)
-        lp_shape = dict(lp, mask=mask)
-        if (not s or s.get("feed") or s.get(key) is None or s[key].shape != A.shape or s.get("single") != pose_in.get("single")
-                or shapes(s) != shapes(lp_shape)):
-            s.update(A=None, idx=None, feed=None, single=pose_in.get("single"))      # (the step reads A, or the tables' rows at idx: not both)
-            s.update({key: A.clone(), "gt": gt_rgb.clone(), "mask": mask.clone()})
-            s.update({k: (None if v is None else v.clone()) for k, v in lp.items()})
-            self.captured = None
-        else:
-            s[key].copy_(A); s["gt"].copy_(gt_rgb); s["mask"].copy_(mask)
-            for k, v in lp.items():
-                if v is not None:
-                    s[k].copy_(v)
+        on_dev = lambda v: None if v is None else torch.as_tensor(v).to(self.dev)
+        lp_origins = on_dev(lpips_origins)
+        if lp_origins is not None:
+            lp_origins = lp_origins.to(torch.int32)
+        # (the step reads A, or the tables' rows at idx: not both)
+        if self.inputs.bind(source, single, gt=gt_rgb, mask=mask, lp_origins=lp_origins, lp_bg=on_dev(lpips_bg), **{source: pose}):
+            self._drop_graph()
         return self._run()
 
     def step_next(self, lpips_bg=None):
@@ -460,17 +407,10 @@ class AvatarTrainer:
         the static inputs ARE the feed's tensors.  ``lpips_bg``: as in ``step``."""
         if self.frames is None:
             raise RuntimeError("AvatarTrainer.step_next needs frames=FrameFeed(...)")
-        s, fd = self._static, self.frames
-        single = fd.K == 1
-        lp_bg = None if lpips_bg is None else torch.as_tensor(lpips_bg).to(self.dev)
-        shape = lambda t: None if t is None else tuple(t.shape)
-        if not s.get("feed") or shape(s.get("lp_bg")) != shape(lp_bg):
-            s.clear()
-            s.update(feed=True, A=None, idx=fd.idx, single=single, gt=fd.gt[0] if single else fd.gt,
-                     mask=fd.mask[0] if single else fd.mask, lp_origins=None, lp_bg=None if lp_bg is None else lp_bg.clone())
-            self.captured = None
-        elif lp_bg is not None:
-            s["lp_bg"].copy_(lp_bg)
+        fd, (gt, mask) = self.frames, self._feed_views
+        if self.inputs.bind("feed", fd.K == 1, adopted=dict(idx=fd.idx, gt=gt, mask=mask),
+                            lp_bg=None if lpips_bg is None else torch.as_tensor(lpips_bg).to(self.dev)):
+            self._drop_graph()
         return self._run()
 
     def _run(self):
@@ -515,12 +455,12 @@ class AvatarTrainer:
             self.sh_degree += 1
             self.m.topology_version += 1
             self.rs = self.settings_fn(self.sh_degree)
-            self.captured = None
+            self._drop_graph()
 
     def _reduce_stats(self):
         """With ``fp``: the statistics summed / maximised over the ranks, in place, so that every rank takes the same decision."""
         if self.fp is not None:
-            self.fp.reduce_densification_stats(self.m.xyz_gradient_accum, self.m.denom, self.m.max_radii2D)
+            self.fp.reduce_densification_stats(*self.m.stats_tensors())
 
     def _scales_canon(self, attrs):
         """human_gs_out['scales_canon']: the decoded scales, times smpl_scale when the step has one (sings_hybrid.py:411-413, 455)."""
@@ -540,7 +480,7 @@ class AvatarTrainer:
         group = next(g for g in self.opt.param_groups if g["name"] == "xyz")
         old = group["params"][0]
         state = None if self.fused else self.opt.state.pop(old, None)
-        stats = [take_rows(getattr(m, k), src) for k in self.STATS] if keep_stats else None
+        stats = [take_rows(t, src) for t in m.stats_tensors()] if keep_stats else None
         m.set_topology(new_xyz, new_lbs_weights, scaling_multiplier=scaling_multiplier)
         if self.fused:
             self.opt.reindex_rows(old, m.xyz, src)
@@ -553,7 +493,7 @@ class AvatarTrainer:
             then()
         self._rebuild()
         if keep_stats:                                           # (set_topology and the rebuild start the statistics at zero)
-            m.xyz_gradient_accum, m.denom, m.max_radii2D = stats
+            m.set_stats(stats)
 
     def _appended(self, n_old, n_new):                           # the row map of n_new new rows behind n_old kept ones
         return torch.cat([torch.arange(n_old, device=self.dev), torch.full((n_new,), -1, dtype=torch.int64, device=self.dev)])
@@ -635,7 +575,7 @@ class AvatarTrainer:
         if self.mesh is None:
             raise RuntimeError("AvatarTrainer.prune_and_simplify needs mesh=MeshState(...)")
         m, mesh = self.m, self.mesh
-        own = [getattr(m, k).clone() for k in self.STATS] if self.fp is not None else None
+        own = [t.clone() for t in m.stats_tensors()] if self.fp is not None else None
         self._reduce_stats()
         with torch.no_grad():
             attrs = m.decode()
@@ -650,8 +590,8 @@ class AvatarTrainer:
                 reason = None if int(edges.shape[0]) else "no_edges"
             result = None if reason else _topo.collapse_edges(attrs["xyz_canon"], m.lbs_weights, edges, mesh.faces, return_collapses=True)
             if own is not None:                                      # (the decision is taken: back to this rank's own sums)
-                for k, t in zip(self.STATS, own):
-                    getattr(m, k).copy_(t)
+                for dst, t in zip(m.stats_tensors(), own):
+                    dst.copy_(t)
             if result is None:
                 self.last_simplification = {"skipped": reason, "selected_edges": int(edges.shape[0])}
                 return vert_mask, torch.zeros(n_old, dtype=torch.bool, device=self.dev), n_old, n_old

@@ -188,6 +188,16 @@ class AvatarStep(torch.nn.Module):
         self.denom = torch.zeros((n, 1), dtype=torch.float32, device=dev)
         self.max_radii2D = torch.zeros(n, dtype=torch.float32, device=dev)
 
+    def stats_tensors(self):
+        """The three statistics, one row per Gaussian, in the fixed order (accum, denom, max radii); () before
+        ``enable_densification_stats``.  Every run of a step's body adds to them: a run that is not a step (a capture's warm-up) is
+        followed by putting them back."""
+        return () if self.xyz_gradient_accum is None else (self.xyz_gradient_accum, self.denom, self.max_radii2D)
+
+    def set_stats(self, triple):
+        """Replace the three statistics (the order of ``stats_tensors``): the rows a change of the set carried over."""
+        self.xyz_gradient_accum, self.denom, self.max_radii2D = triple
+
     def add_densification_stats(self, extras):
         """``xyz_gradient_accum[vis] += |viewspace_points.grad[vis, :2]|``, ``denom[vis] += 1``, ``max_radii2D[vis] = max(., radii[vis])``
         for every frame of the step.  Masked arithmetic instead of boolean indexing: the same sums without a host round trip, so the

@@ -160,11 +160,11 @@ def test_the_body_reads_the_feeds_tensors(scene):
         feed = ff.FrameFeed(store, seed=SEED)
         tr = _feed_trainer(sc, store.device, "torch", False, feed)
         tr.step_next()
-        s, f = tr._static, int(ff.indices_host(F, SEED, 0, 1)[0])
-        assert s["idx"] is feed.idx and s["gt"].data_ptr() == feed.gt.data_ptr() and s["mask"].data_ptr() == feed.mask.data_ptr()
-        assert tuple(s["gt"].shape) == (3, H, W) and tuple(s["mask"].shape) == (H, W) and feed.last_indices.tolist() == [f]
+        s, f = tr.inputs, int(ff.indices_host(F, SEED, 0, 1)[0])
+        assert s.idx is feed.idx and s.gt.data_ptr() == feed.gt.data_ptr() and s.mask.data_ptr() == feed.mask.data_ptr()
+        assert tuple(s.gt.shape) == (3, H, W) and tuple(s.mask.shape) == (H, W) and feed.last_indices.tolist() == [f]
         gt, mask = store.frames([f])
-        assert _bits_equal(s["gt"], gt[0]) and _bits_equal(s["mask"], mask[0])
+        assert _bits_equal(s.gt, gt[0]) and _bits_equal(s.mask, mask[0])
         assert np.array_equal(tr.bg.cpu().numpy().view(np.int32), ff.bg_host(SEED, 0).view(np.int32))
     finally:
         _reset()
