@@ -208,6 +208,20 @@ class MeshTerms:
             self.last_grads = {"xyz_canon": f32(V, 3), "scales": f32(V, 3), "shs_dc": f32(V, 3)}
         self.V, self.E, self.nnz = V, E, int(nnz)
 
+    # ---- checkpoint
+    def state_dict(self):
+        """What the last ``reset`` was given besides the mesh: ``verts`` and ``normals`` [V,3].  Everything else the terms hold -- both
+        CSRs, the degrees, the constant edge term -- is rebuilt from them and the mesh, and ``reset`` is deterministic; the step
+        weights follow ``set_iteration``."""
+        if self.V == 0:
+            raise RuntimeError("MeshTerms.state_dict: call reset(mesh, normals, verts) first")
+        return {"verts": self.verts, "normals": self.normals}
+
+    def load_state_dict(self, sd, mesh):
+        """``reset`` for ``mesh`` (the saved run's ``MeshState``) with the saved vertices and normals."""
+        dev = mesh.vertex_label.device
+        self.reset(mesh, sd["normals"].to(dev), sd["verts"].to(dev))
+
     # ---- the terms
     def __call__(self, attrs):
         if self.V == 0:

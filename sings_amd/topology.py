@@ -331,3 +331,21 @@ class MeshState:
 
     def checkpoint_entries(self):
         return {"vertex_label": self.vertex_label, "level_id": self.level_id, "gs_level_mark": list(self.gs_level_mark)}
+
+    def state_dict(self):
+        """The three ``CHECKPOINT_KEYS`` plus ``faces`` and ``edges`` (which the reference does not save: a reloaded model of its own has
+        lost its mesh after the first density event)."""
+        return dict(self.checkpoint_entries(), faces=self.faces, edges=self.edges)
+
+    def load_state_dict(self, sd, device=None):
+        """The five arrays as saved (the edges are NOT recomputed: they are the saved mesh's, bit for bit), on ``device`` (None: where
+        the current arrays live).  The caller has checked the indices against the vertex count (``checkpoint.validate_model``)."""
+        dev = self.vertex_label.device if device is None else device
+        n = int(sd["vertex_label"].shape[0])
+        level = sd.get("level_id")
+        self.faces = sd["faces"].to(dev, torch.int32).contiguous()
+        self.edges = sd["edges"].to(dev, torch.int32).contiguous()
+        self.vertex_label = sd["vertex_label"].to(dev, torch.int32).reshape(-1).contiguous()
+        self.level_id = torch.zeros(n, dtype=torch.float32, device=dev) if level is None else level.to(dev).contiguous()
+        mark = sd.get("gs_level_mark")
+        self.gs_level_mark = [0, n] if mark is None else [int(x) for x in mark]

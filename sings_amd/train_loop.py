@@ -31,8 +31,11 @@ A topology change (or a new SH degree) invalidates everything that was sized or 
 Nothing renders with stale sizes: the old anchors' parameter object is dropped, ``AvatarStep.topology_version`` moves on, and every holder
 of an old version refuses.
 """
+import os
+
 import torch
 
+from . import checkpoint as _ckpt
 from . import decode as _dec
 from . import overflow
 from . import topology as _topo
@@ -124,7 +127,10 @@ class AvatarTrainer:
                           frames and the background colour.  Needs ``poses=`` with one row per frame of the store.  §18.
     ``set_density_schedule(schedule)``  a ``sings_amd.density.HybridDensitySchedule`` -- gated statistics, the L2 term's keys, the SH
                           degree and both changes of the set after the optimiser step, recorded in ``density_log``; ``run(n_steps)``
-                          is ``step_next()`` that many times.  Needs ``mesh=``.  §19."""
+                          is ``step_next()`` that many times.  Needs ``mesh=``.  §19.
+    ``state_dict()`` / ``load_state_dict(sd, strict=True)`` / ``save_checkpoint(path)`` / ``load_checkpoint(path)``  the whole run, every
+                          part above included, in the reference's ``SinGS.state_dict()`` layout plus one key; ``run_until(num_steps,
+                          save_every, save_dir)`` saves on the reference's rule.  Host work between steps.  §20."""
 
     POSE_GROUPS = ("global_orient", "body_pose", "transl")
 
@@ -157,7 +163,7 @@ class AvatarTrainer:
         self.lpips_sampler = lpips_sampler
         if mesh_terms is not None and mesh is None:
             raise ValueError("AvatarTrainer: mesh_terms needs mesh=MeshState(...) (the edges and labels the terms are built from)")
-        self.mesh_terms, self._mesh_verts = mesh_terms, None
+        self.mesh_terms, self._mesh_verts, self._mesh_normals = mesh_terms, None, None
         if mesh_terms is not None:
             module.mesh_terms = mesh_terms
         if mesh is not None and mesh.num_verts != int(module.xyz.shape[0]):
@@ -239,9 +245,10 @@ class AvatarTrainer:
         if self.mesh.num_verts != int(verts.shape[0]):
             raise RuntimeError(f"AvatarTrainer: the mesh has {self.mesh.num_verts} vertices, the new set {int(verts.shape[0])} Gaussians: "
                                "with mesh_terms the set changes through densify_and_subdivide / prune_and_simplify only")
-        self._mesh_verts = None
-        with torch.no_grad():
-            normals = initial_attributes(verts.contiguous(), self.mesh.faces, self.mesh.edges)["normals"]
+        normals, self._mesh_verts, self._mesh_normals = self._mesh_normals, None, None
+        if normals is None:                                      # (given: a loaded checkpoint's, the ones its terms were reset with)
+            with torch.no_grad():
+                normals = initial_attributes(verts.contiguous(), self.mesh.faces, self.mesh.edges)["normals"]
         self.mesh_terms.reset(self.mesh, normals, verts)
 
     def active_groups(self):
@@ -316,6 +323,43 @@ class AvatarTrainer:
         if self.frames is None:
             raise RuntimeError("AvatarTrainer.run needs frames=FrameFeed(...)")
         return [{k: v.clone() for k, v in self.step_next().items()} for _ in range(int(n_steps))]
+
+    def run_until(self, num_steps, save_every=None, save_dir=None):
+        """``step_next()`` for the iterations ``self.iteration .. num_steps`` (the reference's ``range(init_iter, num_steps + 1)``) -> the
+        list of the steps' loss dicts.  With ``save_every`` and ``save_dir``: behind the step of iteration ``t`` the run is saved as
+        ``human_{t:06d}.pth`` when ``t % save_every == 0 or t == num_steps`` (gs_trainer.py:426-428); the file resumes at ``t + 1``."""
+        if self.frames is None:
+            raise RuntimeError("AvatarTrainer.run_until needs frames=FrameFeed(...)")
+        if (save_every is None) != (save_dir is None) or (save_every is not None and int(save_every) < 1):
+            raise ValueError("AvatarTrainer.run_until: save_every (>= 1) and save_dir go together")
+        out = []
+        while self.iteration <= int(num_steps):
+            t = self.iteration
+            out.append({k: v.clone() for k, v in self.step_next().items()})
+            if save_every is not None and (t % int(save_every) == 0 or t == int(num_steps)):
+                self.save_checkpoint(os.path.join(save_dir, f"human_{t:06d}.pth"))
+        return out
+
+    # ---- checkpoint / resume (sings_amd.checkpoint; INTEGRATION.md §20): host work between steps, nothing a step executes
+    def state_dict(self, spatial_lr_scale=None, betas=None):
+        """The whole run as one dict: the reference's ``SinGS.state_dict()`` layout plus the key ``"sings_amd"``
+        (``checkpoint.trainer_state_dict``).  ``spatial_lr_scale`` / ``betas``: the caller's, passed through."""
+        return _ckpt.trainer_state_dict(self, spatial_lr_scale=spatial_lr_scale, betas=betas)
+
+    def load_state_dict(self, sd, strict=True):
+        """Make this trainer -- built the usual way, with the same optional parts -- the saved one; -> a report.  Everything is validated
+        before anything changes: a refusal (ValueError naming the entry) leaves the trainer as it was.  ``strict=False``: a part only
+        the file or only the trainer has is skipped and named in the report.  A dict without ``"sings_amd"`` (the reference's
+        ``save_ckpt``): ``checkpoint.load_reference``."""
+        return _ckpt.load_trainer_state_dict(self, sd, strict=strict)
+
+    def save_checkpoint(self, path, spatial_lr_scale=None, betas=None):
+        """``state_dict()`` into ``path``: written to a temporary file beside it, then ``os.replace``."""
+        _ckpt.atomic_save(self.state_dict(spatial_lr_scale=spatial_lr_scale, betas=betas), path)
+
+    def load_checkpoint(self, path, strict=True):
+        """``load_state_dict`` of a file of ``save_checkpoint`` (read with ``torch.load(..., weights_only=True)``)."""
+        return self.load_state_dict(_ckpt.load_file(path), strict=strict)
 
     def _body(self):
         for p in self.params:

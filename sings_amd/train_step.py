@@ -237,6 +237,49 @@ class AvatarStep(torch.nn.Module):
         if self.xyz_gradient_accum is not None:
             self.enable_densification_stats()
 
+    # ---- checkpoint: the model's entries of the reference's ``SinGS.state_dict()`` (sings_hybrid.py:169-199)
+    def checkpoint_entries(self):
+        """``xyz``, ``triplane`` / ``geometry_dec_0`` / ``appearance_dec_0`` (the modules' own ``state_dict()``s), ``scaling_multiplier`` (None,
+        a number, or a tensor: [N,1] once a densification has made it per-Gaussian), the three statistics and ``lbs_weights`` -- the
+        live objects, not copies (``sings_amd.checkpoint`` copies them to the host).  One entry is not the reference's: ``opacity_offset``,
+        the [N,1] tensor the appearance decoder's ``reset_opacity`` leaves behind every change of the set (None before the first).  It
+        is a plain attribute, in no module's ``state_dict()`` -- the reference's file loses it, and with it the opacities."""
+        stats = self.stats_tensors() or (None, None, None)
+        offset = getattr(self.appearance_dec, "opacity_offset", None)
+        return {"xyz": self.xyz.detach(), "triplane": dict(self.triplane.state_dict()),
+                "geometry_dec_0": dict(self.geometry_dec.state_dict()), "appearance_dec_0": dict(self.appearance_dec.state_dict()),
+                "scaling_multiplier": self.scaling_multiplier, "xyz_gradient_accum": stats[0], "denom": stats[1], "max_radii2D": stats[2],
+                "lbs_weights": self.lbs_weights, "opacity_offset": offset if torch.is_tensor(offset) else None}
+
+    @torch.no_grad()
+    def load_checkpoint_entries(self, entries, replace_set=None):
+        """The reverse, for entries whose shapes the caller has checked (``checkpoint.validate_model``): the three modules load in place
+        (their parameter objects stay), the set is replaced at the saved N -- through ``replace_set(xyz, lbs_weights,
+        scaling_multiplier)`` when a trainer owns the optimiser and what is sized by N, else ``set_topology`` -- and the statistics, if
+        the entries carry them, are put back behind it.  ``opacity_offset``: the saved tensor, or -- None, or a file of the
+        reference's that has no such entry -- the decoder's initial 0, as a model the reference reloads has it."""
+        dev = self.xyz.device
+        self.triplane.load_state_dict(entries["triplane"])
+        self.geometry_dec.load_state_dict(entries["geometry_dec_0"])
+        self.appearance_dec.load_state_dict(entries["appearance_dec_0"])
+        if not getattr(self.appearance_dec, "fixed_opacity", False):
+            offset = entries.get("opacity_offset")
+            self.appearance_dec.opacity_offset = 0 if offset is None else offset.to(dev, torch.float32).clone().contiguous()
+        xyz, sm = entries["xyz"].to(dev), entries["scaling_multiplier"]
+        n = int(xyz.shape[0])
+        per_gaussian = torch.is_tensor(sm) and sm.dim() == 2 and tuple(sm.shape) == (n, 1) and n != 1
+        if torch.is_tensor(sm):
+            sm = sm.to(dev).clone()
+        if not per_gaussian:
+            self.scaling_multiplier, sm = sm, None               # (a scalar for every Gaussian: nothing to pass for the new set)
+        if replace_set is not None:
+            replace_set(xyz, entries["lbs_weights"].to(dev), sm)
+        else:
+            self.set_topology(xyz, entries["lbs_weights"].to(dev), scaling_multiplier=sm)
+        stats = [entries.get(k) for k in ("xyz_gradient_accum", "denom", "max_radii2D")]
+        if all(t is not None for t in stats):
+            self.set_stats([t.to(dev, torch.float32).clone().contiguous() for t in stats])
+
     def set_trainable(self, opt_geo=True, opt_app=True):
         """The decoders that learn from now on (gs_trainer.py:225-226; sings_hybrid.py:265-277: a decoder whose flag is False is decoded
         under no_grad -- here by ``decode.decode_attributes(opt_geo=, opt_app=)``).  With both False the tri-plane gets no gradient
