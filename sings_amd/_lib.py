@@ -20,6 +20,7 @@ HAS_SAMPLER = False                  # set by load(): the library exports the ta
 HAS_FROZEN = False                   # set by load(): the library exports the table of include/sings_frozen.h
 HAS_FEED = False                     # set by load(): the library exports the table of include/sings_feed.h
 HAS_DENSITY = False                  # set by load(): the library exports the table of include/sings_density.h
+HAS_SHEET = False                    # set by load(): the library exports the table of include/sings_sheet.h
 
 
 class SgRasterSettings(C.Structure):
@@ -212,6 +213,10 @@ _PROTOTYPES_FEED = {
 _PROTOTYPES_DENSITY = {
     "sg_density_stats": "i: i2 p7",
 }
+# The finished 8-bit sheets of a run's pictures, include/sings_sheet.h: a ninth header and a ninth table, for the same reason.
+_PROTOTYPES_SHEET = {
+    "sg_image_sheets": "i: i6 f i2 p5",
+}
 _P = C.POINTER
 _CTYPE = {"i": C.c_int, "z": C.c_size_t, "f": C.c_float, "s": C.c_char_p,
           "p": C.c_void_p,                        # a raw device pointer (or NULL), and the stream
@@ -244,6 +249,9 @@ FEED_MAX_K = 16                      # SG_FEED_MAX_K
 FEED_STATE_WORDS = 4                 # SG_FEED_STATE_WORDS
 DENSITY_MAX_K = 16                   # SG_DENSITY_MAX_K
 DENSITY_BLOCK = 256                  # SG_DENSITY_BLOCK: Gaussians per workgroup of the gated statistics
+SHEET_TRUNC, SHEET_ROUND = 0, 1      # SG_SHEET_TRUNC, SG_SHEET_ROUND
+SHEET_MAX_SHEETS = 65535             # SG_SHEET_MAX_SHEETS
+SHEET_BLOCK = 256                    # SG_SHEET_BLOCK: threads per workgroup, 4 pixels of a sheet each
 FROZEN_BLOCK = 128                   # SG_FROZEN_BLOCK: points per workgroup of the fused no-gradient decode
 FROZEN_SHS = 48                      # SG_FROZEN_SHS
 MESH_TERMS_INFO_INTS = 2             # SG_MESH_TERMS_INFO_INTS
@@ -289,20 +297,22 @@ def load():
                            "(include/sings_hip.h SG_ABI_VERSION): rebuild with `make -C sings_amd/csrc`")
     # (SINGS_HIP_LIB may name a library that predates include/sings_order.h -- an A/B run against a parent build: it exports none of
     # that table, HAS_ORDER says so, and the engines then make the unordered calls that library knows)
-    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN, HAS_FEED, HAS_DENSITY
+    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN, HAS_FEED, HAS_DENSITY, HAS_SHEET
     HAS_ORDER = all(hasattr(lib, name) for name in _PROTOTYPES_ORDER)
     HAS_SAMPLER = all(hasattr(lib, name) for name in _PROTOTYPES_SAMPLER)    # (the same, for include/sings_sampler.h)
     HAS_FROZEN = all(hasattr(lib, name) for name in _PROTOTYPES_FROZEN)      # (the same, for include/sings_frozen.h)
     HAS_FEED = all(hasattr(lib, name) for name in _PROTOTYPES_FEED)          # (the same, for include/sings_feed.h)
     HAS_DENSITY = all(hasattr(lib, name) for name in _PROTOTYPES_DENSITY)    # (the same, for include/sings_density.h)
+    HAS_SHEET = all(hasattr(lib, name) for name in _PROTOTYPES_SHEET)        # (the same, for include/sings_sheet.h)
     for has, header in ((HAS_ORDER, "sings_order.h"), (HAS_SAMPLER, "sings_sampler.h"), (HAS_FROZEN, "sings_frozen.h"),
-                        (HAS_FEED, "sings_feed.h"), (HAS_DENSITY, "sings_density.h")):
+                        (HAS_FEED, "sings_feed.h"), (HAS_DENSITY, "sings_density.h"), (HAS_SHEET, "sings_sheet.h")):
         if not has and LIB_PATH == os.path.join(_HERE, "libsings_hip.so"):
             raise RuntimeError(f"sings_amd: {LIB_PATH} lacks the entry points of include/{header}: rebuild with `make -C sings_amd/csrc`")
     for name, signature in (*_PROTOTYPES.items(), *_PROTOTYPES_EVAL.items(), *_PROTOTYPES_MESH_TERMS.items(),
                             *(_PROTOTYPES_ORDER.items() if HAS_ORDER else ()), *(_PROTOTYPES_SAMPLER.items() if HAS_SAMPLER else ()),
                             *(_PROTOTYPES_FROZEN.items() if HAS_FROZEN else ()), *(_PROTOTYPES_FEED.items() if HAS_FEED else ()),
-                            *(_PROTOTYPES_DENSITY.items() if HAS_DENSITY else ())):
+                            *(_PROTOTYPES_DENSITY.items() if HAS_DENSITY else ()),
+                            *(_PROTOTYPES_SHEET.items() if HAS_SHEET else ())):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = _ctypes_of(signature)
     _lib = lib

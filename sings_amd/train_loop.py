@@ -128,6 +128,8 @@ class AvatarTrainer:
     ``set_density_schedule(schedule)``  a ``sings_amd.density.HybridDensitySchedule`` -- gated statistics, the L2 term's keys, the SH
                           degree and both changes of the set after the optimiser step, recorded in ``density_log``; ``run(n_steps)``
                           is ``step_next()`` that many times.  Needs ``mesh=``.  §19.
+    ``set_outputs(outputs)``  a ``sings_amd.run_outputs.RunOutputs`` -- the run's pictures, turntable and splat file on the reference's
+                          intervals, written behind the optimiser step and in front of the density schedule's changes.  §21.
     ``state_dict()`` / ``load_state_dict(sd, strict=True)`` / ``save_checkpoint(path)`` / ``load_checkpoint(path)``  the whole run, every
                           part above included, in the reference's ``SinGS.state_dict()`` layout plus one key; ``run_until(num_steps,
                           save_every, save_dir)`` saves on the reference's rule.  Host work between steps.  §20."""
@@ -197,6 +199,8 @@ class AvatarTrainer:
         else:
             self.opt = torch.optim.Adam(self._groups(), betas=betas, eps=eps)
         self.captured = self.flat = self.views = None
+        # set_outputs(): the run's pictures (sings_amd.run_outputs.RunOutputs) and, kept for them only, the step's raw render
+        self.outputs, self.last_render = None, None
         self.iteration = 0
         self.inputs = StepInputs()
         self._rebuild()
@@ -292,6 +296,17 @@ class AvatarTrainer:
         self.m.stats_gate = self._gate
         self._drop_graph()
 
+    def set_outputs(self, outputs):
+        """Attach (or, with None, detach) a ``sings_amd.run_outputs.RunOutputs``: behind the optimiser step of iteration ``t`` -- and in front
+        of the density schedule's SH degree and changes of the set, the reference's order (gs_trainer.py:271-274, :457-458) -- the run
+        calls ``outputs.after_step(self, t)``.  With outputs the body keeps a reference to the step's raw render (the tensor a replayed
+        graph rewrites), so the graph is dropped when outputs come or go; without them a step does what it did.  INTEGRATION.md §21."""
+        if (outputs is None) != (self.outputs is None):
+            self._drop_graph()
+        self.outputs = outputs
+        if outputs is None:
+            self.last_render = None
+
     def _apply_density_schedule_before(self):
         """In front of step ``self.iteration``: the gate's word (a stream-ordered fill, only when it changes) and the L2 term's keys."""
         sch, t = self.density_schedule, self.iteration
@@ -385,6 +400,8 @@ class AvatarTrainer:
         else:
             loss.backward()
         self.m.add_densification_stats(ex)
+        if self.outputs is not None:
+            self.last_render = ex["render_raw"].detach()         # (the training picture shows the step's own image)
         if self.fused and self.fp is None:
             self.opt.apply()                                     # (the Adam launch: part of the body, and so of a captured step)
         return {k: v.detach().reshape(()).clone() for k, v in ld.items()}
@@ -485,6 +502,8 @@ class AvatarTrainer:
                 self.opt.apply(sync=False)                       # (the arena holds the reduced gradients)
         if not self.fused:
             self.opt.step()
+        if self.outputs is not None:                             # (before the SH degree and the set change: the reference's order)
+            self.outputs.after_step(self, self.iteration)
         if self.density_schedule is not None:
             if self._gate_value:                                 # (a change of the set drops the graph whose outputs these may be)
                 ld = {k: v.clone() for k, v in ld.items()}
