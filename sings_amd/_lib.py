@@ -21,6 +21,7 @@ HAS_FROZEN = False                   # set by load(): the library exports the ta
 HAS_FEED = False                     # set by load(): the library exports the table of include/sings_feed.h
 HAS_DENSITY = False                  # set by load(): the library exports the table of include/sings_density.h
 HAS_SHEET = False                    # set by load(): the library exports the table of include/sings_sheet.h
+HAS_SCENE = False                    # set by load(): the library exports the table of include/sings_scene.h
 
 
 class SgRasterSettings(C.Structure):
@@ -52,7 +53,15 @@ class SgFrameBatch(C.Structure):
     reserved = property(lambda self: self.placement, lambda self, v: setattr(self, "placement", v))
 
 
+class SgSceneAvatar(C.Structure):
+    """One avatar of a scene (include/sings_scene.h): a host array of them is read during the call."""
+    _fields_ = [(n, C.c_int32) for n in ("P", "J", "rot_format", "reserved")] + [(n, C.c_void_p) for n in (
+        "xyz_canon", "rot_canon", "lbs_weights", "scales", "opacities", "shs", "A", "transl", "smpl_scale", "ext_trans", "ext_rot",
+        "ext_scale")]
+
+
 MAX_FRAMES = 16                      # SG_MAX_FRAMES
+SCENE_MAX_AVATARS = 8                # SG_SCENE_MAX_AVATARS
 POSE_NB = 23                         # SG_POSE_NB: body joints per row of the body_pose table
 PLACEMENT_EXT_TFS = 1                # SG_PLACEMENT_EXT_TFS: ext_tfs [K,3] / [K,9] / [K], one set per frame
 PLACEMENT_SMPL_SCALE = 2             # SG_PLACEMENT_SMPL_SCALE: smpl_scale [K], one per frame
@@ -217,10 +226,16 @@ _PROTOTYPES_DENSITY = {
 _PROTOTYPES_SHEET = {
     "sg_image_sheets": "i: i6 f i2 p5",
 }
+# Several avatars in one frame, include/sings_scene.h: a tenth header and a tenth table, for the same reason.
+_PROTOTYPES_SCENE = {
+    "sg_scene_forward_frames": "i: S i3 A p2 z p6 n p",
+    "sg_scene_forward_frames_aux": "i: S i3 A p2 z p6 n p4",
+}
 _P = C.POINTER
 _CTYPE = {"i": C.c_int, "z": C.c_size_t, "f": C.c_float, "s": C.c_char_p,
           "p": C.c_void_p,                        # a raw device pointer (or NULL), and the stream
           "S": _P(SgRasterSettings), "F": _P(SgFrameBatch), "K": _P(SgSkinInputs), "L": _P(SgLayout), "T": _P(SgTriplane),
+          "A": _P(SgSceneAvatar),                 # SgSceneAvatar[S] (host)
           "D": _P(SgLinearSide),                  # SgLinearSide[2]
           "n": _P(C.c_int64), "Z": _P(C.c_size_t), "d": _P(C.c_double),     # host outputs (one value or an array)
           "V": _P(C.c_void_p),                    # void **
@@ -297,22 +312,25 @@ def load():
                            "(include/sings_hip.h SG_ABI_VERSION): rebuild with `make -C sings_amd/csrc`")
     # (SINGS_HIP_LIB may name a library that predates include/sings_order.h -- an A/B run against a parent build: it exports none of
     # that table, HAS_ORDER says so, and the engines then make the unordered calls that library knows)
-    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN, HAS_FEED, HAS_DENSITY, HAS_SHEET
+    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN, HAS_FEED, HAS_DENSITY, HAS_SHEET, HAS_SCENE
     HAS_ORDER = all(hasattr(lib, name) for name in _PROTOTYPES_ORDER)
     HAS_SAMPLER = all(hasattr(lib, name) for name in _PROTOTYPES_SAMPLER)    # (the same, for include/sings_sampler.h)
     HAS_FROZEN = all(hasattr(lib, name) for name in _PROTOTYPES_FROZEN)      # (the same, for include/sings_frozen.h)
     HAS_FEED = all(hasattr(lib, name) for name in _PROTOTYPES_FEED)          # (the same, for include/sings_feed.h)
     HAS_DENSITY = all(hasattr(lib, name) for name in _PROTOTYPES_DENSITY)    # (the same, for include/sings_density.h)
     HAS_SHEET = all(hasattr(lib, name) for name in _PROTOTYPES_SHEET)        # (the same, for include/sings_sheet.h)
+    HAS_SCENE = all(hasattr(lib, name) for name in _PROTOTYPES_SCENE)        # (the same, for include/sings_scene.h)
     for has, header in ((HAS_ORDER, "sings_order.h"), (HAS_SAMPLER, "sings_sampler.h"), (HAS_FROZEN, "sings_frozen.h"),
-                        (HAS_FEED, "sings_feed.h"), (HAS_DENSITY, "sings_density.h"), (HAS_SHEET, "sings_sheet.h")):
+                        (HAS_FEED, "sings_feed.h"), (HAS_DENSITY, "sings_density.h"), (HAS_SHEET, "sings_sheet.h"),
+                        (HAS_SCENE, "sings_scene.h")):
         if not has and LIB_PATH == os.path.join(_HERE, "libsings_hip.so"):
             raise RuntimeError(f"sings_amd: {LIB_PATH} lacks the entry points of include/{header}: rebuild with `make -C sings_amd/csrc`")
     for name, signature in (*_PROTOTYPES.items(), *_PROTOTYPES_EVAL.items(), *_PROTOTYPES_MESH_TERMS.items(),
                             *(_PROTOTYPES_ORDER.items() if HAS_ORDER else ()), *(_PROTOTYPES_SAMPLER.items() if HAS_SAMPLER else ()),
                             *(_PROTOTYPES_FROZEN.items() if HAS_FROZEN else ()), *(_PROTOTYPES_FEED.items() if HAS_FEED else ()),
                             *(_PROTOTYPES_DENSITY.items() if HAS_DENSITY else ()),
-                            *(_PROTOTYPES_SHEET.items() if HAS_SHEET else ())):
+                            *(_PROTOTYPES_SHEET.items() if HAS_SHEET else ()),
+                            *(_PROTOTYPES_SCENE.items() if HAS_SCENE else ())):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = _ctypes_of(signature)
     _lib = lib

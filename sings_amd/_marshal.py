@@ -123,6 +123,25 @@ def _skin_frames(dev, xyz_canon, rotmat_canon, lbs_weights, A, smpl_scale, trans
     return k, _frame_batch(K, camera_stride, tstride, placement), ext_tfs is not None or bool(placement)
 
 
+def _scene_structs(dev, avatars, keep):
+    """The avatars of a scene (include/sings_scene.h) -> the host array ``SgSceneAvatar[S]``.  ``avatars``: one dict per avatar of
+    fp32 tensors on ``dev`` -- ``xyz_canon`` [P,3], ``rot_canon`` [P,9] / [P,6] / None, ``lbs_weights`` [P,J], ``scales``,
+    ``opacities``, ``shs`` [P,M,3], ``A`` [K,J,16], and with K rows each or None: ``transl``, ``smpl_scale``, ``ext_trans``, ``ext_rot``,
+    ``ext_scale`` (shapes are the caller's to check: SceneFramesEngine.set_frames).  ``keep``: receives every tensor the structs
+    point at; the array itself must also outlive the call."""
+    arr = (_lib.SgSceneAvatar * len(avatars))()
+    for a, av in zip(arr, avatars):
+        ts = {n: _f32(av.get(n), n, dev) for n in ("xyz_canon", "rot_canon", "lbs_weights", "scales", "opacities", "shs", "A", "transl",
+                                                  "smpl_scale", "ext_trans", "ext_rot", "ext_scale")}
+        a.P, a.J = int(ts["xyz_canon"].shape[0]), int(ts["A"].shape[-2])
+        rot = ts["rot_canon"]
+        a.rot_format, a.reserved = (1 if rot is not None and rot.dim() == 2 and rot.shape[-1] == 6 else 0), 0
+        for n, t in ts.items():
+            setattr(a, n, None if t is None else t.data_ptr())
+        keep.extend(t for t in ts.values() if t is not None)
+    return arr
+
+
 def adam_step(segments, chunks, hyper, grad_flat, exp_avg, exp_avg_sq):
     """``sg_adam_step`` on torch's current stream: ``segments`` [S,4] int64, ``chunks`` [C,2] int32 and ``hyper`` [G,8] fp32 are
     device tensors (``sings_amd.optim.build_tables`` / ``hyper_row``), the other three the flat fp32 buffers of one layout."""

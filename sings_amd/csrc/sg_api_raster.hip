@@ -2,6 +2,7 @@
 // and the forward / backward entry points of the plain and the skinned paths, with and without the depth / alpha maps.
 #include "sg_host.h"
 #include "../../include/sings_order.h"
+#include "../../include/sings_scene.h"
 
 #include <chrono>
 #include <stdlib.h>
@@ -164,8 +165,9 @@ static int sg_forward_impl(const char *who, const SgRasterSettings *s, const SgF
                            size_t cap, void *image_ws, float *out_color, int32_t *radii, float *posed_xyz, float *posed_rotq,
                            float *posed_scales, int write_point_keys, int64_t *num_rendered_host, void *stream,
                            SgAux aux = SG_AUX_NONE, void *aux_ws = nullptr, float *out_depth = nullptr, float *out_alpha = nullptr,
-                           const uint32_t *order = nullptr, int order_len = 0)
+                           const uint32_t *order = nullptr, int order_len = 0, const SgSceneAvatar *scene = nullptr, int scene_S = 0)
 {
+    // (scene != null, include/sings_scene.h: scene_S checked avatars whose Gaussians sum to P; the preprocess launch is theirs)
     hipStream_t st = (hipStream_t)stream;
     SgCam c;
     if (sg_check_order(who, order, order_len, P)) return 1;
@@ -175,7 +177,10 @@ static int sg_forward_impl(const char *who, const SgRasterSettings *s, const SgF
         if (sg_aux_flags(who, c.flags, aux == SG_AUX_FRAMES)) return 1;
         if (!out_depth || !out_alpha) return sg_failf("%s: null pointer (out_depth / out_alpha)", who);
     }
-    if (skin) {
+    if (scene) {
+        if (!geom_ws || !binning_ws || !image_ws || !out_color || !radii) return sg_failf("%s: null pointer", who);
+        if (s->sh_coeffs < (s->sh_degree + 1) * (s->sh_degree + 1)) return sg_failf("%s: sh_coeffs smaller than (sh_degree+1)^2", who);
+    } else if (skin) {
         if (sg_check_skin(skin, P, true)) return sg_failf("%s: bad skin inputs (J in 1..64, ext_tfs all or none)", who);
         if (sg_check_placement(who, fb, skin)) return 1;
         if (P < 0 || !geom_ws || !binning_ws || !image_ws || !out_color || (P > 0 && (!shs || !opacities || !scales || !radii)))
@@ -207,7 +212,8 @@ static int sg_forward_impl(const char *who, const SgRasterSettings *s, const SgF
             const size_t zb = (L.bin_tile_count - L.bin_header) + sg_ctr_count((uint32_t)c.gx, (uint32_t)c.gy) * 4;
             for (int f = 0; f < bt.K; f++) sg_zero_async((char *)b.header + (size_t)f * bt.bin, zb, st);
         }
-        if (skin) sg_launch_skin_fwd(c, bt, P, skin, shs, opacities, scales, g, b, cap, radii, posed_xyz, posed_rotq, posed_scales, st);
+        if (scene) sg_launch_scene_fwd(c, bt, scene_S, scene, g, b, cap, radii, posed_xyz, posed_rotq, posed_scales, st);
+        else if (skin) sg_launch_skin_fwd(c, bt, P, skin, shs, opacities, scales, g, b, cap, radii, posed_xyz, posed_rotq, posed_scales, st);
         else sg_launch_preprocess_fwd_ordered(c, bt, P, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, g, b, cap,
                                               radii, order, st);
         SG_CHECK_LAST("preprocess_fwd", s, st);
@@ -646,4 +652,64 @@ extern "C" int sg_work_order_codes(int P, const float *means3D, void *ws, uint32
     if (!means3D || !ws || !codes) return sg_failf("sg_work_order_codes: null pointer");
     sg_launch_morton_codes(P, means3D, (float *)ws, codes, (hipStream_t)stream);
     return sg_launched("sg_work_order_codes");
+}
+
+// ---- several avatars in one frame (include/sings_scene.h) ------------------------------------------------------------------------
+// Everything of the scene is checked here, before the shared forward sees it: -> Ptot, or -1 with the error set
+static long long sg_check_scene(const char *who, int K, int camera_stride, int S, const SgSceneAvatar *av)
+{
+    if (S < 1 || S > SG_SCENE_MAX_AVATARS) { sg_failf("%s: S = %d outside 1..%d", who, S, SG_SCENE_MAX_AVATARS); return -1; }
+    if (K < 1 || K > SG_MAX_FRAMES) { sg_failf("%s: K = %d outside 1..%d", who, K, SG_MAX_FRAMES); return -1; }
+    if (camera_stride != 0 && camera_stride != 1) { sg_failf("%s: camera_stride = %d, not 0 or 1", who, camera_stride); return -1; }
+    if (!av) { sg_failf("%s: null pointer (avatars)", who); return -1; }
+    long long total = 0;
+    for (int i = 0; i < S; i++) {
+        const SgSceneAvatar &a = av[i];
+        if (a.P < 1) { sg_failf("%s: avatar %d: P = %d, at least one Gaussian is needed", who, i, a.P); return -1; }
+        if (a.J < 1 || a.J > 64) { sg_failf("%s: avatar %d: J = %d outside 1..64", who, i, a.J); return -1; }
+        if (a.rot_format != SG_ROT_CANON_MATRIX && a.rot_format != SG_ROT_CANON_6D) {
+            sg_failf("%s: avatar %d: unknown rot_format %d", who, i, a.rot_format); return -1;
+        }
+        if (a.reserved != 0) { sg_failf("%s: avatar %d: reserved = %d, must be 0", who, i, a.reserved); return -1; }
+        const int e = (a.ext_trans != nullptr) + (a.ext_rot != nullptr) + (a.ext_scale != nullptr);
+        if (e != 0 && e != 3) { sg_failf("%s: avatar %d: ext_trans / ext_rot / ext_scale must be all or none", who, i); return -1; }
+        if (!a.xyz_canon || !a.lbs_weights || !a.scales || !a.opacities || !a.shs || !a.A) {
+            sg_failf("%s: avatar %d: null pointer", who, i); return -1;
+        }
+        total += a.P;
+    }
+    if (total > 0x7fffffffll) { sg_failf("%s: %lld Gaussians in the scene, at most 2^31 - 1", who, total); return -1; }
+    return total;
+}
+
+static int sg_scene_impl(const char *who, const SgRasterSettings *s, int K, int camera_stride, int S, const SgSceneAvatar *avatars,
+                         void *geom_ws, void *binning_ws, size_t cap, void *image_ws, float *out_color, int32_t *radii,
+                         float *posed_xyz, float *posed_rotq, float *posed_scales, int64_t *num_rendered_host, void *stream,
+                         SgAux aux, void *aux_ws, float *out_depth, float *out_alpha)
+{
+    const long long P = sg_check_scene(who, K, camera_stride, S, avatars);
+    if (P < 0) return 1;
+    const SgFrameBatch fb = { K, camera_stride, 0, 0 };
+    return sg_forward_impl(who, s, &fb, (int)P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, geom_ws,
+                           binning_ws, cap, image_ws, out_color, radii, posed_xyz, posed_rotq, posed_scales, 0, num_rendered_host,
+                           stream, aux, aux_ws, out_depth, out_alpha, nullptr, 0, avatars, S);
+}
+
+extern "C" int sg_scene_forward_frames(const SgRasterSettings *s, int K, int camera_stride, int S, const SgSceneAvatar *avatars,
+                                       void *geom_ws, void *binning_ws, size_t cap, void *image_ws, float *out_color, int32_t *radii,
+                                       float *posed_xyz, float *posed_rotq, float *posed_scales, int64_t *num_rendered_host,
+                                       void *stream)
+{
+    return sg_scene_impl("sg_scene_forward_frames", s, K, camera_stride, S, avatars, geom_ws, binning_ws, cap, image_ws, out_color,
+                         radii, posed_xyz, posed_rotq, posed_scales, num_rendered_host, stream, SG_AUX_NONE, nullptr, nullptr, nullptr);
+}
+
+extern "C" int sg_scene_forward_frames_aux(const SgRasterSettings *s, int K, int camera_stride, int S, const SgSceneAvatar *avatars,
+                                           void *geom_ws, void *binning_ws, size_t cap, void *image_ws, float *out_color,
+                                           int32_t *radii, float *posed_xyz, float *posed_rotq, float *posed_scales,
+                                           int64_t *num_rendered_host, void *aux_ws, float *out_depth, float *out_alpha, void *stream)
+{
+    return sg_scene_impl("sg_scene_forward_frames_aux", s, K, camera_stride, S, avatars, geom_ws, binning_ws, cap, image_ws,
+                         out_color, radii, posed_xyz, posed_rotq, posed_scales, num_rendered_host, stream, SG_AUX_FRAMES, aux_ws,
+                         out_depth, out_alpha);
 }

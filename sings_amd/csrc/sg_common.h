@@ -337,6 +337,11 @@ void sg_prof_end(int id, hipStream_t st);
 void sg_launch_skin_fwd(const SgCam &c, const SgBatch &bt, int P, const SgSkinInputs *in, const float *shs, const float *opacities,
                         const float *scales, SgGeom g, SgBin b, size_t cap, int32_t *radii, float *posed_xyz,
                         float *posed_rotq, float *posed_scales, hipStream_t st);
+// several avatars in one launch (include/sings_scene.h): S checked avatars in host memory; bt.P = the sum of their P, every per-frame
+// array K rows.  Avatar s owns the Gaussian ids [start_s, start_s + P_s) of the workspaces, radii and posed outputs.
+struct SgSceneAvatar;
+void sg_launch_scene_fwd(const SgCam &c, const SgBatch &bt, int S, const SgSceneAvatar *avatars, SgGeom g, SgBin b, size_t cap,
+                         int32_t *radii, float *posed_xyz, float *posed_rotq, float *posed_scales, hipStream_t st);
 size_t sg_skin_slab_floats(int P, int K);
 size_t sg_photo_loss_ws_bytes_impl(int W, int H);
 int sg_tp_check(const SgTriplane *tp);

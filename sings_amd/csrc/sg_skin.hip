@@ -12,6 +12,7 @@
 // segments through LDS (HBM-bound: 4J bytes per Gaussian dominate).
 #include "sg_project.h"
 #include "sg_rot.h"
+#include "../../include/sings_scene.h"
 
 #define SG_SKIN_THREADS 256
 #define SG_SKIN_WAVES 4
@@ -297,6 +298,80 @@ sg_skin_fwd_kernel(SgCam c, SgBatch bt, int P, SgSkin k, const float *__restrict
         if (posed_xyz) { posed_xyz[3 * idx] = ps.p[0]; posed_xyz[3 * idx + 1] = ps.p[1]; posed_xyz[3 * idx + 2] = ps.p[2]; }
         if (posed_rotq) { posed_rotq[4 * idx] = ps.q[0]; posed_rotq[4 * idx + 1] = ps.q[1]; posed_rotq[4 * idx + 2] = ps.q[2]; posed_rotq[4 * idx + 3] = ps.q[3]; }
         if (posed_scales) { posed_scales[3 * idx] = ps.s3[0]; posed_scales[3 * idx + 1] = ps.s3[1]; posed_scales[3 * idx + 2] = ps.s3[2]; }
+    }
+    uint32_t *hist = nullptr;
+    if (hist_tiles) {                                         // the skinning-weight tiles are dead: reuse them as histogram
+        __syncthreads();
+        hist = (uint32_t *)&sW[0][0];
+    }
+    sg_store_proj(live, idx, o, opac, g, bn, c.gx, cap, radii, (uint32_t *)sT[wave], hist, hist_tiles, sg_key_pitch_of(hist_tiles != 0, c.flags));
+}
+
+// ---- several avatars in one launch (include/sings_scene.h) -----------------------------------------------------------------------
+// The reference poses every avatar, concatenates the posed sets -- SH block included: 192 B per Gaussian at M = 16 -- and rasterizes
+// once (gs_renderer_multiple.py:12-68).  Here a workgroup of the kernel above first looks up which avatar its block of 256 Gaussians
+// belongs to: the avatars (at most SG_SCENE_MAX_AVATARS) ride in the kernel arguments with the first block of each, so the segment
+// is found with S - 1 workgroup-uniform compares.  It then skins with that avatar's J, A of the frame, weights and placement -- the
+// device helpers of sg_skin_fwd_kernel in the same order: the same bits -- and writes the records of the scene's Gaussian ids
+// start_s + local.  A segment's blocks start at its own Gaussian 0, so a wave's 64 ids are consecutive (sg_store_proj: g0 = idx -
+// lane) and only a segment's last block has dead lanes; they reach every barrier of sg_store_proj as the dead lanes of the
+// single-avatar kernel's last block do.  Every per-frame array has K rows: no placement bits.
+struct SgSceneSeg {
+    SgSkin k;                                                  // (A, transl, smpl_scale, ext_*: frame 0's)
+    const float *shs, *opacities, *scales;
+    int P, start, block0, pad;                                 // Gaussians, first Gaussian id, first block of 256
+};
+struct SgScene { int S; SgSceneSeg seg[SG_SCENE_MAX_AVATARS]; };
+
+template <int D>
+__global__ void __launch_bounds__(SG_SKIN_THREADS)
+sg_scene_fwd_kernel(SgCam c, SgBatch bt, SgScene sc, SgGeom g, SgBin bn, uint32_t cap, int32_t *__restrict__ radii,
+                    float *__restrict__ posed_xyz, float *__restrict__ posed_rotq, float *__restrict__ posed_scales,
+                    int hist_tiles, int nblocks)
+{
+    __shared__ float sA[SG_JMAX * 16];
+    __shared__ float sW[SG_SKIN_WAVES][64 * SG_WSTRIDE];
+    __shared__ float sT[SG_SKIN_WAVES][64 * 13];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int gblock, frame;
+    if (!sg_block_frame((int)blockIdx.x, bt.K, nblocks, gblock, frame)) return;
+    int s = 0;                                                 // (workgroup-uniform; block0 ascends)
+#pragma unroll
+    for (int t = 1; t < SG_SCENE_MAX_AVATARS; t++)
+        if (t < sc.S && gblock >= sc.seg[t].block0) s = t;
+    const SgSceneSeg &sg = sc.seg[s];
+    SgSkin k = sg.k;
+    k.A += (size_t)frame * k.J * 16;
+    if (k.transl) k.transl += 3 * (size_t)frame;
+    if (k.smpl_scale) k.smpl_scale += frame;
+    if (k.ext_rot) { k.ext_trans += 3 * (size_t)frame; k.ext_rot += 9 * (size_t)frame; k.ext_scale += frame; }
+    const float *__restrict__ shs = sg.shs, *__restrict__ opacities = sg.opacities, *__restrict__ scales = sg.scales;
+    const int P = sg.P, start = sg.start;
+    c = sg_frame(c, frame, bt.cam_stride);
+    g = sg_frame(g, (size_t)frame * bt.geom); bn = sg_frame(bn, (size_t)frame * bt.bin);
+    radii += (size_t)frame * bt.P;
+    if (posed_xyz) posed_xyz += 3 * (size_t)frame * bt.P;
+    if (posed_rotq) posed_rotq += 4 * (size_t)frame * bt.P;
+    if (posed_scales) posed_scales += 3 * (size_t)frame * bt.P;
+    const int g0 = ((gblock - sg.block0) * SG_SKIN_WAVES + wave) * 64;      // of the segment's own Gaussians
+    const int local = g0 + lane, idx = start + local;                        // ... and the scene's id
+    sg_load_A(k, sA);
+    __syncthreads();
+    float T[12];
+    sg_skin_T(k.lbs_w, k.J, P, g0, lane, sA, sW[wave], sT[wave], T);
+    const bool live = local < P;
+    SgProj o;
+    o.mr = 0; o.tt = 0; o.clampbits = 0; o.x0 = o.y0 = o.x1 = o.y1 = 0;
+    o.pix[0] = o.pix[1] = 0; o.conic[0] = o.conic[1] = o.conic[2] = 0; o.rgb[0] = o.rgb[1] = o.rgb[2] = 0; o.depth = 0;
+    float opac = 0.0f;
+    if (live) {
+        SgPosed ps;
+        sg_pose_gaussian(k, local, T, scales, ps);
+        sg_project_fwd<D>(c, ps.p, ps.s3, ps.q, nullptr, nullptr, shs + (size_t)local * c.M * 3, o);
+        opac = opacities[local];
+        if (posed_xyz) { posed_xyz[3 * (size_t)idx] = ps.p[0]; posed_xyz[3 * (size_t)idx + 1] = ps.p[1]; posed_xyz[3 * (size_t)idx + 2] = ps.p[2]; }
+        if (posed_rotq) { posed_rotq[4 * (size_t)idx] = ps.q[0]; posed_rotq[4 * (size_t)idx + 1] = ps.q[1]; posed_rotq[4 * (size_t)idx + 2] = ps.q[2]; posed_rotq[4 * (size_t)idx + 3] = ps.q[3]; }
+        if (posed_scales) { posed_scales[3 * (size_t)idx] = ps.s3[0]; posed_scales[3 * (size_t)idx + 1] = ps.s3[1]; posed_scales[3 * (size_t)idx + 2] = ps.s3[2]; }
     }
     uint32_t *hist = nullptr;
     if (hist_tiles) {                                         // the skinning-weight tiles are dead: reuse them as histogram
@@ -1062,6 +1137,33 @@ void sg_launch_skin_fwd(const SgCam &c, const SgBatch &bt, int P, const SgSkinIn
     switch (c.D) { case 0: SG_SF(0); break; case 1: SG_SF(1); break; case 2: SG_SF(2); break; default: SG_SF(3); break; }
     sg_prof_end(SG_K_PREPROCESS_FWD, st);
 #undef SG_SF
+}
+
+void sg_launch_scene_fwd(const SgCam &c, const SgBatch &bt, int S, const SgSceneAvatar *avatars, SgGeom g, SgBin b, size_t cap,
+                         int32_t *radii, float *posed_xyz, float *posed_rotq, float *posed_scales, hipStream_t st)
+{
+    SgScene sc = {};
+    sc.S = S;
+    int nblocks = 0, start = 0;
+    for (int s = 0; s < S; s++) {
+        const SgSceneAvatar &a = avatars[s];
+        SgSceneSeg &q = sc.seg[s];
+        q.k = SgSkin{ a.J, a.rot_format == SG_ROT_CANON_6D, a.xyz_canon, a.rot_canon, a.lbs_weights, a.A, a.smpl_scale, a.transl,
+                      a.ext_trans, a.ext_rot, a.ext_scale };
+        q.shs = a.shs; q.opacities = a.opacities; q.scales = a.scales;
+        q.P = a.P; q.start = start; q.block0 = nblocks; q.pad = 0;
+        start += a.P;
+        nblocks += (a.P + SG_SKIN_THREADS - 1) / SG_SKIN_THREADS;
+    }
+    if (nblocks <= 0) return;
+    dim3 grid(sg_frame_grid(nblocks, bt.K)), block(SG_SKIN_THREADS);
+    const int ht = sg_lds_hist(c.gx, c.gy) ? (int)sg_ctr_count((uint32_t)c.gx, (uint32_t)c.gy) : 0;     // histogram words (= tile counters)
+#define SG_SCF(DD) hipLaunchKernelGGL(sg_scene_fwd_kernel<DD>, grid, block, 0, st, c, bt, sc, g, b, sg_cap32(cap), radii, posed_xyz, \
+                                      posed_rotq, posed_scales, ht, nblocks)
+    sg_prof_begin(SG_K_PREPROCESS_FWD, st);
+    switch (c.D) { case 0: SG_SCF(0); break; case 1: SG_SCF(1); break; case 2: SG_SCF(2); break; default: SG_SCF(3); break; }
+    sg_prof_end(SG_K_PREPROCESS_FWD, st);
+#undef SG_SCF
 }
 
 // dynamic LDS above 64 KB needs the kernel's limit raised (once per kernel and process; J = 64: 88 KB)

@@ -153,13 +153,40 @@ def _batch_rows(ts, K, width):
     return torch.stack([t.reshape(width) for t in ts] + [ts[-1].reshape(width)] * (K - len(ts))).contiguous()
 
 
+def _stack_poses(rows, K):
+    """The (A, transl | None, smpl_scale | None, ext_tfs | None) of a batch's k <= K frames of ONE avatar -> what ``set_frames``
+    takes: A [K,J,16] and transl [K,3] stacked, the tail padded with the last frame's; smpl_scale and ext_tfs through
+    ``_batch_rows``."""
+    k = len(rows)
+    A = torch.stack([r[0].reshape(-1, 16) for r in rows] + [rows[-1][0].reshape(-1, 16)] * (K - k)).contiguous()
+    tr = None
+    if rows[0][1] is not None:
+        tr = torch.stack([r[1].reshape(3) for r in rows] + [rows[-1][1].reshape(3)] * (K - k)).contiguous()
+    sc = None if rows[0][2] is None else _batch_rows([r[2] for r in rows], K, 1)
+    ext = None
+    if rows[0][3] is not None:
+        ext = tuple(_batch_rows([r[3][n] for r in rows], K, w) for n, w in enumerate((3, 9, 1)))
+    return A, tr, sc, ext
+
+
+def _stack_cameras(cams, K, bg_color, scaling_modifier, sh_degree):
+    """The settings of a batch of k <= K frames: the one camera dict they share, or their cameras stacked [K,4,4] / [K,3] (the tail
+    padded with the last frame's)."""
+    rs = _settings(cams[0], bg_color, scaling_modifier, sh_degree)
+    if any(cm is not cams[0] for cm in cams):
+        pad = cams + [cams[-1]] * (K - len(cams))
+        rs = rs._replace(viewmatrix=torch.stack([cm['world_view_transform'] for cm in pad]).contiguous(),
+                         projmatrix=torch.stack([cm['full_proj_transform'] for cm in pad]).contiguous(),
+                         campos=torch.stack([cm['camera_center'] for cm in pad]).contiguous())
+    return rs
+
+
 _capacity_floor, _grown = EngineCapacity.floor, EngineCapacity.grown      # (the names the two rules had in this module)
 
 
-def _batches(jobs, K):
-    """The job stream as (index of the first job, batch): at most K consecutive jobs per batch, and a new batch where
-    ``(smpl_scale is None, ext_tfs is None)`` changes (frames with and without scale / placement cannot share a launch)."""
-    kind = lambda job: (job[3] is None, job[4] is None)
+def _batches(jobs, K, kind=lambda job: (job[3] is None, job[4] is None)):
+    """The job stream as (index of the first job, batch): at most K consecutive jobs per batch, and a new batch where ``kind(job)``
+    -- ``(smpl_scale is None, ext_tfs is None)`` -- changes (frames with and without scale / placement cannot share a launch)."""
     batch, i0 = [], 0
     for i, job in enumerate(jobs):
         if batch and kind(job) != kind(batch[0]):
@@ -193,21 +220,34 @@ class FrameAnimator:
     long_rows = property(lambda self: self.policy.long_rows)
 
     def _engines(self, key, cap):
-        """The ``n`` engines of ``key`` = (P, J, W, H, M, K, rot width | None, aux) that hold at least ``cap`` pairs: SkinnedEngine
-        (K None) or SkinnedFramesEngine.  A set of another key or a smaller capacity is replaced."""
+        """The ``n`` engines of ``key`` (``_unit_key``) that hold at least ``cap`` pairs.  A set of another key or a smaller capacity
+        is replaced."""
         if key != self.key or cap > self.cap:
-            from .engine import SkinnedEngine, SkinnedFramesEngine
-            P, J, W, H, M, K, rw, aux = key
             if self.engs:
                 torch.cuda.synchronize(self.dev)                 # (engines in flight are about to be replaced)
             self.engs = []                                       # (drop the old workspaces before the new ones are sized)
-            if K is None:
-                self.engs = [SkinnedEngine(P, J, W, H, M, self.dev, capacity_pairs=cap) for _ in range(self.n)]
-            else:
-                self.engs = [SkinnedFramesEngine(P, J, W, H, M, K, self.dev, capacity_pairs=cap, with_rot=rw is not None,
-                                                 rot_width=9 if rw is None else rw, aux=aux) for _ in range(self.n)]
+            self.engs = [self._build(key, cap) for _ in range(self.n)]
             self.key, self.cap = key, cap
         return self.engs
+
+    def _unit_key(self, unit, K, aux):
+        """What decides the engines a unit needs -> (key, Gaussians, image width, height); key = (P, J, W, H, M, K, rot width | None,
+        aux)."""
+        cam, A = unit[0][0], unit[0][1]
+        c = self.canon
+        P, rot = int(c['xyz_canon'].shape[0]), c.get('rotmat_canon')
+        key = (P, int(A.reshape(-1, 16).shape[0]), int(cam['image_width']), int(cam['image_height']), int(c['shs'].shape[1]), K,
+               None if rot is None else int(rot.reshape(P, -1).shape[1]), bool(aux))
+        return key, P, key[2], key[3]
+
+    def _build(self, key, cap):
+        """One engine of ``key`` with ``cap`` pairs: SkinnedEngine (K None) or SkinnedFramesEngine."""
+        from .engine import SkinnedEngine, SkinnedFramesEngine
+        P, J, W, H, M, K, rw, aux = key
+        if K is None:
+            return SkinnedEngine(P, J, W, H, M, self.dev, capacity_pairs=cap)
+        return SkinnedFramesEngine(P, J, W, H, M, K, self.dev, capacity_pairs=cap, with_rot=rw is not None,
+                                   rot_width=9 if rw is None else rw, aux=aux)
 
     def _pipeline(self, units, launch, K=None, aux=False, depth=None):
         """What the three public methods go through.  ``units``: an iterable of (index of the first job, unit); a unit is a list of
@@ -225,12 +265,8 @@ class FrameAnimator:
 
         def render(s, unit, cap, slot=None):
             """Unit number s on engine and stream s % n of a set that holds at least ``cap`` pairs -> (engine, stream, tensors)."""
-            cam, A = unit[0][0], unit[0][1]
-            c = self.canon
-            P, rot = int(c['xyz_canon'].shape[0]), c.get('rotmat_canon')
-            key = (P, int(A.reshape(-1, 16).shape[0]), int(cam['image_width']), int(cam['image_height']), int(c['shs'].shape[1]), K,
-                   None if rot is None else int(rot.reshape(P, -1).shape[1]), bool(aux))
-            e = self._engines(key, EngineCapacity.floor(max(cap, self.cap), P, key[2], key[3]))[s % self.n]
+            key, P, W, H = self._unit_key(unit, K, aux)
+            e = self._engines(key, EngineCapacity.floor(max(cap, self.cap), P, W, H))[s % self.n]
             st = self.streams[s % self.n]
             st.wait_stream(cur)                                  # the jobs' tensors were produced on the caller's stream
             with torch.cuda.stream(st):
@@ -318,22 +354,8 @@ class FrameAnimator:
         K = max(1, min(int(frames_per_launch), 16))
 
         def launch(e, batch):
-            k = len(batch)
-            cams = [j[0] for j in batch]
-            A = torch.stack([j[1].reshape(-1, 16) for j in batch] + [batch[-1][1].reshape(-1, 16)] * (K - k)).contiguous()
-            tr = None
-            if batch[0][2] is not None:
-                tr = torch.stack([j[2].reshape(3) for j in batch] + [batch[-1][2].reshape(3)] * (K - k)).contiguous()
-            sc = None if batch[0][3] is None else _batch_rows([j[3] for j in batch], K, 1)
-            ext = None
-            if batch[0][4] is not None:
-                ext = tuple(_batch_rows([j[4][n] for j in batch], K, w) for n, w in enumerate((3, 9, 1)))
-            rs = _settings(cams[0], bg_color, scaling_modifier, c['active_sh_degree'])
-            if any(cm is not cams[0] for cm in cams):            # per-frame cameras: stacked [K,4,4] / [K,3]
-                pad = cams + [cams[-1]] * (K - k)
-                rs = rs._replace(viewmatrix=torch.stack([cm['world_view_transform'] for cm in pad]).contiguous(),
-                                 projmatrix=torch.stack([cm['full_proj_transform'] for cm in pad]).contiguous(),
-                                 campos=torch.stack([cm['camera_center'] for cm in pad]).contiguous())
+            A, tr, sc, ext = _stack_poses([j[1:] for j in batch], K)
+            rs = _stack_cameras([j[0] for j in batch], K, bg_color, scaling_modifier, c['active_sh_degree'])
             e.set_camera(rs, long_rows=self.long_rows)
             e.set_frames(c['xyz_canon'], c.get('rotmat_canon'), c['lbs_weights'], A, sc, tr, ext)
             e.forward(c['shs'], c['opacity'], c['scales'])
