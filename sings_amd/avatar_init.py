@@ -18,8 +18,8 @@ import numpy as np
 import torch
 
 from . import _marshal
-from . import decode as _dec
 from . import rotations as _rot
+from .grad_arena import set_gradient_arena
 from .optim import FusedAdam
 from .photo_loss import _is_unit
 from .topology import MeshState
@@ -320,7 +320,7 @@ def fit_initial_attributes(module, targets, lrs, init_steps=500, patience=100, f
         params = [p for g in opt.param_groups for p in g["params"]]
         flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
         try:
-            opt.bind_arena(flat, _dec.set_gradient_arena(params, flat))
+            opt.bind_arena(flat, set_gradient_arena(params, flat))
             engine = AttrMSEEngine(N, dev, keys)
             plateau = DevicePlateau([g["lr"] for g in groups], dev, patience=patience, factor=factor, log_steps=steps, n_terms=7)
 
@@ -357,7 +357,7 @@ def fit_initial_attributes(module, targets, lrs, init_steps=500, patience=100, f
             graph = None
             for p in params:
                 p.grad = None
-            _dec.set_gradient_arena(None, None)
+            set_gradient_arena(None, None)
     base = np.array([g["lr"] for g in groups], np.float64)
     cols = [ATTR_KEYS.index(k) for k in keys] + [6]
     return {"keys": ["loss_" + k for k in keys] + ["loss"], "losses": log[:, cols].astype(np.float32), "lr_steps": mult_steps * base,

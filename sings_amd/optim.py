@@ -4,8 +4,8 @@ reference's two learning-rate schedules (utils/general.py:76-126) as plain host 
 
 What the launch reads:
 
-    the flat fp32 gradient arena           ``decode.set_gradient_arena``: the big gradients are written there by the kernels that produce
-                                           them, the small ones are copied in by ``decode.arena_sync``
+    the flat fp32 gradient arena           ``grad_arena.set_gradient_arena``: the big gradients are written there by the kernels that produce
+                                           them, the small ones are copied in by ``grad_arena.arena_sync``
     two flat moment buffers                ``exp_avg`` / ``exp_avg_sq`` with the arena's layout (a feature-minor plane is walked in
                                            memory order in all four arrays)
     a segment and a chunk table            one record per parameter tensor / per 4 096 consecutive elements of one tensor
@@ -23,8 +23,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import decode as _dec
 from ._marshal import adam_step as _adam_step
+from .grad_arena import arena_sync, is_feature_minor, like_layout
 
 HYPER_COLUMNS = 8                        # floats per group row (six used)
 _RING = 64                               # pinned copies of the table in flight before advance() would have to wait for one
@@ -106,12 +106,12 @@ class FusedAdam:
     """``torch.optim.Adam`` (no weight decay, no amsgrad, not maximize) for GPU fp32 parameters whose gradients live in a flat arena.
 
     ``param_groups``: dicts with ``params``, ``lr`` and ``name`` (as ``AvatarTrainer`` builds them); ``param_groups[i]["lr"]`` may be
-    assigned before every step.  ``grad_flat`` / ``grad_views``: the arena and what ``decode.set_gradient_arena`` returned for the same
+    assigned before every step.  ``grad_flat`` / ``grad_views``: the arena and what ``grad_arena.set_gradient_arena`` returned for the same
     parameters in the same order (``None``: bound later with ``bind_arena``).
 
         advance()    host half, once per step: step counts, the [G][8] table into a pinned buffer, its copy enqueued on the current
                      stream.  Never synchronises (a ring of pinned buffers; the host would have to run 64 steps ahead of the GPU).
-        apply()      device half, capturable: ``decode.arena_sync(params, views, True)``, then the one launch
+        apply()      device half, capturable: ``grad_arena.arena_sync(params, views, True)``, then the one launch
         step()       advance(); apply()
     """
 
@@ -164,7 +164,7 @@ class FusedAdam:
 
     def _moment_views(self, flat):
         """Per-parameter views of a flat moment buffer, in each parameter's own shape and memory layout."""
-        return [_dec._like_layout(flat[o:o + p.numel()], p) for o, p in zip(self._offsets(), self._params())]
+        return [like_layout(flat[o:o + p.numel()], p) for o, p in zip(self._offsets(), self._params())]
 
     def _active_groups(self):
         return None if self._active is None else {gi for gi, g in enumerate(self.param_groups) if g["name"] in self._active}
@@ -209,7 +209,7 @@ class FusedAdam:
         if len(grad_views) != len(params) or any(tuple(v.shape) != tuple(p.shape) for v, p in zip(grad_views, params)):
             raise ValueError("FusedAdam: grad_views do not match the parameters")
         for name, p in zip(self._names(), params):
-            if not (p.is_contiguous() or _dec._is_feature_minor(p)):
+            if not (p.is_contiguous() or is_feature_minor(p)):
                 raise ValueError(f"FusedAdam: parameter {name} must be contiguous (or a feature-minor tri-plane plane)")
         if self.exp_avg.numel() != n:
             raise RuntimeError("FusedAdam: the moments were not re-indexed for the new sizes (remap_rows)")
@@ -265,7 +265,7 @@ class FusedAdam:
         the arena holds e.g. all-reduced gradients), then ONE launch updates every parameter and both moments."""
         params = self._check()
         if sync:
-            _dec.arena_sync(params, self.grad_views, True)
+            arena_sync(params, self.grad_views, True)
         _adam_step(self.segments, self.chunks, self.hyper, self.grad_flat, self.exp_avg, self.exp_avg_sq)
 
     def step(self):

@@ -22,9 +22,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import decode as _dec
 from ._marshal import _ptr, _stream
 from .body import SMPL_PARENTS
+from .grad_arena import arena_out
 
 NB = _lib.POSE_NB                                          # body joints per row of the body_pose table (SMPL's 23)
 _LAYOUT = {"smpl": (24, 23), "smplh": (52, 21)}            # body -> (J, NBu: body joints of the row the chain uses)
@@ -78,8 +78,8 @@ class _PoseTransforms(torch.autograd.Function):
         dA = dA.contiguous().float()
         want_t = ctx.needs_input_grad[2]
         # the dense gradients, straight into the parameters' slots of a registered gradient arena
-        d_go, d_bp = _dec._arena_out(global_orient), _dec._arena_out(body_pose)
-        d_t = _dec._arena_out(transl) if want_t else None
+        d_go, d_bp = arena_out(global_orient), arena_out(body_pose)
+        d_t = arena_out(transl) if want_t else None
         d_rows = d_rows.contiguous().float() if want_t else None
         with torch.cuda.device(dev):
             _lib.check(lib.sg_pose_transforms_backward(K, F, table.J, table.NBu, _ptr(frame_idx), _ptr(global_orient), _ptr(body_pose),

@@ -20,7 +20,7 @@ For the hot path what matters is THAT the set changes: P(t) != P(t-1).
 A topology change (or a new SH degree) invalidates everything that was sized or captured for the old set:
 
     the captured HIP graph          ``CapturedStep.replay`` raises until ``AvatarTrainer`` has captured the step again
-    the gradient arena              ``decode.arena_sync`` raises for a stale registration; the trainer registers the new parameters
+    the gradient arena              ``grad_arena.arena_sync`` raises for a stale registration; the trainer registers the new parameters
     the pair-capacity hint          re-measured with synchronous steps before the overflow check is deferred again
     Adam's moments, the statistics  ONE row map ``src`` per change (``_replace_set``): new row i takes its moments (``prune_and_simplify``: its
                                     statistics too) from old row ``src[i]`` or, at -1, starts at zero (``optim.take_rows``), as the reference does
@@ -36,10 +36,10 @@ import os
 import torch
 
 from . import checkpoint as _ckpt
-from . import decode as _dec
 from . import overflow
 from . import topology as _topo
 from .avatar_init import initial_attributes
+from .grad_arena import arena_sync, set_gradient_arena
 from .optim import FusedAdam, take_rows
 from .step_inputs import StepInputs, preserved
 from .train_step import capture_step
@@ -233,7 +233,7 @@ class AvatarTrainer:
         if self.fp is not None or self.fused:
             n = sum(p.numel() for p in self.params)
             self.flat = torch.zeros(n, dtype=torch.float32, device=self.dev)
-            self.views = _dec.set_gradient_arena(self.params, self.flat)
+            self.views = set_gradient_arena(self.params, self.flat)
         if self.fused:
             self.opt.bind_arena(self.flat, self.views)
         if self.mesh_terms is not None:
@@ -495,9 +495,9 @@ class AvatarTrainer:
             ld = self._body()                                    # eager (and the synchronous sizing steps in front of a capture)
             self._sizing = max(0, self._sizing - 1)
         if self.fp is not None:
-            _dec.arena_sync(self.params, self.views, True)
+            arena_sync(self.params, self.views, True)
             self.fp.all_reduce_grads(self.flat)
-            _dec.arena_sync(self.params, self.views, False)
+            arena_sync(self.params, self.views, False)
             if self.fused:
                 self.opt.apply(sync=False)                       # (the arena holds the reduced gradients)
         if not self.fused:

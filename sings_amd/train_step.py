@@ -1,7 +1,7 @@
 """One SinGS training step on one posed frame, composed from the library's pieces (what ``scripts/train_avatar.py`` ->
 ``GaussianTrainer.train`` does per iteration, SURVEY.md 3.1, without the optimiser / densification bookkeeping):
 
-    decode_attributes (tri-plane + decoders)          sings_hybrid.py:249-313      sings_amd/decode.py
+    decode_attributes (tri-plane + decoders)          sings_hybrid.py:249-313      sings_amd/decode.py (triplane.py, linear_layers.py)
     fused LBS + projection + binning + composite      sings_hybrid.py:398-428, gs_renderer_single.py:12-107   sings_amd/skinned.py
     clamp + L1 + SSIM                                 losses/loss.py:55-69         sings_amd/photo_loss.py
     LPIPS-VGG patch term (optional)                   losses/loss.py:71-80         sings_amd/lpips.py
@@ -23,15 +23,16 @@ gradients -- computed by its kernel with the value, in front of the query on the
 and the decoders' backward starts from the sums.  The k-NN regulariser's gradient (scales only) enters at an identity node placed on
 the geometry decoder's outputs BEFORE the appearance decoder is issued: autograd visits the youngest nodes first, so the appearance
 decoder's backward is issued -- and runs beside the query -- before the main stream waits for the side stream at that node.  The
-order of the launches is then the order the graph executor needs to keep the critical chain on ONE queue (sings_amd/decode.py
+order of the launches is then the order the graph executor needs to keep the critical chain on ONE queue (sings_amd/side_launch.py
 "capture order"; 2.18 -> 1.97-2.05 ms per step with the deferred weight gradients, profiles/r05_graph_queues.log).
 """
 import torch
 
-from . import decode as _dec
 from .decode import decode_attributes
+from .grad_arena import invalidate_gradient_arena
 from .lpips import lpips_patch_loss
 from .photo_loss import photometric_loss, photometric_loss_frames
+from .side_launch import flush_triplane_prepare, reset_deferred, triplane_prepare_held
 from .skinned import rasterize_skinned_frames, rasterize_skinned_gaussians
 
 
@@ -233,7 +234,7 @@ class AvatarStep(torch.nn.Module):
         elif torch.is_tensor(self.scaling_multiplier) and self.scaling_multiplier.dim() > 0 and self.scaling_multiplier.shape[0] != xyz_anchor.shape[0]:
             raise ValueError("set_topology: the per-Gaussian scaling_multiplier must be passed for the new set")
         self.topology_version += 1
-        _dec.invalidate_gradient_arena()
+        invalidate_gradient_arena()
         if self.xyz_gradient_accum is not None:
             self.enable_densification_stats()
 
@@ -313,20 +314,15 @@ class AvatarStep(torch.nn.Module):
                  and hasattr(self.gaussian_connect, "prepare"))
         inject = {} if defer else None                           # the k-NN regulariser's gradient (scales only: its edge lengths are
         hook = (lambda x, sc: (x, _Inject.apply(sc, inject, "scales"))) if defer else None          # detached, loss_items.py:75)
-        # the tri-plane backward's point sorts (decode.py: "the point-only half ... early") are held back: beside the first decoder
+        # the tri-plane backward's point sorts (side_launch.py: "the point-only half ... early") are held back: beside the first decoder
         # layers they cost the forward chain ~70 us (the first layer: 121 instead of 53 us); here they are issued on the regularisers'
         # stream behind the k-NN query, long before the tri-plane backward needs them
-        late_prev = _dec._TP["late"]
-        _dec._TP["late"] = bool(defer)
-        del _dec._TP_PENDING[:]                                  # (a preparation left behind by a forward that raised)
-        try:
+        with triplane_prepare_held(defer):                       # (also drops a preparation left behind by a forward that raised)
             attrs = self.decode(geometry_hook=hook, opt_geo=self.opt_geo, opt_app=self.opt_app)
-        finally:
-            _dec._TP["late"] = late_prev
         # Two roots (defer): the render and the regularisers read DETACHED views of the decoded attributes (`use`), so that the
         # backward pass can be staged by hand (AvatarStep.backward): photometric gradients on this stream, the regularisers' on the
         # side stream, one addition, then the decoders' backward -- in an order the graph executor turns into ONE queue for the
-        # critical chain (sings_amd/decode.py "capture order").  One root: `use` IS `attrs`, plain autograd.
+        # critical chain (sings_amd/side_launch.py "capture order").  One root: `use` IS `attrs`, plain autograd.
         use = attrs
         if defer:
             use = {k: (v.detach().requires_grad_(v.requires_grad) if torch.is_tensor(v) else v) for k, v in attrs.items()}
@@ -407,7 +403,7 @@ class AvatarStep(torch.nn.Module):
         """The two-roots tail of ``forward``, no join: the regularisers' gradients are waited for where they are consumed
         (``AvatarStep.backward``).  ``decoded`` / ``rendered``: the main stream's events behind the decode and the raster forward."""
         photo_root = _sum_terms(loss_dict)
-        # the regularisers, ISSUED last (the main chain keeps its queue in the graph executor, sings_amd/decode.py "capture
+        # the regularisers, ISSUED last (the main chain keeps its queue in the graph executor, sings_amd/side_launch.py "capture
         # order") but waiting only for what they read: L2Norm and the k-NN grids for the decode, the k-NN QUERY -- 9 waves per
         # SIMD on every CU for 0.23 ms -- for the raster forward.  (Measured, profiles/r05_graph_queues.log: the executor starts
         # a second queue's chain 60-160 us after its dependency is met, so part of the query is still exposed behind the
@@ -445,7 +441,7 @@ class AvatarStep(torch.nn.Module):
             reg_root = edge.reshape(())
             inject["ready"] = torch.cuda.Event()
             inject["ready"].record(side)
-            _dec.flush_triplane_prepare(side)                # (same stream, behind the query: executed in this order)
+            flush_triplane_prepare(side)                # (same stream, behind the query: executed in this order)
         loss_dict.update(reg)
         extras["loss_roots"] = (photo_root, reg_root)
         extras["staged"] = (attrs, use, inject, l2_grads)
@@ -480,7 +476,7 @@ class AvatarStep(torch.nn.Module):
         try:
             return self._backward_staged(loss_dict, extras)
         except BaseException:
-            _dec.reset_deferred()                                # (closures with raw gradient pointers must not outlive the pass)
+            reset_deferred()                                # (closures with raw gradient pointers must not outlive the pass)
             raise
 
     def _backward_staged(self, loss_dict, extras):

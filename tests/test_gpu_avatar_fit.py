@@ -62,7 +62,7 @@ def _twin(module, targets, steps, patience):
 @pytest.fixture(scope="module")
 def runs():
     """The three runs from identically initialised modules, computed once."""
-    from sings_amd import avatar_init, decode
+    from sings_amd import avatar_init, grad_arena
     out = {}
     seen, made = [], []
     real_capture, real_adam = avatar_init.capture_step, avatar_init.FusedAdam
@@ -85,7 +85,7 @@ def runs():
             module, mesh, targets = _sphere_module()
             before = [p.detach().clone() for p in module.parameters() if p.requires_grad]
             res = avatar_init.fit_initial_attributes(module, targets, FIT_LRS, init_steps=STEPS, patience=PATIENCE, use_graph=use_graph)
-            out[name] = dict(res=res, module=module, before=before, arena=(dict(decode._ARENA), decode._ARENA_REG["params"]))
+            out[name] = dict(res=res, module=module, before=before, arena=grad_arena.arena_registration())
     finally:
         avatar_init.capture_step, avatar_init.FusedAdam = real_capture, real_adam
     module, mesh, targets = _sphere_module()
@@ -116,7 +116,7 @@ def test_fit_eager_graph_and_torch_twin_agree(runs):
 
 
 def test_fit_leaves_a_fitted_module_and_nothing_else(runs):
-    from sings_amd import decode
+    from sings_amd import grad_arena
     for name in ("eager", "graph"):
         r = runs[name]
         after = [p for p in r["module"].parameters() if p.requires_grad]
@@ -125,7 +125,7 @@ def test_fit_leaves_a_fitted_module_and_nothing_else(runs):
         assert all(moved), name                                         # every group moved, the anchors included
         assert all(p.grad is None for p in after)
         assert r["arena"] == ({}, None)                                 # decode has no arena set
-    assert decode._ARENA == {} and decode._ARENA_REG["params"] is None
+    assert grad_arena.arena_registration() == ({}, None)
     # the capture saw only detached tensors (2 warm-up runs and the capture itself)
     assert runs["captured_outputs_with_graph"] == [0, 0, 0]
     # the optimiser the fit used, and with it the moments, is gone

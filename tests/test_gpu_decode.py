@@ -472,7 +472,7 @@ def test_triplane_backward_prepared_early_or_inline():
         decode.prepare_triplane_backward_early(True)
         dx1, dp1 = grads()
     finally:
-        decode._TP["mode"] = None
+        decode.prepare_triplane_backward_early(None)
     assert torch.equal(dx0, dx1)
     for a, b in zip(dp0, dp1):
         _close(a.cpu().numpy(), b.cpu().numpy(), rtol=1e-4, atol_scale=2e-6, what="plane gradient")
@@ -526,7 +526,7 @@ def test_feature_minor_planes_are_used_in_place(early, arena):
         dx0, dp0 = grads(f0)
         dx1, dp1 = grads(f1)
     finally:
-        decode._TP["mode"] = None
+        decode.prepare_triplane_backward_early(None)
     assert torch.equal(dx0, dx1)
     for a, b, p in zip(dp0, dp1, planes1):
         assert b.shape == a.shape and b.stride() == p.stride()

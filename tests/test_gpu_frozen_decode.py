@@ -138,7 +138,7 @@ def _field(dev, feature_minor=False):
 
 @pytest.mark.parametrize("iso, fixed_opacity", [(True, False), (False, False), (True, True)])
 def test_decode_frozen_applies_thickness_and_multiplier_like_decode_attributes(iso, fixed_opacity):
-    from sings_amd import decode
+    from sings_amd import decode, side_launch
     dev = _dev()
     N = 3 * R + 5
     g, a, sdg, sda = _decoders(dev, iso, fixed_opacity)
@@ -151,7 +151,7 @@ def test_decode_frozen_applies_thickness_and_multiplier_like_decode_attributes(i
     got = decode.decode_frozen(xyz, f, g, a, thickness_factor=0.7, scaling_multiplier=sm)
     slow = decode.decode_frozen(xyz, f, g, a, thickness_factor=0.7, scaling_multiplier=sm, fused=False)
     assert set(got) == set(want) == set(slow)
-    assert not decode._TP_PENDING
+    assert not side_launch.pending()[1]
     # fp64: the features from the oracle's lookup, the decoders on them
     feats = do.triplane_features(xyz.cpu().double(), [[p.detach().cpu().double() for p in gp] for gp in f.grids], f.aabb.detach().cpu().double())
     og = do.geometry_decoder(feats, sdg, isotropic=iso)
@@ -187,7 +187,7 @@ def _weighted_sum(out, w):
 @pytest.mark.parametrize("feature_minor", [False, True])
 @pytest.mark.parametrize("opt_geo, opt_app", [(False, False), (False, True), (True, False)])
 def test_flags_values_and_gradients(opt_geo, opt_app, feature_minor):
-    from sings_amd import decode
+    from sings_amd import decode, side_launch
     from sings_amd.decode import AppearanceDecoder, GeometryDecoder
     dev = _dev()
     N = 3 * R + 5
@@ -200,19 +200,15 @@ def test_flags_values_and_gradients(opt_geo, opt_app, feature_minor):
     w = _weights(N, dev)
     with torch.no_grad():
         full = decode.decode_attributes(xyz, f, g, a, thickness_factor=0.7)
-    del decode._TP_PENDING[:]
-    decode.prepare_triplane_backward_late(True)                          # (as the training step decodes: a preparation would be QUEUED)
-    try:
+    with side_launch.triplane_prepare_held(True):                        # (as the training step decodes: a preparation would be QUEUED)
         out = decode.decode_attributes(xyz, f, g, a, thickness_factor=0.7, opt_geo=opt_geo, opt_app=opt_app)
-    finally:
-        decode.prepare_triplane_backward_late(False)
     for k in OUT_KEYS:
         _close(_np(out[k]), _np(full[k]), what=f"flags ({opt_geo}, {opt_app}) {k} vs the unfrozen call")
     frozen_keys = (() if opt_geo else ("xyz_offsets", "rot6d_canon", "scales_aux", "scales")) + (() if opt_app else ("opacity", "shs"))
     for k in OUT_KEYS:
         assert out[k].requires_grad == (k not in frozen_keys), k          # (xyz_canon = xyz + offsets keeps the gradient to xyz)
     if not (opt_geo or opt_app):
-        assert not decode._TP_PENDING, "a tri-plane backward preparation was queued for a lookup nobody differentiates"
+        assert not side_launch.pending()[1], "a tri-plane backward preparation was queued for a lookup nobody differentiates"
     _weighted_sum(out, w).backward()
     # ---- fp64 autograd over the oracle, the frozen decoder under no_grad: the reference's literal construct
     x64 = xyz.detach().cpu().double().requires_grad_(True)
@@ -258,4 +254,4 @@ def test_flags_values_and_gradients(opt_geo, opt_app, feature_minor):
                 _close(_np(p.grad), sd[k].grad.numpy(), atol_scale=2e-5, atol=2e-5, what=f"parameter gradient {k}")
             else:
                 assert p.grad is None and sd[k].grad is None, k
-    assert not decode._TP_PENDING
+    assert not side_launch.pending()[1]

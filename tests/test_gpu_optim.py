@@ -31,6 +31,7 @@ class _Run:
 
     def __init__(self, dev, spec, p0, n_groups=4, p_from=None):
         from sings_amd import decode
+        from sings_amd.grad_arena import is_feature_minor
         from sings_amd.optim import FusedAdam
         self.dev, self.spec = dev, spec
         self.params, self.offsets, self.align = [], [], []
@@ -43,7 +44,7 @@ class _Run:
                 cfg = {'grid_dimensions': 2, 'input_coordinate_dim': 3, 'output_coordinate_dim': shape[1], 'resolution': [shape[3]] * 3,
                        'multires': [1]}
                 p = decode.HexPlaneField(cfg, device=dev, feature_minor=True).grids[0][0]
-                assert tuple(p.shape) == tuple(shape) and decode._is_feature_minor(p)
+                assert tuple(p.shape) == tuple(shape) and is_feature_minor(p)
                 with torch.no_grad():
                     p.copy_(vals)
             elif kind == "plain":

@@ -452,7 +452,7 @@ def test_a_backward_that_raises_leaves_no_deferred_launch_behind():
     gradient tensors; a pass that RAISES half-way (here: a tensor hook on a first-layer weight, reached after most layers have
     deferred theirs) must not leave them for the next pass: `AvatarStep.backward` resets the deferred state, and the next step's
     gradients equal an undisturbed step's, with the weight gradients on their side stream."""
-    from sings_amd import decode
+    from sings_amd import decode, side_launch
     from sings_amd.body import joint_transforms
     from sings_amd.decode import AppearanceDecoder, GeometryDecoder, HexPlaneField
     from sings_amd.rasterizer import GaussianRasterizationSettings
@@ -496,7 +496,7 @@ def test_a_backward_that_raises_leaves_no_deferred_launch_behind():
         with pytest.raises(RuntimeError, match="hook"):
             run()
         h.remove()
-        assert not decode._DEFER and not decode._TP_PENDING and not decode._WG["armed"]
+        assert side_launch.pending() == (0, 0, False)
         torch.cuda.synchronize()
         l1, g1 = run()
         assert abs(l1 - l0) <= 1e-6 * abs(l0)

@@ -21,7 +21,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import torch                                                      # noqa: E402
 
 from density_stats_time import build_trainer, warm_up            # noqa: E402
-from sings_amd import decode, overflow                            # noqa: E402
+from sings_amd import grad_arena, overflow                        # noqa: E402
 
 
 def timed(fn):
@@ -63,7 +63,7 @@ def main():
         out.update({k: stats(v) for k, v in ms.items()})
     finally:
         overflow.set_overflow_check("sync"); overflow.reset_overflow_state()
-        decode.set_gradient_arena(None, None)
+        grad_arena.set_gradient_arena(None, None)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)

@@ -31,7 +31,7 @@ sys.path.insert(0, ROOT)
 import numpy as np                                                # noqa: E402
 import torch                                                      # noqa: E402
 
-from sings_amd import decode, overflow                            # noqa: E402
+from sings_amd import grad_arena, overflow                        # noqa: E402
 from sings_amd.decode import AppearanceDecoder, GeometryDecoder, HexPlaneField      # noqa: E402
 from sings_amd.density import densify_stats                       # noqa: E402
 from sings_amd.pose import PoseTable                              # noqa: E402
@@ -212,10 +212,10 @@ def main():
                         "open_against_closed": verdict(ms["fused_closed"], ms["fused_open"])}
                     del tr, step
                     overflow.set_overflow_check("sync"); overflow.reset_overflow_state()
-                    decode.set_gradient_arena(None, None)
+                    grad_arena.set_gradient_arena(None, None)
         finally:
             overflow.set_overflow_check("sync"); overflow.reset_overflow_state()
-            decode.set_gradient_arena(None, None)
+            grad_arena.set_gradient_arena(None, None)
     dump()
     print(json.dumps(out))
 

@@ -34,7 +34,7 @@ sys.path.insert(0, ROOT)
 import numpy as np                                                # noqa: E402
 import torch                                                      # noqa: E402
 
-from sings_amd import decode, overflow                            # noqa: E402
+from sings_amd import grad_arena, overflow                        # noqa: E402
 from sings_amd.decode import AppearanceDecoder, GeometryDecoder, HexPlaneField      # noqa: E402
 from sings_amd.frame_feed import MAX_FRAMES, FrameFeed, FrameStore                  # noqa: E402
 from sings_amd.pose import PoseTable                              # noqa: E402
@@ -205,12 +205,12 @@ def main():
                     steps[k] += [wall_block(step, a.steps) for _ in range(a.reps)]
                     del tr, step
                     overflow.set_overflow_check("sync"); overflow.reset_overflow_state()
-                    decode.set_gradient_arena(None, None)
+                    grad_arena.set_gradient_arena(None, None)
             out["captured_step_wall_ms"] = {k: stats(x) for k, x in steps.items()}
             out["captured_step_frames_against_next"] = verdict(steps["step_next"], steps["step_frames_fp32_cache"])
         finally:
             overflow.set_overflow_check("sync"); overflow.reset_overflow_state()
-            decode.set_gradient_arena(None, None)
+            grad_arena.set_gradient_arena(None, None)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)

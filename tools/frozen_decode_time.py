@@ -26,7 +26,7 @@ sys.path.insert(0, ROOT)
 import numpy as np                                                # noqa: E402
 import torch                                                      # noqa: E402
 
-from sings_amd import decode, overflow                            # noqa: E402
+from sings_amd import decode, grad_arena, overflow                # noqa: E402
 from sings_amd.decode import AppearanceDecoder, GeometryDecoder, HexPlaneField      # noqa: E402
 from sings_amd.rasterizer import GaussianRasterizationSettings   # noqa: E402
 from sings_amd.regularizers import GaussiansEdgeLoss, L2Norm      # noqa: E402
@@ -156,12 +156,12 @@ def main():
                         steps[k] += [block(lambda: tr.step(A, gt, mask), a.steps) for _ in range(a.reps)]
                         del tr
                         overflow.set_overflow_check("sync"); overflow.reset_overflow_state()
-                        decode.set_gradient_arena(None, None)
+                        grad_arena.set_gradient_arena(None, None)
                 res["captured_step_ms"] = {k: stats(v) for k, v in steps.items()}
                 res["captured_step_frozen_against_unfrozen"] = verdict(steps["frozen"], steps["unfrozen"])
             finally:
                 overflow.set_overflow_check("sync"); overflow.reset_overflow_state()
-                decode.set_gradient_arena(None, None)
+                grad_arena.set_gradient_arena(None, None)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)

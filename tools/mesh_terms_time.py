@@ -31,7 +31,7 @@ import numpy as np                                                # noqa: E402
 import torch                                                      # noqa: E402
 
 from mesh_case import bumpy_sphere                                # noqa: E402
-from sings_amd import avatar_init, decode, overflow, topology     # noqa: E402
+from sings_amd import avatar_init, grad_arena, overflow, topology # noqa: E402
 from sings_amd.decode import AppearanceDecoder, GeometryDecoder, HexPlaneField      # noqa: E402
 from sings_amd.mesh_terms import MeshTerms                        # noqa: E402
 from sings_amd.rasterizer import GaussianRasterizationSettings   # noqa: E402
@@ -201,12 +201,12 @@ def main():
                     steps[k] += [block(lambda: tr.step(A, gt, mask), a.steps) for _ in range(a.reps)]
                     del tr
                     overflow.set_overflow_check("sync"); overflow.reset_overflow_state()
-                    decode.set_gradient_arena(None, None)
+                    grad_arena.set_gradient_arena(None, None)
             out["captured_step_ms"] = {k: stats(x) for k, x in steps.items()}
             out["captured_step_terms_cost"] = verdict(steps["without"], steps["with_mesh_terms"])
         finally:
             overflow.set_overflow_check("sync"); overflow.reset_overflow_state()
-            decode.set_gradient_arena(None, None)
+            grad_arena.set_gradient_arena(None, None)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)

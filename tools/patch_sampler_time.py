@@ -33,7 +33,7 @@ import numpy as np                                                # noqa: E402
 import torch                                                      # noqa: E402
 
 import lpips_case as lc                                           # noqa: E402
-from sings_amd import decode, overflow                            # noqa: E402
+from sings_amd import grad_arena, overflow                        # noqa: E402
 from sings_amd.decode import AppearanceDecoder, GeometryDecoder, HexPlaneField      # noqa: E402
 from sings_amd.lpips import LPIPS, PatchSampler                   # noqa: E402
 from sings_amd.patch_sampler import DevicePatchSampler            # noqa: E402
@@ -167,12 +167,12 @@ def main():
                     steps[k] += [wall_block(step, a.steps) for _ in range(a.reps)]
                     del tr, step
                     overflow.set_overflow_check("sync"); overflow.reset_overflow_state()
-                    decode.set_gradient_arena(None, None)
+                    grad_arena.set_gradient_arena(None, None)
             out["captured_step_wall_ms"] = {k: stats(x) for k, x in steps.items()}
             out["captured_step_host_against_device"] = verdict(steps["device_sampler"], steps["host_sampler"])
         finally:
             overflow.set_overflow_check("sync"); overflow.reset_overflow_state()
-            decode.set_gradient_arena(None, None)
+            grad_arena.set_gradient_arena(None, None)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)
