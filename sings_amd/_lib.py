@@ -22,6 +22,7 @@ HAS_FEED = False                     # set by load(): the library exports the ta
 HAS_DENSITY = False                  # set by load(): the library exports the table of include/sings_density.h
 HAS_SHEET = False                    # set by load(): the library exports the table of include/sings_sheet.h
 HAS_SCENE = False                    # set by load(): the library exports the table of include/sings_scene.h
+HAS_JPEG = False                     # set by load(): the library exports the table of include/sings_jpeg.h
 
 
 class SgRasterSettings(C.Structure):
@@ -231,6 +232,11 @@ _PROTOTYPES_SCENE = {
     "sg_scene_forward_frames": "i: S i3 A p2 z p6 n p",
     "sg_scene_forward_frames_aux": "i: S i3 A p2 z p6 n p4",
 }
+# Frames to JPEG files, include/sings_jpeg.h: an eleventh header and an eleventh table, for the same reason.
+_PROTOTYPES_JPEG = {
+    "sg_jpeg_layout": "i: i5 Z",
+    "sg_jpeg_encode_frames": "i: i5 p3 i p z p z p2",
+}
 _P = C.POINTER
 _CTYPE = {"i": C.c_int, "z": C.c_size_t, "f": C.c_float, "s": C.c_char_p,
           "p": C.c_void_p,                        # a raw device pointer (or NULL), and the stream
@@ -267,6 +273,12 @@ DENSITY_BLOCK = 256                  # SG_DENSITY_BLOCK: Gaussians per workgroup
 SHEET_TRUNC, SHEET_ROUND = 0, 1      # SG_SHEET_TRUNC, SG_SHEET_ROUND
 SHEET_MAX_SHEETS = 65535             # SG_SHEET_MAX_SHEETS
 SHEET_BLOCK = 256                    # SG_SHEET_BLOCK: threads per workgroup, 4 pixels of a sheet each
+JPEG_MAX_FRAMES = 16                 # SG_JPEG_MAX_FRAMES
+JPEG_MAX_DIM = 65535                 # SG_JPEG_MAX_DIM
+JPEG_TABLE_WORDS = 800               # SG_JPEG_TABLE_WORDS
+JPEG_HUFF_STRIDE = 272               # SG_JPEG_HUFF_STRIDE
+JPEG_MCU_BYTES = 1248                # SG_JPEG_MCU_BYTES
+JPEG_LAYOUT = ("ws_bytes", "mcus", "segments", "slot_pitch", "worst_bytes", "default_capacity")      # SG_JPEG_L_*, SG_JPEG_LAYOUT_WORDS
 FROZEN_BLOCK = 128                   # SG_FROZEN_BLOCK: points per workgroup of the fused no-gradient decode
 FROZEN_SHS = 48                      # SG_FROZEN_SHS
 MESH_TERMS_INFO_INTS = 2             # SG_MESH_TERMS_INFO_INTS
@@ -312,7 +324,7 @@ def load():
                            "(include/sings_hip.h SG_ABI_VERSION): rebuild with `make -C sings_amd/csrc`")
     # (SINGS_HIP_LIB may name a library that predates include/sings_order.h -- an A/B run against a parent build: it exports none of
     # that table, HAS_ORDER says so, and the engines then make the unordered calls that library knows)
-    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN, HAS_FEED, HAS_DENSITY, HAS_SHEET, HAS_SCENE
+    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN, HAS_FEED, HAS_DENSITY, HAS_SHEET, HAS_SCENE, HAS_JPEG
     HAS_ORDER = all(hasattr(lib, name) for name in _PROTOTYPES_ORDER)
     HAS_SAMPLER = all(hasattr(lib, name) for name in _PROTOTYPES_SAMPLER)    # (the same, for include/sings_sampler.h)
     HAS_FROZEN = all(hasattr(lib, name) for name in _PROTOTYPES_FROZEN)      # (the same, for include/sings_frozen.h)
@@ -320,9 +332,10 @@ def load():
     HAS_DENSITY = all(hasattr(lib, name) for name in _PROTOTYPES_DENSITY)    # (the same, for include/sings_density.h)
     HAS_SHEET = all(hasattr(lib, name) for name in _PROTOTYPES_SHEET)        # (the same, for include/sings_sheet.h)
     HAS_SCENE = all(hasattr(lib, name) for name in _PROTOTYPES_SCENE)        # (the same, for include/sings_scene.h)
+    HAS_JPEG = all(hasattr(lib, name) for name in _PROTOTYPES_JPEG)          # (the same, for include/sings_jpeg.h)
     for has, header in ((HAS_ORDER, "sings_order.h"), (HAS_SAMPLER, "sings_sampler.h"), (HAS_FROZEN, "sings_frozen.h"),
                         (HAS_FEED, "sings_feed.h"), (HAS_DENSITY, "sings_density.h"), (HAS_SHEET, "sings_sheet.h"),
-                        (HAS_SCENE, "sings_scene.h")):
+                        (HAS_SCENE, "sings_scene.h"), (HAS_JPEG, "sings_jpeg.h")):
         if not has and LIB_PATH == os.path.join(_HERE, "libsings_hip.so"):
             raise RuntimeError(f"sings_amd: {LIB_PATH} lacks the entry points of include/{header}: rebuild with `make -C sings_amd/csrc`")
     for name, signature in (*_PROTOTYPES.items(), *_PROTOTYPES_EVAL.items(), *_PROTOTYPES_MESH_TERMS.items(),
@@ -330,7 +343,8 @@ def load():
                             *(_PROTOTYPES_FROZEN.items() if HAS_FROZEN else ()), *(_PROTOTYPES_FEED.items() if HAS_FEED else ()),
                             *(_PROTOTYPES_DENSITY.items() if HAS_DENSITY else ()),
                             *(_PROTOTYPES_SHEET.items() if HAS_SHEET else ()),
-                            *(_PROTOTYPES_SCENE.items() if HAS_SCENE else ())):
+                            *(_PROTOTYPES_SCENE.items() if HAS_SCENE else ()),
+                            *(_PROTOTYPES_JPEG.items() if HAS_JPEG else ())):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = _ctypes_of(signature)
     _lib = lib

@@ -390,3 +390,41 @@ def density_stats(grad, radii, gate, accum, denom, max_radii):
     with torch.cuda.device(dev):
         _lib.check(lib.sg_density_stats(K, N, _ptr(grad), _ptr(radii), _ptr(gate), _ptr(accum), _ptr(denom), _ptr(max_radii),
                                         _stream(dev)), "sg_density_stats")
+
+
+# ---- frames to JPEG files (csrc/sg_jpeg.hip)
+def _jpeg_lib():
+    lib = _lib.load()
+    if not _lib.HAS_JPEG:
+        raise RuntimeError("the loaded library predates include/sings_jpeg.h (no fallback): rebuild it")
+    return lib
+
+
+def jpeg_layout(W, H, K, restart_interval, header_bytes):
+    """``sg_jpeg_layout`` -> dict of ``_lib.JPEG_LAYOUT``: the workspace bytes of K frames, MCUs and restart segments per frame, the
+    bytes of a segment's slot, the largest file a frame can become and the default capacity."""
+    out = (C.c_size_t * len(_lib.JPEG_LAYOUT))()
+    _lib.check(_jpeg_lib().sg_jpeg_layout(int(W), int(H), int(K), int(restart_interval), int(header_bytes), out), "sg_jpeg_layout")
+    return {name: int(v) for name, v in zip(_lib.JPEG_LAYOUT, out)}
+
+
+def jpeg_encode_frames(K, W, H, restart_interval, bgr, frames, tables, header, ws, out, capacity, sizes, stream):
+    """``sg_jpeg_encode_frames`` on ``stream`` (a torch stream): ``frames`` uint8 [K,H,W,3]; ``tables`` ``_lib.JPEG_TABLE_WORDS`` int32
+    words and ``header`` uint8, the caller's (``sings_amd.video``); ``ws`` uint8, ``jpeg_layout``'s ``ws_bytes``; ``out`` uint8 rows of
+    ``capacity`` bytes (its row pitch) and ``sizes`` int32 [K].  Nothing is allocated here."""
+    dev = frames.device
+    for name, t, dt, least in (("frames", frames, torch.uint8, int(K) * int(H) * int(W) * 3), ("tables", tables, torch.int32, _lib.JPEG_TABLE_WORDS),
+                               ("header", header, torch.uint8, 1), ("ws", ws, torch.uint8, 1),
+                               ("out", out, torch.uint8, (int(K) - 1) * int(out.stride(0)) + int(capacity)), ("sizes", sizes, torch.int32, int(K))):
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != dev or t.dtype != dt:
+            raise RuntimeError(f"jpeg_encode_frames: {name} must be a {dt} tensor on {dev} (no CPU fallback)")
+        if name != "out" and not t.is_contiguous():
+            raise RuntimeError(f"jpeg_encode_frames: {name} must be contiguous")
+        if t.numel() < least and name != "out":
+            raise ValueError(f"jpeg_encode_frames: {name} holds {t.numel()} elements, {least} needed")
+    if out.dim() != 2 or out.stride(1) != 1 or out.stride(0) != int(capacity) or out.shape[0] < int(K) or out.shape[1] != int(capacity):
+        raise ValueError(f"jpeg_encode_frames: out must be [>= {int(K)}, {int(capacity)}] uint8 with rows of capacity bytes, got "
+                         f"{tuple(out.shape)} strides {tuple(out.stride())}")
+    _lib.check(_jpeg_lib().sg_jpeg_encode_frames(int(K), int(W), int(H), int(restart_interval), int(bool(bgr)), _ptr(frames), _ptr(tables),
+                                                 _ptr(header), int(header.numel()), _ptr(ws), int(ws.numel()), _ptr(out), int(capacity),
+                                                 _ptr(sizes), C.c_void_p(stream.cuda_stream)), "sg_jpeg_encode_frames")

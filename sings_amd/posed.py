@@ -128,13 +128,46 @@ def frames_to_u8(img, bgr=False):
     return out
 
 
-_OUT = {"float32": None, "rgb8": False, "bgr8": True}      # out= of the animation paths -> frames_to_u8(bgr=...)
+# out= of the animation paths -> frames_to_u8(bgr=...); "jpeg": RGB bytes, then ``video.JpegEncoder`` (a ``bytes`` per frame)
+_OUT = {"float32": None, "rgb8": False, "bgr8": True, "jpeg": False}
+JPEG_QUALITY = 90                    # of out="jpeg"; out=("jpeg", quality) names another
 
 
 def _out_bgr(out):
-    if out not in _OUT:
-        raise ValueError(f"out must be one of {sorted(_OUT)}, got {out!r}")
+    if _out_jpeg(out) is not None:
+        return _OUT["jpeg"]
+    if not isinstance(out, str) or out not in _OUT:
+        raise ValueError(f"out must be one of {sorted(_OUT)} (or (\"jpeg\", quality)), got {out!r}")
     return _OUT[out]
+
+
+def _out_jpeg(out):
+    """The JPEG quality ``out`` asks for -- "jpeg": ``JPEG_QUALITY``; ("jpeg", q): q in 1..100 -- or None for every other output."""
+    if out == "jpeg":
+        return JPEG_QUALITY
+    if isinstance(out, tuple) and len(out) == 2 and out[0] == "jpeg":
+        if not isinstance(out[1], int) or not 1 <= out[1] <= 100:
+            raise ValueError(f"out=(\"jpeg\", quality): quality must be an int in 1..100, got {out[1]!r}")
+        return out[1]
+    return None
+
+
+class _JpegOut:
+    """The ``out="jpeg"`` step behind ``frames_to_u8``: ``u8`` [k,H,W,3] RGB bytes of a batch that has been handed out -> k ``bytes``
+    (``video.JpegEncoder.encode_to_host`` on the caller's stream: one read of the sizes, one of the used bytes).  One encoder per
+    (W, H, K, quality) -- what of an engine key decides an encoder; frames of another size replace it, as they replace the engines."""
+
+    def __init__(self, dev):
+        self.dev, self.key, self.enc = dev, None, None
+
+    def __call__(self, u8, K, quality):
+        key = (int(u8.shape[2]), int(u8.shape[1]), int(K), int(quality))
+        if key != self.key:
+            from .video import JpegEncoder
+            self.enc = None                                      # (drop the old workspaces before the new ones are sized)
+            self.enc = JpegEncoder(key[0], key[1], key[2], self.dev, quality=key[3])
+            self.key = key
+        return self.enc.encode_to_host(u8)
 
 
 def _shared(ts):
@@ -216,6 +249,7 @@ class FrameAnimator:
         self.streams = [torch.cuda.Stream(self.dev) for _ in range(self.n)]
         self.engs, self.key, self.cap = [], None, 0
         self.policy = EngineCapacity()
+        self._jpeg = _JpegOut(self.dev)
 
     long_rows = property(lambda self: self.policy.long_rows)
 
@@ -347,11 +381,16 @@ class FrameAnimator:
         share one: the same tensor, or rows of an ``.expand`` view).  A frame without ``smpl_scale`` / ``ext_tfs`` starts a new batch
         when its neighbour has one.  Yields (index, clamped image) in order; images are bit-identical to the per-frame path's.
         ``out``: "float32" (the clamped [3,H,W] image), "rgb8" / "bgr8" (uint8 [H,W,3], ``frames_to_u8``: one conversion launch
-        per batch).  ``return_aux``: yields (index, image, depth [1,H,W], alpha [1,H,W]) -- the maps of
+        per batch), "jpeg" or ("jpeg", quality) (a ``bytes`` per frame: a complete baseline JPEG file at quality 90 or ``quality``,
+        encoded on the device behind that conversion -- ``video.JpegEncoder``, one per engine key; the padded frames of a last batch
+        are not encoded).
+        ``return_aux``: yields (index, image, depth [1,H,W], alpha [1,H,W]) -- the maps of
         ``get_render_pkg_fused(return_aux=True)``, re-rendered fallbacks included; the maps stay fp32."""
         c = self.canon
         bgr = _out_bgr(out)
         K = max(1, min(int(frames_per_launch), 16))
+        quality = _out_jpeg(out)
+        jpeg = None if quality is None else (lambda u8: self._jpeg(u8, K, quality))
 
         def launch(e, batch):
             A, tr, sc, ext = _stack_poses([j[1:] for j in batch], K)
@@ -364,6 +403,8 @@ class FrameAnimator:
             return (img, e.depth.clone(), e.alpha.clone()) if return_aux else (img,)
 
         for i0, batch, outs in self._pipeline(_batches(jobs, K), launch, K=K, aux=return_aux):
+            if jpeg is not None:
+                outs = (jpeg(outs[0][:len(batch)]),) + tuple(outs[1:])
             for k in range(len(batch)):
                 yield (i0 + k,) + tuple(t[k] for t in outs)
 
@@ -382,12 +423,17 @@ def animate_chunk(canon, poses, joints_rest, A_t2cano, cameras, bg_color, transl
     frames_per_launch = K > 1: K consecutive frames per DISPATCH (FrameAnimator.render_frames_batched), one such launch per stream
     in flight, with or without ext_tfs / per-frame smpl_scale; same images.
     out: "float32" (clamped [3,H,W]) or "rgb8" / "bgr8": uint8 [H,W,3] on the GPU (frames_to_u8: one launch per batch of K frames,
-    per frame elsewhere) -- the reference's (clamp * 255).astype(uint8) + cvtColor (gs_trainer.py:717-719).
+    per frame elsewhere) -- the reference's (clamp * 255).astype(uint8) + cvtColor (gs_trainer.py:717-719) -- or "jpeg" /
+    ("jpeg", quality): a ``bytes`` per frame, a complete JPEG file at quality 90 / ``quality`` encoded on the device
+    (``video.JpegEncoder``; ``video.animate_to_video`` writes them into a Motion-JPEG AVI).
     return_aux: yields (f, image, depth [1,H,W], alpha [1,H,W]) -- the maps of get_render_pkg_fused(return_aux=True), fp32 -- on the
     K-frame path and on the plain per-frame loop; the ``streams`` > 1 per-frame path (render_frames) has no maps: ValueError."""
     F = poses.shape[0]
     bgr = _out_bgr(out)
     to_out = (lambda img: img) if bgr is None else (lambda img: frames_to_u8(img, bgr))
+    if _out_jpeg(out) is not None:
+        one = _JpegOut(canon['xyz_canon'].device)
+        to_out = lambda img: one(frames_to_u8(img, False)[None], 1, _out_jpeg(out))[0]
     inv_cano = torch.inverse(A_t2cano)
     batched = int(frames_per_launch) > 1
     # one smpl_scale per frame ([F,1] / [F]: frame f's row) or one for all

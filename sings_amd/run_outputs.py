@@ -7,9 +7,12 @@ as an opt-in component of ``AvatarTrainer`` (``trainer.set_outputs(RunOutputs(..
     viz         canon/{idx:05d}.png                      the ``canon_nframes`` turntable frames (``canonical.render_canonical``)
     viz         meshes/human_pcd_{t:06d}_splat.ply       ``export.save_ply`` of the decoded set, when ``save_ply``
     progress    train_progress/{t:06d}.png               the progress sheet (``canonical.progress_sheet``)
+    progress    train_{video_name}.avi                   with ``progress_video``: the same sheets as Motion-JPEG at 10 frames a second
+                                                         (``_end_training``, gs_trainer.py:461-466), closed by ``finish()``
 
-Every picture becomes bytes on the device (``sheets.image_sheets``) and crosses to the host once.  The reference's videos (ffmpeg), its
-ellipsoid meshes and the text label on the progress sheet are not written.  The component keeps nothing a resumed run needs: it adds
+Every picture becomes bytes on the device (``sheets.image_sheets``) and crosses to the host once.  The progress video is encoded on the
+device too (``video.JpegEncoder``) and is off by default; the sheets stay on disk beside it (the reference deletes them).  The
+reference's ellipsoid meshes and the text label on the progress sheet are not written.  The component keeps nothing a resumed run needs: it adds
 nothing to a checkpoint.
 """
 import os
@@ -37,7 +40,9 @@ class RunOutputs:
     """``after_step(trainer, t)`` behind the optimiser step of iteration ``t`` writes what ``due(t)`` names (the module docstring's
     table).  ``A_static``: A_cano2pose [J,4,4] of the canonical pose (``canonical.static_A``); ``bg_color``: the background of the
     canonical renders; ``progress_interval`` None: no progress sheets (``save_progress_images`` off).  ``write(path, uint8 array)``:
-    the writer of the pictures, PNG through PIL by default; the directories are made here."""
+    the writer of the pictures, PNG through PIL by default; the directories are made here.  ``progress_video`` (an attribute, like the
+    sizes: off by default, set it before the first step): every progress sheet is also appended to ``train_<video_name>.avi`` at JPEG
+    quality ``video_quality``; call ``finish()`` at the end of the run."""
 
     def __init__(self, logdir, A_static, bg_color, viz_interval, progress_interval=None, canon_nframes=60, save_ply=True, write=None):
         if int(viz_interval) < 1 or (progress_interval is not None and int(progress_interval) < 1):
@@ -53,6 +58,8 @@ class RunOutputs:
         self.progress_interval = None if progress_interval is None else int(progress_interval)
         self.canon_nframes, self.save_ply, self.write = int(canon_nframes), bool(save_ply), write
         self.canon_size, self.progress_size, self.frames_per_launch = 512, 256, 8       # gs_trainer.py:767
+        self.progress_video, self.video_name, self.video_quality = False, "progress", 90
+        self._video = self._video_encoder = None
 
     def due(self, t):
         """The outputs of iteration ``t``, a subset of {"viz", "progress"}: gs_trainer.py:439 and :453 as written."""
@@ -98,8 +105,28 @@ class RunOutputs:
             if self.save_ply:
                 self._save_ply(trainer, attrs, os.path.join(self.logdir, "meshes", f"human_pcd_{t:06d}_splat.ply"))
         if "progress" in due:
-            self._put(f"train_progress/{t:06d}.png", _canon.progress_sheet(canon, self.A_static, self.bg_color,
-                                                                           img_size=self.progress_size))
+            sheet = _canon.progress_sheet(canon, self.A_static, self.bg_color, img_size=self.progress_size)
+            self._put(f"train_progress/{t:06d}.png", sheet)
+            if self.progress_video:
+                self._append_video(sheet)
+
+    video_path = property(lambda self: os.path.join(self.logdir, f"train_{self.video_name}.avi"))
+
+    def _append_video(self, sheet):
+        """``sheet``: uint8 [Hs,Ws,3] on the GPU -> one more frame of the progress video (opened at the first sheet)."""
+        from .video import JpegEncoder, MjpegWriter
+        Hs, Ws = int(sheet.shape[0]), int(sheet.shape[1])
+        if self._video is None:
+            os.makedirs(self.logdir, exist_ok=True)
+            self._video_encoder = JpegEncoder(Ws, Hs, 1, sheet.device, quality=int(self.video_quality))
+            self._video = MjpegWriter(self.video_path, Ws, Hs, 10)                 # fps=10: gs_trainer.py:465
+        self._video.write(self._video_encoder.encode_to_host(sheet[None].contiguous())[0])
+
+    def finish(self):
+        """Closes the progress video (the file appears under its name here); nothing to do without ``progress_video``."""
+        if self._video is not None:
+            self._video.close()
+            self._video = self._video_encoder = None
 
     def _save_ply(self, trainer, attrs, path):
         from . import rotations as R

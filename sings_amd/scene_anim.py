@@ -21,7 +21,7 @@ from . import _lib
 from ._marshal import _frame_rows, _ptr, _scene_structs
 from .body import SMPL_PARENTS
 from .engine import _FramesEngine
-from .posed import (FrameAnimator, _batches, _out_bgr, _stack_cameras, _stack_poses, frames_to_u8, joint_transforms_batch)
+from .posed import (FrameAnimator, _batches, _out_bgr, _out_jpeg, _stack_cameras, _stack_poses, frames_to_u8, joint_transforms_batch)
 
 _FORWARD_ONLY = "SceneFramesEngine: a scene of avatars is forward-only (the reference renders it under no_grad)"
 
@@ -188,9 +188,12 @@ class SceneAnimator(FrameAnimator):
         """``jobs``: an iterable of (camera dict, [(A [J,4,4], transl | None, smpl_scale | None, ext_tfs | None) per avatar]); K =
         ``frames_per_launch`` consecutive jobs per dispatch, the last batch padded with its last frame; a job whose avatars carry
         other optional inputs than its neighbour's starts a new batch.  Yields (index, clamped image) in order -- with ``out`` "rgb8" /
-        "bgr8" uint8 [H,W,3] (``frames_to_u8``), with ``return_aux`` (index, image, depth [1,H,W], alpha [1,H,W])."""
+        "bgr8" uint8 [H,W,3] (``frames_to_u8``), with "jpeg" / ("jpeg", quality) a ``bytes`` per frame (a JPEG file, encoded on the device as in
+        ``FrameAnimator.render_frames_batched``), with ``return_aux`` (index, image, depth [1,H,W], alpha [1,H,W])."""
         bgr = _out_bgr(out)
         K = max(1, min(int(frames_per_launch), _lib.MAX_FRAMES))
+        quality = _out_jpeg(out)
+        jpeg = None if quality is None else (lambda u8: self._jpeg(u8, K, quality))
         deg = self.canons[0]['active_sh_degree']
 
         def launch(e, batch):
@@ -206,6 +209,8 @@ class SceneAnimator(FrameAnimator):
 
         kind = lambda job: tuple(x is None for p in job[1] for x in p[1:])
         for i0, batch, outs in self._pipeline(_batches(jobs, K, kind), launch, K=K, aux=return_aux):
+            if jpeg is not None:
+                outs = (jpeg(outs[0][:len(batch)]),) + tuple(outs[1:])
             for k in range(len(batch)):
                 yield (i0 + k,) + tuple(t[k] for t in outs)
 
@@ -238,3 +243,15 @@ def animate_scene(canons, poses, joints_rest, A_t2cano, cameras, bg_color, trans
                        [(A[s][i], None if transl[s] is None else transl[s][f], scale_of(s, f),
                          None if ext_tfs[s] is None else tuple(x[f] for x in ext_tfs[s])) for s in range(S)])
     yield from animator.render_frames_batched(jobs(), bg_color, frames_per_launch=int(frames_per_launch), out=out, return_aux=return_aux)
+
+
+def animate_scene_to_video(path, canons, poses, joints_rest, A_t2cano, cameras, bg_color, fps=20, quality=90, frames_per_launch=8, **kwargs):
+    """``video.animate_to_video`` for a scene: ``animate_scene(..., out="jpeg")`` into a Motion-JPEG AVI at ``path`` (``kwargs``:
+    ``animate_scene``'s other arguments).  Returns the number of frames written."""
+    from .video import MjpegWriter
+    cam = cameras[0] if isinstance(cameras, (list, tuple)) else cameras
+    with MjpegWriter(path, int(cam["image_width"]), int(cam["image_height"]), fps) as w:
+        for _, data in animate_scene(canons, poses, joints_rest, A_t2cano, cameras, bg_color, frames_per_launch=frames_per_launch,
+                                     out=("jpeg", int(quality)), **kwargs):
+            w.write(data)
+        return w.frames
