@@ -23,6 +23,7 @@ HAS_DENSITY = False                  # set by load(): the library exports the ta
 HAS_SHEET = False                    # set by load(): the library exports the table of include/sings_sheet.h
 HAS_SCENE = False                    # set by load(): the library exports the table of include/sings_scene.h
 HAS_JPEG = False                     # set by load(): the library exports the table of include/sings_jpeg.h
+HAS_PNG = False                      # set by load(): the library exports the table of include/sings_png.h
 
 
 class SgRasterSettings(C.Structure):
@@ -237,6 +238,11 @@ _PROTOTYPES_JPEG = {
     "sg_jpeg_layout": "i: i5 Z",
     "sg_jpeg_encode_frames": "i: i5 p3 i p z p z p2",
 }
+# Frames to PNG files, include/sings_png.h: a twelfth header and a twelfth table, for the same reason.
+_PROTOTYPES_PNG = {
+    "sg_png_layout": "i: i5 Z",
+    "sg_png_encode_frames": "i: i7 p3 i p z p z p2",
+}
 _P = C.POINTER
 _CTYPE = {"i": C.c_int, "z": C.c_size_t, "f": C.c_float, "s": C.c_char_p,
           "p": C.c_void_p,                        # a raw device pointer (or NULL), and the stream
@@ -279,6 +285,21 @@ JPEG_TABLE_WORDS = 800               # SG_JPEG_TABLE_WORDS
 JPEG_HUFF_STRIDE = 272               # SG_JPEG_HUFF_STRIDE
 JPEG_MCU_BYTES = 1248                # SG_JPEG_MCU_BYTES
 JPEG_LAYOUT = ("ws_bytes", "mcus", "segments", "slot_pitch", "worst_bytes", "default_capacity")      # SG_JPEG_L_*, SG_JPEG_LAYOUT_WORDS
+PNG_MAX_FRAMES = 16                  # SG_PNG_MAX_FRAMES
+PNG_MAX_WIDTH = 10922                # SG_PNG_MAX_WIDTH
+PNG_MAX_HEIGHT = 65535               # SG_PNG_MAX_HEIGHT
+PNG_MAX_SEGMENT_BYTES = 32768        # SG_PNG_MAX_SEGMENT_BYTES
+PNG_HEADER_BYTES = 47                # SG_PNG_HEADER_BYTES
+PNG_TABLES = 5                       # SG_PNG_TABLES
+PNG_TABLE_STRIDE = 520               # SG_PNG_TABLE_STRIDE
+PNG_PREFIX_STRIDE = 48               # SG_PNG_PREFIX_STRIDE
+PNG_T_PREFIX = 2600                  # SG_PNG_T_PREFIX
+PNG_T_CRC = 2840                     # SG_PNG_T_CRC
+PNG_T_POW = 3096                     # SG_PNG_T_POW
+PNG_POW_WORDS = 20                   # SG_PNG_POW_WORDS
+PNG_TABLE_WORDS = 3120               # SG_PNG_TABLE_WORDS
+PNG_FILTER_ADAPTIVE = 5              # SG_PNG_FILTER_ADAPTIVE (0..4: SG_PNG_FILTER_NONE, _SUB, _UP, _AVERAGE, _PAETH)
+PNG_LAYOUT = ("ws_bytes", "segments", "segment_bytes", "slot_pitch", "worst_bytes")      # SG_PNG_L_*, SG_PNG_LAYOUT_WORDS
 FROZEN_BLOCK = 128                   # SG_FROZEN_BLOCK: points per workgroup of the fused no-gradient decode
 FROZEN_SHS = 48                      # SG_FROZEN_SHS
 MESH_TERMS_INFO_INTS = 2             # SG_MESH_TERMS_INFO_INTS
@@ -324,7 +345,7 @@ def load():
                            "(include/sings_hip.h SG_ABI_VERSION): rebuild with `make -C sings_amd/csrc`")
     # (SINGS_HIP_LIB may name a library that predates include/sings_order.h -- an A/B run against a parent build: it exports none of
     # that table, HAS_ORDER says so, and the engines then make the unordered calls that library knows)
-    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN, HAS_FEED, HAS_DENSITY, HAS_SHEET, HAS_SCENE, HAS_JPEG
+    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN, HAS_FEED, HAS_DENSITY, HAS_SHEET, HAS_SCENE, HAS_JPEG, HAS_PNG
     HAS_ORDER = all(hasattr(lib, name) for name in _PROTOTYPES_ORDER)
     HAS_SAMPLER = all(hasattr(lib, name) for name in _PROTOTYPES_SAMPLER)    # (the same, for include/sings_sampler.h)
     HAS_FROZEN = all(hasattr(lib, name) for name in _PROTOTYPES_FROZEN)      # (the same, for include/sings_frozen.h)
@@ -333,9 +354,10 @@ def load():
     HAS_SHEET = all(hasattr(lib, name) for name in _PROTOTYPES_SHEET)        # (the same, for include/sings_sheet.h)
     HAS_SCENE = all(hasattr(lib, name) for name in _PROTOTYPES_SCENE)        # (the same, for include/sings_scene.h)
     HAS_JPEG = all(hasattr(lib, name) for name in _PROTOTYPES_JPEG)          # (the same, for include/sings_jpeg.h)
+    HAS_PNG = all(hasattr(lib, name) for name in _PROTOTYPES_PNG)            # (the same, for include/sings_png.h)
     for has, header in ((HAS_ORDER, "sings_order.h"), (HAS_SAMPLER, "sings_sampler.h"), (HAS_FROZEN, "sings_frozen.h"),
                         (HAS_FEED, "sings_feed.h"), (HAS_DENSITY, "sings_density.h"), (HAS_SHEET, "sings_sheet.h"),
-                        (HAS_SCENE, "sings_scene.h"), (HAS_JPEG, "sings_jpeg.h")):
+                        (HAS_SCENE, "sings_scene.h"), (HAS_JPEG, "sings_jpeg.h"), (HAS_PNG, "sings_png.h")):
         if not has and LIB_PATH == os.path.join(_HERE, "libsings_hip.so"):
             raise RuntimeError(f"sings_amd: {LIB_PATH} lacks the entry points of include/{header}: rebuild with `make -C sings_amd/csrc`")
     for name, signature in (*_PROTOTYPES.items(), *_PROTOTYPES_EVAL.items(), *_PROTOTYPES_MESH_TERMS.items(),
@@ -344,7 +366,8 @@ def load():
                             *(_PROTOTYPES_DENSITY.items() if HAS_DENSITY else ()),
                             *(_PROTOTYPES_SHEET.items() if HAS_SHEET else ()),
                             *(_PROTOTYPES_SCENE.items() if HAS_SCENE else ()),
-                            *(_PROTOTYPES_JPEG.items() if HAS_JPEG else ())):
+                            *(_PROTOTYPES_JPEG.items() if HAS_JPEG else ()),
+                            *(_PROTOTYPES_PNG.items() if HAS_PNG else ())):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = _ctypes_of(signature)
     _lib = lib

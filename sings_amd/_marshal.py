@@ -428,3 +428,43 @@ def jpeg_encode_frames(K, W, H, restart_interval, bgr, frames, tables, header, w
     _lib.check(_jpeg_lib().sg_jpeg_encode_frames(int(K), int(W), int(H), int(restart_interval), int(bool(bgr)), _ptr(frames), _ptr(tables),
                                                  _ptr(header), int(header.numel()), _ptr(ws), int(ws.numel()), _ptr(out), int(capacity),
                                                  _ptr(sizes), C.c_void_p(stream.cuda_stream)), "sg_jpeg_encode_frames")
+
+
+# ---- frames to PNG files (csrc/sg_png.hip)
+def _png_lib():
+    lib = _lib.load()
+    if not _lib.HAS_PNG:
+        raise RuntimeError("the loaded library predates include/sings_png.h (no fallback): rebuild it")
+    return lib
+
+
+def png_layout(W, H, K, rows_per_segment, header_bytes):
+    """``sg_png_layout`` -> dict of ``_lib.PNG_LAYOUT``: the workspace bytes of K frames, segments per frame, the bytes of a segment and
+    of its slot, and the largest file a frame can become (the default capacity)."""
+    out = (C.c_size_t * len(_lib.PNG_LAYOUT))()
+    _lib.check(_png_lib().sg_png_layout(int(W), int(H), int(K), int(rows_per_segment), int(header_bytes), out), "sg_png_layout")
+    return {name: int(v) for name, v in zip(_lib.PNG_LAYOUT, out)}
+
+
+def png_encode_frames(K, W, H, rows_per_segment, filter, bgr, force, frames, tables, header, ws, out, capacity, sizes, stream):
+    """``sg_png_encode_frames`` on ``stream`` (a torch stream): ``frames`` uint8 [K,H,W,3]; ``filter`` 0..5 (SG_PNG_FILTER_*); ``force``
+    -1 or a candidate; ``tables`` ``_lib.PNG_TABLE_WORDS`` int32 words and ``header`` uint8, the caller's (``sings_amd.png``); ``ws``
+    uint8, ``png_layout``'s ``ws_bytes``; ``out`` uint8 rows of ``capacity`` bytes (its row pitch) and ``sizes`` int32 [K].  Nothing is
+    allocated here."""
+    dev = frames.device
+    for name, t, dt, least in (("frames", frames, torch.uint8, int(K) * int(H) * int(W) * 3), ("tables", tables, torch.int32, _lib.PNG_TABLE_WORDS),
+                               ("header", header, torch.uint8, 1), ("ws", ws, torch.uint8, 1),
+                               ("out", out, torch.uint8, 0), ("sizes", sizes, torch.int32, int(K))):
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != dev or t.dtype != dt:
+            raise RuntimeError(f"png_encode_frames: {name} must be a {dt} tensor on {dev} (no CPU fallback)")
+        if name != "out" and not t.is_contiguous():
+            raise RuntimeError(f"png_encode_frames: {name} must be contiguous")
+        if t.numel() < least:
+            raise ValueError(f"png_encode_frames: {name} holds {t.numel()} elements, {least} needed")
+    if out.dim() != 2 or out.stride(1) != 1 or out.stride(0) != int(capacity) or out.shape[0] < int(K) or out.shape[1] != int(capacity):
+        raise ValueError(f"png_encode_frames: out must be [>= {int(K)}, {int(capacity)}] uint8 with rows of capacity bytes, got "
+                         f"{tuple(out.shape)} strides {tuple(out.stride())}")
+    _lib.check(_png_lib().sg_png_encode_frames(int(K), int(W), int(H), int(rows_per_segment), int(filter), int(bool(bgr)), int(force),
+                                               _ptr(frames), _ptr(tables), _ptr(header), int(header.numel()), _ptr(ws), int(ws.numel()),
+                                               _ptr(out), int(capacity), _ptr(sizes), C.c_void_p(stream.cuda_stream)),
+               "sg_png_encode_frames")

@@ -128,8 +128,9 @@ def frames_to_u8(img, bgr=False):
     return out
 
 
-# out= of the animation paths -> frames_to_u8(bgr=...); "jpeg": RGB bytes, then ``video.JpegEncoder`` (a ``bytes`` per frame)
-_OUT = {"float32": None, "rgb8": False, "bgr8": True, "jpeg": False}
+# out= of the animation paths -> frames_to_u8(bgr=...); "jpeg" / "png": RGB bytes, then ``video.JpegEncoder`` / ``png.PngEncoder`` (a
+# ``bytes`` per frame)
+_OUT = {"float32": None, "rgb8": False, "bgr8": True, "jpeg": False, "png": False}
 JPEG_QUALITY = 90                    # of out="jpeg"; out=("jpeg", quality) names another
 
 
@@ -150,6 +151,23 @@ def _out_jpeg(out):
             raise ValueError(f"out=(\"jpeg\", quality): quality must be an int in 1..100, got {out[1]!r}")
         return out[1]
     return None
+
+
+class _PngOut:
+    """The ``out="png"`` step behind ``frames_to_u8``, as ``_JpegOut``: ``u8`` [k,H,W,3] RGB bytes -> k ``bytes``, each a PNG file
+    (``png.PngEncoder.encode_to_host``).  One encoder per (W, H, K)."""
+
+    def __init__(self, dev):
+        self.dev, self.key, self.enc = dev, None, None
+
+    def __call__(self, u8, K):
+        key = (int(u8.shape[2]), int(u8.shape[1]), int(K))
+        if key != self.key:
+            from .png import PngEncoder
+            self.enc = None                                      # (drop the old workspaces before the new ones are sized)
+            self.enc = PngEncoder(key[0], key[1], key[2], self.dev)
+            self.key = key
+        return self.enc.encode_to_host(u8)
 
 
 class _JpegOut:
@@ -250,6 +268,7 @@ class FrameAnimator:
         self.engs, self.key, self.cap = [], None, 0
         self.policy = EngineCapacity()
         self._jpeg = _JpegOut(self.dev)
+        self._png = _PngOut(self.dev)
 
     long_rows = property(lambda self: self.policy.long_rows)
 
@@ -383,7 +402,7 @@ class FrameAnimator:
         ``out``: "float32" (the clamped [3,H,W] image), "rgb8" / "bgr8" (uint8 [H,W,3], ``frames_to_u8``: one conversion launch
         per batch), "jpeg" or ("jpeg", quality) (a ``bytes`` per frame: a complete baseline JPEG file at quality 90 or ``quality``,
         encoded on the device behind that conversion -- ``video.JpegEncoder``, one per engine key; the padded frames of a last batch
-        are not encoded).
+        are not encoded), "png" (a ``bytes`` per frame: a complete PNG file, lossless, by ``png.PngEncoder`` in the same place).
         ``return_aux``: yields (index, image, depth [1,H,W], alpha [1,H,W]) -- the maps of
         ``get_render_pkg_fused(return_aux=True)``, re-rendered fallbacks included; the maps stay fp32."""
         c = self.canon
@@ -391,6 +410,8 @@ class FrameAnimator:
         K = max(1, min(int(frames_per_launch), 16))
         quality = _out_jpeg(out)
         jpeg = None if quality is None else (lambda u8: self._jpeg(u8, K, quality))
+        if out == "png":
+            jpeg = lambda u8: self._png(u8, K)
 
         def launch(e, batch):
             A, tr, sc, ext = _stack_poses([j[1:] for j in batch], K)
@@ -425,7 +446,8 @@ def animate_chunk(canon, poses, joints_rest, A_t2cano, cameras, bg_color, transl
     out: "float32" (clamped [3,H,W]) or "rgb8" / "bgr8": uint8 [H,W,3] on the GPU (frames_to_u8: one launch per batch of K frames,
     per frame elsewhere) -- the reference's (clamp * 255).astype(uint8) + cvtColor (gs_trainer.py:717-719) -- or "jpeg" /
     ("jpeg", quality): a ``bytes`` per frame, a complete JPEG file at quality 90 / ``quality`` encoded on the device
-    (``video.JpegEncoder``; ``video.animate_to_video`` writes them into a Motion-JPEG AVI).
+    (``video.JpegEncoder``; ``video.animate_to_video`` writes them into a Motion-JPEG AVI) -- or "png": a ``bytes`` per frame, a
+    complete PNG file encoded on the device (``png.PngEncoder``; ``png.animate_to_frames`` writes them into numbered files).
     return_aux: yields (f, image, depth [1,H,W], alpha [1,H,W]) -- the maps of get_render_pkg_fused(return_aux=True), fp32 -- on the
     K-frame path and on the plain per-frame loop; the ``streams`` > 1 per-frame path (render_frames) has no maps: ValueError."""
     F = poses.shape[0]
@@ -434,6 +456,9 @@ def animate_chunk(canon, poses, joints_rest, A_t2cano, cameras, bg_color, transl
     if _out_jpeg(out) is not None:
         one = _JpegOut(canon['xyz_canon'].device)
         to_out = lambda img: one(frames_to_u8(img, False)[None], 1, _out_jpeg(out))[0]
+    if out == "png":
+        one_png = _PngOut(canon['xyz_canon'].device)
+        to_out = lambda img: one_png(frames_to_u8(img, False)[None], 1)[0]
     inv_cano = torch.inverse(A_t2cano)
     batched = int(frames_per_launch) > 1
     # one smpl_scale per frame ([F,1] / [F]: frame f's row) or one for all

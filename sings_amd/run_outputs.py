@@ -12,6 +12,7 @@ as an opt-in component of ``AvatarTrainer`` (``trainer.set_outputs(RunOutputs(..
 
 Every picture becomes bytes on the device (``sheets.image_sheets``) and crosses to the host once.  The progress video is encoded on the
 device too (``video.JpegEncoder``) and is off by default; the sheets stay on disk beside it (the reference deletes them).  The
+``device_png`` (off by default) encodes the pictures themselves on the device (``png.PngEncoder``) and writes the file bytes directly.  The
 reference's ellipsoid meshes and the text label on the progress sheet are not written.  The component keeps nothing a resumed run needs: it adds
 nothing to a checkpoint.
 """
@@ -42,7 +43,10 @@ class RunOutputs:
     canonical renders; ``progress_interval`` None: no progress sheets (``save_progress_images`` off).  ``write(path, uint8 array)``:
     the writer of the pictures, PNG through PIL by default; the directories are made here.  ``progress_video`` (an attribute, like the
     sizes: off by default, set it before the first step): every progress sheet is also appended to ``train_<video_name>.avi`` at JPEG
-    quality ``video_quality``; call ``finish()`` at the end of the run."""
+    quality ``video_quality``; call ``finish()`` at the end of the run.  ``device_png`` (an attribute too, off by default): the
+    ``train/``, ``canon/`` and ``train_progress/`` pictures are encoded to PNG on the device (``png.PngEncoder``, the turntable
+    ``frames_per_launch`` frames per call) and the file bytes written under a temporary name, then renamed; ``write`` is then used for
+    nothing.  The files decode to the same pixels either way."""
 
     def __init__(self, logdir, A_static, bg_color, viz_interval, progress_interval=None, canon_nframes=60, save_ply=True, write=None):
         if int(viz_interval) < 1 or (progress_interval is not None and int(progress_interval) < 1):
@@ -60,6 +64,8 @@ class RunOutputs:
         self.canon_size, self.progress_size, self.frames_per_launch = 512, 256, 8       # gs_trainer.py:767
         self.progress_video, self.video_name, self.video_quality = False, "progress", 90
         self._video = self._video_encoder = None
+        self.device_png = False
+        self._png_encoders = {}
 
     def due(self, t):
         """The outputs of iteration ``t``, a subset of {"viz", "progress"}: gs_trainer.py:439 and :453 as written."""
@@ -75,6 +81,25 @@ class RunOutputs:
         path = os.path.join(self.logdir, rel)
         os.makedirs(os.path.dirname(path), exist_ok=True)
         self.write(path, array.cpu().numpy() if torch.is_tensor(array) else array)
+
+    def _put_png(self, rels, u8):
+        """``device_png``: ``u8`` uint8 [k,H,W,3] on the GPU -> the k files ``rels``, encoded in one call (one encoder per (W, H, K))."""
+        from .png import PngEncoder, write_atomic
+        k, H, W = (int(n) for n in u8.shape[:3])
+        K = max(k, self.frames_per_launch if k > 1 else 1)
+        if (W, H, K) not in self._png_encoders:
+            self._png_encoders[W, H, K] = PngEncoder(W, H, K, u8.device)
+        for rel, data in zip(rels, self._png_encoders[W, H, K].encode_to_host(u8.contiguous())):
+            path = os.path.join(self.logdir, rel)
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            write_atomic(path, data)
+
+    def _picture(self, rel, u8):
+        """One picture, uint8 [H,W,3] on the GPU, to ``rel``."""
+        if self.device_png:
+            self._put_png([rel], u8[None])
+        else:
+            self._put(rel, u8)
 
     @staticmethod
     def training_picture(gt, mask, bg, render_raw):
@@ -97,16 +122,19 @@ class RunOutputs:
             if trainer.last_render is None:
                 raise RuntimeError("RunOutputs: the trainer has kept no render of this step (set_outputs before the step)")
             inp = trainer.inputs
-            self._put(f"train/{t:06d}.png", self.training_picture(inp.gt, inp.mask, trainer.bg, trainer.last_render))
+            self._picture(f"train/{t:06d}.png", self.training_picture(inp.gt, inp.mask, trainer.bg, trainer.last_render))
             for i0, u8 in _canon.render_canonical_chunks(canon, self.A_static, self.bg_color, nframes=self.canon_nframes,
                                                          img_size=self.canon_size, frames_per_launch=self.frames_per_launch):
+                if self.device_png:
+                    self._put_png([f"canon/{i0 + j:05d}.png" for j in range(int(u8.shape[0]))], u8)
+                    continue
                 for j, frame in enumerate(u8.cpu().numpy()):     # (one copy per launch)
                     self._put(f"canon/{i0 + j:05d}.png", frame)
             if self.save_ply:
                 self._save_ply(trainer, attrs, os.path.join(self.logdir, "meshes", f"human_pcd_{t:06d}_splat.ply"))
         if "progress" in due:
             sheet = _canon.progress_sheet(canon, self.A_static, self.bg_color, img_size=self.progress_size)
-            self._put(f"train_progress/{t:06d}.png", sheet)
+            self._picture(f"train_progress/{t:06d}.png", sheet)
             if self.progress_video:
                 self._append_video(sheet)
 

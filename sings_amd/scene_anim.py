@@ -188,12 +188,14 @@ class SceneAnimator(FrameAnimator):
         """``jobs``: an iterable of (camera dict, [(A [J,4,4], transl | None, smpl_scale | None, ext_tfs | None) per avatar]); K =
         ``frames_per_launch`` consecutive jobs per dispatch, the last batch padded with its last frame; a job whose avatars carry
         other optional inputs than its neighbour's starts a new batch.  Yields (index, clamped image) in order -- with ``out`` "rgb8" /
-        "bgr8" uint8 [H,W,3] (``frames_to_u8``), with "jpeg" / ("jpeg", quality) a ``bytes`` per frame (a JPEG file, encoded on the device as in
-        ``FrameAnimator.render_frames_batched``), with ``return_aux`` (index, image, depth [1,H,W], alpha [1,H,W])."""
+        "bgr8" uint8 [H,W,3] (``frames_to_u8``), with "jpeg" / ("jpeg", quality) or "png" a ``bytes`` per frame (a JPEG / PNG file, encoded on
+        the device as in ``FrameAnimator.render_frames_batched``), with ``return_aux`` (index, image, depth [1,H,W], alpha [1,H,W])."""
         bgr = _out_bgr(out)
         K = max(1, min(int(frames_per_launch), _lib.MAX_FRAMES))
         quality = _out_jpeg(out)
         jpeg = None if quality is None else (lambda u8: self._jpeg(u8, K, quality))
+        if out == "png":
+            jpeg = lambda u8: self._png(u8, K)
         deg = self.canons[0]['active_sh_degree']
 
         def launch(e, batch):

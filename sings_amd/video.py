@@ -15,7 +15,7 @@ The stream is fixed so that bytes can be compared: baseline sequential DCT (SOF0
 block: a Y, a Cb and a Cr coefficient block), the Annex K tables scaled by libjpeg's quality rule, a DRI segment always, restart
 markers every ``restart_interval`` MCUs (default: one MCU row).  The arithmetic is pinned: fp32, every multiply and add rounded on
 its own, sums left to right, quantisation ``rint(F / Q)`` with ties to even.  Out of scope: chroma subsampling, progressive streams,
-optimised Huffman tables, mp4 / H.264, audio, a device PNG.
+optimised Huffman tables, mp4 / H.264, audio (lossless files: sings_amd/png.py).
 """
 import math
 import os
