@@ -24,6 +24,7 @@ HAS_SHEET = False                    # set by load(): the library exports the ta
 HAS_SCENE = False                    # set by load(): the library exports the table of include/sings_scene.h
 HAS_JPEG = False                     # set by load(): the library exports the table of include/sings_jpeg.h
 HAS_PNG = False                      # set by load(): the library exports the table of include/sings_png.h
+HAS_UNPNG = False                    # set by load(): the library exports the table of include/sings_unpng.h
 
 
 class SgRasterSettings(C.Structure):
@@ -243,6 +244,11 @@ _PROTOTYPES_PNG = {
     "sg_png_layout": "i: i5 Z",
     "sg_png_encode_frames": "i: i7 p3 i p z p z p2",
 }
+# PNG files to the frame store, include/sings_unpng.h: a thirteenth header and a thirteenth table, for the same reason.
+_PROTOTYPES_UNPNG = {
+    "sg_unpng_layout": "i: i z Z",
+    "sg_unpng_decode": "i: i p3 z p i3 p2",
+}
 _P = C.POINTER
 _CTYPE = {"i": C.c_int, "z": C.c_size_t, "f": C.c_float, "s": C.c_char_p,
           "p": C.c_void_p,                        # a raw device pointer (or NULL), and the stream
@@ -300,6 +306,11 @@ PNG_POW_WORDS = 20                   # SG_PNG_POW_WORDS
 PNG_TABLE_WORDS = 3120               # SG_PNG_TABLE_WORDS
 PNG_FILTER_ADAPTIVE = 5              # SG_PNG_FILTER_ADAPTIVE (0..4: SG_PNG_FILTER_NONE, _SUB, _UP, _AVERAGE, _PAETH)
 PNG_LAYOUT = ("ws_bytes", "segments", "segment_bytes", "slot_pitch", "worst_bytes")      # SG_PNG_L_*, SG_PNG_LAYOUT_WORDS
+UNPNG_MAX_STREAMS = 65535            # SG_UNPNG_MAX_STREAMS
+UNPNG_MAX_ROW_BYTES = 16384          # SG_UNPNG_MAX_ROW_BYTES
+UNPNG_MAX_HEIGHT = 65535             # SG_UNPNG_MAX_HEIGHT
+UNPNG_TABLE_COLS = 6                 # SG_UNPNG_TABLE_COLS (SG_UNPNG_T_*: offset, length, width, height, channels, dest)
+UNPNG_LAYOUT = ("ws_bytes", "slot_pitch")        # SG_UNPNG_L_*, SG_UNPNG_LAYOUT_WORDS
 FROZEN_BLOCK = 128                   # SG_FROZEN_BLOCK: points per workgroup of the fused no-gradient decode
 FROZEN_SHS = 48                      # SG_FROZEN_SHS
 MESH_TERMS_INFO_INTS = 2             # SG_MESH_TERMS_INFO_INTS
@@ -345,7 +356,7 @@ def load():
                            "(include/sings_hip.h SG_ABI_VERSION): rebuild with `make -C sings_amd/csrc`")
     # (SINGS_HIP_LIB may name a library that predates include/sings_order.h -- an A/B run against a parent build: it exports none of
     # that table, HAS_ORDER says so, and the engines then make the unordered calls that library knows)
-    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN, HAS_FEED, HAS_DENSITY, HAS_SHEET, HAS_SCENE, HAS_JPEG, HAS_PNG
+    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN, HAS_FEED, HAS_DENSITY, HAS_SHEET, HAS_SCENE, HAS_JPEG, HAS_PNG, HAS_UNPNG
     HAS_ORDER = all(hasattr(lib, name) for name in _PROTOTYPES_ORDER)
     HAS_SAMPLER = all(hasattr(lib, name) for name in _PROTOTYPES_SAMPLER)    # (the same, for include/sings_sampler.h)
     HAS_FROZEN = all(hasattr(lib, name) for name in _PROTOTYPES_FROZEN)      # (the same, for include/sings_frozen.h)
@@ -355,9 +366,11 @@ def load():
     HAS_SCENE = all(hasattr(lib, name) for name in _PROTOTYPES_SCENE)        # (the same, for include/sings_scene.h)
     HAS_JPEG = all(hasattr(lib, name) for name in _PROTOTYPES_JPEG)          # (the same, for include/sings_jpeg.h)
     HAS_PNG = all(hasattr(lib, name) for name in _PROTOTYPES_PNG)            # (the same, for include/sings_png.h)
+    HAS_UNPNG = all(hasattr(lib, name) for name in _PROTOTYPES_UNPNG)        # (the same, for include/sings_unpng.h)
     for has, header in ((HAS_ORDER, "sings_order.h"), (HAS_SAMPLER, "sings_sampler.h"), (HAS_FROZEN, "sings_frozen.h"),
                         (HAS_FEED, "sings_feed.h"), (HAS_DENSITY, "sings_density.h"), (HAS_SHEET, "sings_sheet.h"),
-                        (HAS_SCENE, "sings_scene.h"), (HAS_JPEG, "sings_jpeg.h"), (HAS_PNG, "sings_png.h")):
+                        (HAS_SCENE, "sings_scene.h"), (HAS_JPEG, "sings_jpeg.h"), (HAS_PNG, "sings_png.h"),
+                        (HAS_UNPNG, "sings_unpng.h")):
         if not has and LIB_PATH == os.path.join(_HERE, "libsings_hip.so"):
             raise RuntimeError(f"sings_amd: {LIB_PATH} lacks the entry points of include/{header}: rebuild with `make -C sings_amd/csrc`")
     for name, signature in (*_PROTOTYPES.items(), *_PROTOTYPES_EVAL.items(), *_PROTOTYPES_MESH_TERMS.items(),
@@ -367,7 +380,8 @@ def load():
                             *(_PROTOTYPES_SHEET.items() if HAS_SHEET else ()),
                             *(_PROTOTYPES_SCENE.items() if HAS_SCENE else ()),
                             *(_PROTOTYPES_JPEG.items() if HAS_JPEG else ()),
-                            *(_PROTOTYPES_PNG.items() if HAS_PNG else ())):
+                            *(_PROTOTYPES_PNG.items() if HAS_PNG else ()),
+                            *(_PROTOTYPES_UNPNG.items() if HAS_UNPNG else ())):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = _ctypes_of(signature)
     _lib = lib

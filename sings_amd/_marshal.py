@@ -468,3 +468,39 @@ def png_encode_frames(K, W, H, rows_per_segment, filter, bgr, force, frames, tab
                                                _ptr(frames), _ptr(tables), _ptr(header), int(header.numel()), _ptr(ws), int(ws.numel()),
                                                _ptr(out), int(capacity), _ptr(sizes), C.c_void_p(stream.cuda_stream)),
                "sg_png_encode_frames")
+
+
+# ---- PNG files to the frame store (csrc/sg_unpng.hip)
+def _unpng_lib():
+    lib = _lib.load()
+    if not _lib.HAS_UNPNG:
+        raise RuntimeError("the loaded library predates include/sings_unpng.h (no fallback): rebuild it")
+    return lib
+
+
+def unpng_layout(n_streams, max_raw_bytes):
+    """``sg_unpng_layout`` -> dict of ``_lib.UNPNG_LAYOUT``: the workspace bytes of ``n_streams`` streams of at most ``max_raw_bytes``
+    filtered scanline bytes each, and the bytes of a stream's slot."""
+    out = (C.c_size_t * len(_lib.UNPNG_LAYOUT))()
+    _lib.check(_unpng_lib().sg_unpng_layout(int(n_streams), int(max_raw_bytes), out), "sg_unpng_layout")
+    return {name: int(v) for name, v in zip(_lib.UNPNG_LAYOUT, out)}
+
+
+def unpng_decode(n, streams, table, ws, dst, status, stream):
+    """``sg_unpng_decode`` on ``stream`` (a torch stream): ``streams`` uint8, the concatenated zlib streams; ``table`` int64
+    [>= n, ``_lib.UNPNG_TABLE_COLS``], whose offsets and lengths are checked against ``streams`` by the caller; ``ws`` uint8,
+    ``unpng_layout``'s ``ws_bytes``; ``dst`` uint8 [F,H,W,4]; ``status`` int32 [>= n].  Nothing is allocated here."""
+    dev = dst.device
+    for name, t, dt, least in (("streams", streams, torch.uint8, 1), ("table", table, torch.int64, int(n) * _lib.UNPNG_TABLE_COLS),
+                               ("ws", ws, torch.uint8, 1), ("dst", dst, torch.uint8, 1), ("status", status, torch.int32, int(n))):
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != dev or t.dtype != dt:
+            raise RuntimeError(f"unpng_decode: {name} must be a {dt} tensor on {dev} (no CPU fallback)")
+        if not t.is_contiguous():
+            raise RuntimeError(f"unpng_decode: {name} must be contiguous")
+        if t.numel() < least:
+            raise ValueError(f"unpng_decode: {name} holds {t.numel()} elements, {least} needed")
+    if dst.dim() != 4 or dst.shape[3] != 4:
+        raise ValueError(f"unpng_decode: dst must be uint8 [F,H,W,4], got {tuple(dst.shape)}")
+    F, H, W = (int(v) for v in dst.shape[:3])
+    _lib.check(_unpng_lib().sg_unpng_decode(int(n), _ptr(streams), _ptr(table), _ptr(ws), int(ws.numel()), _ptr(dst), F, H, W,
+                                            _ptr(status), C.c_void_p(stream.cuda_stream)), "sg_unpng_decode")

@@ -141,6 +141,35 @@ class FrameStore:
                              "(the store would be lossy)")
         return cls(rgb_u8, mask_u8, device=dev)
 
+    @classmethod
+    def from_png_files(cls, image_paths, mask_paths, device=None, verify_crc=True, max_workspace_bytes=1 << 31, checked=None):
+        """From a kit's files: frame f is ``image_paths[f]`` (8-bit RGB or RGBA PNG; alpha is dropped) and ``mask_paths[f]`` (8-bit
+        grey PNG), all of one size.  The store is allocated, then filled on the device by ``unpng.PngDecoder`` (the files' zlib
+        streams are uploaded, not their pixels), in batches whose workspace stays below ``max_workspace_bytes``.  ``ValueError``
+        naming the file for unequal counts, a file the decoder does not read, a size that is not the first image's, and every stream
+        the device refuses.  ``checked``: what ``unpng.check_kit_files`` returned for these very lists, from a caller that has
+        already read the headers (``load_kit``); they are not read again.
+
+        Memory: while the load runs the device holds, beside the store, the decoder's workspace -- one slot of the largest file's
+        ``H * (1 + W * channels)`` scanline bytes per stream of a batch, a mask's slot as large as an image's, ``max_workspace_bytes``
+        at the most (2 GiB by default; a kit of 80 frames of 512 x 896 takes 220 MB) -- and the files' compressed bytes.  A smaller
+        ``max_workspace_bytes`` means more batches, and a load is about as long as the longest stream of each of its batches.  The
+        workspace goes back to torch's allocator when this returns."""
+        import torch
+        from . import unpng
+        dev = _device(device)
+        images, masks = [str(p) for p in image_paths], [str(p) for p in mask_paths]
+        W, H, raw = checked if checked is not None else unpng.check_kit_files(images, masks)
+        self = cls.__new__(cls)
+        self.device, self.F, self.H, self.W = dev, len(images), H, W
+        if self.F > MAX_FRAMES or self.H * self.W >= 1 << 31:
+            raise ValueError(f"FrameStore: at most {MAX_FRAMES} frames of fewer than 2**31 pixels")
+        self.data = torch.empty((self.F, self.H, self.W, 4), dtype=torch.uint8, device=dev)
+        batch = max(1, min(2 * self.F, unpng.MAX_STREAMS, int(max_workspace_bytes) // raw))
+        decoder = unpng.PngDecoder(dev, batch, raw, verify_crc=verify_crc)
+        decoder.decode_into(self.data, images + masks, [4 * f for f in range(self.F)] + [4 * f + 3 for f in range(self.F)])
+        return self
+
     nbytes = property(lambda self: self.data.numel())
 
     def expand(self, idx, gt, mask):
