@@ -552,7 +552,8 @@ int sg_scales_head_backward(int N, const float *z, const float *dscales, const f
  * the input-gradient GEMM.  x [N,Cin], W [Cout,Cin] (nn.Linear.weight), bias [Cout] | NULL, 1 <= Cin, Cout <= 128; `act`
  * and `row_offset` as for sg_bias_act_*.
  *   forward : h_out [N,Cout] = act(x W^T + bias); aux_out [N,Cout] | NULL receives what the backward needs besides h:
- *             GELU: gelu'(z) itself (the erf is evaluated once, here), softplus: z; nothing for act = 0 and sigmoid (NULL).
+ *             GELU: gelu'(z) itself (the erf is evaluated once, here, in the narrow and the wide kernel alike), softplus: z; act = 0
+ *             and sigmoid need nothing: pass NULL (an array given all the same receives z = x W^T + bias, without row_offset).
  *   backward: aux = the forward's aux_out (GELU, softplus) or its h_out (sigmoid: s' = h (1 - h)); NULL when act = 0.
  *             dz_out [N,Cout] | NULL = dh * act' (input of sg_weight_grad; NULL when act = 0: dz is dh), dx_out [N,Cin] = dz W. */
 int sg_linear_forward(int N, int Cin, int Cout, int act, const float *x, const float *W, const float *bias,
