@@ -392,115 +392,96 @@ def density_stats(grad, radii, gate, accum, denom, max_radii):
                                         _stream(dev)), "sg_density_stats")
 
 
-# ---- frames to JPEG files (csrc/sg_jpeg.hip)
-def _jpeg_lib():
+
+
+# ---- frames to JPEG and PNG files, PNG files to the frame store (csrc/sg_jpeg.hip, sg_png.hip, sg_unpng.hip)
+def _codec_lib(codec):
+    """The library, once ``_lib.HAS_<CODEC>`` says that it holds include/sings_<codec>.h."""
     lib = _lib.load()
-    if not _lib.HAS_JPEG:
-        raise RuntimeError("the loaded library predates include/sings_jpeg.h (no fallback): rebuild it")
+    if not getattr(_lib, f"HAS_{codec.upper()}"):
+        raise RuntimeError(f"the loaded library predates include/sings_{codec}.h (no fallback): rebuild it")
     return lib
+
+
+def _codec_layout(codec, *args):
+    """``sg_<codec>_layout(*args, out)`` -> dict of ``_lib.<CODEC>_LAYOUT``."""
+    names, fn = getattr(_lib, f"{codec.upper()}_LAYOUT"), f"sg_{codec}_layout"
+    out = (C.c_size_t * len(names))()
+    _lib.check(getattr(_codec_lib(codec), fn)(*(int(a) for a in args), out), fn)
+    return {name: int(v) for name, v in zip(names, out)}
+
+
+def _codec_tensors(who, dev, rows):
+    """``rows`` of (name, tensor, dtype, least elements): every tensor of its type on ``dev``, contiguous and large enough.  ``out``
+    alone may be a view with a row pitch: ``_encoder_tensors`` checks its shape."""
+    for name, t, dt, least in rows:
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != dev or t.dtype != dt:
+            raise RuntimeError(f"{who}: {name} must be a {dt} tensor on {dev} (no CPU fallback)")
+        if name == "out":
+            continue
+        if not t.is_contiguous():
+            raise RuntimeError(f"{who}: {name} must be contiguous")
+        if t.numel() < least:
+            raise ValueError(f"{who}: {name} holds {t.numel()} elements, {least} needed")
+
+
+def _encoder_tensors(who, K, W, H, table_words, frames, tables, header, ws, out, capacity, sizes):
+    """What the two ``*_encode_frames`` take: ``frames`` uint8 [K,H,W,3]; ``tables`` int32 words and ``header`` uint8, the caller's; ``ws``
+    uint8; ``out`` uint8 rows of ``capacity`` bytes (its row pitch) and ``sizes`` int32 [K]."""
+    _codec_tensors(who, frames.device, (("frames", frames, torch.uint8, int(K) * int(H) * int(W) * 3), ("tables", tables, torch.int32, table_words),
+                                        ("header", header, torch.uint8, 1), ("ws", ws, torch.uint8, 1), ("out", out, torch.uint8, 0),
+                                        ("sizes", sizes, torch.int32, int(K))))
+    if out.dim() != 2 or out.stride(1) != 1 or out.stride(0) != int(capacity) or out.shape[0] < int(K) or out.shape[1] != int(capacity):
+        raise ValueError(f"{who}: out must be [>= {int(K)}, {int(capacity)}] uint8 with rows of capacity bytes, got "
+                         f"{tuple(out.shape)} strides {tuple(out.stride())}")
 
 
 def jpeg_layout(W, H, K, restart_interval, header_bytes):
     """``sg_jpeg_layout`` -> dict of ``_lib.JPEG_LAYOUT``: the workspace bytes of K frames, MCUs and restart segments per frame, the
     bytes of a segment's slot, the largest file a frame can become and the default capacity."""
-    out = (C.c_size_t * len(_lib.JPEG_LAYOUT))()
-    _lib.check(_jpeg_lib().sg_jpeg_layout(int(W), int(H), int(K), int(restart_interval), int(header_bytes), out), "sg_jpeg_layout")
-    return {name: int(v) for name, v in zip(_lib.JPEG_LAYOUT, out)}
+    return _codec_layout("jpeg", W, H, K, restart_interval, header_bytes)
 
 
 def jpeg_encode_frames(K, W, H, restart_interval, bgr, frames, tables, header, ws, out, capacity, sizes, stream):
-    """``sg_jpeg_encode_frames`` on ``stream`` (a torch stream): ``frames`` uint8 [K,H,W,3]; ``tables`` ``_lib.JPEG_TABLE_WORDS`` int32
-    words and ``header`` uint8, the caller's (``sings_amd.video``); ``ws`` uint8, ``jpeg_layout``'s ``ws_bytes``; ``out`` uint8 rows of
-    ``capacity`` bytes (its row pitch) and ``sizes`` int32 [K].  Nothing is allocated here."""
-    dev = frames.device
-    for name, t, dt, least in (("frames", frames, torch.uint8, int(K) * int(H) * int(W) * 3), ("tables", tables, torch.int32, _lib.JPEG_TABLE_WORDS),
-                               ("header", header, torch.uint8, 1), ("ws", ws, torch.uint8, 1),
-                               ("out", out, torch.uint8, (int(K) - 1) * int(out.stride(0)) + int(capacity)), ("sizes", sizes, torch.int32, int(K))):
-        if not torch.is_tensor(t) or not t.is_cuda or t.device != dev or t.dtype != dt:
-            raise RuntimeError(f"jpeg_encode_frames: {name} must be a {dt} tensor on {dev} (no CPU fallback)")
-        if name != "out" and not t.is_contiguous():
-            raise RuntimeError(f"jpeg_encode_frames: {name} must be contiguous")
-        if t.numel() < least and name != "out":
-            raise ValueError(f"jpeg_encode_frames: {name} holds {t.numel()} elements, {least} needed")
-    if out.dim() != 2 or out.stride(1) != 1 or out.stride(0) != int(capacity) or out.shape[0] < int(K) or out.shape[1] != int(capacity):
-        raise ValueError(f"jpeg_encode_frames: out must be [>= {int(K)}, {int(capacity)}] uint8 with rows of capacity bytes, got "
-                         f"{tuple(out.shape)} strides {tuple(out.stride())}")
-    _lib.check(_jpeg_lib().sg_jpeg_encode_frames(int(K), int(W), int(H), int(restart_interval), int(bool(bgr)), _ptr(frames), _ptr(tables),
-                                                 _ptr(header), int(header.numel()), _ptr(ws), int(ws.numel()), _ptr(out), int(capacity),
-                                                 _ptr(sizes), C.c_void_p(stream.cuda_stream)), "sg_jpeg_encode_frames")
-
-
-# ---- frames to PNG files (csrc/sg_png.hip)
-def _png_lib():
-    lib = _lib.load()
-    if not _lib.HAS_PNG:
-        raise RuntimeError("the loaded library predates include/sings_png.h (no fallback): rebuild it")
-    return lib
+    """``sg_jpeg_encode_frames`` on ``stream`` (a torch stream): ``_encoder_tensors`` with ``_lib.JPEG_TABLE_WORDS`` table words
+    (``sings_amd.video``) and ``jpeg_layout``'s ``ws_bytes``.  Nothing is allocated here."""
+    _encoder_tensors("jpeg_encode_frames", K, W, H, _lib.JPEG_TABLE_WORDS, frames, tables, header, ws, out, capacity, sizes)
+    _lib.check(_codec_lib("jpeg").sg_jpeg_encode_frames(int(K), int(W), int(H), int(restart_interval), int(bool(bgr)), _ptr(frames),
+                                                        _ptr(tables), _ptr(header), int(header.numel()), _ptr(ws), int(ws.numel()), _ptr(out),
+                                                        int(capacity), _ptr(sizes), C.c_void_p(stream.cuda_stream)), "sg_jpeg_encode_frames")
 
 
 def png_layout(W, H, K, rows_per_segment, header_bytes):
     """``sg_png_layout`` -> dict of ``_lib.PNG_LAYOUT``: the workspace bytes of K frames, segments per frame, the bytes of a segment and
     of its slot, and the largest file a frame can become (the default capacity)."""
-    out = (C.c_size_t * len(_lib.PNG_LAYOUT))()
-    _lib.check(_png_lib().sg_png_layout(int(W), int(H), int(K), int(rows_per_segment), int(header_bytes), out), "sg_png_layout")
-    return {name: int(v) for name, v in zip(_lib.PNG_LAYOUT, out)}
+    return _codec_layout("png", W, H, K, rows_per_segment, header_bytes)
 
 
 def png_encode_frames(K, W, H, rows_per_segment, filter, bgr, force, frames, tables, header, ws, out, capacity, sizes, stream):
-    """``sg_png_encode_frames`` on ``stream`` (a torch stream): ``frames`` uint8 [K,H,W,3]; ``filter`` 0..5 (SG_PNG_FILTER_*); ``force``
-    -1 or a candidate; ``tables`` ``_lib.PNG_TABLE_WORDS`` int32 words and ``header`` uint8, the caller's (``sings_amd.png``); ``ws``
-    uint8, ``png_layout``'s ``ws_bytes``; ``out`` uint8 rows of ``capacity`` bytes (its row pitch) and ``sizes`` int32 [K].  Nothing is
+    """``sg_png_encode_frames`` on ``stream`` (a torch stream): ``filter`` 0..5 (SG_PNG_FILTER_*); ``force`` -1 or a candidate;
+    ``_encoder_tensors`` with ``_lib.PNG_TABLE_WORDS`` table words (``sings_amd.png``) and ``png_layout``'s ``ws_bytes``.  Nothing is
     allocated here."""
-    dev = frames.device
-    for name, t, dt, least in (("frames", frames, torch.uint8, int(K) * int(H) * int(W) * 3), ("tables", tables, torch.int32, _lib.PNG_TABLE_WORDS),
-                               ("header", header, torch.uint8, 1), ("ws", ws, torch.uint8, 1),
-                               ("out", out, torch.uint8, 0), ("sizes", sizes, torch.int32, int(K))):
-        if not torch.is_tensor(t) or not t.is_cuda or t.device != dev or t.dtype != dt:
-            raise RuntimeError(f"png_encode_frames: {name} must be a {dt} tensor on {dev} (no CPU fallback)")
-        if name != "out" and not t.is_contiguous():
-            raise RuntimeError(f"png_encode_frames: {name} must be contiguous")
-        if t.numel() < least:
-            raise ValueError(f"png_encode_frames: {name} holds {t.numel()} elements, {least} needed")
-    if out.dim() != 2 or out.stride(1) != 1 or out.stride(0) != int(capacity) or out.shape[0] < int(K) or out.shape[1] != int(capacity):
-        raise ValueError(f"png_encode_frames: out must be [>= {int(K)}, {int(capacity)}] uint8 with rows of capacity bytes, got "
-                         f"{tuple(out.shape)} strides {tuple(out.stride())}")
-    _lib.check(_png_lib().sg_png_encode_frames(int(K), int(W), int(H), int(rows_per_segment), int(filter), int(bool(bgr)), int(force),
-                                               _ptr(frames), _ptr(tables), _ptr(header), int(header.numel()), _ptr(ws), int(ws.numel()),
-                                               _ptr(out), int(capacity), _ptr(sizes), C.c_void_p(stream.cuda_stream)),
+    _encoder_tensors("png_encode_frames", K, W, H, _lib.PNG_TABLE_WORDS, frames, tables, header, ws, out, capacity, sizes)
+    _lib.check(_codec_lib("png").sg_png_encode_frames(int(K), int(W), int(H), int(rows_per_segment), int(filter), int(bool(bgr)), int(force),
+                                                      _ptr(frames), _ptr(tables), _ptr(header), int(header.numel()), _ptr(ws), int(ws.numel()),
+                                                      _ptr(out), int(capacity), _ptr(sizes), C.c_void_p(stream.cuda_stream)),
                "sg_png_encode_frames")
-
-
-# ---- PNG files to the frame store (csrc/sg_unpng.hip)
-def _unpng_lib():
-    lib = _lib.load()
-    if not _lib.HAS_UNPNG:
-        raise RuntimeError("the loaded library predates include/sings_unpng.h (no fallback): rebuild it")
-    return lib
 
 
 def unpng_layout(n_streams, max_raw_bytes):
     """``sg_unpng_layout`` -> dict of ``_lib.UNPNG_LAYOUT``: the workspace bytes of ``n_streams`` streams of at most ``max_raw_bytes``
     filtered scanline bytes each, and the bytes of a stream's slot."""
-    out = (C.c_size_t * len(_lib.UNPNG_LAYOUT))()
-    _lib.check(_unpng_lib().sg_unpng_layout(int(n_streams), int(max_raw_bytes), out), "sg_unpng_layout")
-    return {name: int(v) for name, v in zip(_lib.UNPNG_LAYOUT, out)}
+    return _codec_layout("unpng", n_streams, max_raw_bytes)
 
 
 def unpng_decode(n, streams, table, ws, dst, status, stream):
     """``sg_unpng_decode`` on ``stream`` (a torch stream): ``streams`` uint8, the concatenated zlib streams; ``table`` int64
     [>= n, ``_lib.UNPNG_TABLE_COLS``], whose offsets and lengths are checked against ``streams`` by the caller; ``ws`` uint8,
     ``unpng_layout``'s ``ws_bytes``; ``dst`` uint8 [F,H,W,4]; ``status`` int32 [>= n].  Nothing is allocated here."""
-    dev = dst.device
-    for name, t, dt, least in (("streams", streams, torch.uint8, 1), ("table", table, torch.int64, int(n) * _lib.UNPNG_TABLE_COLS),
-                               ("ws", ws, torch.uint8, 1), ("dst", dst, torch.uint8, 1), ("status", status, torch.int32, int(n))):
-        if not torch.is_tensor(t) or not t.is_cuda or t.device != dev or t.dtype != dt:
-            raise RuntimeError(f"unpng_decode: {name} must be a {dt} tensor on {dev} (no CPU fallback)")
-        if not t.is_contiguous():
-            raise RuntimeError(f"unpng_decode: {name} must be contiguous")
-        if t.numel() < least:
-            raise ValueError(f"unpng_decode: {name} holds {t.numel()} elements, {least} needed")
+    _codec_tensors("unpng_decode", dst.device, (("streams", streams, torch.uint8, 1), ("table", table, torch.int64, int(n) * _lib.UNPNG_TABLE_COLS),
+                                                ("ws", ws, torch.uint8, 1), ("dst", dst, torch.uint8, 1), ("status", status, torch.int32, int(n))))
     if dst.dim() != 4 or dst.shape[3] != 4:
         raise ValueError(f"unpng_decode: dst must be uint8 [F,H,W,4], got {tuple(dst.shape)}")
     F, H, W = (int(v) for v in dst.shape[:3])
-    _lib.check(_unpng_lib().sg_unpng_decode(int(n), _ptr(streams), _ptr(table), _ptr(ws), int(ws.numel()), _ptr(dst), F, H, W,
-                                            _ptr(status), C.c_void_p(stream.cuda_stream)), "sg_unpng_decode")
+    _lib.check(_codec_lib("unpng").sg_unpng_decode(int(n), _ptr(streams), _ptr(table), _ptr(ws), int(ws.numel()), _ptr(dst), F, H, W,
+                                                   _ptr(status), C.c_void_p(stream.cuda_stream)), "sg_unpng_decode")

@@ -11,7 +11,7 @@
 //                 slot behind the header, followed by its RST marker or EOI.  A frame that does not fit writes nothing.
 //
 // The restart segments are what makes the entropy stage parallel: a segment starts byte-aligned with its DC predictors at 0.
-#include "sg_host.h"
+#include "sg_codec.h"
 #include "../../include/sings_jpeg.h"
 
 #define SG_JPEG_BLOCK_WAVES 4
@@ -222,24 +222,10 @@ sg_jpeg_scan_kernel(int nseg, int header_bytes, size_t capacity, const uint32_t 
                     int32_t *__restrict__ sizes)
 {
     __shared__ uint32_t sm[256];
-    const int tid = threadIdx.x, k = blockIdx.x;
-    uint32_t running = (uint32_t)header_bytes;                    // (< 2^31 with every segment at its worst: refused otherwise)
-    for (int s0 = 0; s0 < nseg; s0 += 256) {
-        const int s = s0 + tid;
-        const uint32_t v = s < nseg ? seg_bytes[(size_t)k * (size_t)nseg + (size_t)s] + 2u : 0u;      // + its RST marker / EOI
-        sm[tid] = v;
-        __syncthreads();
-        for (int d = 1; d < 256; d <<= 1) {
-            const uint32_t t = tid >= d ? sm[tid - d] : 0u;
-            __syncthreads();
-            sm[tid] += t;
-            __syncthreads();
-        }
-        if (s < nseg) seg_off[(size_t)k * (size_t)nseg + (size_t)s] = running + sm[tid] - v;
-        running += sm[255];
-        __syncthreads();
-    }
-    if (tid == 0) sizes[k] = (size_t)running <= capacity ? (int32_t)running : -(int32_t)running;
+    const int k = blockIdx.x;
+    // a segment, then its RST marker / EOI (the end is < 2^31 with every segment at its worst: refused otherwise)
+    const uint32_t running = (uint32_t)sg_codec_segment_offsets(k, nseg, 2u, header_bytes, seg_bytes, seg_off, sm);
+    if (threadIdx.x == 0) sizes[k] = (size_t)running <= capacity ? (int32_t)running : -(int32_t)running;
 }
 
 // grid: (segments, K)
@@ -317,11 +303,7 @@ extern "C" int sg_jpeg_encode_frames(int K, int width, int height, int restart_i
     if (!frames || !tables || !header || !ws || !out || !sizes) return sg_failf("%s: null pointer", who);
     SgJpegPlan p;
     if (sg_jpeg_plan(who, width, height, K, restart_interval, header_bytes, &p)) return 1;
-    if (capacity < 1 || capacity >= ((size_t)1 << 31)) return sg_failf("%s: capacity = %llu bytes per frame", who, (unsigned long long)capacity);
-    if (ws_bytes < p.ws_bytes)
-        return sg_failf("%s: a workspace of %llu bytes, sg_jpeg_layout asks for %llu", who, (unsigned long long)ws_bytes,
-                        (unsigned long long)p.ws_bytes);
-    if ((uintptr_t)ws & 15) return sg_failf("%s: the workspace must be 16-byte aligned", who);
+    if (sg_codec_check_buffers(who, "sg_jpeg_layout", capacity, ws, ws_bytes, p.ws_bytes)) return 1;
     hipStream_t st = (hipStream_t)stream;
     uint8_t *base = (uint8_t *)ws;
     int16_t *coef = (int16_t *)(base + p.coef_off);

@@ -14,7 +14,7 @@
 //   scan          per frame: where every chunk starts, the file's size (or -needed), the Adler-32 from the rows' partials, and the
 //                 last 30 bytes of the file (the closing IDAT with its CRC, and IEND).
 //   gather        one workgroup per segment: length, "IDAT", data, CRC behind the header; the last one appends the 30 bytes.
-#include "sg_host.h"
+#include "sg_codec.h"
 #include "../../include/sings_png.h"
 
 #define SG_PNG_LDS_WORDS 256                     // a round's bits: < 32 carried + 3215 (a 32 767-byte run closed) + 960 (64 literals) + 15
@@ -338,22 +338,8 @@ sg_png_scan_kernel(int H, int L, int nseg, int header_bytes, size_t capacity, co
     __shared__ uint32_t sm[256];
     __shared__ unsigned long long red[4][2];
     const int tid = threadIdx.x, k = blockIdx.x;
-    unsigned long long running = (unsigned long long)header_bytes;
-    for (int s0 = 0; s0 < nseg; s0 += 256) {
-        const int s = s0 + tid;
-        const uint32_t v = s < nseg ? seg_bytes[(size_t)k * (size_t)nseg + (size_t)s] + 12u : 0u;     // + length, type and CRC
-        sm[tid] = v;
-        __syncthreads();
-        for (int d = 1; d < 256; d <<= 1) {
-            const uint32_t t = tid >= d ? sm[tid - d] : 0u;
-            __syncthreads();
-            sm[tid] += t;
-            __syncthreads();
-        }
-        if (s < nseg) seg_off[(size_t)k * (size_t)nseg + (size_t)s] = (uint32_t)running + sm[tid] - v;
-        running += sm[255];
-        __syncthreads();
-    }
+    // a segment inside its chunk: + length, type and CRC
+    const unsigned long long running = sg_codec_segment_offsets(k, nseg, 12u, header_bytes, seg_bytes, seg_off, sm);
     // Adler-32 of the H scanlines from their partials: a = 1 + sum A_r, b = H L + sum (B_r + (H - 1 - r) L A_r), modulo 65521
     unsigned long long sa = 0, sb = 0;
     for (int r = tid; r < H; r += 256) {
@@ -486,11 +472,7 @@ extern "C" int sg_png_encode_frames(int K, int width, int height, int rows_per_s
     if (sg_png_plan(who, width, height, K, rows_per_segment, header_bytes, &p)) return 1;
     if (filter < SG_PNG_FILTER_NONE || filter > SG_PNG_FILTER_ADAPTIVE) return sg_failf("%s: filter = %d, 0..%d", who, filter, SG_PNG_FILTER_ADAPTIVE);
     if (force < -1 || force > SG_PNG_TABLES) return sg_failf("%s: force = %d, -1 or a candidate 0..%d", who, force, SG_PNG_TABLES);
-    if (capacity < 1 || capacity >= ((size_t)1 << 31)) return sg_failf("%s: capacity = %llu bytes per frame", who, (unsigned long long)capacity);
-    if (ws_bytes < p.ws_bytes)
-        return sg_failf("%s: a workspace of %llu bytes, sg_png_layout asks for %llu", who, (unsigned long long)ws_bytes,
-                        (unsigned long long)p.ws_bytes);
-    if ((uintptr_t)ws & 15) return sg_failf("%s: the workspace must be 16-byte aligned", who);
+    if (sg_codec_check_buffers(who, "sg_png_layout", capacity, ws, ws_bytes, p.ws_bytes)) return 1;
     hipStream_t st = (hipStream_t)stream;
     uint8_t *base = (uint8_t *)ws;
     uint8_t *lines = base + p.lines_off, *tails = base + p.tails_off, *slots = base + p.slots_off;

@@ -1,11 +1,11 @@
 """Frames out as PNG files encoded on the device.
 
-Every picture the reference writes is a PNG.  Here the K uint8 frames an animation launch already produces (``posed.frames_to_u8``) are
+Every picture the reference writes is a PNG.  Here the K uint8 frames an animation launch already produces (``frame_out.frames_to_u8``) are
 filtered, deflated and wrapped into K complete PNG files by four HIP launches (``sg_png_encode_frames``, include/sings_png.h) and read
 back in one copy.
 
- * ``PngEncoder``: pre-allocated workspaces for K frames of W x H; ``encode`` (device buffers, legal inside a graph capture) and
-   ``encode_to_host`` (a list of ``bytes``).
+ * ``PngEncoder`` (on ``codec._FrameEncoder``): pre-allocated workspaces for K frames of W x H; ``encode`` (device buffers, legal
+   inside a graph capture) and ``encode_to_host`` (a list of ``bytes``).
  * ``png_encode_host``: the numpy twin -- the same stream, byte for byte, without a device.  It is the restatement the device path is
    tested against, not a fallback: nothing in the product calls it.
  * ``animate_to_frames``: ``posed.animate_chunk(out="png")`` into numbered files -- the reference's ``animate(keep_images=True)``.
@@ -23,7 +23,8 @@ import zlib
 
 import numpy as np
 
-MAX_FRAMES = 16                      # SG_PNG_MAX_FRAMES
+from .codec import MAX_FRAMES, _FrameEncoder       # MAX_FRAMES: SG_PNG_MAX_FRAMES
+
 MAX_WIDTH = 10922                    # SG_PNG_MAX_WIDTH: a scanline (1 + 3 W bytes) must fit in a segment
 MAX_HEIGHT = 65535                   # SG_PNG_MAX_HEIGHT
 MAX_SEGMENT_BYTES = 32768            # SG_PNG_MAX_SEGMENT_BYTES
@@ -362,76 +363,40 @@ def png_encode_host(frames_u8, filter="adaptive", rows_per_segment=None, bgr=Fal
 
 
 # ---- the device encoder
-class PngEncoder:
+class PngEncoder(_FrameEncoder):
     """K frames of W x H, uint8 RGB (or BGR), to K PNG files per call (``sg_png_encode_frames``: filter pass, deflate pass, scan and
     gather, on torch's current stream or ``stream``).  Everything is allocated here: ``encode`` allocates and synchronises nothing, so
     it may be captured into a graph.  ``capacity``: bytes per frame of the output; the default is the largest file a frame can
     become, so nothing ever overflows it.  With a smaller capacity a frame that needs more reports ``sizes[k] = -needed`` and writes
-    nothing (so does a frame whose forced candidate outgrows the default)."""
+    nothing (so does a frame whose forced candidate outgrows the default), and ``encode_to_host`` raises RuntimeError."""
+    _INCLUDE, _FLAG, _TWIN, _DEFAULT_CAPACITY = "sings_png.h", "HAS_PNG", "png_encode_host", "worst_bytes"
 
     def __init__(self, W, H, K, device, filter="adaptive", rows_per_segment=None, capacity=None):
-        import torch
-        from . import _lib, _marshal
         self.W, self.H, self.rows_per_segment = _check_geometry(W, H, rows_per_segment)
         self.filter = filter
         self._filter = _check_filter(filter)
-        self.K = int(K)
-        if not 1 <= self.K <= MAX_FRAMES:
-            raise ValueError(f"PngEncoder: K = {K} outside 1..{MAX_FRAMES}")
-        if capacity is not None and int(capacity) < 1:
-            raise ValueError(f"PngEncoder: capacity = {capacity} bytes per frame")
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise RuntimeError("sings_amd.png.PngEncoder runs on the MI355X only; there is no CPU fallback (png_encode_host is the "
-                               "numpy restatement the tests compare it with)")
-        _lib.load()
-        if not _lib.HAS_PNG:
-            raise RuntimeError("PngEncoder: the loaded library predates include/sings_png.h (no fallback): rebuild it")
-        self.header = png_header(self.W, self.H)
-        self.layout = _marshal.png_layout(self.W, self.H, self.K, self.rows_per_segment, len(self.header))
-        self.capacity = self.layout["worst_bytes"] if capacity is None else int(capacity)
-        with torch.cuda.device(self.dev):
-            self._tables = torch.from_numpy(device_tables().view(np.int32)).to(self.dev)
-            self._header = torch.frombuffer(bytearray(self.header), dtype=torch.uint8).to(self.dev)
-            self._ws = torch.empty(self.layout["ws_bytes"], dtype=torch.uint8, device=self.dev)
-            self.sizes = torch.zeros(self.K, dtype=torch.int32, device=self.dev)
-            self.buf = torch.empty((self.K, self.capacity), dtype=torch.uint8, device=self.dev)
+        super().__init__(K, device, capacity)
 
-    def encode(self, frames_u8, bgr=False, stream=None, force=-1, out=None):
-        """``frames_u8``: uint8 [k,H,W,3] on the device, k <= K -> (buf [k, capacity] uint8, sizes [k] int32), views of the encoder's
-        own buffers: the next ``encode`` overwrites them.  ``sizes[i]`` bytes of row i are frame i's file; a negative size is minus
-        the bytes that frame needs (nothing of it was written).  ``force``: -1, or the candidate every segment takes.  ``out``: (buf
-        [K', capacity'] uint8, sizes int32) of the caller's to write instead."""
-        import torch
+    def _describe(self):
         from . import _marshal
-        if (not torch.is_tensor(frames_u8) or frames_u8.device != self.dev or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4
-                or tuple(frames_u8.shape[1:]) != (self.H, self.W, 3) or not 1 <= frames_u8.shape[0] <= self.K):
-            raise ValueError(f"PngEncoder.encode: uint8 [1..{self.K},{self.H},{self.W},3] on {self.dev} expected, got "
-                             f"{getattr(frames_u8, 'dtype', type(frames_u8).__name__)} {tuple(getattr(frames_u8, 'shape', ()))}")
+        header = png_header(self.W, self.H)
+        return header, device_tables(), _marshal.png_layout(self.W, self.H, self.K, self.rows_per_segment, len(header))
+
+    def _launch(self, k, frames, bgr, buf, sizes, stream, force=-1):
+        from . import _marshal
         if not -1 <= int(force) <= TABLES:
             raise ValueError(f"PngEncoder.encode: force = {force} outside -1..{TABLES}")
-        x = frames_u8.contiguous()
-        k = int(x.shape[0])
-        buf, sizes = (self.buf, self.sizes) if out is None else out
-        if stream is None:
-            stream = torch.cuda.current_stream(self.dev)
-        _marshal.png_encode_frames(k, self.W, self.H, self.rows_per_segment, self._filter, bgr, int(force), x, self._tables,
+        _marshal.png_encode_frames(k, self.W, self.H, self.rows_per_segment, self._filter, bgr, int(force), frames, self._tables,
                                    self._header, self._ws, buf, int(buf.shape[1]), sizes, stream)
-        return buf[:k], sizes[:k]
+
+    def encode(self, frames_u8, bgr=False, stream=None, force=-1, out=None):
+        """``_FrameEncoder.encode``; ``force``: -1, or the candidate every segment takes."""
+        return super().encode(frames_u8, bgr, stream, out, force=force)
 
     def encode_to_host(self, frames_u8, bgr=False, force=-1):
-        """-> a list of k ``bytes``.  One copy of ``sizes``, then one copy of the used bytes to pinned memory.  RuntimeError when a
-        frame does not fit ``capacity`` (a capacity of the caller's, or a forced candidate)."""
-        import torch
-        buf, sizes = self.encode(frames_u8, bgr, force=force)
-        n = sizes.cpu().tolist()
-        if min(n) < 0:
-            raise RuntimeError(f"PngEncoder: a frame needs {-min(n)} bytes, the capacity is {self.capacity}")
-        m = max(n)
-        host = torch.empty((len(n), m), dtype=torch.uint8).pin_memory()
-        host.copy_(buf[:, :m])
-        rows = host.numpy()
-        return [rows[i, :n[i]].tobytes() for i in range(len(n))]
+        """``_FrameEncoder.encode_to_host``: RuntimeError when a frame does not fit ``capacity`` (a capacity of the caller's, or a
+        forced candidate)."""
+        return super().encode_to_host(frames_u8, bgr, force=force)
 
 
 def write_atomic(path, data):

@@ -19,8 +19,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._marshal import _ptr, _stream
 from .body import SMPL_PARENTS, rodrigues
+from .frame_out import JPEG_QUALITY, FrameOut, frames_to_u8, parse_out       # noqa: F401 (frames_to_u8, JPEG_QUALITY: their names here)
 from .overflow import EngineCapacity
 from .renderer import _settings, get_render_pkg_fused
 
@@ -109,85 +109,6 @@ def forward_chunk(gs_attrs, lbs_weights, A_t2pose, inv_A_t2cano=None, transl=Non
     }
 
 
-def frames_to_u8(img, bgr=False):
-    """[3,H,W] or [K,3,H,W] fp32 frames on the GPU -> uint8 [H,W,3] / [K,H,W,3] on the GPU: the reference's last step,
-    ``(clamp(x, 0, 1) * 255).astype(uint8)`` (+ cvtColor to BGR with ``bgr``: gs_trainer.py:717-719), in ONE launch
-    (sg_frames_to_u8; NaN gives 0).  A quarter of the fp32 bytes to copy to the host."""
-    import ctypes as C
-    if not torch.is_tensor(img) or img.device.type != "cuda":
-        raise RuntimeError("sings_amd.posed.frames_to_u8 runs on the MI355X only; there is no CPU fallback")
-    if img.dtype != torch.float32 or img.dim() not in (3, 4) or img.shape[-3] != 3:
-        raise ValueError(f"frames_to_u8: fp32 [3,H,W] or [K,3,H,W] expected, got {img.dtype} {tuple(img.shape)}")
-    x = img.contiguous()
-    K, H, W = (1 if x.dim() == 3 else int(x.shape[0])), int(x.shape[-2]), int(x.shape[-1])
-    out = torch.empty(tuple(x.shape[:-3]) + (H, W, 3), dtype=torch.uint8, device=x.device)
-    if out.numel() == 0:
-        return out
-    _lib.check(_lib.load().sg_frames_to_u8(K, W, H, _ptr(x), int(bool(bgr)), _ptr(out),
-                                           _stream(x.device)), "frames_to_u8")
-    return out
-
-
-# out= of the animation paths -> frames_to_u8(bgr=...); "jpeg" / "png": RGB bytes, then ``video.JpegEncoder`` / ``png.PngEncoder`` (a
-# ``bytes`` per frame)
-_OUT = {"float32": None, "rgb8": False, "bgr8": True, "jpeg": False, "png": False}
-JPEG_QUALITY = 90                    # of out="jpeg"; out=("jpeg", quality) names another
-
-
-def _out_bgr(out):
-    if _out_jpeg(out) is not None:
-        return _OUT["jpeg"]
-    if not isinstance(out, str) or out not in _OUT:
-        raise ValueError(f"out must be one of {sorted(_OUT)} (or (\"jpeg\", quality)), got {out!r}")
-    return _OUT[out]
-
-
-def _out_jpeg(out):
-    """The JPEG quality ``out`` asks for -- "jpeg": ``JPEG_QUALITY``; ("jpeg", q): q in 1..100 -- or None for every other output."""
-    if out == "jpeg":
-        return JPEG_QUALITY
-    if isinstance(out, tuple) and len(out) == 2 and out[0] == "jpeg":
-        if not isinstance(out[1], int) or not 1 <= out[1] <= 100:
-            raise ValueError(f"out=(\"jpeg\", quality): quality must be an int in 1..100, got {out[1]!r}")
-        return out[1]
-    return None
-
-
-class _PngOut:
-    """The ``out="png"`` step behind ``frames_to_u8``, as ``_JpegOut``: ``u8`` [k,H,W,3] RGB bytes -> k ``bytes``, each a PNG file
-    (``png.PngEncoder.encode_to_host``).  One encoder per (W, H, K)."""
-
-    def __init__(self, dev):
-        self.dev, self.key, self.enc = dev, None, None
-
-    def __call__(self, u8, K):
-        key = (int(u8.shape[2]), int(u8.shape[1]), int(K))
-        if key != self.key:
-            from .png import PngEncoder
-            self.enc = None                                      # (drop the old workspaces before the new ones are sized)
-            self.enc = PngEncoder(key[0], key[1], key[2], self.dev)
-            self.key = key
-        return self.enc.encode_to_host(u8)
-
-
-class _JpegOut:
-    """The ``out="jpeg"`` step behind ``frames_to_u8``: ``u8`` [k,H,W,3] RGB bytes of a batch that has been handed out -> k ``bytes``
-    (``video.JpegEncoder.encode_to_host`` on the caller's stream: one read of the sizes, one of the used bytes).  One encoder per
-    (W, H, K, quality) -- what of an engine key decides an encoder; frames of another size replace it, as they replace the engines."""
-
-    def __init__(self, dev):
-        self.dev, self.key, self.enc = dev, None, None
-
-    def __call__(self, u8, K, quality):
-        key = (int(u8.shape[2]), int(u8.shape[1]), int(K), int(quality))
-        if key != self.key:
-            from .video import JpegEncoder
-            self.enc = None                                      # (drop the old workspaces before the new ones are sized)
-            self.enc = JpegEncoder(key[0], key[1], key[2], self.dev, quality=key[3])
-            self.key = key
-        return self.enc.encode_to_host(u8)
-
-
 def _shared(ts):
     """The tensors of a batch's frames are one and the same values: the same object, or views of the same memory (the frames'
     rows of an ``.expand`` view)."""
@@ -235,7 +156,11 @@ def _stack_cameras(cams, K, bg_color, scaling_modifier, sh_degree):
 _capacity_floor, _grown = EngineCapacity.floor, EngineCapacity.grown      # (the names the two rules had in this module)
 
 
-def _batches(jobs, K, kind=lambda job: (job[3] is None, job[4] is None)):
+def _optional_inputs(job):
+    return job[3] is None, job[4] is None
+
+
+def _batches(jobs, K, kind=_optional_inputs):
     """The job stream as (index of the first job, batch): at most K consecutive jobs per batch, and a new batch where ``kind(job)``
     -- ``(smpl_scale is None, ext_tfs is None)`` -- changes (frames with and without scale / placement cannot share a launch)."""
     batch, i0 = [], 0
@@ -267,8 +192,7 @@ class FrameAnimator:
         self.streams = [torch.cuda.Stream(self.dev) for _ in range(self.n)]
         self.engs, self.key, self.cap = [], None, 0
         self.policy = EngineCapacity()
-        self._jpeg = _JpegOut(self.dev)
-        self._png = _PngOut(self.dev)
+        self._out = FrameOut(self.dev)
 
     long_rows = property(lambda self: self.policy.long_rows)
 
@@ -406,26 +330,30 @@ class FrameAnimator:
         ``return_aux``: yields (index, image, depth [1,H,W], alpha [1,H,W]) -- the maps of
         ``get_render_pkg_fused(return_aux=True)``, re-rendered fallbacks included; the maps stay fp32."""
         c = self.canon
-        bgr = _out_bgr(out)
-        K = max(1, min(int(frames_per_launch), 16))
-        quality = _out_jpeg(out)
-        jpeg = None if quality is None else (lambda u8: self._jpeg(u8, K, quality))
-        if out == "png":
-            jpeg = lambda u8: self._png(u8, K)
 
-        def launch(e, batch):
-            A, tr, sc, ext = _stack_poses([j[1:] for j in batch], K)
-            rs = _stack_cameras([j[0] for j in batch], K, bg_color, scaling_modifier, c['active_sh_degree'])
+        def set_inputs(e, batch):
+            A, tr, sc, ext = _stack_poses([j[1:] for j in batch], e.K)
+            rs = _stack_cameras([j[0] for j in batch], e.K, bg_color, scaling_modifier, c['active_sh_degree'])
             e.set_camera(rs, long_rows=self.long_rows)
             e.set_frames(c['xyz_canon'], c.get('rotmat_canon'), c['lbs_weights'], A, sc, tr, ext)
             e.forward(c['shs'], c['opacity'], c['scales'])
+
+        return self._render_batched(jobs, set_inputs, _optional_inputs, frames_per_launch, out, return_aux)
+
+    def _render_batched(self, jobs, set_inputs, kind, frames_per_launch, out, return_aux):
+        """The body of ``render_frames_batched``, here and in ``scene_anim.SceneAnimator``: ``set_inputs(e, batch)`` renders a batch of
+        at most ``e.K`` jobs through engine ``e`` on the current stream; ``kind(job)``: what must agree within a batch (``_batches``)."""
+        spec = parse_out(out)
+        K = max(1, min(int(frames_per_launch), _lib.MAX_FRAMES))
+
+        def launch(e, batch):
+            set_inputs(e, batch)
             # [K,3,H,W] (or [K,H,W,3] uint8): a new tensor, the engine's image buffer is reused (so are its map buffers)
-            img = torch.clamp(e.color, 0.0, 1.0) if bgr is None else frames_to_u8(e.color, bgr)
+            img = self._out.convert(spec, e.color)
             return (img, e.depth.clone(), e.alpha.clone()) if return_aux else (img,)
 
-        for i0, batch, outs in self._pipeline(_batches(jobs, K), launch, K=K, aux=return_aux):
-            if jpeg is not None:
-                outs = (jpeg(outs[0][:len(batch)]),) + tuple(outs[1:])
+        for i0, batch, outs in self._pipeline(_batches(jobs, K, kind), launch, K=K, aux=return_aux):
+            outs = (self._out.finish(spec, outs[0], len(batch)),) + tuple(outs[1:])
             for k in range(len(batch)):
                 yield (i0 + k,) + tuple(t[k] for t in outs)
 
@@ -451,18 +379,28 @@ def animate_chunk(canon, poses, joints_rest, A_t2cano, cameras, bg_color, transl
     return_aux: yields (f, image, depth [1,H,W], alpha [1,H,W]) -- the maps of get_render_pkg_fused(return_aux=True), fp32 -- on the
     K-frame path and on the plain per-frame loop; the ``streams`` > 1 per-frame path (render_frames) has no maps: ValueError."""
     F = poses.shape[0]
-    bgr = _out_bgr(out)
-    to_out = (lambda img: img) if bgr is None else (lambda img: frames_to_u8(img, bgr))
-    if _out_jpeg(out) is not None:
-        one = _JpegOut(canon['xyz_canon'].device)
-        to_out = lambda img: one(frames_to_u8(img, False)[None], 1, _out_jpeg(out))[0]
-    if out == "png":
-        one_png = _PngOut(canon['xyz_canon'].device)
-        to_out = lambda img: one_png(frames_to_u8(img, False)[None], 1)[0]
+    spec = parse_out(out)
+    one = FrameOut(canon['xyz_canon'].device)                     # of the two per-frame paths: K = 1
+
+    def per_frame(img):
+        """A clamped frame [3,H,W] of a per-frame path through the output stage."""
+        return img if spec.bgr is None else one.finish(spec, one.convert(spec, img[None]), 1)[0]
+
     inv_cano = torch.inverse(A_t2cano)
     batched = int(frames_per_launch) > 1
     # one smpl_scale per frame ([F,1] / [F]: frame f's row) or one for all
     scale_of = (lambda f: smpl_scale) if smpl_scale is None or smpl_scale.numel() == 1 else (lambda f: smpl_scale.reshape(-1, 1)[f])
+
+    def jobs(jt):
+        """The frames as ``FrameAnimator.render_round``'s tuples, the kinematic chain ``jt`` frames at a time."""
+        for c0 in range(0, F, jt):
+            A = joint_transforms_batch(poses[c0:c0 + jt], joints_rest, parents) @ inv_cano[None]
+            for i in range(A.shape[0]):
+                f = c0 + i
+                yield (cameras[f] if isinstance(cameras, (list, tuple)) else cameras, A[i],
+                       None if transl is None else transl[f], scale_of(f),
+                       None if ext_tfs is None else (ext_tfs[0][f], ext_tfs[1][f], ext_tfs[2][f]))
+
     if animator is None and (streams > 1 or batched):
         animator = FrameAnimator(canon, streams)
     if animator is not None:
@@ -470,34 +408,19 @@ def animate_chunk(canon, poses, joints_rest, A_t2cano, cameras, bg_color, transl
         # the frames of chunk k are still in flight -- nothing drains between chunks
         # (the kinematic chain is ~80 small launches per chunk whatever its size: at least 128 frames per chain here)
         jt = max(int(chunk_size), 128)
-
-        def jobs():
-            for c0 in range(0, F, jt):
-                A = joint_transforms_batch(poses[c0:c0 + jt], joints_rest, parents) @ inv_cano[None]
-                for i in range(A.shape[0]):
-                    f = c0 + i
-                    yield (cameras[f] if isinstance(cameras, (list, tuple)) else cameras, A[i],
-                           None if transl is None else transl[f], scale_of(f),
-                           None if ext_tfs is None else (ext_tfs[0][f], ext_tfs[1][f], ext_tfs[2][f]))
         if batched:
-            yield from animator.render_frames_batched(jobs(), bg_color, frames_per_launch=int(frames_per_launch), out=out,
+            yield from animator.render_frames_batched(jobs(jt), bg_color, frames_per_launch=int(frames_per_launch), out=out,
                                                       return_aux=return_aux)
         elif return_aux:
             raise ValueError("animate_chunk: return_aux needs frames_per_launch > 1 or the per-frame loop (streams=1, no animator); "
                              "FrameAnimator.render_frames has no depth / alpha maps")
         else:
-            for f, img in animator.render_frames(jobs(), bg_color):
-                yield f, to_out(img)
+            for f, img in animator.render_frames(jobs(jt), bg_color):
+                yield f, per_frame(img)
         return
-    for c0 in range(0, F, chunk_size):
-        A = joint_transforms_batch(poses[c0:c0 + chunk_size], joints_rest, parents) @ inv_cano[None]
-        for i in range(A.shape[0]):
-            f = c0 + i
-            cam = cameras[f] if isinstance(cameras, (list, tuple)) else cameras
-            ext = None if ext_tfs is None else (ext_tfs[0][f], ext_tfs[1][f], ext_tfs[2][f])
-            pkg = get_render_pkg_fused(cam, canon, A[i], bg_color, smpl_scale=scale_of(f),
-                                       transl=None if transl is None else transl[f], ext_tfs=ext, return_aux=return_aux)
-            if return_aux:
-                yield f, to_out(pkg["render"]), pkg["depth"], pkg["alpha"]
-            else:
-                yield f, to_out(pkg["render"])
+    for f, (cam, A, tr, sc, ext) in enumerate(jobs(chunk_size)):
+        pkg = get_render_pkg_fused(cam, canon, A, bg_color, smpl_scale=sc, transl=tr, ext_tfs=ext, return_aux=return_aux)
+        if return_aux:
+            yield f, per_frame(pkg["render"]), pkg["depth"], pkg["alpha"]
+        else:
+            yield f, per_frame(pkg["render"])

@@ -84,11 +84,12 @@ class RunOutputs:
 
     def _put_png(self, rels, u8):
         """``device_png``: ``u8`` uint8 [k,H,W,3] on the GPU -> the k files ``rels``, encoded in one call (one encoder per (W, H, K))."""
-        from .png import PngEncoder, write_atomic
+        from .frame_out import new_encoder
+        from .png import write_atomic
         k, H, W = (int(n) for n in u8.shape[:3])
         K = max(k, self.frames_per_launch if k > 1 else 1)
-        if (W, H, K) not in self._png_encoders:
-            self._png_encoders[W, H, K] = PngEncoder(W, H, K, u8.device)
+        if (W, H, K) not in self._png_encoders:                  # (kept for the run: the pictures alternate between three sizes)
+            self._png_encoders[W, H, K] = new_encoder("png", W, H, K, u8.device)
         for rel, data in zip(rels, self._png_encoders[W, H, K].encode_to_host(u8.contiguous())):
             path = os.path.join(self.logdir, rel)
             os.makedirs(os.path.dirname(path), exist_ok=True)
@@ -142,11 +143,12 @@ class RunOutputs:
 
     def _append_video(self, sheet):
         """``sheet``: uint8 [Hs,Ws,3] on the GPU -> one more frame of the progress video (opened at the first sheet)."""
-        from .video import JpegEncoder, MjpegWriter
+        from .frame_out import new_encoder
+        from .video import MjpegWriter
         Hs, Ws = int(sheet.shape[0]), int(sheet.shape[1])
         if self._video is None:
             os.makedirs(self.logdir, exist_ok=True)
-            self._video_encoder = JpegEncoder(Ws, Hs, 1, sheet.device, quality=int(self.video_quality))
+            self._video_encoder = new_encoder("jpeg", Ws, Hs, 1, sheet.device, self.video_quality)
             self._video = MjpegWriter(self.video_path, Ws, Hs, 10)                 # fps=10: gs_trainer.py:465
         self._video.write(self._video_encoder.encode_to_host(sheet[None].contiguous())[0])
 

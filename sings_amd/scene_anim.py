@@ -21,7 +21,7 @@ from . import _lib
 from ._marshal import _frame_rows, _ptr, _scene_structs
 from .body import SMPL_PARENTS
 from .engine import _FramesEngine
-from .posed import (FrameAnimator, _batches, _out_bgr, _out_jpeg, _stack_cameras, _stack_poses, frames_to_u8, joint_transforms_batch)
+from .posed import FrameAnimator, _stack_cameras, _stack_poses, joint_transforms_batch
 
 _FORWARD_ONLY = "SceneFramesEngine: a scene of avatars is forward-only (the reference renders it under no_grad)"
 
@@ -190,31 +190,19 @@ class SceneAnimator(FrameAnimator):
         other optional inputs than its neighbour's starts a new batch.  Yields (index, clamped image) in order -- with ``out`` "rgb8" /
         "bgr8" uint8 [H,W,3] (``frames_to_u8``), with "jpeg" / ("jpeg", quality) or "png" a ``bytes`` per frame (a JPEG / PNG file, encoded on
         the device as in ``FrameAnimator.render_frames_batched``), with ``return_aux`` (index, image, depth [1,H,W], alpha [1,H,W])."""
-        bgr = _out_bgr(out)
-        K = max(1, min(int(frames_per_launch), _lib.MAX_FRAMES))
-        quality = _out_jpeg(out)
-        jpeg = None if quality is None else (lambda u8: self._jpeg(u8, K, quality))
-        if out == "png":
-            jpeg = lambda u8: self._png(u8, K)
         deg = self.canons[0]['active_sh_degree']
 
-        def launch(e, batch):
-            e.set_camera(_stack_cameras([j[0] for j in batch], K, bg_color, scaling_modifier, deg), long_rows=self.long_rows)
+        def set_inputs(e, batch):
+            e.set_camera(_stack_cameras([j[0] for j in batch], e.K, bg_color, scaling_modifier, deg), long_rows=self.long_rows)
             frames = []
             for s, c in enumerate(self.canons):
-                A, tr, sc, ext = _stack_poses([j[1][s] for j in batch], K)
+                A, tr, sc, ext = _stack_poses([j[1][s] for j in batch], e.K)
                 frames.append(dict(canon=c, A=A, transl=tr, smpl_scale=sc, ext_tfs=ext))
             e.set_frames(frames)
             e.forward()
-            img = torch.clamp(e.color, 0.0, 1.0) if bgr is None else frames_to_u8(e.color, bgr)
-            return (img, e.depth.clone(), e.alpha.clone()) if return_aux else (img,)
 
         kind = lambda job: tuple(x is None for p in job[1] for x in p[1:])
-        for i0, batch, outs in self._pipeline(_batches(jobs, K, kind), launch, K=K, aux=return_aux):
-            if jpeg is not None:
-                outs = (jpeg(outs[0][:len(batch)]),) + tuple(outs[1:])
-            for k in range(len(batch)):
-                yield (i0 + k,) + tuple(t[k] for t in outs)
+        return self._render_batched(jobs, set_inputs, kind, frames_per_launch, out, return_aux)
 
 
 @torch.no_grad()
@@ -250,10 +238,6 @@ def animate_scene(canons, poses, joints_rest, A_t2cano, cameras, bg_color, trans
 def animate_scene_to_video(path, canons, poses, joints_rest, A_t2cano, cameras, bg_color, fps=20, quality=90, frames_per_launch=8, **kwargs):
     """``video.animate_to_video`` for a scene: ``animate_scene(..., out="jpeg")`` into a Motion-JPEG AVI at ``path`` (``kwargs``:
     ``animate_scene``'s other arguments).  Returns the number of frames written."""
-    from .video import MjpegWriter
-    cam = cameras[0] if isinstance(cameras, (list, tuple)) else cameras
-    with MjpegWriter(path, int(cam["image_width"]), int(cam["image_height"]), fps) as w:
-        for _, data in animate_scene(canons, poses, joints_rest, A_t2cano, cameras, bg_color, frames_per_launch=frames_per_launch,
-                                     out=("jpeg", int(quality)), **kwargs):
-            w.write(data)
-        return w.frames
+    from .video import _write_video
+    return _write_video(path, cameras, fps, animate_scene(canons, poses, joints_rest, A_t2cano, cameras, bg_color,
+                                                          frames_per_launch=frames_per_launch, out=("jpeg", int(quality)), **kwargs))

@@ -1,11 +1,11 @@
 """Frames out as JPEG streams encoded on the device, and Motion-JPEG video.
 
 The reference turns its animation frames into a video by shelling out to ffmpeg (``create_video``, utils/general.py:36).  Here the
-K uint8 frames an animation launch already produces (``posed.frames_to_u8``) are encoded to K complete baseline JPEG files by four
+K uint8 frames an animation launch already produces (``frame_out.frames_to_u8``) are encoded to K complete baseline JPEG files by four
 HIP launches (``sg_jpeg_encode_frames``, include/sings_jpeg.h), read back in one copy, and wrapped into an AVI by a small host writer.
 
- * ``JpegEncoder``: pre-allocated workspaces for K frames of W x H; ``encode`` (device buffers, legal inside a graph capture) and
-   ``encode_to_host`` (a list of ``bytes``; a frame that does not fit its capacity grows the buffer and is encoded again).
+ * ``JpegEncoder`` (on ``codec._FrameEncoder``): pre-allocated workspaces for K frames of W x H; ``encode`` (device buffers, legal
+   inside a graph capture) and ``encode_to_host`` (a list of ``bytes``; a frame that does not fit its capacity grows the buffer and is encoded again).
  * ``jpeg_encode_host``: the numpy twin -- the same stream, byte for byte, without a device.  It is the restatement the device path
    is tested against, not a fallback: nothing in the product calls it.
  * ``MjpegWriter``: RIFF AVI 1.0 with one ``MJPG`` video stream, written atomically, below 2 GiB (no OpenDML).
@@ -23,6 +23,8 @@ import struct
 from fractions import Fraction
 
 import numpy as np
+
+from .codec import MAX_FRAMES, _FrameEncoder       # MAX_FRAMES: SG_JPEG_MAX_FRAMES
 
 # ---- the Annex K tables, as a non-optimised libjpeg file at quality 50 carries them (tests/golden/gen_jpeg_tables.py reads such a
 # file into tests/golden/jpeg_tables.npz; tests/test_video_host.py holds these literals to it).  Quantisation: zig-zag order.
@@ -63,7 +65,6 @@ AC1_VALS = (
 )
 HUFFMAN = (("dc0", DC0_BITS, DC0_VALS), ("ac0", AC0_BITS, AC0_VALS), ("dc1", DC1_BITS, DC1_VALS), ("ac1", AC1_BITS, AC1_VALS))
 
-MAX_FRAMES = 16                      # SG_JPEG_MAX_FRAMES
 MAX_DIM = 65535                      # SG_JPEG_MAX_DIM: a SOF0 dimension is 16 bit
 TABLE_WORDS = 800                    # SG_JPEG_TABLE_WORDS: basis 64 | quantisers 2 x 64 | zig-zag position 64 | Huffman 2 x 272
 HUFF_STRIDE = 272                    # SG_JPEG_HUFF_STRIDE: 16 DC categories, then the 256 AC run/size symbols
@@ -264,83 +265,28 @@ def jpeg_encode_host(frames_u8, quality=90, restart_interval=None, bgr=False, sy
 
 
 # ---- the device encoder
-class JpegEncoder:
+class JpegEncoder(_FrameEncoder):
     """K frames of W x H, uint8 RGB (or BGR), to K baseline JPEG files per call (``sg_jpeg_encode_frames``: block pass, entropy pass,
     scan and gather, on torch's current stream or ``stream``).  Everything is allocated here: ``encode`` allocates and synchronises
     nothing, so it may be captured into a graph.  ``capacity``: bytes per frame of the output (default: header + H W 3 / 2); a frame
-    that needs more reports ``sizes[k] = -needed`` and writes nothing, and ``encode_to_host`` grows the buffer and encodes again."""
+    that needs more reports ``sizes[k] = -needed`` and writes nothing, and ``encode_to_host`` grows the buffer and encodes again (at
+    most twice, RuntimeError after that)."""
+    _INCLUDE, _FLAG, _TWIN, _DEFAULT_CAPACITY, _GROWS = "sings_jpeg.h", "HAS_JPEG", "jpeg_encode_host", "default_capacity", True
 
     def __init__(self, W, H, K, device, quality=90, restart_interval=None, capacity=None):
-        import torch
-        from . import _lib, _marshal
         self.W, self.H, self.ri = _check_geometry(W, H, restart_interval)
-        self.K, self.quality = int(K), int(quality)
-        if not 1 <= self.K <= MAX_FRAMES:
-            raise ValueError(f"JpegEncoder: K = {K} outside 1..{MAX_FRAMES}")
-        self.dev = torch.device(device)
-        if self.dev.type != "cuda":
-            raise RuntimeError("sings_amd.video.JpegEncoder runs on the MI355X only; there is no CPU fallback (jpeg_encode_host is the "
-                               "numpy restatement the tests compare it with)")
-        _lib.load()
-        if not _lib.HAS_JPEG:
-            raise RuntimeError("JpegEncoder: the loaded library predates include/sings_jpeg.h (no fallback): rebuild it")
-        self.header = jpeg_header(self.W, self.H, self.quality, self.ri)
-        self.layout = _marshal.jpeg_layout(self.W, self.H, self.K, self.ri, len(self.header))
-        with torch.cuda.device(self.dev):
-            self._tables = torch.from_numpy(device_tables(self.quality).view(np.int32)).to(self.dev)
-            self._header = torch.frombuffer(bytearray(self.header), dtype=torch.uint8).to(self.dev)
-            self._ws = torch.empty(self.layout["ws_bytes"], dtype=torch.uint8, device=self.dev)
-            self.sizes = torch.zeros(self.K, dtype=torch.int32, device=self.dev)
-        self.buf = None
-        self._allocate(self.layout["default_capacity"] if capacity is None else int(capacity))
+        self.quality = int(quality)
+        super().__init__(K, device, capacity)
 
-    def _allocate(self, capacity):
-        import torch
-        if capacity < 1:
-            raise ValueError(f"JpegEncoder: capacity = {capacity} bytes per frame")
-        self.capacity = int(capacity)
-        self.buf = None                                           # (drop the old buffer before the new one is sized)
-        self.buf = torch.empty((self.K, self.capacity), dtype=torch.uint8, device=self.dev)
-
-    def encode(self, frames_u8, bgr=False, stream=None, out=None):
-        """``frames_u8``: uint8 [k,H,W,3] on the device, k <= K -> (buf [k, capacity] uint8, sizes [k] int32), views of the encoder's
-        own buffers: the next ``encode`` overwrites them.  ``sizes[i]`` bytes of row i are frame i's file; a negative size is minus
-        the bytes that frame needs (nothing of it was written).  ``out``: (buf [K', capacity'] uint8, sizes int32) of the caller's to
-        write instead (a buffer with a guard region behind it, in tests)."""
-        import torch
+    def _describe(self):
         from . import _marshal
-        if (not torch.is_tensor(frames_u8) or frames_u8.device != self.dev or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4
-                or tuple(frames_u8.shape[1:]) != (self.H, self.W, 3) or not 1 <= frames_u8.shape[0] <= self.K):
-            raise ValueError(f"JpegEncoder.encode: uint8 [1..{self.K},{self.H},{self.W},3] on {self.dev} expected, got "
-                             f"{getattr(frames_u8, 'dtype', type(frames_u8).__name__)} {tuple(getattr(frames_u8, 'shape', ()))}")
-        x = frames_u8.contiguous()
-        k = int(x.shape[0])
-        buf, sizes = (self.buf, self.sizes) if out is None else out
-        if stream is None:
-            stream = torch.cuda.current_stream(self.dev)
-        _marshal.jpeg_encode_frames(k, self.W, self.H, self.ri, bgr, x, self._tables, self._header, self._ws, buf, int(buf.shape[1]),
-                                    sizes, stream)
-        return buf[:k], sizes[:k]
+        header = jpeg_header(self.W, self.H, self.quality, self.ri)
+        return header, device_tables(self.quality), _marshal.jpeg_layout(self.W, self.H, self.K, self.ri, len(header))
 
-    def encode_to_host(self, frames_u8, bgr=False):
-        """-> a list of k ``bytes``.  One copy of ``sizes``, then one copy of the used bytes to pinned memory.  A frame that overflows
-        ``capacity`` grows the buffer to what the largest frame needs and the batch is encoded again: at most twice, RuntimeError
-        after that."""
-        import torch
-        for attempt in range(3):
-            buf, sizes = self.encode(frames_u8, bgr)
-            n = sizes.cpu().tolist()
-            if min(n) >= 0:
-                break
-            if attempt == 2:
-                raise RuntimeError(f"JpegEncoder: frames still overflow {self.capacity} bytes after two retries (needed: {-min(n)})")
-            torch.cuda.current_stream(self.dev).synchronize()     # (the buffer is about to be replaced)
-            self._allocate(-min(n))
-        m = max(n)
-        host = torch.empty((len(n), m), dtype=torch.uint8).pin_memory()
-        host.copy_(buf[:, :m])
-        rows = host.numpy()
-        return [rows[i, :n[i]].tobytes() for i in range(len(n))]
+    def _launch(self, k, frames, bgr, buf, sizes, stream):
+        from . import _marshal
+        _marshal.jpeg_encode_frames(k, self.W, self.H, self.ri, bgr, frames, self._tables, self._header, self._ws, buf, int(buf.shape[1]),
+                                    sizes, stream)
 
 
 # ---- Motion-JPEG in a RIFF AVI
@@ -438,14 +384,20 @@ class MjpegWriter:
         return False
 
 
+def _write_video(path, cameras, fps, frames):
+    """``frames``: an iterable of (index, JPEG ``bytes``), in order, of the size of ``cameras`` (one camera dict or a list: the first
+    one's) -> a Motion-JPEG AVI at ``path``.  Returns the number of frames written."""
+    cam = cameras[0] if isinstance(cameras, (list, tuple)) else cameras
+    with MjpegWriter(path, int(cam["image_width"]), int(cam["image_height"]), fps) as w:
+        for _, data in frames:
+            w.write(data)
+        return w.frames
+
+
 def animate_to_video(path, canon, poses, joints_rest, A_t2cano, cameras, bg_color, fps=20, quality=90, frames_per_launch=8, **kwargs):
     """``posed.animate_chunk(..., out=("jpeg", quality))`` into a Motion-JPEG AVI at ``path``: the reference's ``animate_chunk(save_video=True)``
     without ffmpeg.  ``kwargs``: ``animate_chunk``'s other arguments (transl, smpl_scale, ext_tfs, parents, streams, animator).
     Returns the number of frames written."""
     from .posed import animate_chunk
-    cam = cameras[0] if isinstance(cameras, (list, tuple)) else cameras
-    with MjpegWriter(path, int(cam["image_width"]), int(cam["image_height"]), fps) as w:
-        for _, data in animate_chunk(canon, poses, joints_rest, A_t2cano, cameras, bg_color, frames_per_launch=frames_per_launch,
-                                     out=("jpeg", int(quality)), **kwargs):
-            w.write(data)
-        return w.frames
+    return _write_video(path, cameras, fps, animate_chunk(canon, poses, joints_rest, A_t2cano, cameras, bg_color,
+                                                          frames_per_launch=frames_per_launch, out=("jpeg", int(quality)), **kwargs))

@@ -3,7 +3,8 @@ streams of them, computed once per process.
 
 A case is (name, frames uint8 [k,H,W,3], filter, rows_per_segment, bgr).  The sizes are the smallest at which the encoder takes another
 path: one pixel; scanlines of 64, 67 and 256 bytes (a round of the deflate pass is 64 bytes); 200 x 40 in segments of 7 rows, which
-leaves a short last segment and cuts the run of black rows at the top across a segment boundary.
+leaves a short last segment and cuts the run of black rows at the top across a segment boundary; 5 x 260 in segments of one row, more
+segments than the 256 threads of the offset scan take in one round.
 """
 import numpy as np
 
@@ -43,6 +44,7 @@ def cases():
         ("200x40-bgr", body(40, 200, 6, 5)[None], "adaptive", 7, True),
         ("runs", runs_frame(), "none", None, False),
         ("black-85x7", np.zeros((1, 7, 85, 3), dtype=np.uint8), "none", None, False),
+        ("5x260", np.stack([body(260, 5, a, 9) for a in (0, 24)]), "adaptive", 1, False),      # 260 segments: the scan's second round
     ]
     for f in ("none", "sub", "up", "average", "paeth"):
         out.append((f"22x9-{f}", body(9, 22, 6, 6)[None], f, None, False))

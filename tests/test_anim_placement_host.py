@@ -195,7 +195,7 @@ def test_frames_to_u8_refuses_bad_sizes_and_null_pointers():
 
 def test_python_surface():
     import inspect
-    from sings_amd import posed
+    from sings_amd import frame_out, posed
     from sings_amd.engine import SkinnedFramesEngine
     assert list(inspect.signature(SkinnedFramesEngine.set_frames).parameters)[-1] == "ext_tfs"
     for fn in (posed.FrameAnimator.render_frames_batched, posed.animate_chunk):
@@ -204,7 +204,7 @@ def test_python_surface():
     with pytest.raises(RuntimeError, match="no CPU fallback"):
         posed.frames_to_u8(torch.zeros(3, 4, 4))
     with pytest.raises(ValueError, match="out must be one of"):
-        posed._out_bgr("bgr16")
+        frame_out.parse_out("bgr16")
 
 
 def test_frame_rows_shared_or_per_frame():

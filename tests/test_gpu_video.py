@@ -231,6 +231,23 @@ def test_animate_chunk_hands_out_the_twins_streams_and_a_video_of_them(tmp_path)
         assert np.array_equal(bgr8[f].cpu().numpy(), (np.clip(f32[f].cpu().numpy(), 0, 1) * np.float32(255)).astype(np.uint8).transpose(1, 2, 0)[..., ::-1])
 
 
+@pytest.mark.parametrize("out", ["bgr8", "jpeg", ("jpeg", 50), "png"], ids=str)
+def test_the_pipelined_per_frame_path_hands_out_what_the_batched_path_does(out):
+    """``streams=2, frames_per_launch=1``: ``FrameAnimator.render_frames``, the output applied frame by frame behind the hand-out."""
+    from sings_amd.posed import animate_chunk
+    canon, poses, jr, A_cano, data, kw = _one_avatar()
+    bg = torch.ones(3, device=_dev())
+    want = dict(animate_chunk(canon, poses, jr, A_cano, data, bg, frames_per_launch=2, out=out, **kw))
+    got = dict(animate_chunk(canon, poses, jr, A_cano, data, bg, streams=2, frames_per_launch=1, out=out, **kw))
+    assert sorted(got) == sorted(want) == list(range(F_A))
+    for f in range(F_A):
+        if out == "bgr8":
+            assert got[f].dtype == torch.uint8 and tuple(got[f].shape) == (H_A, W_A, 3) and torch.equal(got[f], want[f]), f
+        else:
+            assert isinstance(got[f], bytes) and got[f] == want[f], f
+    assert len({got[f] if isinstance(got[f], bytes) else got[f].cpu().numpy().tobytes() for f in range(F_A)}) == F_A, "five different frames"
+
+
 def test_animate_scene_hands_out_the_twins_streams(tmp_path):
     from test_gpu_scene import _avatar, _cameras
     from sings_amd.body import joint_transforms

@@ -291,7 +291,8 @@ def test_animate_to_frames_and_device_png_attributes_defaults_and_refusals(tmp_p
     assert (sig["filter"].default, sig["rows_per_segment"].default, sig["capacity"].default) == ("adaptive", None, None)
     sig = inspect.signature(P.png_encode_host).parameters
     assert [sig[k].default for k in ("filter", "rows_per_segment", "bgr", "force", "log")] == ["adaptive", None, False, -1, None]
-    assert posed._out_bgr("png") is False and posed._out_jpeg("png") is None
+    from sings_amd.frame_out import parse_out
+    assert parse_out("png").bgr is False and parse_out("png")[1:] == ("png", None)
     for fn in (posed.FrameAnimator.render_frames_batched, posed.animate_chunk, scene_anim.SceneAnimator.render_frames_batched,
                scene_anim.animate_scene):
         assert list(inspect.signature(fn).parameters)[-2:] == ["out", "return_aux"]

@@ -308,15 +308,16 @@ def test_a_writer_closed_by_an_exception_leaves_no_file(tmp_path):
 def test_out_jpeg_is_an_output_of_the_animation_paths():
     import inspect
     from sings_amd import posed, run_outputs, scene_anim
-    assert posed._out_bgr("jpeg") is False and posed._out_bgr("bgr8") is True and posed._out_bgr("float32") is None
-    assert posed._out_bgr(("jpeg", 75)) is False
-    assert posed._out_jpeg("jpeg") == 90 and posed._out_jpeg(("jpeg", 75)) == 75 and posed._out_jpeg("bgr8") is None
+    from sings_amd.frame_out import parse_out
+    assert parse_out("jpeg").bgr is False and parse_out("bgr8").bgr is True and parse_out("float32").bgr is None
+    assert parse_out(("jpeg", 75)).bgr is False
+    assert parse_out("jpeg")[1:] == ("jpeg", 90) and parse_out(("jpeg", 75))[1:] == ("jpeg", 75) and parse_out("bgr8")[1:] == (None, None)
     for bad in (("jpeg", 0), ("jpeg", 101), ("jpeg", 7.5)):
         with pytest.raises(ValueError, match="quality"):
-            posed._out_jpeg(bad)
+            parse_out(bad)
     for bad in (("png", 3), "jpg", None):
         with pytest.raises(ValueError, match="out must be one of"):
-            posed._out_bgr(bad)
+            parse_out(bad)
     for fn in (posed.FrameAnimator.render_frames_batched, posed.animate_chunk, scene_anim.SceneAnimator.render_frames_batched,
                scene_anim.animate_scene):                            # (the quality travels in ``out``: the signatures are what they were)
         assert list(inspect.signature(fn).parameters)[-2:] == ["out", "return_aux"]

@@ -51,6 +51,7 @@ def cases():
         "noise_q100_ri48": (_noise(64, 48, 4), 100, 48),         # one segment of 144 coefficient blocks: more than 64, a partial last 64
         "cosine_q10": (_cosine(32, 16), 10, None),               # runs of 16 zeros and more: ZRL
         "one_segment": (_noise(40, 24, 8), 60, 65535),           # a restart interval beyond the MCU count
+        "152x112_ri1": (avatar_like(152, 112), 90, 1),           # 19 x 14 = 266 segments: more than 256, the scan's second round
     }
 
 
