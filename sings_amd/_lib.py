@@ -25,6 +25,7 @@ HAS_SCENE = False                    # set by load(): the library exports the ta
 HAS_JPEG = False                     # set by load(): the library exports the table of include/sings_jpeg.h
 HAS_PNG = False                      # set by load(): the library exports the table of include/sings_png.h
 HAS_UNPNG = False                    # set by load(): the library exports the table of include/sings_unpng.h
+HAS_BODY = False                     # set by load(): the library exports the table of include/sings_body.h
 
 
 class SgRasterSettings(C.Structure):
@@ -249,6 +250,14 @@ _PROTOTYPES_UNPNG = {
     "sg_unpng_layout": "i: i z Z",
     "sg_unpng_decode": "i: i p3 z p i3 p2",
 }
+# The body model, include/sings_body.h: a fourteenth header and a fourteenth table, for the same reason.
+_PROTOTYPES_BODY = {
+    "sg_body_renorm": "i: i2 p3",
+    "sg_body_joint_basis": "i: i3 p6",
+    "sg_body_shaped": "i: i4 p10",
+    "sg_body_smooth_ws_bytes": "z: i2",
+    "sg_body_smooth": "i: i3 f p8",
+}
 _P = C.POINTER
 _CTYPE = {"i": C.c_int, "z": C.c_size_t, "f": C.c_float, "s": C.c_char_p,
           "p": C.c_void_p,                        # a raw device pointer (or NULL), and the stream
@@ -311,6 +320,13 @@ UNPNG_MAX_ROW_BYTES = 16384          # SG_UNPNG_MAX_ROW_BYTES
 UNPNG_MAX_HEIGHT = 65535             # SG_UNPNG_MAX_HEIGHT
 UNPNG_TABLE_COLS = 6                 # SG_UNPNG_TABLE_COLS (SG_UNPNG_T_*: offset, length, width, height, channels, dest)
 UNPNG_LAYOUT = ("ws_bytes", "slot_pitch")        # SG_UNPNG_L_*, SG_UNPNG_LAYOUT_WORDS
+BODY_MAX_JOINTS = 64                 # SG_BODY_MAX_JOINTS
+BODY_MAX_BETAS = 32                  # SG_BODY_MAX_BETAS
+BODY_MAX_VERTS = 4194304             # SG_BODY_MAX_VERTS
+BODY_MAX_ROWS = 1024                 # SG_BODY_MAX_ROWS
+BODY_MAX_ITERATIONS = 64             # SG_BODY_MAX_ITERATIONS
+BODY_INFO_INTS = 4                   # SG_BODY_INFO_INTS
+BODY_ISOLATED, BODY_NOT_FINITE, BODY_BAD_SLOPE, BODY_BAD_FACE = 1, 2, 4, 8       # SG_BODY_ISOLATED, _NOT_FINITE, _BAD_SLOPE, _BAD_FACE
 FROZEN_BLOCK = 128                   # SG_FROZEN_BLOCK: points per workgroup of the fused no-gradient decode
 FROZEN_SHS = 48                      # SG_FROZEN_SHS
 MESH_TERMS_INFO_INTS = 2             # SG_MESH_TERMS_INFO_INTS
@@ -356,7 +372,7 @@ def load():
                            "(include/sings_hip.h SG_ABI_VERSION): rebuild with `make -C sings_amd/csrc`")
     # (SINGS_HIP_LIB may name a library that predates include/sings_order.h -- an A/B run against a parent build: it exports none of
     # that table, HAS_ORDER says so, and the engines then make the unordered calls that library knows)
-    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN, HAS_FEED, HAS_DENSITY, HAS_SHEET, HAS_SCENE, HAS_JPEG, HAS_PNG, HAS_UNPNG
+    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN, HAS_FEED, HAS_DENSITY, HAS_SHEET, HAS_SCENE, HAS_JPEG, HAS_PNG, HAS_UNPNG, HAS_BODY
     HAS_ORDER = all(hasattr(lib, name) for name in _PROTOTYPES_ORDER)
     HAS_SAMPLER = all(hasattr(lib, name) for name in _PROTOTYPES_SAMPLER)    # (the same, for include/sings_sampler.h)
     HAS_FROZEN = all(hasattr(lib, name) for name in _PROTOTYPES_FROZEN)      # (the same, for include/sings_frozen.h)
@@ -367,10 +383,11 @@ def load():
     HAS_JPEG = all(hasattr(lib, name) for name in _PROTOTYPES_JPEG)          # (the same, for include/sings_jpeg.h)
     HAS_PNG = all(hasattr(lib, name) for name in _PROTOTYPES_PNG)            # (the same, for include/sings_png.h)
     HAS_UNPNG = all(hasattr(lib, name) for name in _PROTOTYPES_UNPNG)        # (the same, for include/sings_unpng.h)
+    HAS_BODY = all(hasattr(lib, name) for name in _PROTOTYPES_BODY)          # (the same, for include/sings_body.h)
     for has, header in ((HAS_ORDER, "sings_order.h"), (HAS_SAMPLER, "sings_sampler.h"), (HAS_FROZEN, "sings_frozen.h"),
                         (HAS_FEED, "sings_feed.h"), (HAS_DENSITY, "sings_density.h"), (HAS_SHEET, "sings_sheet.h"),
                         (HAS_SCENE, "sings_scene.h"), (HAS_JPEG, "sings_jpeg.h"), (HAS_PNG, "sings_png.h"),
-                        (HAS_UNPNG, "sings_unpng.h")):
+                        (HAS_UNPNG, "sings_unpng.h"), (HAS_BODY, "sings_body.h")):
         if not has and LIB_PATH == os.path.join(_HERE, "libsings_hip.so"):
             raise RuntimeError(f"sings_amd: {LIB_PATH} lacks the entry points of include/{header}: rebuild with `make -C sings_amd/csrc`")
     for name, signature in (*_PROTOTYPES.items(), *_PROTOTYPES_EVAL.items(), *_PROTOTYPES_MESH_TERMS.items(),
@@ -381,7 +398,8 @@ def load():
                             *(_PROTOTYPES_SCENE.items() if HAS_SCENE else ()),
                             *(_PROTOTYPES_JPEG.items() if HAS_JPEG else ()),
                             *(_PROTOTYPES_PNG.items() if HAS_PNG else ()),
-                            *(_PROTOTYPES_UNPNG.items() if HAS_UNPNG else ())):
+                            *(_PROTOTYPES_UNPNG.items() if HAS_UNPNG else ()),
+                            *(_PROTOTYPES_BODY.items() if HAS_BODY else ())):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = _ctypes_of(signature)
     _lib = lib

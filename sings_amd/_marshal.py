@@ -392,6 +392,94 @@ def density_stats(grad, radii, gate, accum, denom, max_radii):
                                         _stream(dev)), "sg_density_stats")
 
 
+# ---- the body model (csrc/sg_body.hip)
+def _body_lib():
+    lib = _lib.load()
+    if not _lib.HAS_BODY:
+        raise RuntimeError("the loaded library predates include/sings_body.h (no fallback): rebuild it")
+    return lib
+
+
+def body_renorm(Jt):
+    """``sg_body_renorm`` on torch's current stream: ``Jt`` [V,J] fp32 (the subdivided J_regressor^T) -> J_regressor [J,V], every row
+    divided by its sum."""
+    dev = Jt.device if torch.is_tensor(Jt) else None
+    Jt = _mesh_arg(Jt, "Jt", torch.float32, dev)
+    V, J = int(Jt.shape[0]), int(Jt.shape[1])
+    with torch.cuda.device(dev):
+        out = torch.empty((J, V), dtype=torch.float32, device=dev)
+        _lib.check(_body_lib().sg_body_renorm(J, V, _ptr(Jt), _ptr(out), _stream(dev)), "sg_body_renorm")
+    return out
+
+
+def body_joint_basis(v_template, shapedirs, J_regressor):
+    """``sg_body_joint_basis`` on torch's current stream: ``v_template`` [V,3], ``shapedirs`` [V,3,B], ``J_regressor`` [J,V] fp32 ->
+    (J0 [J,3], JS [J,3,B])."""
+    dev = v_template.device if torch.is_tensor(v_template) else None
+    v_template = _mesh_arg(v_template, "v_template", torch.float32, dev, (3,))
+    V, B, J = int(v_template.shape[0]), int(shapedirs.shape[-1]), int(J_regressor.shape[0])
+    shapedirs = _mesh_arg(shapedirs, "shapedirs", torch.float32, dev, (3, B))
+    J_regressor = _mesh_arg(J_regressor, "J_regressor", torch.float32, dev, (V,))
+    if shapedirs.shape[0] != V:
+        raise ValueError(f"body_joint_basis: shapedirs has {shapedirs.shape[0]} rows, the template {V} vertices")
+    with torch.cuda.device(dev):
+        J0 = torch.empty((J, 3), dtype=torch.float32, device=dev)
+        JS = torch.empty((J, 3, B), dtype=torch.float32, device=dev)
+        _lib.check(_body_lib().sg_body_joint_basis(V, J, B, _ptr(v_template), _ptr(shapedirs), _ptr(J_regressor), _ptr(J0), _ptr(JS),
+                                                   _stream(dev)), "sg_body_joint_basis")
+    return J0, JS
+
+
+def body_shaped(v_template, shapedirs, betas, posedirs=None, pose_feature=None):
+    """``sg_body_shaped`` on torch's current stream: ``betas`` [K,B]; ``posedirs`` [P,3V] with ``pose_feature`` [K,P], or both None ->
+    (v_shaped, shape_offsets, pose_offsets, v_posed), [K,V,3] fp32 each."""
+    dev = v_template.device if torch.is_tensor(v_template) else None
+    v_template = _mesh_arg(v_template, "v_template", torch.float32, dev, (3,))
+    V, B = int(v_template.shape[0]), int(shapedirs.shape[-1])
+    shapedirs = _mesh_arg(shapedirs, "shapedirs", torch.float32, dev, (3, B))
+    betas = _mesh_arg(betas, "betas", torch.float32, dev, (B,))
+    K, P = int(betas.shape[0]), 0
+    if shapedirs.shape[0] != V:
+        raise ValueError(f"body_shaped: shapedirs has {shapedirs.shape[0]} rows, the template {V} vertices")
+    if (posedirs is None) != (pose_feature is None):
+        raise ValueError("body_shaped: posedirs and pose_feature come together")
+    if posedirs is not None:
+        posedirs = _mesh_arg(posedirs, "posedirs", torch.float32, dev, (3 * V,))
+        P = int(posedirs.shape[0])
+        pose_feature = _mesh_arg(pose_feature, "pose_feature", torch.float32, dev, (P,))
+        if pose_feature.shape[0] != K:
+            raise ValueError(f"body_shaped: pose_feature has {pose_feature.shape[0]} rows, betas {K}")
+    with torch.cuda.device(dev):
+        outs = [torch.empty((K, V, 3), dtype=torch.float32, device=dev) for _ in range(4)]
+        _lib.check(_body_lib().sg_body_shaped(V, B, K, P, _ptr(v_template), _ptr(shapedirs), _ptr(betas), _ptr(posedirs), _ptr(pose_feature),
+                                              *(_ptr(o) for o in outs), _stream(dev)), "sg_body_shaped")
+    return tuple(outs)
+
+
+def body_smooth(verts, faces, row_ptr, col, lamb, iterations):
+    """``sg_body_smooth`` on torch's current stream: ``verts`` [V,3] fp32, ``faces`` [F,3] int32, ``row_ptr`` [V+1] / ``col`` int32 (the
+    CSR of the unique edges) -> (x_out [V,3] fp32, written only when no error bit is set; info [``_lib.BODY_INFO_INTS``] int32 on the
+    device: the caller reads it)."""
+    dev = verts.device if torch.is_tensor(verts) else None
+    verts = _mesh_arg(verts, "verts", torch.float32, dev, (3,))
+    faces = _mesh_arg(faces, "faces", torch.int32, dev, (3,))
+    row_ptr = _mesh_arg(row_ptr, "row_ptr", torch.int32, dev)
+    col = _mesh_arg(col, "col", torch.int32, dev)
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if tuple(row_ptr.shape) != (V + 1,):
+        raise ValueError(f"body_smooth: row_ptr must be [{V + 1}], got {tuple(row_ptr.shape)}")
+    lib = _body_lib()
+    nbytes = int(lib.sg_body_smooth_ws_bytes(V, F))
+    if nbytes == 0:
+        raise ValueError(f"body_smooth: {V} vertices / {F} faces are outside what the kernels cover (1 <= V <= {_lib.BODY_MAX_VERTS}, "
+                         "1 <= F, 3 F < 2^31)")
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+        out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        info = torch.empty(_lib.BODY_INFO_INTS, dtype=torch.int32, device=dev)
+        _lib.check(lib.sg_body_smooth(V, F, int(iterations), float(lamb), _ptr(verts), _ptr(faces), _ptr(row_ptr), _ptr(col), _ptr(ws),
+                                      _ptr(out), _ptr(info), _stream(dev)), "sg_body_smooth")
+    return out, info
 
 
 # ---- frames to JPEG and PNG files, PNG files to the frame store (csrc/sg_jpeg.hip, sg_png.hip, sg_unpng.hip)

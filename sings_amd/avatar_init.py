@@ -8,6 +8,8 @@
     fit_initial_attributes    :608-671                  the 500-step pre-fit: ``FusedAdam``, no host read per step, replayed from a graph
     from_mesh                                           mesh -> (``AvatarStep``, ``MeshState``, targets): the three-call sequence of
                                                         INTEGRATION.md 13
+    from_body                                           the same from a ``body_model.BodyModel`` and betas: the canonical-pose mesh is
+                                                        made here too
 
 Kernels: csrc/sg_init.hip.  There is no CPU fallback: host tensors raise.
 """
@@ -378,3 +380,13 @@ def from_mesh(verts, faces, lbs_weights, vertex_label, triplane, geometry_dec, a
                         thickness_factor=init_kwargs.get("thickness_factor", 1.0),
                         scaling_multiplier=torch.ones((V, 1), dtype=torch.float32, device=dev)).to(dev)
     return module, mesh, targets
+
+
+def from_body(body, betas, triplane, geometry_dec, appearance_dec, canonical_pose_type="da_pose", **init_kwargs):
+    """``body_model.BodyModel`` + betas [B] -> ``(module, mesh, targets, canon)``: ``canon = body.canonical(betas, canonical_pose_type,
+    'smplh' for 52 joints, else 'smpl')`` and ``from_mesh(canon['verts'], body.faces, body.lbs_weights, body.vertex_label, ...)``.  ``canon``
+    carries what the pose tables take: ``joints_rest`` and ``A_t2cano``."""
+    canon = body.canonical(betas, canonical_pose_type, "smplh" if body.num_joints == 52 else "smpl")
+    module, mesh, targets = from_mesh(canon["verts"], body.faces, body.lbs_weights, body.vertex_label, triplane, geometry_dec,
+                                      appearance_dec, **init_kwargs)
+    return module, mesh, targets, canon
