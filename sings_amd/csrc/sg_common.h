@@ -299,9 +299,9 @@ void sg_launch_render_bwd(const SgCam &c, const SgBatch &bt, SgGeom g, SgBin b, 
 // sum into the spare float of the 48-byte block (float 9)
 void sg_launch_record_sums(const SgBatch &bt, int P, const int32_t *radii, SgGeom g, SgRec grec, size_t cap, const uint32_t *header,
                            const uint8_t *rec_valid, float4 *a9out, hipStream_t st, const float *dz = nullptr, size_t dz_stride = 0);
-// bytes behind the K record buffers of a K-frame backward workspace (K > 1), 64 per (frame, Gaussian): the K-camera per-Gaussian
-// backward's rows [K][P][4 vectors] (sg_preprocess.hip: sg_gauss_frame_bwd_kernel writes them, sg_gauss_sum_frames_kernel adds them
-// in frame order); the skinned path keeps its a9 sums [K][P][12] in the front of the same block
+// bytes behind the K record buffers of a K-frame backward workspace (K > 1), 64 per (frame, Gaussian): the skinned path keeps its
+// a9 sums [K][P][12] in the front of the block.  (The raster path's K-camera per-Gaussian backward kept its rows [K][P][4 vectors]
+// here in round 12; sg_gauss_frames_bwd_kernel sums the frames in LDS and no longer touches the region.)
 static inline size_t sg_a9_bytes(int P, int K) { return K > 1 ? sg_align((size_t)K * (size_t)P * 64 + 256) : 0; }
 void sg_launch_preprocess_bwd(const SgCam &c, const SgBatch &bt, int P, const float *means3D, const float *shs,
                               const float *colors_precomp, const float *opacities, const float *scales,

@@ -3,6 +3,7 @@
 #pragma once
 #include "sg_common.h"
 
+#include <atomic>
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -23,6 +24,25 @@ static inline int sg_launched(const char *what)
 {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : sg_set_error(what, e);
+}
+
+// Raising a kernel's dynamic-LDS limit is a host-side call into the runtime (a table update under a lock): asked ONCE per
+// (kernel, device) and remembered per device id -- not in a process-wide flag (a second GPU used from the same process must get
+// its own call), and a refusal is remembered too (the callers then take their fallback paths).  Round 3 asked on every forward.
+// One SgLdsLimit (static storage: zeroes) per kernel.
+struct SgLdsLimit { std::atomic<signed char> state[64]; };       // per device: 0 unknown, 1 granted, -1 refused
+static inline bool sg_dyn_lds_limit(SgLdsLimit &m, const void *fn, int bytes)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
+        return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess || ((void)hipGetLastError(), false);
+    signed char st = m.state[dev].load(std::memory_order_acquire);
+    if (st == 0) {
+        st = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? 1 : -1;
+        if (st < 0) (void)hipGetLastError();
+        m.state[dev].store(st, std::memory_order_release);
+    }
+    return st > 0;
 }
 
 // The reference's 11-tap SSIM window (losses/utils.py:28-30): the fp32 values exp(-(x-5)^2 / (2 * 1.5^2)) divided by their sum AS

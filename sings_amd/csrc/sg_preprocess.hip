@@ -141,288 +141,257 @@ void sg_launch_preprocess_fwd_ordered(const SgCam &c, const SgBatch &bt, int P, 
 #include "sg_preprocess_bwd.inc"
 #undef SG_PBWD_AUX
 
-// ---- K cameras per launch (round 4; two kernels since round 12) ---------------------------------------------------------------
+// ---- K cameras per launch (round 4; one kernel, the frames summed in LDS, since round 13) ---------------------------------------
 // K cameras (bt.K frames) of the SAME Gaussians: the K gradients of a Gaussian are summed in frame order (frame 0 assigns, frame
 // f > 0 adds: bit for bit what K single-camera calls leave behind when the first writes the gradient buffer and the others run with
 // accumulate = 1) and the 248-byte gradient row is written ONCE: K - 1 read-modify-write passes over the buffer less (at cfg3
 // 2 x 47 MB per view).  dL_dmeans2D (the densifier's per-view statistic) is per frame.
 //
-// Only the ADDITIONS are ordered; what a frame contributes depends on that frame alone.  So the work is two kernels:
-//  1. sg_gauss_frame_bwd_kernel: one (Gaussian, frame) per lane at full grid, in the (block, frame) order of the forward
-//     (sg_block_frame: the K frames of a block back to back on one XCD -- positions, scales, rotations and SH rows come from HBM
-//     once and from L2 K - 1 times).  Steps 0-2 of the single-camera kernel -- visibility, sg_sum_records_coop, sg_project_bwd --
-//     without forming dL/dsh: it writes the frame's dL_dmeans2D row and one 64-byte row per VISIBLE (frame, Gaussian) into the
-//     block behind the K record buffers (sg_a9_bytes):
-//         vector 0: dmean.xyz, dop      vector 1: dsc.xyz, -      vector 2: drot.xyzw      vector 3: dRGB.xyz, -
-//     dRGB: the colour gradient after the clamp mask (no SH rows: the plain colour gradient); with cov3D_precomp the six g6 values
-//     take vectors 1-2 instead (g6[0..3] | g6[4], g6[5], -, -).
-//  2. sg_gauss_sum_frames_kernel: one Gaussian per lane, the ordered part and nothing else.  It walks the K rows of its Gaussian
-//     (the next one requested ahead), adds the geometry values as the single-camera accumulate does (new + old) and forms
-//     dL/dsh = basis(dir_f) * dRGB_f from the position and the frame's camera centre -- the expressions of sg_project_bwd --
-//     in 48 registers: no SH coefficient, record, slot or flag word is read here.
-// (The one-kernel form this replaces held the chain rule INSIDE the frame loop: 168 registers and 48 KiB of LDS per workgroup,
-//  two waves per SIMD, the 192-byte SH row re-read per trip: 119 us + 63 us of record sums at cfg3, K = 8 -- LAB.md.)
-#define SG_GROW_VEC 4                                       // 16-byte vectors per (frame, Gaussian) row
-template <int D>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
-sg_gauss_frame_bwd_kernel(SgCam c, SgBatch bt, int P, const float *__restrict__ means3D, const float *__restrict__ shs,
-                          const float *__restrict__ scales, const float *__restrict__ rotations,
-                          const float *__restrict__ cov3D_precomp, const int32_t *__restrict__ radii, SgGeom g, SgRec grec,
-                          size_t cap, const uint32_t *__restrict__ header, const uint8_t *__restrict__ rec_valid,
-                          float4 *__restrict__ rows, float *__restrict__ dL_dmeans2D, int nblocks)
+// Only the ADDITIONS are ordered; what a frame contributes depends on that frame alone.  sg_gauss_frames_bwd_kernel: a workgroup is
+// 64 consecutive Gaussians x K frames, K waves; wave f works on frame f (camera, geometry, record and header pointers stay
+// wave-uniform), lane = Gaussian.  The K waves read the same positions, scales, rotations and SH rows: from HBM once, from the
+// CU's cache K - 1 times.
+//  1. per wave: steps 0-2 of the single-camera kernel -- visibility, sg_sum_records_coop, sg_project_bwd -- without forming dL/dsh.
+//     The wave stores the frame's dL_dmeans2D row and leaves one row per (frame, Gaussian) in ITS block of LDS (the record-chunk
+//     block, free once the record loop is over; SG_GF_PITCH floats, an odd pitch: lane-strided writes hit distinct banks):
+//         0-2 dmean, 3 dop | 4-6 dsc, 7-10 drot (cov3D_precomp: 4-9 the six g6) | 11-13 dRGB | 14-29 sg_sh_basis(dir) | 30 visible
+//     dRGB: the colour gradient after the clamp mask (no SH rows: the plain colour gradient).  A frame that does not see the
+//     Gaussian leaves +0 in slots 0-13 and `visible` = 0.
+//  2. behind ONE workgroup barrier the 64 K threads share the 64 Gaussians' outputs, dealt so that consecutive lanes hold
+//     consecutive floats of an output array (whole lines are stored): per (Gaussian, coefficient) the three dL/dsh channels, per
+//     (Gaussian, value) a geometry sum.  Each walks the frames 0 .. K - 1 in order with the single-camera accumulate's expressions
+//     (geometry: new + old, an invisible frame enters as +0; dL/dsh = basis * dRGB, an invisible frame leaves the sums alone).
+// No wave leaves between kernel entry and the barrier: a wave whose 64 Gaussians lie behind P, that sees nothing
+// (sg_sum_records_coop returns to its caller, not from the kernel) or whose frame overflowed (header[1]) still writes its 64
+// `visible` words and arrives.
+// (Rounds 4-11 held the chain rule INSIDE a frame loop: 168 registers, 48 KiB of LDS, two waves per SIMD.  Round 12 split it into
+//  a per-(Gaussian, frame) kernel that wrote 64-byte rows to memory and a sum kernel that read them back: K P 128 bytes of traffic
+//  and a launch that existed only to order K additions -- LAB.md.)
+#define SG_GF_PITCH 31                                      // floats per (frame, Gaussian) row in LDS
+#define SG_GF_BLOCK 2048                                    // floats per wave: 64 rows (1 984), or a record chunk (SG_REC_CHUNK * 12)
+#define SG_GF_RGB 11
+#define SG_GF_BAS 14
+#define SG_GF_VIS 30
+#define SG_GF_BATCH 8                                       // frames whose rows step 2 reads at once
+static_assert(64 * SG_GF_PITCH <= SG_GF_BLOCK && SG_REC_CHUNK * 12 <= SG_GF_BLOCK, "a wave's LDS block holds its rows and a record chunk");
+// ACC: the sums START from what the gradient buffer holds (read once, in step 2), so that the K frames are added in the order K
+// single-camera calls with accumulate = 1 would add them: ((old + g0) + g1) + ...; otherwise frame 0 ASSIGNS (a -0 survives).
+template <int D, bool ACC>
+__global__ void __launch_bounds__(1024)
+sg_gauss_frames_bwd_kernel(SgCam c, SgBatch bt, int P, const float *__restrict__ means3D, const float *__restrict__ shs,
+                           const float *__restrict__ scales, const float *__restrict__ rotations,
+                           const float *__restrict__ cov3D_precomp, const int32_t *__restrict__ radii, SgGeom g, SgRec grec,
+                           size_t cap, const uint32_t *__restrict__ header, const uint8_t *__restrict__ rec_valid,
+                           float *__restrict__ dL_dmeans2D, float *__restrict__ dL_dmeans3D, float *__restrict__ dL_dsh,
+                           float *__restrict__ dL_dcolors, float *__restrict__ dL_dopacity, float *__restrict__ dL_dscales,
+                           float *__restrict__ dL_drots, float *__restrict__ dL_dcov3D)
 {
-    __shared__ float lds_all[4][32 * SG_ROW_LDS];          // 6.5 KiB per wave: the record chunks
-    int gblock, frame;
-    if (!sg_block_frame((int)blockIdx.x, bt.K, nblocks, gblock, frame)) return;
-    c = sg_frame(c, frame, bt.cam_stride); g = sg_frame(g, (size_t)frame * bt.geom); grec = sg_frame(grec, (size_t)frame * bt.rec);
-    header = sg_at(header, (size_t)frame * bt.bin); rec_valid = sg_at(rec_valid, (size_t)frame * bt.bin);
-    radii += (size_t)frame * bt.P;
-    const int idx = gblock * 256 + (int)threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (idx - lane >= P) return;                            // whole wave out of range
-    const bool live = idx < P;
-    // after a forward that overflowed (header[1] != 0) the backward composite wrote no records: the frame contributes nothing
-    const bool vis = live && radii[idx] > 0 && header[1] == 0u;
-    const int Mrows = c.M;
+    extern __shared__ float sg_gf_lds[];                    // K blocks of SG_GF_BLOCK floats
+    const int lane = threadIdx.x & 63;
+    const int frame = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (scalar: the frame's pointers stay in SGPRs)
+    const int g0 = (int)blockIdx.x * 64;
     constexpr int nc = (D + 1) * (D + 1);
     const bool want_sh = shs != nullptr;
-    // 0. every load that does not depend on another one up front
-    float4 rc = make_float4(0, 0, 0, 0);
-    float p[3] = { 0, 0, 0 }, s3[3] = { 0, 0, 0 }, q[4] = { 0, 0, 0, 0 }, sh[nc * 3];
-    uint32_t flags = 0;
-    if (vis) {
-        { const uint2 sl = g.slot[idx]; rc.y = __uint_as_float(sl.x); rc.w = __uint_as_float(sl.y); }
-        flags = g.flags[idx];
-        p[0] = means3D[3 * idx]; p[1] = means3D[3 * idx + 1]; p[2] = means3D[3 * idx + 2];
-        if (!cov3D_precomp) {
-            s3[0] = scales[3 * idx]; s3[1] = scales[3 * idx + 1]; s3[2] = scales[3 * idx + 2];
-            q[0] = rotations[4 * idx]; q[1] = rotations[4 * idx + 1]; q[2] = rotations[4 * idx + 2]; q[3] = rotations[4 * idx + 3];
-        }
-    }
-    // 1. this Gaussian's gradient records of this frame (wave-cooperative, coalesced)
-    float a9[9];
-    sg_sum_records_coop(grec, cap, vis, rc, lane, lds_all[wave], a9, rec_valid);
-    if (!live) return;
-    // the screen-space gradient is per VIEW (the densifier's statistic): zeros for a Gaussian this frame does not see
-    float *m2 = dL_dmeans2D + 3 * ((size_t)frame * bt.P + idx);
-    if (!vis) { m2[0] = 0.0f; m2[1] = 0.0f; m2[2] = 0.0f; return; }
-    // 2. the chain rule without its SH block (dL/dsh is NOT formed: the rows below carry dRGB, the sum kernel multiplies by the basis)
-    SgGaussGrad G;
-    sg_project_bwd<D>(c, p, s3, q, cov3D_precomp ? cov3D_precomp + 6 * (size_t)idx : nullptr, nullptr, flags, a9, false, nullptr, G);
-    m2[0] = G.g2[0]; m2[1] = G.g2[1]; m2[2] = 0.0f;
-    float dRGB[3] = { G.dcol[0], G.dcol[1], G.dcol[2] };
-    if (want_sh) {
-        // the SH block of sg_project_bwd, its expressions in its order: dL/ddir and its share of dL/dmean.  The coefficient row is
-        // requested HERE (opaque index: not in front of the record loop or the cov2D / cov3D chain, where its 48 registers would be
-        // live across both) and consumed in order by the dL/ddir sums.
-        int ish = idx;
-        asm volatile("" : "+v"(ish), "+v"(G.dmean[2]), "+v"(G.drot[3]));
-        const float *src = shs + (size_t)ish * Mrows * 3;
-        if (D == 3 && Mrows == 16) {
-#pragma unroll
-            for (int k = 0; k < nc * 3 / 4; k++) {
-                const float4 v = ((const float4 *)src)[k];
-                sh[4 * k] = v.x; sh[4 * k + 1] = v.y; sh[4 * k + 2] = v.z; sh[4 * k + 3] = v.w;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < nc * 3; k++) sh[k] = src[k];
-        }
-        float dorig[3] = { p[0] - c.campos[0], p[1] - c.campos[1], p[2] - c.campos[2] };
-        float sum2 = dorig[0] * dorig[0] + dorig[1] * dorig[1] + dorig[2] * dorig[2];
-        float len = sqrtf(sum2);
-        float dir[3] = { dorig[0] / len, dorig[1] / len, dorig[2] / len };
-        float db[48];
-        sg_sh_basis_grad<D>(dir, db);
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) dRGB[ch] = (flags >> ch) & 1u ? 0.0f : G.dcol[ch];
-        float ddir[3] = { 0, 0, 0 };
-#pragma unroll
-        for (int k = 1; k < nc; k++)
-#pragma unroll
-            for (int ch = 0; ch < 3; ch++) {
-                float sv = sh[3 * k + ch] * dRGB[ch];
-                ddir[0] += db[3 * k] * sv; ddir[1] += db[3 * k + 1] * sv; ddir[2] += db[3 * k + 2] * sv;
-            }
-        float inv32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
-        float vx = dorig[0], vy = dorig[1], vz = dorig[2];
-        G.dmean[0] += ((sum2 - vx * vx) * ddir[0] - vy * vx * ddir[1] - vz * vx * ddir[2]) * inv32;
-        G.dmean[1] += (-vx * vy * ddir[0] + (sum2 - vy * vy) * ddir[1] - vz * vy * ddir[2]) * inv32;
-        G.dmean[2] += (-vx * vz * ddir[0] - vy * vz * ddir[1] + (sum2 - vz * vz) * ddir[2]) * inv32;
-    }
-    float4 *o = rows + SG_GROW_VEC * ((size_t)frame * bt.P + idx);
-    o[0] = make_float4(G.dmean[0], G.dmean[1], G.dmean[2], G.dop);
-    if (cov3D_precomp) {
-        o[1] = make_float4(G.g6[0], G.g6[1], G.g6[2], G.g6[3]);
-        o[2] = make_float4(G.g6[4], G.g6[5], 0.0f, 0.0f);
-    } else {
-        o[1] = make_float4(G.dsc[0], G.dsc[1], G.dsc[2], 0.0f);
-        o[2] = make_float4(G.drot[0], G.drot[1], G.drot[2], G.drot[3]);
-    }
-    o[3] = make_float4(dRGB[0], dRGB[1], dRGB[2], 0.0f);
-}
-
-// ACC: the sums START from what the gradient buffer holds (read once, here), so that the K frames are added in the order K
-// single-camera calls with accumulate = 1 would add them: ((old + g0) + g1) + ...; otherwise frame 0 ASSIGNS (a -0 survives).
-// A frame that does not see the Gaussian enters the geometry sums as +0 -- what the single-camera kernel adds for it -- and
-// leaves the dL/dsh sums alone.
-template <int D, bool ACC>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
-sg_gauss_sum_frames_kernel(SgCam c0, SgBatch bt, int P, const float *__restrict__ means3D, const int32_t *__restrict__ radii0,
-                           const uint32_t *__restrict__ header0, const float4 *__restrict__ rows, int g6rows,
-                           float *__restrict__ dL_dmeans3D, float *__restrict__ dL_dsh, float *__restrict__ dL_dcolors,
-                           float *__restrict__ dL_dopacity, float *__restrict__ dL_dscales, float *__restrict__ dL_drots,
-                           float *__restrict__ dL_dcov3D)
-{
-    __shared__ float lds_all[4][32 * SG_ROW_LDS];          // the staging rows of the dL/dsh store
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g0 = idx - lane;
-    if (g0 >= P) return;                                    // whole wave out of range
-    const bool live = idx < P;
-    const int Mrows = c0.M;
-    const int nframes = bt.K;
-    constexpr int nc = (D + 1) * (D + 1);
-    const bool want_sh = dL_dsh != nullptr;
-    const bool planar = c0.flags & SG_FLAG_SH_PLANAR;
-    const bool staged = D == 3 && Mrows == 16 && want_sh && !planar;
-    // frame f + 1's (visible, row) are requested while frame f is added; frame 0's go out with the position
-    bool vis_n = live && radii0[idx] > 0 && header0[1] == 0u;
-    const float4 z4 = make_float4(0, 0, 0, 0);
-    float4 n[SG_GROW_VEC] = { z4, z4, z4, z4 };
-    if (vis_n) {
-        const float4 *src = rows + SG_GROW_VEC * (size_t)idx;
-#pragma unroll
-        for (int v = 0; v < SG_GROW_VEC; v++) n[v] = src[v];
-    }
-    float p[3] = { 0, 0, 0 };
-    if (live) { p[0] = means3D[3 * idx]; p[1] = means3D[3 * idx + 1]; p[2] = means3D[3 * idx + 2]; }
-    // the sums over the frames.  Geometry, in the rows' layout: A[0..3] = dmean.xyz, dop; A[4..11] = dsc.xyz, -, drot.xyzw (g6rows:
-    // the six g6, -, -); A[12..14] = the colour gradient -- kept in the wave's LDS block while the frames are walked ([value][lane]:
-    // conflict-free; the dL/dsh sums, the requested row and the basis take the 128 registers of four waves per SIMD)
-    constexpr int NA = 4 * SG_GROW_VEC - 1;
-    static_assert(NA * 64 <= 32 * SG_ROW_LDS, "the geometry sums fit the wave's staging block");
-    float *sA = lds_all[wave] + lane;
-    float A[NA];
-#pragma unroll
-    for (int k = 0; k < NA; k++) A[k] = 0.0f;
-    float acc[nc * 3];
-#pragma unroll
-    for (int k = 0; k < nc * 3; k++) acc[k] = 0.0f;
-    if (ACC && live) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) A[k] = dL_dmeans3D[3 * idx + k];
-        A[3] = dL_dopacity[idx];
-        if (g6rows) {
-#pragma unroll
-            for (int k = 0; k < 6; k++) A[4 + k] = dL_dcov3D ? dL_dcov3D[6 * idx + k] : 0.0f;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 3; k++) A[4 + k] = dL_dscales ? dL_dscales[3 * idx + k] : 0.0f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) A[8 + k] = dL_drots ? dL_drots[4 * idx + k] : 0.0f;
-        }
-#pragma unroll
-        for (int k = 0; k < 3; k++) A[12 + k] = dL_dcolors ? dL_dcolors[3 * idx + k] : 0.0f;
-        if (want_sh) {
-            const float *row = dL_dsh + (size_t)idx * Mrows * 3;
-#pragma unroll
-            for (int k = 0; k < nc * 3; k++) acc[k] = planar ? dL_dsh[((size_t)(k / 3) * P + idx) * 3 + k % 3] : row[k];
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NA; k++) sA[64 * k] = A[k];
-#pragma unroll 1
-    for (int f = 0; f < nframes; f++) {
-        const bool vis = vis_n;
-        const bool first = !ACC && f == 0;
-        // (opaque per trip: keeps hipcc from promoting the LDS sums to registers across the loop)
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        float *sAf = lds_all[wave] + ln;
-        // (operand order of the single-camera accumulate: new + old)
-#pragma unroll
-        for (int v = 0; v < SG_GROW_VEC; v++) {
-            const float r[4] = { n[v].x, n[v].y, n[v].z, n[v].w };
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (4 * v + k < NA) sAf[64 * (4 * v + k)] = first ? r[k] : r[k] + sAf[64 * (4 * v + k)];
-        }
-        const float dRGB[3] = { n[3].x, n[3].y, n[3].z };
-        if (f + 1 < nframes) {
-            vis_n = live && radii0[(size_t)(f + 1) * bt.P + idx] > 0 && sg_at(header0, (size_t)(f + 1) * bt.bin)[1] == 0u;
-#pragma unroll
-            for (int v = 0; v < SG_GROW_VEC; v++) n[v] = z4;
-            if (vis_n) {
-                const float4 *src = rows + SG_GROW_VEC * ((size_t)(f + 1) * bt.P + idx);
-#pragma unroll
-                for (int v = 0; v < SG_GROW_VEC; v++) n[v] = src[v];
+    {
+        // ---- 1. frame `frame` of Gaussian g0 + lane
+        const int idx = g0 + lane;
+        float *L = sg_gf_lds + frame * SG_GF_BLOCK;
+        const SgCam cf = sg_frame(c, frame, bt.cam_stride);
+        const SgGeom gf = sg_frame(g, (size_t)frame * bt.geom);
+        const SgRec grf = sg_frame(grec, (size_t)frame * bt.rec);
+        const uint32_t *hf = sg_at(header, (size_t)frame * bt.bin);
+        const uint8_t *rvf = sg_at(rec_valid, (size_t)frame * bt.bin);
+        const int32_t *rad = radii + (size_t)frame * bt.P;
+        const bool live = idx < P;
+        // after a forward that overflowed (header[1] != 0) the backward composite wrote no records: the frame contributes nothing
+        const bool vis = live && rad[idx] > 0 && hf[1] == 0u;
+        const int Mrows = cf.M;
+        // 0. every load that does not depend on another one up front
+        float4 rc = make_float4(0, 0, 0, 0);
+        float p[3] = { 0, 0, 0 }, s3[3] = { 0, 0, 0 }, q[4] = { 0, 0, 0, 0 }, sh[nc * 3];
+        uint32_t flags = 0;
+        if (vis) {
+            { const uint2 sl = gf.slot[idx]; rc.y = __uint_as_float(sl.x); rc.w = __uint_as_float(sl.y); }
+            flags = gf.flags[idx];
+            p[0] = means3D[3 * idx]; p[1] = means3D[3 * idx + 1]; p[2] = means3D[3 * idx + 2];
+            if (!cov3D_precomp) {
+                s3[0] = scales[3 * idx]; s3[1] = scales[3 * idx + 1]; s3[2] = scales[3 * idx + 2];
+                q[0] = rotations[4 * idx]; q[1] = rotations[4 * idx + 1]; q[2] = rotations[4 * idx + 2]; q[3] = rotations[4 * idx + 3];
             }
         }
-        if (want_sh && vis) {
-            // the view direction and the basis: sg_project_bwd's expressions
-            const float *campos = c0.campos + 3 * (size_t)f * (size_t)bt.cam_stride;
-            float dorig[3] = { p[0] - campos[0], p[1] - campos[1], p[2] - campos[2] };
-            float sum2 = dorig[0] * dorig[0] + dorig[1] * dorig[1] + dorig[2] * dorig[2];
-            float len = sqrtf(sum2);
-            float dir[3] = { dorig[0] / len, dorig[1] / len, dorig[2] / len };
-            float bas[16];
-            sg_sh_basis<D>(dir, bas);
+        // 1. this Gaussian's gradient records of this frame (wave-cooperative, coalesced)
+        float a9[9];
+        sg_sum_records_coop(grf, cap, vis, rc, lane, L, a9, rvf);
+        float *row = L + lane * SG_GF_PITCH;                // (the record loop is over: the block is this wave's to reuse)
+        row[SG_GF_VIS] = vis ? 1.0f : 0.0f;
+        if (!vis) {                                         // the geometry slots of a frame that does not see the Gaussian: +0
 #pragma unroll
-            for (int k = 0; k < nc; k++)
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++)
-                    acc[3 * k + ch] = first ? bas[k] * dRGB[ch] : acc[3 * k + ch] + bas[k] * dRGB[ch];
+            for (int k = 0; k < SG_GF_BAS; k++) row[k] = 0.0f;
         }
-    }
-#pragma unroll
-    for (int k = 0; k < NA; k++) A[k] = sA[64 * k];
-    __builtin_amdgcn_s_waitcnt(0xC07F);                     // every lane holds its sums: the block is free for the staging rows
-    __builtin_amdgcn_wave_barrier();
-    // dL/dsh out: coefficient-major planes [M][P][3], only the (D+1)^2 in use (SG_FLAG_SH_PLANAR); or the reference's rows
-    // (every one of the M rows is written; coalesced through LDS when staged).  (ACC: the sums already hold old + frames)
-    if (want_sh && planar) {
         if (live) {
-#pragma unroll
-            for (int k = 0; k < nc * 3; k++) dL_dsh[((size_t)(k / 3) * P + idx) * 3 + k % 3] = acc[k];
+            // the screen-space gradient is per VIEW (the densifier's statistic): zeros for a Gaussian this frame does not see
+            float *m2 = dL_dmeans2D + 3 * ((size_t)frame * bt.P + idx);
+            if (!vis) { m2[0] = 0.0f; m2[1] = 0.0f; m2[2] = 0.0f; }
         }
-    } else if (want_sh) {
-        if (staged) {
-            float *L = lds_all[wave];
+        if (vis) {
+            float *m2 = dL_dmeans2D + 3 * ((size_t)frame * bt.P + idx);
+            // 2. the chain rule without its SH block (dL/dsh is NOT formed: the row carries dRGB and the basis, step 2 multiplies)
+            SgGaussGrad G;
+            sg_project_bwd<D>(cf, p, s3, q, cov3D_precomp ? cov3D_precomp + 6 * (size_t)idx : nullptr, nullptr, flags, a9, false, nullptr, G);
+            m2[0] = G.g2[0]; m2[1] = G.g2[1]; m2[2] = 0.0f;
+            float dRGB[3] = { G.dcol[0], G.dcol[1], G.dcol[2] };
+            if (want_sh) {
+                // the SH block of sg_project_bwd, its expressions in its order: dL/ddir and its share of dL/dmean.  The coefficient
+                // row is requested HERE (opaque index: not in front of the record loop or the cov2D / cov3D chain, where its 48
+                // registers would be live across both) and consumed in order by the dL/ddir sums.
+                int ish = idx;
+                asm volatile("" : "+v"(ish), "+v"(G.dmean[2]), "+v"(G.drot[3]));
+                const float *src = shs + (size_t)ish * Mrows * 3;
+                if (D == 3 && Mrows == 16) {
 #pragma unroll
-            for (int h = 0; h < 2; h++) {                    // 32 rows at a time
-                if ((lane >> 5) == h) {
+                    for (int k = 0; k < nc * 3 / 4; k++) {
+                        const float4 v = ((const float4 *)src)[k];
+                        sh[4 * k] = v.x; sh[4 * k + 1] = v.y; sh[4 * k + 2] = v.z; sh[4 * k + 3] = v.w;
+                    }
+                } else {
 #pragma unroll
-                    for (int k = 0; k < nc * 3 / 4; k++)
-                        *(float4 *)(L + (lane & 31) * SG_ROW_LDS + 4 * k) = make_float4(acc[4 * k], acc[4 * k + 1], acc[4 * k + 2], acc[4 * k + 3]);
+                    for (int k = 0; k < nc * 3; k++) sh[k] = src[k];
                 }
-                __builtin_amdgcn_s_waitcnt(0xC07F);
-                __builtin_amdgcn_wave_barrier();
-                sg_rows48_store(dL_dsh, g0 + 32 * h, P, lane, L, 32, false);
-                __builtin_amdgcn_s_waitcnt(0xC07F);
-                __builtin_amdgcn_wave_barrier();
+                float dorig[3] = { p[0] - cf.campos[0], p[1] - cf.campos[1], p[2] - cf.campos[2] };
+                float sum2 = dorig[0] * dorig[0] + dorig[1] * dorig[1] + dorig[2] * dorig[2];
+                float len = sqrtf(sum2);
+                float dir[3] = { dorig[0] / len, dorig[1] / len, dorig[2] / len };
+                {
+                    float bas[16];
+                    sg_sh_basis<D>(dir, bas);
+#pragma unroll
+                    for (int k = 0; k < nc; k++) row[SG_GF_BAS + k] = bas[k];
+                }
+                float db[48];
+                sg_sh_basis_grad<D>(dir, db);
+#pragma unroll
+                for (int ch = 0; ch < 3; ch++) dRGB[ch] = (flags >> ch) & 1u ? 0.0f : G.dcol[ch];
+                float ddir[3] = { 0, 0, 0 };
+#pragma unroll
+                for (int k = 1; k < nc; k++)
+#pragma unroll
+                    for (int ch = 0; ch < 3; ch++) {
+                        float sv = sh[3 * k + ch] * dRGB[ch];
+                        ddir[0] += db[3 * k] * sv; ddir[1] += db[3 * k + 1] * sv; ddir[2] += db[3 * k + 2] * sv;
+                    }
+                float inv32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
+                float vx = dorig[0], vy = dorig[1], vz = dorig[2];
+                G.dmean[0] += ((sum2 - vx * vx) * ddir[0] - vy * vx * ddir[1] - vz * vx * ddir[2]) * inv32;
+                G.dmean[1] += (-vx * vy * ddir[0] + (sum2 - vy * vy) * ddir[1] - vz * vy * ddir[2]) * inv32;
+                G.dmean[2] += (-vx * vz * ddir[0] - vy * vz * ddir[1] + (sum2 - vz * vz) * ddir[2]) * inv32;
             }
-        } else if (live) {
-            float *dsh_row = dL_dsh + (size_t)idx * Mrows * 3;
+            row[0] = G.dmean[0]; row[1] = G.dmean[1]; row[2] = G.dmean[2]; row[3] = G.dop;
+            if (cov3D_precomp) {
 #pragma unroll
-            for (int k = 0; k < nc * 3; k++) dsh_row[k] = acc[k];
-            if (!ACC)
-                for (int k = nc * 3; k < Mrows * 3; k++) dsh_row[k] = 0.0f;
+                for (int k = 0; k < 6; k++) row[4 + k] = G.g6[k];
+            } else {
+                row[4] = G.dsc[0]; row[5] = G.dsc[1]; row[6] = G.dsc[2];
+                row[7] = G.drot[0]; row[8] = G.drot[1]; row[9] = G.drot[2]; row[10] = G.drot[3];
+            }
+            row[SG_GF_RGB] = dRGB[0]; row[SG_GF_RGB + 1] = dRGB[1]; row[SG_GF_RGB + 2] = dRGB[2];
         }
     }
-    if (!live) return;
-    dL_dmeans3D[3 * idx] = A[0]; dL_dmeans3D[3 * idx + 1] = A[1]; dL_dmeans3D[3 * idx + 2] = A[2];
-    dL_dopacity[idx] = A[3];
-    if (dL_dcolors) { dL_dcolors[3 * idx] = A[12]; dL_dcolors[3 * idx + 1] = A[13]; dL_dcolors[3 * idx + 2] = A[14]; }
-    if (g6rows) {
-        if (dL_dcov3D) {
+    __syncthreads();                                        // every wave of the workgroup arrives (no return above)
+    // ---- 2. the sums over the frames, in frame order; thread t takes items t, t + 64 K, ...
+    const int tid = (int)threadIdx.x, nthr = bt.K * 64, nframes = bt.K;
+    const int nlive = P - g0 < 64 ? P - g0 : 64;
+    if (want_sh) {
+        // an item: the three channels of (Gaussian j, coefficient k).  Coefficient-major planes [M][P][3], only the (D+1)^2 in use
+        // (SG_FLAG_SH_PLANAR), or the reference's rows [P][M][3]: every one of the M rows is written (ACC: those in use)
+        const bool planar = c.flags & SG_FLAG_SH_PLANAR;
+        const int Mrows = c.M;
+        const int nitems = 64 * (planar ? nc : Mrows);
+        for (int it = tid; it < nitems; it += nthr) {
+            int j, k;
+            float *dst;
+            if (planar) { k = it >> 6; j = it & 63; dst = dL_dsh + ((size_t)k * P + (size_t)(g0 + j)) * 3; }
+            else { j = it / Mrows; k = it - j * Mrows; dst = dL_dsh + ((size_t)(g0 + j) * Mrows + k) * 3; }
+            if (j >= nlive) continue;
+            if (k >= nc) {
+                if (!ACC) { dst[0] = 0.0f; dst[1] = 0.0f; dst[2] = 0.0f; }
+                continue;
+            }
+            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
+            if (ACC) { a0 = dst[0]; a1 = dst[1]; a2 = dst[2]; }
+            const float *r = sg_gf_lds + j * SG_GF_PITCH;
+            // SG_GF_BATCH frames at a time: every read of the batch goes out before the first value is used (the opaque point
+            // below; as a plain loop hipcc tested `visible` per frame and read dRGB under the branch: two LDS round trips per
+            // frame and item).  A frame index past K is clamped to K - 1 (a valid row, its values unused); an invisible frame's
+            // row holds stale record bytes behind slot SG_GF_BAS -- read, multiplied and dropped by the select.
+            for (int f0 = 0; f0 < nframes; f0 += SG_GF_BATCH) {
+                float vv[SG_GF_BATCH], bb[SG_GF_BATCH], d0[SG_GF_BATCH], d1[SG_GF_BATCH], d2[SG_GF_BATCH];
 #pragma unroll
-            for (int k = 0; k < 6; k++) dL_dcov3D[6 * idx + k] = A[4 + k];
+                for (int u = 0; u < SG_GF_BATCH; u++) {
+                    const float *rf = r + (f0 + u < nframes ? f0 + u : nframes - 1) * SG_GF_BLOCK;
+                    vv[u] = rf[SG_GF_VIS]; bb[u] = rf[SG_GF_BAS + k];
+                    d0[u] = rf[SG_GF_RGB]; d1[u] = rf[SG_GF_RGB + 1]; d2[u] = rf[SG_GF_RGB + 2];
+                }
+#pragma unroll
+                for (int u = 0; u < SG_GF_BATCH; u++) asm volatile("" : "+v"(vv[u]), "+v"(bb[u]), "+v"(d0[u]), "+v"(d1[u]), "+v"(d2[u]));
+#pragma unroll
+                for (int u = 0; u < SG_GF_BATCH; u++) {
+                    const bool seen = f0 + u < nframes && vv[u] != 0.0f, first = !ACC && f0 + u == 0;
+                    const float p0 = bb[u] * d0[u], p1 = bb[u] * d1[u], p2 = bb[u] * d2[u];
+                    a0 = seen ? (first ? p0 : a0 + p0) : a0;
+                    a1 = seen ? (first ? p1 : a1 + p1) : a1;
+                    a2 = seen ? (first ? p2 : a2 + p2) : a2;
+                }
+            }
+            dst[0] = a0; dst[1] = a1; dst[2] = a2;
         }
-    } else {
-        if (dL_dscales) { dL_dscales[3 * idx] = A[4]; dL_dscales[3 * idx + 1] = A[5]; dL_dscales[3 * idx + 2] = A[6]; }
-        if (dL_drots) { dL_drots[4 * idx] = A[8]; dL_drots[4 * idx + 1] = A[9]; dL_drots[4 * idx + 2] = A[10]; dL_drots[4 * idx + 3] = A[11]; }
     }
+    // an item: one geometry value of one Gaussian, in the order of the output arrays (means | opacity | scales, rotations or the six
+    // covariances | colours), float t of an array's 64-Gaussian piece on consecutive lanes
+    const bool g6rows = cov3D_precomp != nullptr;
+    const int nB = g6rows ? 6 * 64 : 3 * 64, nC = g6rows ? 0 : 4 * 64;
+    const int ngeo = 3 * 64 + 64 + nB + nC + (dL_dcolors ? 3 * 64 : 0);
+    for (int it = tid; it < ngeo; it += nthr) {
+        int t = it, j, s;
+        float *dst;
+        if (t < 3 * 64) { j = t / 3; s = t - 3 * j; dst = dL_dmeans3D + 3 * (size_t)g0 + t; }
+        else if ((t -= 3 * 64) < 64) { j = t; s = 3; dst = dL_dopacity + (size_t)g0 + t; }
+        else if ((t -= 64) < nB) {
+            if (g6rows) { j = t / 6; s = 4 + t - 6 * j; dst = dL_dcov3D ? dL_dcov3D + 6 * (size_t)g0 + t : nullptr; }
+            else { j = t / 3; s = 4 + t - 3 * j; dst = dL_dscales ? dL_dscales + 3 * (size_t)g0 + t : nullptr; }
+        }
+        else if ((t -= nB) < nC) { j = t >> 2; s = 7 + (t & 3); dst = dL_drots ? dL_drots + 4 * (size_t)g0 + t : nullptr; }
+        else { t -= nC; j = t / 3; s = SG_GF_RGB + t - 3 * j; dst = dL_dcolors + 3 * (size_t)g0 + t; }
+        if (!dst || j >= nlive) continue;
+        float a = 0.0f;
+        if (ACC) a = *dst;
+        const float *r = sg_gf_lds + j * SG_GF_PITCH;
+        // (operand order of the single-camera accumulate: new + old)
+        // (an invisible frame's row holds +0 in the geometry slots: what the single-camera kernel adds for it)
+        for (int f0 = 0; f0 < nframes; f0 += SG_GF_BATCH) {
+            float v[SG_GF_BATCH];
+#pragma unroll
+            for (int u = 0; u < SG_GF_BATCH; u++) v[u] = r[(f0 + u < nframes ? f0 + u : nframes - 1) * SG_GF_BLOCK + s];
+#pragma unroll
+            for (int u = 0; u < SG_GF_BATCH; u++) asm volatile("" : "+v"(v[u]));
+#pragma unroll
+            for (int u = 0; u < SG_GF_BATCH; u++)
+                if (f0 + u < nframes) a = (!ACC && f0 + u == 0) ? v[u] : v[u] + a;
+        }
+        *dst = a;
+    }
+}
+// the kernel's dynamic LDS (K blocks) is above the default 64-KiB limit from K = 9 on: raised once per device, to the K = 16 size
+template <int D, bool ACC> static bool sg_gauss_frames_lds(size_t bytes)
+{
+    static SgLdsLimit limit;
+    return bytes <= 64 * 1024 ||
+           sg_dyn_lds_limit(limit, (const void *)sg_gauss_frames_bwd_kernel<D, ACC>, SG_MAX_FRAMES * SG_GF_BLOCK * 4);
+}
+static bool sg_gauss_frames_fit(int D, bool acc, size_t bytes)
+{
+#define SG_GF_FIT(DD) (acc ? sg_gauss_frames_lds<DD, true>(bytes) : sg_gauss_frames_lds<DD, false>(bytes))
+    switch (D) { case 0: return SG_GF_FIT(0); case 1: return SG_GF_FIT(1); case 2: return SG_GF_FIT(2); default: return SG_GF_FIT(3); }
+#undef SG_GF_FIT
 }
 
 void sg_launch_preprocess_bwd(const SgCam &c, const SgBatch &bt, int P, const float *means3D, const float *shs,
@@ -433,14 +402,16 @@ void sg_launch_preprocess_bwd(const SgCam &c, const SgBatch &bt, int P, const fl
                               float *dL_dcolors, float *dL_dopacity, float *dL_dscales,
                               float *dL_drots, float *dL_dcov3D, int accumulate, hipStream_t st, const float *dz)
 {
-    (void)opacities;
+    (void)opacities; (void)a9buf;                           // (a9buf: the skinned path's block; the raster path sums in LDS)
     if (P <= 0) return;
     const int nblocks = (P + 255) / 256;
     dim3 grid(nblocks), block(256);
     int D = shs ? c.D : 0;
-    // K > 1 with an output the 64-byte rows have no room for (dL_dcolors beside SH rows; dL_dcov3D without cov3D_precomp -- no
-    // caller of the project asks for either): the chain of K single-camera launches the two kernels are defined by
-    if (bt.K > 1 && ((shs && dL_dcolors) || (!cov3D_precomp && dL_dcov3D))) {
+    // K > 1 with an output the LDS rows do not carry (dL_dcolors beside SH rows; dL_dcov3D without cov3D_precomp -- no caller of
+    // the project asks for either), or on a device whose runtime refuses the kernel its LDS: the chain of K single-camera
+    // launches the kernel is defined by
+    const size_t lds = (size_t)bt.K * SG_GF_BLOCK * sizeof(float);
+    if (bt.K > 1 && ((shs && dL_dcolors) || (!cov3D_precomp && dL_dcov3D) || !sg_gauss_frames_fit(D, accumulate != 0, lds))) {
         SgBatch one = bt;
         one.K = 1;
         for (int f = 0; f < bt.K; f++)
@@ -455,15 +426,10 @@ void sg_launch_preprocess_bwd(const SgCam &c, const SgBatch &bt, int P, const fl
                                      colors_precomp, scales, rotations, cov3D_precomp, radii, g,            \
                                      grec, cap, header, rec_valid, dL_dmeans3D, dL_dmeans2D, dL_dsh, dL_dcolors, \
                                      dL_dopacity, dL_dscales, dL_drots, dL_dcov3D)
-// K > 1: the per-(Gaussian, frame) chain rule at full grid (rows [K][P][4] vectors behind the K record buffers), then the ordered sums
-#define SG_PBK(DD, AA) do {                                                                                                        \
-        hipLaunchKernelGGL((sg_gauss_frame_bwd_kernel<DD>), dim3(sg_frame_grid(nblocks, bt.K)), block, 0, st, c, bt, P, means3D,   \
-                           shs, scales, rotations, cov3D_precomp, radii, g, grec, cap, header, rec_valid, a9buf, dL_dmeans2D,      \
-                           nblocks);                                                                                               \
-        hipLaunchKernelGGL((sg_gauss_sum_frames_kernel<DD, AA>), grid, block, 0, st, c, bt, P, means3D, radii, header, a9buf,      \
-                           cov3D_precomp != nullptr, dL_dmeans3D, dL_dsh, dL_dcolors, dL_dopacity, dL_dscales, dL_drots,           \
-                           dL_dcov3D);                                                                                             \
-    } while (0)
+// K > 1: 64 Gaussians x K frames per workgroup, K waves, the frames' gradients summed through LDS
+#define SG_PBK(DD, AA) hipLaunchKernelGGL((sg_gauss_frames_bwd_kernel<DD, AA>), dim3((P + 63) / 64), dim3(64 * bt.K), lds, st, c, bt, P,  \
+                                     means3D, shs, scales, rotations, cov3D_precomp, radii, g, grec, cap, header, rec_valid,          \
+                                     dL_dmeans2D, dL_dmeans3D, dL_dsh, dL_dcolors, dL_dopacity, dL_dscales, dL_drots, dL_dcov3D)
 #define SG_PB2(DD, AA) do { if (bt.K == 1) SG_PB1(DD, AA); else SG_PBK(DD, AA); } while (0)      // (K = 1: the round-3 kernel, untouched)
 #define SG_PB(DD) do { if (accumulate) SG_PB2(DD, true); else SG_PB2(DD, false); } while (0)
     sg_prof_begin(SG_K_PREPROCESS_BWD, st);

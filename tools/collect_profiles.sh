@@ -43,7 +43,7 @@ for w in cfg3 avatar; do
   extra=""; [ $w = avatar ] && extra="--workload avatar"
   $TO rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${w}_k8t -o $w -- python3 $ROOT/bench.py --full --steps 20 --warmup 5 $K8 --no-cpu-baseline $extra > $OUT/${w}_k8.log 2>&1
   f=$(find $OUT/${w}_k8t -name "*kernel_trace.csv" | head -1)
-  must=sg_record_sums_kernel; [ $w = cfg3 ] && must=sg_gauss_sum_frames_kernel      # a kernel only the K-frame steps launch
+  must=sg_record_sums_kernel; [ $w = cfg3 ] && must=sg_gauss_frames_bwd_kernel      # a kernel only the K-frame steps launch
   python3 $ROOT/tools/timeline.py $f $OUT/${w}_k8_timeline.csv must=$must > /dev/null 2>&1
   find $OUT/${w}_k8t -name "*kernel_stats.csv" -exec cp {} $OUT/${w}_k8_kernel_stats.csv \;
 done
