@@ -87,6 +87,10 @@ struct SgGeom {            // per-Gaussian projected records: recA / recB / recC
     uint32_t *flags;       // bits 0..2: SH colour channel clamped at 0
     uint2 *slot;           // (first gradient-record slot, rect width | height << 16): recC.y / recC.w again, dense, for the per-Gaussian backward
 };
+// The last 16 bytes of Gaussian i's 64-byte record, right behind recC.  The projection kernels of the work-order path leave the bits
+// of view-space z in .x (what SgGeom::depth[i] holds; .yzw = 0), so that sg_bin_ordered_kernel gathers rectangle and depth as 32
+// contiguous bytes of ONE line.  No other path writes or reads them.
+__device__ __forceinline__ float4 *sg_rec_pad(const SgGeom &g, size_t i) { return g.recC + SG_REC_STRIDE * i + 1; }
 
 struct SgBin {
     uint32_t *header;      // [0] R  [1] overflow  [2] pair allocator  [3] ntiles  [4] sort items  [5] backward work items  [6] rank items

@@ -68,9 +68,119 @@ sg_preprocess_fwd_kernel(SgCam c, SgBatch bt, int P, const float *__restrict__ m
                   sg_key_pitch_of(hist_tiles != 0, c.flags));
 }
 
-// The pair expansion of a NOBIN launch, in work order: lane i reads the rectangle (recC) and the depth of Gaussian order[i] -- what
-// the kernel above stored -- and bins it (sg_bin_ordered).  Grid: Gaussian blocks x frames.  An entry >= P is never dereferenced:
-// its lane is idle.
+// ---- K cameras per launch in work order: the forward twin of sg_gauss_frames_bwd_kernel -------------------------------------------
+// What sg_preprocess_fwd_kernel<D, true> does for K frames, with the workgroup turned by 90 degrees: 64 consecutive Gaussians x K
+// frames, K waves, wave f is frame f (camera, geometry and allocator pointers stay wave-uniform), lane = Gaussian; grid ceil(P / 64).
+//  1. The 64 Gaussians' inputs are requested ONCE per workgroup: all K waves fill SG_GFF_PITCH-float rows of LDS with coalesced
+//     loads (16 bytes per lane where the coefficient rows are one contiguous block), one barrier, and every lane takes its row.
+//     (One workgroup per (256 Gaussians, frame) asked for every 192-byte coefficient row K times, at a 192-byte lane stride: from
+//     HBM once and from the XCD's L2 K - 1 times.)  An odd pitch: lane-strided reads hit distinct banks.
+//         0-47 SH coefficients ((D+1)^2 x 3 in use) | 48-50 position | 51-53 scale | 54-57 rotation | 58 opacity
+//     cov3D_precomp / colors_precomp rows are read by sg_project_fwd where it uses them, as in the single-camera kernel.
+//  2. sg_project_fwd<D> -- the coefficients are read from the row where sg_eval_sh uses them, by the Gaussians that get that far:
+//     not 48 registers held across the projection --, then sg_store_proj_wave: a wave holds one frame's 64 Gaussians, so its
+//     record slots need no other wave.
+// No wave leaves between kernel entry and the barrier.
+#define SG_GFF_PITCH 59
+#define SG_GFF_POS 48
+#define SG_GFF_SCALE 51
+#define SG_GFF_ROT 54
+#define SG_GFF_OPAC 58
+template <int D>
+__global__ void __launch_bounds__(1024)
+sg_gauss_frames_fwd_kernel(SgCam c, SgBatch bt, int P, const float *__restrict__ means3D, const float *__restrict__ shs,
+                           const float *__restrict__ colors_precomp, const float *__restrict__ opacities,
+                           const float *__restrict__ scales, const float *__restrict__ rotations,
+                           const float *__restrict__ cov3D_precomp, SgGeom g, SgBin bn, int32_t *__restrict__ radii)
+{
+    extern __shared__ float sg_gff_lds[];                   // 64 rows of SG_GFF_PITCH floats
+    const int lane = threadIdx.x & 63;
+    const int frame = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (scalar: the frame's pointers stay in SGPRs)
+    const int g0 = (int)blockIdx.x * 64;
+    const int tid = (int)threadIdx.x, nthr = bt.K * 64;     // (K >= 2: at least 128 threads share the fill)
+    const int nlive = P - g0 < 64 ? P - g0 : 64;
+    constexpr int nc = (D + 1) * (D + 1);
+    const bool want_sh = shs != nullptr && colors_precomp == nullptr;
+    {
+        // ---- 1. the fill: every request goes out before the first value is written
+        // coefficient rows: with M = (D+1)^2 the 64 rows are ONE block of nlive * nc * 3 floats (16-byte aligned: g0 is a multiple
+        // of 64), taken as 16-byte vectors; what is left (no whole vector, or rows of M > (D+1)^2 coefficients) goes by the float
+        const int nsh = want_sh ? nlive * nc * 3 : 0;
+        const int nv4 = c.M == nc && ((uintptr_t)shs & 15u) == 0 ? nsh >> 2 : 0;
+        const float4 *src4 = (const float4 *)(shs + (size_t)g0 * nc * 3);
+        float4 v4[6];                                       // 64 * 48 / 4 = 768 vectors over >= 128 threads
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            const int f = tid + i * nthr;
+            if (f < nv4) v4[i] = src4[f];
+        }
+        float vp[2], vs[2], vq[2], vo = 0.0f;               // 192, 192, 256 and 64 floats over >= 128 threads
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const int t = tid + i * nthr;
+            if (t < nlive * 3) vp[i] = means3D[3 * (size_t)g0 + t];
+            if (!cov3D_precomp) {
+                if (t < nlive * 3) vs[i] = scales[3 * (size_t)g0 + t];
+                if (t < nlive * 4) vq[i] = rotations[4 * (size_t)g0 + t];
+            }
+        }
+        if (tid < nlive) vo = opacities[g0 + tid];
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            const int f = tid + i * nthr;
+            if (f < nv4) {
+                const float e[4] = { v4[i].x, v4[i].y, v4[i].z, v4[i].w };
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const int t = 4 * f + u, j = t / (nc * 3);
+                    sg_gff_lds[j * SG_GFF_PITCH + (t - j * nc * 3)] = e[u];
+                }
+            }
+        }
+        for (int t = 4 * nv4 + tid; t < nsh; t += nthr) {
+            const int j = t / (nc * 3), k = t - j * nc * 3;
+            sg_gff_lds[j * SG_GFF_PITCH + k] = shs[(size_t)(g0 + j) * c.M * 3 + k];
+        }
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const int t = tid + i * nthr;
+            if (t < nlive * 3) sg_gff_lds[(t / 3) * SG_GFF_PITCH + SG_GFF_POS + t % 3] = vp[i];
+            if (!cov3D_precomp) {
+                if (t < nlive * 3) sg_gff_lds[(t / 3) * SG_GFF_PITCH + SG_GFF_SCALE + t % 3] = vs[i];
+                if (t < nlive * 4) sg_gff_lds[(t >> 2) * SG_GFF_PITCH + SG_GFF_ROT + (t & 3)] = vq[i];
+            }
+        }
+        if (tid < nlive) sg_gff_lds[tid * SG_GFF_PITCH + SG_GFF_OPAC] = vo;
+    }
+    __syncthreads();                                        // every wave of the workgroup arrives (no return above)
+    // ---- 2. frame `frame` of Gaussian g0 + lane
+    const SgCam cf = sg_frame(c, frame, bt.cam_stride);
+    const SgGeom gf = sg_frame(g, (size_t)frame * bt.geom);
+    const SgBin bf = sg_frame(bn, (size_t)frame * bt.bin);
+    const int idx = g0 + lane;
+    const bool live = idx < P;
+    const float *row = sg_gff_lds + lane * SG_GFF_PITCH;
+    SgProj o;
+    o.mr = 0; o.tt = 0; o.clampbits = 0; o.x0 = o.y0 = o.x1 = o.y1 = 0;
+    o.pix[0] = o.pix[1] = 0; o.conic[0] = o.conic[1] = o.conic[2] = 0; o.rgb[0] = o.rgb[1] = o.rgb[2] = 0; o.depth = 0;
+    float opac = 0.0f;
+    if (live) {
+        float p[3] = { row[SG_GFF_POS], row[SG_GFF_POS + 1], row[SG_GFF_POS + 2] };
+        float s3[3] = { 0, 0, 0 }, q[4] = { 0, 0, 0, 0 };
+        if (!cov3D_precomp) {
+            s3[0] = row[SG_GFF_SCALE]; s3[1] = row[SG_GFF_SCALE + 1]; s3[2] = row[SG_GFF_SCALE + 2];
+            q[0] = row[SG_GFF_ROT]; q[1] = row[SG_GFF_ROT + 1]; q[2] = row[SG_GFF_ROT + 2]; q[3] = row[SG_GFF_ROT + 3];
+        }
+        sg_project_fwd<D>(cf, p, s3, q, cov3D_precomp ? cov3D_precomp + 6 * (size_t)idx : nullptr,
+                          colors_precomp ? colors_precomp + 3 * (size_t)idx : nullptr, row, o);
+        opac = row[SG_GFF_OPAC];
+    }
+    sg_store_proj_wave(live, idx, o, opac, gf, bf, radii + (size_t)frame * bt.P);
+}
+
+// The pair expansion of a NOBIN launch, in work order: lane i reads the rectangle (recC) and the depth bits behind it (sg_rec_pad)
+// of Gaussian order[i] -- 32 contiguous bytes of one line of what the kernels above stored -- and bins it (sg_bin_ordered).
+// Grid: Gaussian blocks x frames.  An entry >= P is never dereferenced: its lane is idle.
 __global__ void __launch_bounds__(256)
 sg_bin_ordered_kernel(SgBatch bt, int P, SgGeom g, SgBin bn, int gx, uint32_t key_pitch, const uint32_t *__restrict__ order)
 {
@@ -81,9 +191,9 @@ sg_bin_ordered_kernel(SgBatch bt, int P, SgGeom g, SgBin bn, int gx, uint32_t ke
     uint32_t gid = pos < P ? order[pos] : 0xffffffffu;
     uint32_t rmin = 0u, rwh = 0u, dep = 0u;
     if (gid < (uint32_t)P) {
-        const float4 rc = g.recC[SG_REC_STRIDE * (size_t)gid];
+        const float4 rc = g.recC[SG_REC_STRIDE * (size_t)gid], pad = *sg_rec_pad(g, (size_t)gid);
         rmin = __float_as_uint(rc.z); rwh = __float_as_uint(rc.w);
-        dep = __float_as_uint(g.depth[gid]);
+        dep = __float_as_uint(pad.x);
     } else gid = 0u;
     sg_bin_ordered(gid, rmin, rwh, dep, bn, gx, scratch_all[wave], scratch_all[wave] + 256, key_pitch);
 }
@@ -110,7 +220,10 @@ void sg_launch_preprocess_fwd_ordered(const SgCam &c, const SgBatch &bt, int P, 
     const bool ord = order && sg_order_applies(c);
 #define SG_PPO(DD, OO) hipLaunchKernelGGL((sg_preprocess_fwd_kernel<DD, OO>), grid, block, (size_t)ht * 4, st, c, bt, P, means3D, shs, \
                                      colors_precomp, opacities, scales, rotations, cov3D_precomp, g, b, sg_cap32(cap), radii, ht, nblocks)
-#define SG_PP(DD) do { if (ord) SG_PPO(DD, true); else SG_PPO(DD, false); } while (0)
+// K > 1 in work order: 64 Gaussians x K frames per workgroup, K waves, the inputs staged once in LDS
+#define SG_PPK(DD) hipLaunchKernelGGL((sg_gauss_frames_fwd_kernel<DD>), dim3((P + 63) / 64), dim3(64 * bt.K), 64 * SG_GFF_PITCH * sizeof(float), \
+                                     st, c, bt, P, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, g, b, radii)
+#define SG_PP(DD) do { if (ord && bt.K > 1) SG_PPK(DD); else if (ord) SG_PPO(DD, true); else SG_PPO(DD, false); } while (0)
     int D = colors_precomp ? 0 : c.D;
     sg_prof_begin(SG_K_PREPROCESS_FWD, st);
     switch (D) { case 0: SG_PP(0); break; case 1: SG_PP(1); break; case 2: SG_PP(2); break; default: SG_PP(3); break; }
@@ -118,6 +231,7 @@ void sg_launch_preprocess_fwd_ordered(const SgCam &c, const SgBatch &bt, int P, 
         hipLaunchKernelGGL(sg_bin_ordered_kernel, dim3(nblocks, bt.K), block, 0, st, bt, P, g, b, c.gx, sg_key_pitch_of(false, c.flags), order);
     sg_prof_end(SG_K_PREPROCESS_FWD, st);
 #undef SG_PP
+#undef SG_PPK
 #undef SG_PPO
 }
 

@@ -322,6 +322,40 @@ __device__ __forceinline__ void sg_store_proj_nobin(bool live, int idx, const Sg
     for (int w = 0; w < wave_; w++) base += sWaveTot[w];
     if (live) {
         g.recC[SG_REC_STRIDE * (size_t)idx] = make_float4(o.rgb[2], __uint_as_float(base + incl - o.tt), __uint_as_float(rmin), __uint_as_float(rwh));
+        *sg_rec_pad(g, (size_t)idx) = make_float4(o.depth, 0.0f, 0.0f, 0.0f);      // sg_bin_ordered_kernel's depth, on recC's line
+        g.slot[idx] = make_uint2(base + incl - o.tt, rwh);
+    }
+}
+
+// sg_store_proj_nobin for a WAVE that holds one frame's 64 consecutive Gaussians (sg_gauss_frames_fwd_kernel): the same stores; the
+// wave's slots -- still one contiguous range in lane order, what sg_sum_records_coop relies on -- are reserved by lane 63 with one
+// returning atomic on the frame's allocator word, so the wave needs no other wave: no workgroup barrier, no LDS.
+__device__ __forceinline__ void sg_store_proj_wave(bool live, int idx, const SgProj &o, float opac, SgGeom g, SgBin bn,
+                                                   int32_t *__restrict__ radii)
+{
+    const int lane = threadIdx.x & 63;
+    uint32_t incl = o.tt;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        uint32_t v = __shfl_up(incl, s, 64);
+        if (lane >= s) incl += v;
+    }
+    const uint32_t rmin = (uint32_t)o.x0 | ((uint32_t)o.y0 << 16);
+    const uint32_t rwh = (uint32_t)(o.x1 - o.x0) | ((uint32_t)(o.y1 - o.y0) << 16);
+    if (live) {
+        radii[idx] = o.mr;
+        g.recA[SG_REC_STRIDE * (size_t)idx] = make_float4(o.pix[0], o.pix[1], o.conic[0], o.conic[1]);
+        g.recB[SG_REC_STRIDE * (size_t)idx] = make_float4(o.conic[2], o.mr ? opac : 0.0f, o.rgb[0], o.rgb[1]);
+        g.depth[idx] = o.depth;
+        g.flags[idx] = o.clampbits;
+    }
+    // (behind the stores above: the wave waits for the atomic's answer where it is issued, the stores are on their way meanwhile)
+    uint32_t base = 0u;
+    if (lane == 63 && incl) base = atomicAdd(&bn.header[2], incl);      // (lane 63's inclusive sum: the wave's total)
+    base = __shfl(base, 63, 64);
+    if (live) {
+        g.recC[SG_REC_STRIDE * (size_t)idx] = make_float4(o.rgb[2], __uint_as_float(base + incl - o.tt), __uint_as_float(rmin), __uint_as_float(rwh));
+        *sg_rec_pad(g, (size_t)idx) = make_float4(o.depth, 0.0f, 0.0f, 0.0f);
         g.slot[idx] = make_uint2(base + incl - o.tt, rwh);
     }
 }
