@@ -71,26 +71,29 @@ __device__ __forceinline__ int sg_tile_of_block(int block)
 // Which 8x8 quadrants of the tile at (X0,Y0) can this entry reach with alpha >= 1/255?
 // alpha = min(.99, o exp(power)) >= 1/255  =>  power >= -tau, tau = ln(255 o), i.e. the pixel lies in the
 // ellipse q(d) = A dx^2 + 2 B dx dy + C dy^2 <= 2 tau (d = pixel - mean).  A quadrant is kept iff the
-// minimum of q over its pixel rectangle (0 if the mean is inside, else the minimum over the four edges,
-// each a clamped 1-D parabola) is within the bound.  tau and the comparison carry safety margins far
+// minimum of q over its pixel rectangle (0 if the mean is inside, else the minimum over the edges that face
+// the mean, each a clamped 1-D parabola) is within the bound.  tau and the comparison carry safety margins far
 // above the fp32 rounding of power / exp / this test, so a pixel the blend loop would accept is never
 // dropped; ill-conditioned conics keep all quadrants.
-__device__ __forceinline__ float sg_min_q_rect(float A, float B, float C, float mx, float my, float x0, float x1,
-                                               float y0, float y1)
+// q grows along every ray from the mean, so its minimum over the rectangle lies on the part of the boundary the mean
+// sees: the vertical edge on the mean's side if the mean is outside [x0, x1], the horizontal one on its side if it is
+// outside [y0, y1] -- two clamped parabolas, where all four edges were evaluated before.  Both go through the rectangle's
+// point nearest the mean, (dx, dy2) = the mean's offset clamped into the rectangle: outside a range that is the facing edge;
+// inside it the offset is 0 and the line through the mean yields a point of the other facing edge (never below that
+// edge's own minimum, up to rounding) or, with the mean inside the rectangle, q = 0.  Straight-line, no compare, no select.
+// rA = 1 / A, rC = 1 / C: once per entry (sg_quad_mask).
+__device__ __forceinline__ float sg_min_q_rect(float A, float B, float C, float rA, float rC, float mx, float my, float x0,
+                                               float x1, float y0, float y1)
 {
-    if (mx >= x0 && mx <= x1 && my >= y0 && my <= y1) return 0.0f;
-    const float rA = __builtin_amdgcn_rcpf(A), rC = __builtin_amdgcn_rcpf(C);
-    float best = 3.0e38f;
-#pragma unroll
-    for (int e = 0; e < 2; e++) {
-        float dx = (e ? x1 : x0) - mx;
-        float dy = fminf(fmaxf(-B * dx * rC, y0 - my), y1 - my);
-        best = fminf(best, fmaf(A * dx, dx, fmaf(2.0f * B * dx, dy, C * dy * dy)));
-        float dy2 = (e ? y1 : y0) - my;
-        float dx2 = fminf(fmaxf(-B * dy2 * rA, x0 - mx), x1 - mx);
-        best = fminf(best, fmaf(A * dx2, dx2, fmaf(2.0f * B * dx2, dy2, C * dy2 * dy2)));
-    }
-    return best;
+    const float lx = x0 - mx, hx = x1 - mx, ly = y0 - my, hy = y1 - my;      // the rectangle, relative to the mean
+    const float B2 = 2.0f * B;
+    const float dx = fminf(fmaxf(0.0f, lx), hx);                              // the vertical edge that faces the mean (or the mean's column)
+    const float dy = fminf(fmaxf(-B * dx * rC, ly), hy);
+    const float qv = fmaf(A * dx, dx, fmaf(B2 * dx, dy, C * dy * dy));
+    const float dy2 = fminf(fmaxf(0.0f, ly), hy);                             // the horizontal one (or the mean's row)
+    const float dx2 = fminf(fmaxf(-B * dy2 * rA, lx), hx);
+    const float qh = fmaf(A * dx2, dx2, fmaf(B2 * dx2, dy2, C * dy2 * dy2));
+    return fminf(qv, qh);
 }
 
 // Bounding box (tile-relative pixel coordinates) of the lanes of an 8x8 quadrant whose bit is set in `live`
@@ -129,21 +132,22 @@ __device__ __forceinline__ float4 sg_live_box16(unsigned long long live, int ox,
 __device__ __forceinline__ uint32_t sg_quad_mask(float4 a, float4 b, float X0, float Y0, const float4 *__restrict__ box)
 {
     const float o255 = 255.0f * b.y;
-    if (!(o255 >= 0.999f)) return 0u;
+    const bool reach = o255 >= 0.999f;           // (a select at the end, not a branch: the test is short and few lanes fail it)
     const float bound = 2.0f * (__logf(o255) * 1.002f + 0.004f) + 0.01f;
     const float A = a.z, B = a.w, C = b.x;
     const float det = A * C - B * B;
     const bool illc = !(det > 1e-3f * A * C) || !(A > 0.0f) || !(C > 0.0f);     // ill-conditioned: keep everything live
     const float mx = a.x - X0, my = a.y - Y0;
+    const float rA = __builtin_amdgcn_rcpf(A), rC = __builtin_amdgcn_rcpf(C);
     uint32_t m = 0;
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         const float4 bx = box[q];
         if (!(bx.x <= bx.y)) continue;
-        float mq = illc ? 0.0f : sg_min_q_rect(A, B, C, mx, my, bx.x, bx.y, bx.z, bx.w);
+        float mq = illc ? 0.0f : sg_min_q_rect(A, B, C, rA, rC, mx, my, bx.x, bx.y, bx.z, bx.w);
         if (mq * 0.999f <= bound) m |= 1u << q;
     }
-    return m;
+    return reach ? m : 0u;
 }
 
 
@@ -718,6 +722,8 @@ sg_order_items_kernel(SgBatch bt, const uint32_t *__restrict__ header, const uin
 // No scratch in either.  16 384 B of LDS per workgroup (the entries' sums live in their staged rows) allow ten workgroups per CU, so
 // the registers alone set the count.
 #define SG_BWD_TW_WAVES (SG_BWD_AUX ? 6 : 8)
+// lane mask of the lanes below d (wave-uniform; d <= 0: none, d >= 64: all)
+__device__ __forceinline__ unsigned long long sg_lanes_below(int d) { return d >= 64 ? ~0ull : d > 0 ? (1ull << d) - 1ull : 0ull; }
 #define SG_BWD_AUX 0
 #include "sg_render_bwd.inc"
 #undef SG_BWD_AUX

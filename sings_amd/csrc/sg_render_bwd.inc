@@ -85,9 +85,9 @@ sg_render_bwd_kernel(SG_BWD_PARAMS)
 #if !SG_BWD_AUX
     const SgAuxBwd ax = { };
 #endif
-    // per wave: its staged batch -- (mean x, mean y, A', B') (C', opacity, colour 0, 1) (colour 2, z [AUX], quadrant mask, opacity) and, for the
+    // per wave: its staged batch -- (mean x, mean y, A', B') (C', opacity, colour 0, 1) (colour 2, z [AUX], -, opacity) and, for the
     // record store, (A, B, C, record slot): kept here, not in registers, across the walk.  Row as 16 floats: 0-3 `ga`, 4-7 `gb`, 8 `gc`,
-    // 9 `gz`, 10 the mask, 11 the opacity once more, 12-15 (A, B, C, slot).  An entry's nine (AUX: ten) sums are filed over floats 0-8
+    // 9 `gz`, 10 unused (the batch's quadrant masks are lane masks in scalar registers), 11 the opacity once more, 12-15 (A, B, C, slot).  An entry's nine (AUX: ten) sums are filed over floats 0-8
     // (9) of its OWN row (SG_BWD_FILE through `sG`): the walk has read them by then and every other entry reads only its own row.
     // Floats 10-15 are never overwritten; the record store takes the opacity from float 11.  A row nobody filed still holds staged
     // floats (or an earlier batch's): `filed` keeps the store from reading it.
@@ -185,14 +185,19 @@ sg_render_bwd_kernel(SG_BWD_PARAMS)
                 const float4 a = recA[SG_REC_STRIDE * (size_t)gid], b = recB[SG_REC_STRIDE * (size_t)gid];
                 sR[wave][lane][0] = make_float4(a.x, a.y, SG_KA * a.z, SG_KB * a.w);
                 sR[wave][lane][1] = make_float4(SG_KA * b.x, b.y, b.z, b.w);
-                sR[wave][lane][2] = make_float4(c4.x, AUX ? ax.depth[gid] : 0.0f, __uint_as_float(mk), b.y);
+                sR[wave][lane][2] = make_float4(c4.x, AUX ? ax.depth[gid] : 0.0f, 0.0f, b.y);
                 sR[wave][lane][3] = make_float4(a.z, a.w, b.x, 0.0f);
             }
             const uint32_t goff = __float_as_uint(c4.y), mn = __float_as_uint(c4.z), wh = __float_as_uint(c4.w);
             const int x0 = mn & 0xffff, y0 = mn >> 16, rw = wh & 0xffff;
             sR[wave][lane][3].w = __uint_as_float(goff + (uint32_t)((ty - y0) * rw + (tx - x0)));
         }
-        unsigned long long todo = __ballot(mk != 0u);                  // entries still to walk
+        // the batch's masks, one lane mask per quadrant in scalar registers: bit k of mq[q] = the forward composited entry base + k in
+        // quadrant q and the entry is not behind the quadrant's deepest contributor (base + k < maxq4[q]: the lanes below maxq4[q] - base,
+        // formed on the scalar unit).  The walk tests them on the scalar unit.
+        const unsigned long long mq0 = __ballot(mk & 1u) & sg_lanes_below(maxq4[0] - base), mq1 = __ballot(mk & 2u) & sg_lanes_below(maxq4[1] - base),
+                                 mq2 = __ballot(mk & 4u) & sg_lanes_below(maxq4[2] - base), mq3 = __ballot(mk & 8u) & sg_lanes_below(maxq4[3] - base);
+        unsigned long long todo = mq0 | mq1 | mq2 | mq3;               // entries still to walk
         unsigned long long filed = 0ull;                               // entries whose row of sums was written
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_wave_barrier();
@@ -200,20 +205,14 @@ sg_render_bwd_kernel(SG_BWD_PARAMS)
             const int k = 63 - __builtin_clzll(todo);
             todo &= ~(1ull << k);
             const int pos = base + k;                                   // the entry's position in the tile's list
-            const float4 ga = sR[wave][k][0], gb = sR[wave][k][1], gm = sR[wave][k][2];
-            const float gc = gm.x, gz = gm.y;
-            uint32_t mke = __builtin_amdgcn_readfirstlane(__float_as_uint(gm.z));
-            // the quadrants to evaluate: composited there by the forward, and not behind the quadrant's deepest contributor
-            if (pos >= maxq4[0]) mke &= ~1u;
-            if (pos >= maxq4[1]) mke &= ~2u;
-            if (pos >= maxq4[2]) mke &= ~4u;
-            if (pos >= maxq4[3]) mke &= ~8u;
-            // the entry's partials, added over those quadrants in the order 0, 1, 2, 3
+            const float4 ga = sR[wave][k][0], gb = sR[wave][k][1];
+            const float gc = sR[wave][k][2].x, gz = AUX ? sR[wave][k][2].y : 0.0f;
+            // the entry's partials, added over its quadrants in the order 0, 1, 2, 3
             uint32_t some = 0u;                                         // some pixel of the tile took a gradient from this entry (a scalar register)
-            if (mke & 1u) SG_BWD_QUAD(0);
-            if (mke & 2u) SG_BWD_QUAD(1);
-            if (mke & 4u) SG_BWD_QUAD(2);
-            if (mke & 8u) SG_BWD_QUAD(3);
+            if ((mq0 >> k) & 1ull) SG_BWD_QUAD(0);
+            if ((mq1 >> k) & 1ull) SG_BWD_QUAD(1);
+            if ((mq2 >> k) & 1ull) SG_BWD_QUAD(2);
+            if ((mq3 >> k) & 1ull) SG_BWD_QUAD(3);
             __builtin_amdgcn_wave_barrier();                           // (no instruction: keeps the paths above from being threaded into the tail, with copies)
             if (some) {                                                // (else no pixel of the tile: the row reads as zero)
                 SG_BWD_FILE(acc, acc[9], k);
@@ -229,7 +228,7 @@ sg_render_bwd_kernel(SG_BWD_PARAMS)
             float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0;
             float r2 = 0.0f, r3 = 0.0f;
             if ((filed >> lane) & 1ull) {                         // (an entry nobody filed has no staged record either)
-                const float4 s03 = sR[wave][lane][0], s47 = sR[wave][lane][1], s8o = sR[wave][lane][2];    // the sums, (8, 9 [AUX], mask, opacity)
+                const float4 s03 = sR[wave][lane][0], s47 = sR[wave][lane][1], s8o = sR[wave][lane][2];    // the sums, (8, 9 [AUX], -, opacity)
                 const float s[10] = { s03.x, s03.y, s03.z, s03.w, s47.x, s47.y, s47.z, s47.w, s8o.x, s8o.y };
                 const float no = -s8o.w, nh = 0.5f * no;                            // -opacity, -opacity / 2
                 const float m0 = fmaf(cn.x, s[0], cn.y * s[1]), m1 = fmaf(cn.y, s[0], cn.z * s[1]);   // conic . first moments
