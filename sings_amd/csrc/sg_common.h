@@ -320,6 +320,7 @@ void sg_launch_preprocess_bwd(const SgCam &c, const SgBatch &bt, int P, const fl
 // a HIP graph went wrong on ROCm 7.2 as soon as the host had synchronised once between two replays when the graph
 // contained memset nodes (tools/graph_gap.py reproduces it); a kernel node has no such problem and is no slower.
 void sg_zero_async(void *p, size_t bytes, hipStream_t st);
+// SMPL kinematic chain and learned pose tables (sg_pose.hip)
 void sg_launch_joint_transforms(int B, int J, const float *pose, const float *joints, const int *parents, const float *post,
                                 const float *dA, float *out0, float *out1, hipStream_t st);
 void sg_launch_pose_transforms(int K, int F, int J, int NBu, const int *frame_idx, const float *global_orient, const float *body_pose,
@@ -328,9 +329,11 @@ void sg_launch_pose_transforms(int K, int F, int J, int NBu, const int *frame_id
 void sg_launch_pose_transforms_bwd(int K, int F, int J, int NBu, const int *frame_idx, const float *global_orient, const float *body_pose,
                                    const float *aa, const float *joints, const int *parents, const float *post, const float *dA,
                                    const float *d_transl_rows, float *d_global_orient, float *d_body_pose, float *d_transl, hipStream_t st);
+// stand-alone rotation conversions (sg_rot.hip)
 void sg_launch_m2q(int N, const float *m, const float *dq, float *out, hipStream_t st);
 int sg_launch_rot_map(int op, int N, const float *in, const float *g, float *out, hipStream_t st);
 void sg_launch_qmul(int N, const float *a, const float *b, const float *g, float *out0, float *out1, hipStream_t st);
+// stand-alone lbs_extra (sg_lbs.hip; its backward's slabs go through sg_launch_skin_reduce)
 void sg_launch_lbs_fwd(int P, int J, const float *W, const float *A, const float *v, float *T_out, float *verts, hipStream_t st);
 void sg_launch_lbs_bwd(int P, int J, const float *W, const float *A, const float *v, const float *dT, const float *dverts,
                        float *slab, float *dv, float *dA, hipStream_t st);
@@ -347,6 +350,9 @@ struct SgSceneAvatar;
 void sg_launch_scene_fwd(const SgCam &c, const SgBatch &bt, int S, const SgSceneAvatar *avatars, SgGeom g, SgBin b, size_t cap,
                          int32_t *radii, float *posed_xyz, float *posed_rotq, float *posed_scales, hipStream_t st);
 size_t sg_skin_slab_floats(int P, int K);
+// sums the `nrows` per-wave slab rows (of `stride` floats) of each of K frames, left in `slab` by the skinned backward kernels or
+// by sg_lbs.hip's, into dL_dA [K,J,16] and dL_dtransl [K,3] (or NULL); `slab` has sg_skin_slab_floats
+void sg_launch_skin_reduce(float *slab, int nrows, int stride, int J, int K, float *dL_dA, float *dL_dtransl, hipStream_t st);
 size_t sg_photo_loss_ws_bytes_impl(int W, int H);
 int sg_tp_check(const SgTriplane *tp);
 size_t sg_triplane_ws_bytes_impl(const SgTriplane *tp);

@@ -320,7 +320,7 @@ extern "C" int sg_mesh_subdivide(int V, int F, int Fs, const int32_t *faces, con
 }
 
 // ---- midpoint rows: dst[e] = (src[a] + src[b]) * 0.5f (one add, one exact scaling: the bits of `values[rows].mean(axis=1)`), or
-// src[a] for labels.  Rows of a multiple of four floats on 16-byte boundaries move as float4 (sg_skin.hip's weight rows); any other
+// src[a] for labels.  Rows of a multiple of four floats on 16-byte boundaries move as float4 (sg_skin.h's weight rows); any other
 // width one float per lane, lanes consecutive over the flat [E, C] output.  An endpoint outside [0, V) is never dereferenced.
 template <typename T, bool MEAN>
 __global__ void __launch_bounds__(SG_MESH_THREADS)

@@ -1,7 +1,8 @@
 // Rotation conversions of SinGS' pose / Gaussian-rotation bookkeeping as device functions:
 // value and analytic gradient of the expressions in sings/rec/utils/geometry/rotations.py --
 //   quaternion_to_matrix :38-66, quaternion_multiply (raw product :372-390 + standardize :357) :393-407,
-//   axis_angle_to_quaternion :482-511, quaternion_to_axis_angle :514-545, rotation_6d_to_matrix :545-566.
+//   axis_angle_to_quaternion :482-511, quaternion_to_axis_angle :514-545, rotation_6d_to_matrix :545-566,
+//   matrix_to_quaternion :98-149.
 // Quaternions are real part first.  Gradients are those torch.autograd gives for the reference expressions
 // (torch.where / clamp pass the gradient of the selected branch; F.normalize divides by max(norm, 1e-12)).
 // One lane handles one element; used by the stand-alone kernels of sg_rot.hip and by the LBS-fused kernels
@@ -155,4 +156,64 @@ __device__ __forceinline__ void sg_q2aa_bwd(const float q[4], const float g[3], 
     const float radial = n > 0.0f ? dLdt * dt_dn / n : 0.0f;                      // d|v|/dv = v / |v| (0 at 0)
 #pragma unroll
     for (int k = 0; k < 3; k++) dq[1 + k] = g[k] / f + q[1 + k] * radial;
+}
+
+// ---- matrix -> quaternion (rotations.py:98-149); best / qab: the candidate chosen and its value, kept for the gradient
+__device__ __forceinline__ void sg_m2q(const float m[9], float q[4], int &best, float &qab)
+{
+    float x0 = 1.0f + m[0] + m[4] + m[8], x1 = 1.0f + m[0] - m[4] - m[8];
+    float x2 = 1.0f - m[0] + m[4] - m[8], x3 = 1.0f - m[0] - m[4] + m[8];
+    float a0 = x0 > 0.0f ? sqrtf(x0) : 0.0f, a1 = x1 > 0.0f ? sqrtf(x1) : 0.0f;
+    float a2 = x2 > 0.0f ? sqrtf(x2) : 0.0f, a3 = x3 > 0.0f ? sqrtf(x3) : 0.0f;
+    best = 0; qab = a0;
+    if (a1 > qab) { best = 1; qab = a1; }
+    if (a2 > qab) { best = 2; qab = a2; }
+    if (a3 > qab) { best = 3; qab = a3; }
+    float n0, n1, n2, n3;
+    if (best == 0)      { n0 = a0 * a0;      n1 = m[7] - m[5]; n2 = m[2] - m[6]; n3 = m[3] - m[1]; }
+    else if (best == 1) { n0 = m[7] - m[5];  n1 = a1 * a1;     n2 = m[3] + m[1]; n3 = m[2] + m[6]; }
+    else if (best == 2) { n0 = m[2] - m[6];  n1 = m[3] + m[1]; n2 = a2 * a2;     n3 = m[5] + m[7]; }
+    else                { n0 = m[3] - m[1];  n1 = m[6] + m[2]; n2 = m[7] + m[5]; n3 = a3 * a3; }
+    float den = 2.0f * (qab > 0.1f ? qab : 0.1f);
+    q[0] = n0 / den; q[1] = n1 / den; q[2] = n2 / den; q[3] = n3 / den;
+}
+
+// gradient of sg_m2q: dq[4] -> dm[9] (autograd of the reference expression: zero sub-gradient of
+// sqrt at <= 0, of the 0.1 floor below it, and only the selected candidate receives gradient)
+__device__ __forceinline__ void sg_m2q_bwd(const float q[4], int best, float qab, const float dq[4], float dm[9])
+{
+#pragma unroll
+    for (int i = 0; i < 9; i++) dm[i] = 0.0f;
+    float den = 2.0f * (qab > 0.1f ? qab : 0.1f);
+    float dn0 = dq[0] / den, dn1 = dq[1] / den, dn2 = dq[2] / den, dn3 = dq[3] / den;
+    float dden = -(dq[0] * q[0] + dq[1] * q[1] + dq[2] * q[2] + dq[3] * q[3]) / den;
+    // d(num_best)/dx = 1 (x>0), d(den)/dx = 2 * [qab > 0.1] * 0.5 / qab
+    float dx = 0.0f;
+    if (qab > 0.0f) {
+        float dnb = best == 0 ? dn0 : (best == 1 ? dn1 : (best == 2 ? dn2 : dn3));
+        dx = dnb + (qab > 0.1f ? dden / qab : 0.0f);
+    }
+    if (best == 0) {
+        dm[0] += dx; dm[4] += dx; dm[8] += dx;
+        dm[7] += dn1; dm[5] -= dn1; dm[2] += dn2; dm[6] -= dn2; dm[3] += dn3; dm[1] -= dn3;
+    } else if (best == 1) {
+        dm[0] += dx; dm[4] -= dx; dm[8] -= dx;
+        dm[7] += dn0; dm[5] -= dn0; dm[3] += dn2; dm[1] += dn2; dm[2] += dn3; dm[6] += dn3;
+    } else if (best == 2) {
+        dm[0] -= dx; dm[4] += dx; dm[8] -= dx;
+        dm[2] += dn0; dm[6] -= dn0; dm[3] += dn1; dm[1] += dn1; dm[5] += dn3; dm[7] += dn3;
+    } else {
+        dm[0] -= dx; dm[4] -= dx; dm[8] += dx;
+        dm[3] += dn0; dm[1] -= dn0; dm[6] += dn1; dm[2] += dn1; dm[7] += dn2; dm[5] += dn2;
+    }
+}
+
+// rotations.py:372-407: Hamilton product, real part made non-negative
+__device__ __forceinline__ void sg_qmul_std(const float a[4], const float b[4], float o[4])
+{
+    o[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
+    o[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
+    o[2] = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
+    o[3] = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
+    if (o[0] < 0.0f) { o[0] = -o[0]; o[1] = -o[1]; o[2] = -o[2]; o[3] = -o[3]; }
 }

@@ -130,44 +130,8 @@ sg_skin_bwd_kernel(SG_SKBWD_PARAMS)
         dL_dopacity[idx] = dop;
         dL_dmeans2D[3 * idx] = g2[0]; dL_dmeans2D[3 * idx + 1] = g2[1]; dL_dmeans2D[3 * idx + 2] = 0.0f;
     }
-    // dL/dsh: coefficient-major planes [M][P][3], only the (D+1)^2 in use (SG_FLAG_SH_PLANAR: 12-byte stores, coalesced across
-    // the lanes); or the reference's rows (every one of the M rows is written): through LDS as 16-B-per-lane coalesced stores when
-    // M == 16
-    if (c.flags & SG_FLAG_SH_PLANAR) {
-        if (live) {
-#pragma unroll
-            for (int kq = 0; kq < nc; kq++)
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++) {
-                    float *d = dL_dsh + ((size_t)kq * P + idx) * 3 + ch;
-                    *d = accumulate ? dsh[3 * kq + ch] + *d : dsh[3 * kq + ch];
-                }
-        }
-    } else if (Mrows == 16) {
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            if ((lane >> 5) == h) {
-                float *row = sWw + (lane & 31) * SG_ROW_LDS;
-#pragma unroll
-                for (int i = 0; i < 48; i++) row[i] = i < nc * 3 ? dsh[i < nc * 3 ? i : 0] : 0.0f;
-            }
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            __builtin_amdgcn_wave_barrier();
-            sg_rows48_store(dL_dsh, g0 + 32 * h, P, lane, sWw, 32, accumulate != 0);
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            __builtin_amdgcn_wave_barrier();
-        }
-    } else if (live) {
-        float *dsh_row = dL_dsh + (size_t)idx * Mrows * 3;
-        if (accumulate) {
-#pragma unroll
-            for (int i = 0; i < nc * 3; i++) dsh_row[i] += dsh[i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < nc * 3; i++) dsh_row[i] = dsh[i];
-            for (int i = nc * 3; i < Mrows * 3; i++) dsh_row[i] = 0.0f;
-        }
-    }
+    // dL/dsh: planes, or the reference's rows: every one of the M rows is written (accumulate: the (D+1)^2 in use are added to)
+    sg_skin_store_dsh<D, accumulate, !accumulate>(dsh, c.flags & SG_FLAG_SH_PLANAR, Mrows == 16, Mrows, P, idx, g0, lane, live, dL_dsh, sWw);
     // ---- dA[J x 16] += W^T[J x 64] . dT[64 x 16] on the matrix cores
     float *sdT = sTw;
 #pragma unroll
@@ -202,12 +166,5 @@ sg_skin_bwd_kernel(SG_SKBWD_PARAMS)
         for (int r = 0; r < 4; r++) out[(16 * cch + 4 * (lane >> 4) + r) * 16 + (lane & 15)] = acc[r];
         __builtin_amdgcn_wave_barrier();
     }
-    // dtransl: wave sum
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-        float v = dtr[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        if (lane == 0) out[SG_JMAX * 16 + i] = v;
-    }
+    sg_skin_store_dtransl(dtr, lane, out);
 }

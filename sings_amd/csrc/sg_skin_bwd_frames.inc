@@ -274,13 +274,7 @@ sg_skin_bwd_frames_kernel(SgCam c0, SgBatch bt, int P, SgSkin k0, const float *_
 #pragma unroll
             for (int r = 0; r < 4; r++) out[(16 * cch + 4 * (lane >> 4) + r) * 16 + (lane & 15)] = acc[r];
         }
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            float v = dtr[i];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            if (lane == 0) out[SG_JMAX * 16 + i] = v;
-        }
+        sg_skin_store_dtransl(dtr, lane, out);
         if (more) {
             __syncthreads();                                     // every wave is done with this frame's joint transforms
             *(float4 *)(sA + 4 * (int)threadIdx.x) = an;
@@ -301,33 +295,10 @@ sg_skin_bwd_frames_kernel(SgCam c0, SgBatch bt, int P, SgSkin k0, const float *_
     }
     // dL/dsh rows: every one of the M rows is written (through LDS as 16-B-per-lane coalesced stores when M == 16); ACC: only the
     // (D+1)^2 rows in use are rewritten -- the others keep what the step's first call wrote
-    if (c0.flags & SG_FLAG_SH_PLANAR) {                          // coefficient-major planes, only those in use (see sg_skin_bwd_kernel)
-        if (live) {
-#pragma unroll
-            for (int kq = 0; kq < nc; kq++)
-#pragma unroll
-                for (int ch = 0; ch < 3; ch++) dL_dsh[((size_t)kq * P + idx) * 3 + ch] = dsh[3 * kq + ch];
-        }
-    } else if (Mrows == 16 && (!accumulate || nc == 16) && 64 * WP >= 32 * SG_ROW_LDS) {
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            if ((lane >> 5) == h) {
-                float *row = sWw + (lane & 31) * SG_ROW_LDS;
-#pragma unroll
-                for (int i = 0; i < 48; i++) row[i] = i < nc * 3 ? dsh[i < nc * 3 ? i : 0] : 0.0f;
-            }
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            __builtin_amdgcn_wave_barrier();
-            sg_rows48_store(dL_dsh, g0 + 32 * h, P, lane, sWw, 32, false);
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            __builtin_amdgcn_wave_barrier();
-        }
-    } else if (live) {
-        float *dsh_row = dL_dsh + (size_t)idx * Mrows * 3;
-#pragma unroll
-        for (int i = 0; i < nc * 3; i++) dsh_row[i] = dsh[i];
-        if (!accumulate)
-            for (int i = nc * 3; i < Mrows * 3; i++) dsh_row[i] = 0.0f;
-    }
+    // (the sums are stored, never added; the LDS path writes all 16 rows: not under ACC with rows out of use, and only where the
+    // weight tile holds 32 staged rows)
+    __builtin_amdgcn_wave_barrier();
+    sg_skin_store_dsh<D, false, !accumulate>(dsh, c0.flags & SG_FLAG_SH_PLANAR,
+                                             Mrows == 16 && (!accumulate || nc == 16) && 64 * WP >= 32 * SG_ROW_LDS, Mrows, P, idx, g0, lane,
+                                             live, dL_dsh, sWw);
 }

@@ -2,7 +2,7 @@
 rotation form (sings_hybrid.py:142-150, ``create_global_orient`` / ``create_body_pose``), a row of which every training step converts to
 axis-angle and runs through the SMPL chain (:370-399) so that the photometric loss moves it through Adam (:761-765).
 
-``PoseTable(frame_idx)`` is that path as ONE launch each way (``sg_pose_transforms[_backward]``, csrc/sg_skin.hip): gather of the
+``PoseTable(frame_idx)`` is that path as ONE launch each way (``sg_pose_transforms[_backward]``, csrc/sg_pose.hip): gather of the
 row, rotation_6d_to_matrix -> matrix_to_quaternion -> quaternion_to_axis_angle per joint, Rodrigues, the kinematic chain, ``A = G -
 pad(G J)``, ``@ inverse(A_t2cano)``.  The frame index is read from DEVICE memory, so a step captured into a HIP graph at one frame
 replays at any other; the gradient comes back DENSE over the whole table (zeros for the rows the step did not visit -- what the

@@ -1,7 +1,7 @@
 """The cases of the fused skinning kernels' edge tests (no GPU): tests/test_skin_edge_cases_host.py proves from the oracles alone
 that they test what they claim, tests/test_gpu_skin_edges.py runs them on the device.
 
-What the kernels of sings_amd/csrc/sg_skin.hip branch on: the joint count J -- chunks of 16 joints (``(J + 15) >> 4``), k-steps of
+What the kernels of sings_amd/csrc/sg_skin.hip (weight staging: sg_skin.h) branch on: the joint count J -- chunks of 16 joints (``(J + 15) >> 4``), k-steps of
 4 (``(J + 3) >> 2``), a float4 staging path for J % 4 == 0 and a scalar one otherwise, the K-frame backward's dynamic LDS of
 22528 + 1024 J bytes (past 64 KiB from J = 43) -- and where the Gaussian count P falls inside a 64-lane wave and a 256-thread
 workgroup.  The C ABI takes 1 <= J <= 64 and any P >= 1; ``SINGLE`` and ``FRAMES`` walk those edges, each list stated case by

@@ -1,4 +1,4 @@
-"""sings_amd.pose.PoseTable (sg_pose_transforms[_backward], csrc/sg_skin.hip) on the GPU against tests/golden/pose_golden.npz: the
+"""sings_amd.pose.PoseTable (sg_pose_transforms[_backward], csrc/sg_pose.hip) on the GPU against tests/golden/pose_golden.npz: the
 reference's own fp32 axis-angle and A for the kit's 80 frames, a copy pushed off the rotation manifold and exact-identity rows, and
 its fp64 gradients of both tables for a seeded dA (tests/golden/gen_pose_golden.py; no row is excluded: the generator asserts that
 the quaternion candidates are never within 1e-3 of a tie).

@@ -1,4 +1,4 @@
-"""The fused skinning kernels (sg_skin.hip, sg_skin_bwd.inc, sg_skin_bwd_frames.inc) at every joint-count and tile edge: the
+"""The fused skinning kernels (sg_skin.hip, sg_skin.h, sg_skin_bwd.inc, sg_skin_bwd_frames.inc) at every joint-count and tile edge: the
 cases of tests/skin_edge_case.py (J from 1 to 64 across the chunk, k-step, float4 / scalar staging and 64 KiB LDS boundaries; P
 from 1 across the wave and workgroup boundaries), proved to test what they claim by tests/test_skin_edge_cases_host.py.
 
