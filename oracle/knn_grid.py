@@ -54,7 +54,7 @@ def grids_of(xyz, previous=False):
 
 
 def cell_ids(g, xyz):
-    """Flat cell index of every point (sg_cell_of in sg_reg.hip, restated in fp32)."""
+    """Flat cell index of every point (sg_cell_of in sg_knn.hip, restated in fp32)."""
     xyz = np.asarray(xyz, np.float32)
     c = ((xyz - g["lo"]) * g["inv_h"]).astype(np.float32)
     c = np.minimum(np.maximum(c.astype(np.int64), 0), g["dim"].astype(np.int64) - 1)

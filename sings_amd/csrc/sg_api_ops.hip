@@ -2,6 +2,7 @@
 // LBS, joint and pose transforms, rotation conversions, photometric loss, regularisers, tri-plane decode, linear layers.
 // Each checks its arguments, calls one sg_launch_* and reports the launch.
 #include "sg_host.h"
+#include "sg_reduce.h"                 // sg_launch_rows_laplacian
 
 // ---- stand-alone lbs_extra (a9)
 extern "C" int sg_lbs_forward(int P, int J, const float *lbs_weights, const float *A, const float *v, float *T_out,

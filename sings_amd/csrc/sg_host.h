@@ -75,9 +75,6 @@ int sg_launch_linear_bwd_fan(int N, int Cin, int Cout, int act, const float *z, 
                              float *dx_out, const SgLinearSide *side, hipStream_t st);
 void sg_launch_scales_head(int N, const float *z, float *scales, float *aux, const float *dscales, const float *daux, float *dz,
                            hipStream_t st);
-void sg_launch_rows_laplacian(int R, int V, int C, const float *x, const int *row_ptr, const int *col, const float *val,
-                              const float *rscale, const int *t_row_ptr, const int *t_row, const float *t_val, void *ws, float *g_ws,
-                              float *loss, const float *upstream, float *dL_dx, hipStream_t st);
 
 // ---- work order (include/sings_order.h) ----
 // Where a work order takes effect: many-tile frames binned directly (SG_FLAG_SHORT_LISTS, no whole-image histogram).  Elsewhere the

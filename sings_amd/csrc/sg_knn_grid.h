@@ -1,5 +1,5 @@
 // Sizing of the k-NN search grids: bounding box + cell budget -> cell edge and dims.  Plain C / C++, shared by the device
-// (thread 0 of sg_grid_setup2_kernel) and by the host tests (oracle/knn_grid_host.c), so that what is tested on the CPU is
+// (thread 0 of sg_grid_setup2_kernel, sg_knn.hip) and by the host tests (oracle/knn_grid_host.c), so that what is tested on the CPU is
 // the arithmetic the kernel runs.
 #ifndef SG_KNN_GRID_H
 #define SG_KNN_GRID_H

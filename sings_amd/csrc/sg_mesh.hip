@@ -8,7 +8,7 @@
 //
 //   directed instances  every flagged face contributes its three edges as (a = min, b = max); an instance lives in the ROW of a.
 //                       count[a] (integer atomics: a sum of ones has no order), exclusive scan -> row starts (the three-step scan
-//                       of sg_reg.hip's k-NN cells), then every instance takes a slot of its row with a returning atomic.  WHICH slot
+//                       of sg_scan.h, as the k-NN cells), then every instance takes a slot of its row with a returning atomic.  WHICH slot
 //                       depends on arrival order; nothing that leaves this file does:
 //   rank by counting    an instance's place among the unique edges is computed from the row's CONTENTS, not from its slots: it
 //                       is a head if no instance at a smaller slot of the row holds the same b, its multiplicity is the number of
@@ -21,13 +21,14 @@
 //
 // The host reads info[] once between sg_mesh_edges_build and sg_mesh_edges_emit: E sizes the outputs.
 #include "sg_host.h"
+#include "sg_scan.h"
 
 #define SG_MESH_THREADS 256
 #define SG_MESH_MAX_V (1 << 30)                  // the scan's block table and the 32-bit row offsets cover this many vertices
 #define SG_MESH_MAX_F 715827882                  // 3 F < 2^31: an instance index is an int
 
-// ---- exclusive scan of n uint32 (or of n flags) in three steps: 1024 entries per block, block sums, the sums scanned by one workgroup.
-// prefix(i) = out[i] + bsum[i >> 10].  Two independent jobs per launch (blockIdx.y).
+// ---- exclusive scan of n uint32 (or of n flags), the three steps of sg_scan.h: prefix(i) = out[i] + bsum[i >> 10].  Two independent
+// jobs per launch (blockIdx.y).
 struct SgScanJob {
     const uint32_t *in;         // values, or NULL:
     const uint8_t *in8;         // flags (!= 0 counts 1), or NULL as well: every entry counts 1
@@ -44,53 +45,15 @@ __device__ __forceinline__ uint32_t sg_scan_value(const SgScanJob &J, int i)
 __global__ void __launch_bounds__(256)
 sg_mesh_scan1_kernel(SgScanJobs JJ)
 {
-    __shared__ uint32_t sW[4];
     const SgScanJob &J = JJ.j[blockIdx.y];
-    const int n = J.n;
-    if ((long long)blockIdx.x * 1024 >= n) return;                  // (uniform per workgroup)
-    const int base = blockIdx.x * 1024 + threadIdx.x * 4;
-    uint32_t v[4], s = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { v[k] = base + k < n ? sg_scan_value(J, base + k) : 0u; s += v[k]; }
-    uint32_t incl = s;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
-    if (lane == 63) sW[wave] = incl;
-    __syncthreads();
-    uint32_t off = 0;
-    for (int w = 0; w < wave; w++) off += sW[w];
-    uint32_t ex = off + incl - s;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { if (base + k < n) J.out[base + k] = ex; ex += v[k]; }
-    if (threadIdx.x == 255) J.bsum[blockIdx.x] = ex;
+    sg_scan_block(J.n, [&](int i) { return sg_scan_value(J, i); }, J.out, J.bsum);
 }
 __global__ void __launch_bounds__(1024)
 sg_mesh_scan2_kernel(SgScanJobs JJ)
 {
-    __shared__ uint32_t sW[16];
-    __shared__ uint32_t carry;
     const SgScanJob &J = JJ.j[blockIdx.y];
-    const int nb = (int)(((long long)J.n + 1023) / 1024);
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += 1024) {
-        const int i = b0 + threadIdx.x;
-        const uint32_t v = i < nb ? J.bsum[i] : 0u;
-        uint32_t incl = v;
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(incl, o, 64); if (lane >= o) incl += u; }
-        if (lane == 63) sW[wave] = incl;
-        __syncthreads();
-        uint32_t off = carry;
-        for (int w = 0; w < wave; w++) off += sW[w];
-        if (i < nb) J.bsum[i] = off + incl - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry = off + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *J.total = (int32_t)carry;
+    const uint32_t total = sg_scan_block_sums(J.n, J.bsum);
+    if (threadIdx.x == 0) *J.total = (int32_t)total;
 }
 static void sg_mesh_scan(const SgScanJob &a, const SgScanJob *b, hipStream_t st)
 {

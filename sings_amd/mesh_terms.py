@@ -10,7 +10,7 @@ with ``xyz_anchor_canon = xyz_canon + mean(scales, -1) * n / 2`` (sings_hybrid.p
 current mesh).  New rows inherit the last level id (sings_hybrid.py:1116-1119), so the reference's ``[:num_level_0]`` slices are the whole
 arrays.  Only the ``standard`` Laplacian, which is what the trainer constructs (gs_trainer.py:176-192).
 
-The three Laplacians are ONE forward and ONE backward launch over one CSR (csrc/sg_reg.hip, include/sings_mesh_terms.h): the anchor of a
+The three Laplacians are ONE forward and ONE backward launch over one CSR (csrc/sg_mesh_terms.hip, include/sings_mesh_terms.h): the anchor of a
 neighbour is formed where it is read, the step weights are read from device memory, and the CSR of the same-label edges -- with the
 degrees, the label counts and the per-vertex scales -- is built on the device from ``MeshState.edges`` without a host copy of the mesh.
 

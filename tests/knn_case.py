@@ -1,7 +1,7 @@
 """Point clouds on which a uniform-grid k-NN search can go wrong -- flat, thin, colinear, coincident, barely larger than K,
 on cell faces, at the coarse / fine threshold -- and the fp64 brute force they are compared with.  No GPU in here: the host
 test checks the builders, the GPU test (test_gpu_knn_degenerate.py) runs the kernels on them.  Every cloud is fp32, seeded,
-at most 5 000 points."""
+at most 5 000 points, but for carry_cloud's 48 000 (the smallest with more than 2^20 fine cells)."""
 import functools
 
 import numpy as np
@@ -10,7 +10,7 @@ import torch
 from oracle import knn_grid
 
 KMAX = 17
-SG_KNN_DENSE = 16                      # sg_reg.hip: a point whose coarse cell holds MORE points searches the fine grid
+SG_KNN_DENSE = 16                      # sg_knn.hip: a point whose coarse cell holds MORE points searches the fine grid
 
 
 def sheet(N, flat, const, seed=0):
@@ -87,6 +87,28 @@ def coarse_cell_counts(xyz):
     gc, _ = knn_grid.grids_of(xyz)
     ids = knn_grid.cell_ids(gc, xyz)
     return np.bincount(ids, minlength=int(gc["ncells"]))[ids]
+
+
+def carry_cloud():
+    """48 000 points whose fine grid has 105^3 = 1 157 625 cells -- 1 131 blocks of 1 024, so the scan of the block sums
+    (sg_scan.h) takes a second chunk with a carry -- and whose dense points live in that second chunk: uniform points of the
+    unit cube, rows 0-599 replaced by three tight clusters near the top (z = 0.95 .. 0.985).  550 points share a coarse cell
+    with more than SG_KNN_DENSE others and search the fine grid, 549 of them cluster points, in fine cells 1 089 217 ..
+    1 137 853 (the caller asserts what it relies on).  A wrong carry moves those cells' start offsets."""
+    N = 48000
+    rs = np.random.RandomState(11)
+    xyz = rs.uniform(0.0, 1.0, (N, 3))
+    for k, c in enumerate(((0.3, 0.4, 0.97), (0.7, 0.2, 0.985), (0.5, 0.8, 0.95))):
+        xyz[200 * k:200 * (k + 1)] = np.array(c) + 0.003 * rs.standard_normal((200, 3))
+    return xyz.astype(np.float32)
+
+
+def brute_force_chunked(xyz, K, rows=2000):
+    """brute_force for a cloud too large for one distance matrix: the same fp64 cdist + topk, `rows` rows at a time."""
+    x = torch.as_tensor(xyz, dtype=torch.float32).double()
+    out = [torch.topk(torch.cdist(x[i:i + rows], x, compute_mode="donot_use_mm_for_euclid_dist"), K, dim=1, largest=False)
+           .values[:, 1:].mean(1) for i in range(0, len(x), rows)]
+    return torch.cat(out).numpy()
 
 
 SHEET_N = (9, 64, 362, 1000, 4000)

@@ -1,4 +1,4 @@
-"""The k-NN search (knn_mean_edge, GaussiansEdgeLoss; kernels in sings_amd/csrc/sg_reg.hip) on clouds that are flat, thin,
+"""The k-NN search (knn_mean_edge, GaussiansEdgeLoss; kernels in sings_amd/csrc/sg_knn.hip) on clouds that are flat, thin,
 colinear, coincident, barely larger than K, on cell faces or at the coarse / fine threshold (tests/knn_case.py), against fp64
 brute force.  Bound: the one of test_gpu_reg.py::test_knn_exact_vs_brute_force, rtol 3e-6 + atol 1e-9 -- the SET of the K
 nearest distances is exact, fp32 squares, sums and square roots differ from fp64 by a few ulp -- and exactly 0.0 where all
@@ -98,6 +98,27 @@ def test_cells_on_both_sides_of_the_fine_grid_threshold(K):
     assert (cnt[s16] == knn_case.SG_KNN_DENSE).all() and (cnt[s17] == knn_case.SG_KNN_DENSE + 1).all()
     assert np.array_equal(xyz, knn_case.cloud("threshold"))
     _check("threshold", K)
+
+
+def test_exact_where_the_cell_scan_carries_over_chunks():
+    """More than 2^20 fine cells: the scan of the cells' block sums (sg_scan.h) runs its carry loop, and the points that search
+    the fine grid sit in cells past the first chunk of 1 024 block sums (asserted on the host, with the product's sizing).
+    K = 9 at every one of the 48 000 points against fp64 brute force in chunks of 2 000 rows."""
+    from oracle import knn_grid
+    from sings_amd.regularizers import knn_mean_edge
+    xyz = knn_case.carry_cloud()
+    gc, gf = knn_grid.grids_of(xyz)
+    assert int(gf["ncells"]) > 2 ** 20
+    fine = (knn_case.coarse_cell_counts(xyz) > knn_case.SG_KNN_DENSE) & (knn_grid.cell_ids(gf, xyz) >= 2 ** 20)
+    assert int(fine.sum()) >= 500, int(fine.sum())
+    dev = _dev()
+    got = knn_mean_edge(torch.from_numpy(xyz).to(dev), K=9).cpu().numpy()
+    ref = knn_case.brute_force_chunked(xyz, 9)                   # on the CPU, as every reference of this file
+    rel = np.abs(got - ref) / ref
+    print(f"knn carry cloud K=9: {int(gf['ncells'])} fine cells, {int(fine.sum())} points in fine cells >= 2^20, worst relative "
+          f"difference {rel.max():.3e} (fine-grid points {rel[fine].max():.3e})")
+    assert got.shape == (48000,) and np.isfinite(got).all()
+    np.testing.assert_allclose(got, ref, rtol=RTOL, atol=ATOL)
 
 
 PROPERTY_CLOUDS = ("sheet-N1000-flatx-at0.37", "coincident-N300", "lattice-origin")

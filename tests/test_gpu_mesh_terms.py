@@ -1,4 +1,4 @@
-"""The fused mesh terms (sings_amd/mesh_terms.py, csrc/sg_reg.hip, include/sings_mesh_terms.h) on the GPU: the device build against the
+"""The fused mesh terms (sings_amd/mesh_terms.py, csrc/sg_mesh_terms.hip, include/sings_mesh_terms.h) on the GPU: the device build against the
 host build as integers, each term against the reference's golden values (tests/golden/reg_golden.npz), the composition against an fp64
 torch statement written here, exact zeros at zero weights, the device weights under graph replay, the stale-holder refusal.
 
