@@ -115,3 +115,37 @@ def load_kit(root, split="train", device=None, verify_crc=True):
     for key in ("global_orient", "body_pose", "transl"):
         on_dev[key] = torch.from_numpy(np.ascontiguousarray(smpl[key][idx])).to(dev)
     return Kit(store, on_dev, cam, indices, images, masks)
+
+
+# ---- the keypoints the reference's pose refinement reads (``prepare_kits.sh ... --opt``: preprocess/utils/ooptimize_smpl.py)
+KEYPOINT_DIR = os.path.join("keypoints_coco133", "sapiens_0.6b")
+
+
+def load_keypoints(root, indices=None):
+    """The Sapiens COCO-133 files of a kit, ``keypoints_coco133/sapiens_0.6b/*.json`` in sorted order -> (keypoints [n,133,2],
+    scores [n,133]) fp32 numpy arrays: ``instance_info[0].keypoints`` and ``.keypoint_scores`` of every file (of ``indices`` when given).
+    ``ValueError`` naming the file for a missing key or a wrong shape, and naming the directory when the number of files differs from
+    the number of images."""
+    import json
+    root = str(root)
+    files = sorted(glob.glob(os.path.join(root, KEYPOINT_DIR, "*.json")))
+    images = sorted(glob.glob(os.path.join(root, "images", "*.png")))
+    if len(files) != len(images) or not files:
+        raise ValueError(f"{os.path.join(root, KEYPOINT_DIR)}: {len(files)} keypoint files for {len(images)} images: the counts must be "
+                         "equal and not zero")
+    if indices is not None:
+        files = [files[int(i)] for i in indices]
+    kps, scs = [], []
+    for path in files:
+        try:
+            with open(path) as f:
+                inst = json.load(f)["instance_info"][0]
+            kp, sc = np.asarray(inst["keypoints"], np.float32), np.asarray(inst["keypoint_scores"], np.float32)
+        except (KeyError, IndexError, TypeError, ValueError) as e:
+            raise ValueError(f"{path}: no instance_info[0].keypoints / .keypoint_scores ({type(e).__name__}: {e})") from e
+        if kp.ndim != 2 or kp.shape[0] != 133 or kp.shape[1] < 2 or sc.shape != (133,):
+            raise ValueError(f"{path}: keypoints {kp.shape} / keypoint_scores {sc.shape} are not [133, >= 2] / [133]")
+        kps.append(kp[:, :2])
+        scs.append(sc)
+    return np.stack(kps), np.stack(scs)
+
