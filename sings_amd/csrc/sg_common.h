@@ -7,6 +7,7 @@
 #include "../../include/sings_hip.h"
 
 #define SG_WAVE 64
+typedef float sg_v16f __attribute__((ext_vector_type(16)));   // accumulator of one 32 x 32 fp32 MFMA tile
 // the thread-local error of sg_last_error() (sg_api.hip), for entry points defined in other translation units; returns 1
 int sg_set_error(const char *what, hipError_t e = hipSuccess);
 // (The compile-time experiment switches of rounds 1-2 -- SG_EXP bits that compiled phases of a kernel out for timing -- are no

@@ -26,26 +26,21 @@
 // per CU) and 128 accumulator registers.  LDS: 128 x 132 x 4 B = 66 KiB, two workgroups per CU within the 160 KiB; <= 256 registers.
 // The arithmetic is the floor: 45 k multiply-adds per point on the fp32 matrix cores (64 FLOP / clk / SIMD), ~90 us at 150 k points.
 #include "sg_host.h"
+#include "sg_act.h"
 #include "../../include/sings_frozen.h"
 
 #include <atomic>
 
-typedef float fz_v16f __attribute__((ext_vector_type(16)));
-
 #define FZ_R SG_FROZEN_BLOCK
 #define FZ_MAXC 128
 
-// The GELU of sg_linear_forward's epilogue, value branch of sgl_gelu_both (sg_linear.hip), operation for operation: the two paths
-// round a hidden activation to the same bits from the same sum.  erf by Abramowitz-Stegun 7.1.26.
+// The GELU of sg_linear_forward's epilogue: the same sg_gelu_both, its derivative dropped, so the two paths round a hidden
+// activation to the same bits from the same sum.
 __device__ __forceinline__ float fz_gelu(float z)
 {
-    const float x = fabsf(z) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, x, 1.0f));
-    const float e = __expf(-x * x);
-    const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-    const float erfa = fmaf(-poly, e, 1.0f);
-    const float cdf = 0.5f * (1.0f + copysignf(erfa, z));
-    return z * cdf;
+    float h, dh;
+    sg_gelu_both(z, h, dh);
+    return h;
 }
 
 // up to two weight matrices [rows, CK] stacked into one product: output column c < rows0 is row c of W0, then rows of W1
@@ -54,7 +49,7 @@ struct FzStack { const float *W0, *W1; int rows0, rows1; };
 // acc[i] = W(32 cb + .., :) . X(tile tg TO + i)^T for this wave's column block cb = wave % TO and its TO point tiles.
 // sX [FZ_R][XS]; columns CK .. CKP - 1 of it are zero (CKP = CK rounded up to 8).  Reads only.
 template <int TO>
-__device__ __forceinline__ void fz_product(const float *sX, int XS, int CK, const FzStack &L, int wave, int lane, fz_v16f (&acc)[TO])
+__device__ __forceinline__ void fz_product(const float *sX, int XS, int CK, const FzStack &L, int wave, int lane, sg_v16f (&acc)[TO])
 {
     const int CKP = (CK + 7) & ~7, HALF = CKP >> 1, NQ = CKP >> 3;
     const int cb = wave % TO, tg = wave / TO, j = lane & 31, h = lane >> 5;
@@ -95,7 +90,7 @@ template <int TO>
 __device__ __forceinline__ void fz_hidden(float *sX, int XS, int CK, const float *__restrict__ W, const float *__restrict__ bias,
                                           int wave, int lane)
 {
-    fz_v16f acc[TO];
+    sg_v16f acc[TO];
     const FzStack L = { W, nullptr, 32 * TO, 0 };
     fz_product<TO>(sX, XS, CK, L, wave, lane, acc);
     const int cb = wave % TO, tg = wave / TO, j = lane & 31, h = lane >> 5;
@@ -147,7 +142,7 @@ sg_frozen_geometry_kernel(FzGeoArgs a)
     const int n = n0 + 32 * wave + j;                                      // a narrow head: point tile `wave`, this lane's point
     {   // xyz_offsets (3) and rotations (6) on the trunk, before scales.0 overwrites it
         const int nrot = a.aniso ? 6 : 0;
-        fz_v16f acc[1];
+        sg_v16f acc[1];
         const FzStack L = { a.Wxyz, a.Wrot, 3, nrot };
         fz_product<1>(sX, XS, H, L, wave, lane, acc);
         if (n < a.N) {
@@ -164,14 +159,14 @@ sg_frozen_geometry_kernel(FzGeoArgs a)
     fz_hidden<TH>(sX, XS, H, a.Ws0, a.bs0, wave, lane);                    // (its first barrier: every wave is done with the trunk)
     {   // scales.2: z -> scales_aux, log(exp(z) + 1) -> scales (the isotropic column three times: sg_scales_head_forward)
         const int ns = a.aniso ? 3 : 1;
-        fz_v16f acc[1];
+        sg_v16f acc[1];
         const FzStack L = { a.Ws2, nullptr, ns, 0 };
         fz_product<1>(sX, XS, H, L, wave, lane, acc);
         if (n < a.N && h == 0) {                                           // columns 0..3: register 0..3 of the lower half
             const float z0 = acc[0][0] + a.bs2[0];
             const float z1 = a.aniso ? acc[0][1] + a.bs2[1] : z0, z2 = a.aniso ? acc[0][2] + a.bs2[2] : z0;
-            const float s0 = logf(expf(z0) + 1.0f);
-            const float s1 = a.aniso ? logf(expf(z1) + 1.0f) : s0, s2 = a.aniso ? logf(expf(z2) + 1.0f) : s0;
+            const float s0 = sg_softplus(z0);
+            const float s1 = a.aniso ? sg_softplus(z1) : s0, s2 = a.aniso ? sg_softplus(z2) : s0;
             float *ps = a.scales + (size_t)n * 3, *pa = a.aux + (size_t)n * 3;
             ps[0] = s0; ps[1] = s1; ps[2] = s2;
             pa[0] = z0; pa[1] = z1; pa[2] = z2;
@@ -197,7 +192,7 @@ sg_frozen_appearance_kernel(FzAppArgs a)
     fz_hidden<TH>(sX, XS, a.Cin, a.W0, a.b0, wave, lane);
     fz_hidden<TH>(sX, XS, H, a.W2, a.b2, wave, lane);
     // shs (48) and opacity (1) stacked: two column blocks, two point tiles per wave
-    fz_v16f acc[2];
+    sg_v16f acc[2];
     const FzStack L = { a.Wshs, a.Wop, SG_FROZEN_SHS, a.Wop ? 1 : 0 };
     fz_product<2>(sX, XS, H, L, wave, lane, acc);
     const int cb = wave % 2, tg = wave / 2;
@@ -214,7 +209,7 @@ sg_frozen_appearance_kernel(FzAppArgs a)
                     make_float4(acc[i][4 * g] + bb.x, acc[i][4 * g + 1] + bb.y, acc[i][4 * g + 2] + bb.z, acc[i][4 * g + 3] + bb.w);
             } else if (c == SG_FROZEN_SHS && a.Wop) {                      // sigmoid(z + offset): sg_linear_forward's act 2
                 const float ro = a.off ? a.off[n] : 0.0f;
-                a.opacity[n] = 1.0f / (1.0f + expf(-((acc[i][4 * g] + a.bop[0]) + ro)));
+                a.opacity[n] = sg_sigmoid((acc[i][4 * g] + a.bop[0]) + ro);
             }
         }
     }

@@ -16,47 +16,8 @@
 // and CK/2 + s), so the four values a lane needs next are adjacent.  The 32 x 32 result tiles leave straight from the
 // accumulator registers: a lane holds four consecutive output columns of one point four times -> 16-B stores.  Loads of the
 // next tile are in flight during the MFMAs; the waves of a workgroup meet only at the X' tile.
-#include "sg_common.h"
+#include "sg_act.h"
 #include <type_traits>
-
-typedef float sg_v16f __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float sgl_gelu(float z) { return 0.5f * z * (1.0f + erff(z * 0.70710678118654752440f)); }
-__device__ __forceinline__ float sgl_gelu_grad(float z)
-{
-    const float cdf = 0.5f * (1.0f + erff(z * 0.70710678118654752440f));
-    return cdf + z * 0.39894228040143267794f * __expf(-0.5f * z * z);
-}
-// GELU and its derivative from ONE evaluation of erf: h = z Phi(z), h' = Phi(z) + z phi(z), Phi = (1 + erf(z / sqrt 2)) / 2.
-// erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, i.e. fp32 round-off of Phi): 1 - (a1 t + ... + a5 t^5) e^(-x^2),
-// t = 1 / (1 + p |x|); the e^(-x^2) = e^(-z^2 / 2) it needs is the one phi(z) needs.
-__device__ __forceinline__ void sgl_gelu_both(float z, float &h, float &dh)
-{
-    const float x = fabsf(z) * 0.70710678118654752440f;
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, x, 1.0f));
-    const float e = __expf(-x * x);
-    const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
-    const float erfa = fmaf(-poly, e, 1.0f);                               // erf(|x|)
-    const float cdf = 0.5f * (1.0f + copysignf(erfa, z));
-    h = z * cdf;
-    dh = fmaf(z * 0.39894228040143267794f, e, cdf);
-}
-// act: 0 identity, 1 GELU (erf), 2 sigmoid(z + row_offset), 3 log(exp(z) + 1)   (same codes as sg_bias_act_*)
-__device__ __forceinline__ float sgl_act(int act, float z, float ro)
-{
-    if (act == 1) return sgl_gelu(z);
-    if (act == 2) return 1.0f / (1.0f + expf(-(z + ro)));
-    if (act == 3) return logf(expf(z) + 1.0f);
-    return z;
-}
-// derivative from the forward's aux value: act 1: aux = gelu'(z); act 2: aux = h = sigmoid(.); act 3: aux = z
-__device__ __forceinline__ float sgl_act_grad_aux(int act, float aux)
-{
-    if (act == 1) return aux;
-    if (act == 2) return aux * (1.0f - aux);
-    if (act == 3) { const float e = expf(aux); return e / (e + 1.0f); }
-    return 1.0f;
-}
 
 #define SGL_MAXC 128
 #define SGL_TILE 4352                // floats per LDS tile: 32 x (128 + 4), 64 x (64 + 4), 128 x (32 + 1) all fit (3 x 17 KiB per workgroup)
@@ -156,8 +117,8 @@ sg_linear_kernel(int N, int CK, int CO, int act, const float *__restrict__ X, co
                 float4 v = xr[q];
                 if (BWD && act != 0) {
                     const float4 zz = zr[q];
-                    v.x *= sgl_act_grad_aux(act, zz.x); v.y *= sgl_act_grad_aux(act, zz.y);
-                    v.z *= sgl_act_grad_aux(act, zz.z); v.w *= sgl_act_grad_aux(act, zz.w);
+                    v.x *= sg_act_grad_aux(act, zz.x); v.y *= sg_act_grad_aux(act, zz.y);
+                    v.z *= sg_act_grad_aux(act, zz.z); v.w *= sg_act_grad_aux(act, zz.w);
                     if (out1 && n < N && c < CK) {                                                   // dz
                         if (vec) *(float4 *)(out1 + (size_t)n * CK + c) = v;
                         else {
@@ -217,8 +178,8 @@ sg_linear_kernel(int N, int CK, int CO, int act, const float *__restrict__ X, co
 #pragma unroll
                         for (int u = 0; u < 4; u++) {
                             y[u] += bv[4 * g + u];
-                            if (act == 1) sgl_gelu_both(y[u], hh[u], y[u]);           // h and aux = gelu'(z) share one erf
-                            else hh[u] = sgl_act(act, y[u], ro);
+                            if (act == 1) sg_gelu_both(y[u], hh[u], y[u]);           // h and aux = gelu'(z) share one erf
+                            else hh[u] = sg_act(act, y[u], ro);
                         }
                         if ((CO & 3) == 0) {
                             if (out1) *(float4 *)(out1 + (size_t)n * CO + c) = make_float4(y[0], y[1], y[2], y[3]);    // aux
@@ -421,8 +382,8 @@ sg_linear_wide_kernel(int N, int CK, int CO, int act, const float *__restrict__ 
             float4 v = xr[q];
             if (BWD && act != 0) {
                 const float4 zz = zr[q];
-                v.x *= sgl_act_grad_aux(act, zz.x); v.y *= sgl_act_grad_aux(act, zz.y);
-                v.z *= sgl_act_grad_aux(act, zz.z); v.w *= sgl_act_grad_aux(act, zz.w);
+                v.x *= sg_act_grad_aux(act, zz.x); v.y *= sg_act_grad_aux(act, zz.y);
+                v.z *= sg_act_grad_aux(act, zz.z); v.w *= sg_act_grad_aux(act, zz.w);
                 const int off = xoff[q] == 0x7ffffff0 ? 0x7ffffff0 : xoff[q] + t0;
                 if (vec) {
                     typedef unsigned sgl_u4 __attribute__((ext_vector_type(4)));
@@ -444,8 +405,8 @@ sg_linear_wide_kernel(int N, int CK, int CO, int act, const float *__restrict__ 
         const int vo = voff0 + (n0p + 8 * (r >> 2) + (r & 3)) * CO4;
         if (!BWD) {
             float y = ac[r] + bv, hh;
-            if (GELU) sgl_gelu_both(y, hh, y);                              // h and aux = gelu'(z) from one erf
-            else hh = sgl_act(act, y, 0.0f);
+            if (GELU) sg_gelu_both(y, hh, y);                              // h and aux = gelu'(z) from one erf
+            else hh = sg_act(act, y, 0.0f);
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(hh), rs0, vo, 0, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y), rs1, vo, 0, 0);
         } else __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(ac[r]), rs0, vo, 0, 0);
@@ -577,7 +538,7 @@ sg_linear_skinny_kernel(int N, int act, const float *__restrict__ X, const float
             if (sub == 0 && n < N) {
                 const float ro = (act == 2 && row_offset) ? row_offset[n] : 0.0f;
 #pragma unroll
-                for (int c = 0; c < CO; c++) out[(size_t)n * CO + c] = sgl_act(act, d[c] + bv[c], ro);
+                for (int c = 0; c < CO; c++) out[(size_t)n * CO + c] = sg_act(act, d[c] + bv[c], ro);
             }
         }
     }

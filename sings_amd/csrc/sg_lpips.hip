@@ -18,8 +18,6 @@
 // else is in the batch.
 #include "sg_host.h"
 
-typedef float sg_v16f __attribute__((ext_vector_type(16)));
-
 namespace {
 
 constexpr int LP_NCONV = 13;

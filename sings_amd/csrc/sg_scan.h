@@ -1,6 +1,6 @@
 // Exclusive scan of n uint32 entries in three steps: 1024 entries per block, block sums, the sums scanned by one workgroup.
 // prefix(i) = out[i] + bsum[i >> 10].  Device bodies only: the kernels are in the files that launch them (the k-NN cells of
-// sg_knn.hip, the row / flag / unique-count scans of sg_mesh.hip).
+// sg_knn.hip, the row / flag / unique-count scans of sg_mesh.hip, the key counters of the tri-plane sort in sg_decode.hip).
 #pragma once
 #include "sg_common.h"
 

@@ -155,7 +155,7 @@ def test_triplane_backward_clustered_and_border_points():
 
 
 def test_weight_grad_shapes():
-    """sg_weight_grad over the shapes the decoders use and the edges of its two code paths (streaming
+    """sg_weight_grad (csrc/sg_wgrad.hip) over the shapes the decoders use and the edges of its two code paths (streaming
     dot products up to 12 outputs; more: MFMA tiles): dW = dz^T x, db = column sums, against float64."""
     import ctypes as C
     from sings_amd import _lib

@@ -14,8 +14,8 @@ against the fp64 reference of the same file.  Per case:
 Each test prints the worst entry of its class as a fraction of the bound.  The element-wise kernels beside them (sg_bias_act_*,
 sg_scales_head_*: sg_decode.hip) get the same checks at the end of the file.
 
-Note on the two GELU evaluations: sg_linear.hip's narrow AND wide forward epilogues both call sgl_gelu_both (Abramowitz-Stegun erf,
-h and gelu'(z) from one evaluation); erff is what sg_bias_act_* uses.  test_the_two_gelu_paths_meet holds the two kernels to each
+Note on the two GELU evaluations: sg_linear.hip's narrow AND wide forward epilogues both call sg_gelu_both (sg_act.h: Abramowitz-Stegun
+erf, h and gelu'(z) from one evaluation); erff is what sg_bias_act_* uses.  test_the_two_gelu_paths_meet holds the two kernels to each
 other anyway, and test_bias_act_* holds the erff ones to fp64.
 """
 import ctypes as C
