@@ -26,6 +26,7 @@ HAS_JPEG = False                     # set by load(): the library exports the ta
 HAS_PNG = False                      # set by load(): the library exports the table of include/sings_png.h
 HAS_UNPNG = False                    # set by load(): the library exports the table of include/sings_unpng.h
 HAS_BODY = False                     # set by load(): the library exports the table of include/sings_body.h
+HAS_SILHOUETTE = False               # set by load(): the library exports the table of include/sings_silhouette.h
 
 
 class SgRasterSettings(C.Structure):
@@ -258,6 +259,13 @@ _PROTOTYPES_BODY = {
     "sg_body_smooth_ws_bytes": "z: i2",
     "sg_body_smooth": "i: i3 f p8",
 }
+# The soft silhouette and the pose update, include/sings_silhouette.h: a fifteenth header and a fifteenth table, for the same reason.
+_PROTOTYPES_SILHOUETTE = {
+    "sg_sil_layout": "i: i5 z Z",
+    "sg_sil_forward": "i: i5 f5 z p6",
+    "sg_sil_backward": "i: i5 f5 z p8",
+    "sg_sil_pose_update": "i: i f p10 i p",
+}
 _P = C.POINTER
 _CTYPE = {"i": C.c_int, "z": C.c_size_t, "f": C.c_float, "s": C.c_char_p,
           "p": C.c_void_p,                        # a raw device pointer (or NULL), and the stream
@@ -327,6 +335,14 @@ BODY_MAX_ROWS = 1024                 # SG_BODY_MAX_ROWS
 BODY_MAX_ITERATIONS = 64             # SG_BODY_MAX_ITERATIONS
 BODY_INFO_INTS = 4                   # SG_BODY_INFO_INTS
 BODY_ISOLATED, BODY_NOT_FINITE, BODY_BAD_SLOPE, BODY_BAD_FACE = 1, 2, 4, 8       # SG_BODY_ISOLATED, _NOT_FINITE, _BAD_SLOPE, _BAD_FACE
+SIL_TILE = 16                        # SG_SIL_TILE
+SIL_CHUNK = 256                      # SG_SIL_CHUNK
+SIL_SORT_LDS = 1024                  # SG_SIL_SORT_LDS
+SIL_MAX_FRAMES = 64                  # SG_SIL_MAX_FRAMES
+SIL_GUARD_WORDS = 64                 # SG_SIL_GUARD_WORDS
+SIL_INFO_WORDS = 4                   # SG_SIL_INFO_WORDS
+SIL_POSE = 72                        # SG_SIL_POSE
+SIL_LAYOUT = ("info", "rec", "rect", "tile_count", "tile_start", "cursor", "Q", "face_grad", "list", "partial", "bytes")    # SG_SIL_L_*, SG_SIL_LAYOUT_WORDS
 FROZEN_BLOCK = 128                   # SG_FROZEN_BLOCK: points per workgroup of the fused no-gradient decode
 FROZEN_SHS = 48                      # SG_FROZEN_SHS
 MESH_TERMS_INFO_INTS = 2             # SG_MESH_TERMS_INFO_INTS
@@ -372,7 +388,7 @@ def load():
                            "(include/sings_hip.h SG_ABI_VERSION): rebuild with `make -C sings_amd/csrc`")
     # (SINGS_HIP_LIB may name a library that predates include/sings_order.h -- an A/B run against a parent build: it exports none of
     # that table, HAS_ORDER says so, and the engines then make the unordered calls that library knows)
-    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN, HAS_FEED, HAS_DENSITY, HAS_SHEET, HAS_SCENE, HAS_JPEG, HAS_PNG, HAS_UNPNG, HAS_BODY
+    global HAS_ORDER, HAS_SAMPLER, HAS_FROZEN, HAS_FEED, HAS_DENSITY, HAS_SHEET, HAS_SCENE, HAS_JPEG, HAS_PNG, HAS_UNPNG, HAS_BODY, HAS_SILHOUETTE
     HAS_ORDER = all(hasattr(lib, name) for name in _PROTOTYPES_ORDER)
     HAS_SAMPLER = all(hasattr(lib, name) for name in _PROTOTYPES_SAMPLER)    # (the same, for include/sings_sampler.h)
     HAS_FROZEN = all(hasattr(lib, name) for name in _PROTOTYPES_FROZEN)      # (the same, for include/sings_frozen.h)
@@ -384,10 +400,12 @@ def load():
     HAS_PNG = all(hasattr(lib, name) for name in _PROTOTYPES_PNG)            # (the same, for include/sings_png.h)
     HAS_UNPNG = all(hasattr(lib, name) for name in _PROTOTYPES_UNPNG)        # (the same, for include/sings_unpng.h)
     HAS_BODY = all(hasattr(lib, name) for name in _PROTOTYPES_BODY)          # (the same, for include/sings_body.h)
+    HAS_SILHOUETTE = all(hasattr(lib, name) for name in _PROTOTYPES_SILHOUETTE)      # (the same, for include/sings_silhouette.h)
     for has, header in ((HAS_ORDER, "sings_order.h"), (HAS_SAMPLER, "sings_sampler.h"), (HAS_FROZEN, "sings_frozen.h"),
                         (HAS_FEED, "sings_feed.h"), (HAS_DENSITY, "sings_density.h"), (HAS_SHEET, "sings_sheet.h"),
                         (HAS_SCENE, "sings_scene.h"), (HAS_JPEG, "sings_jpeg.h"), (HAS_PNG, "sings_png.h"),
-                        (HAS_UNPNG, "sings_unpng.h"), (HAS_BODY, "sings_body.h")):
+                        (HAS_UNPNG, "sings_unpng.h"), (HAS_BODY, "sings_body.h"),
+                        (HAS_SILHOUETTE, "sings_silhouette.h")):
         if not has and LIB_PATH == os.path.join(_HERE, "libsings_hip.so"):
             raise RuntimeError(f"sings_amd: {LIB_PATH} lacks the entry points of include/{header}: rebuild with `make -C sings_amd/csrc`")
     for name, signature in (*_PROTOTYPES.items(), *_PROTOTYPES_EVAL.items(), *_PROTOTYPES_MESH_TERMS.items(),
@@ -399,7 +417,8 @@ def load():
                             *(_PROTOTYPES_JPEG.items() if HAS_JPEG else ()),
                             *(_PROTOTYPES_PNG.items() if HAS_PNG else ()),
                             *(_PROTOTYPES_UNPNG.items() if HAS_UNPNG else ()),
-                            *(_PROTOTYPES_BODY.items() if HAS_BODY else ())):
+                            *(_PROTOTYPES_BODY.items() if HAS_BODY else ()),
+                            *(_PROTOTYPES_SILHOUETTE.items() if HAS_SILHOUETTE else ())):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = _ctypes_of(signature)
     _lib = lib

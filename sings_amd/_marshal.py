@@ -573,3 +573,90 @@ def unpng_decode(n, streams, table, ws, dst, status, stream):
     F, H, W = (int(v) for v in dst.shape[:3])
     _lib.check(_codec_lib("unpng").sg_unpng_decode(int(n), _ptr(streams), _ptr(table), _ptr(ws), int(ws.numel()), _ptr(dst), F, H, W,
                                                    _ptr(status), C.c_void_p(stream.cuda_stream)), "sg_unpng_decode")
+
+
+# ---- the soft silhouette and the pose update (csrc/sg_silhouette.hip)
+def _sil_lib():
+    lib = _lib.load()
+    if not _lib.HAS_SILHOUETTE:
+        raise RuntimeError("the loaded library predates include/sings_silhouette.h (no fallback): rebuild it")
+    return lib
+
+
+def sil_layout(K, V, F, H, W, capacity):
+    """``sg_sil_layout`` (host only): dict piece -> byte offset, ``bytes`` the total.  ValueError where the library refuses."""
+    out = (C.c_size_t * len(_lib.SIL_LAYOUT))()
+    if _sil_lib().sg_sil_layout(int(K), int(V), int(F), int(H), int(W), int(capacity), out) != 0:
+        raise ValueError(_lib.load().sg_last_error().decode())
+    return dict(zip(_lib.SIL_LAYOUT, (int(x) for x in out)))
+
+
+def _sil_dims(verts, faces, what):
+    dev = verts.device if torch.is_tensor(verts) else None
+    verts = _mesh_arg(verts, what + ": verts_cam", torch.float32, dev)
+    faces = _mesh_arg(faces, what + ": faces", torch.int32, dev, (3,))
+    if verts.dim() != 3 or verts.shape[2] != 3:
+        raise ValueError(f"{what}: verts_cam must be [K,V,3], got {tuple(verts.shape)}")
+    return dev, int(verts.shape[0]), int(verts.shape[1]), int(faces.shape[0])
+
+
+def sil_forward(verts, faces, intrinsics, H, W, sigma, capacity, ws, alpha, counts=None):
+    """``sg_sil_forward`` on torch's current stream: ``verts`` [K,V,3] fp32, ``faces`` [F,3] int32, ``ws`` the bytes of ``sil_layout``
+    (uint8), ``alpha`` [K,H,W] fp32 and ``counts`` [K] int32 | None are written."""
+    dev, K, V, F = _sil_dims(verts, faces, "sil_forward")
+    _mesh_arg(ws, "sil_forward: ws", torch.uint8, dev); _mesh_arg(alpha, "sil_forward: alpha", torch.float32, dev)
+    if counts is not None:
+        _mesh_arg(counts, "sil_forward: counts", torch.int32, dev)
+    if tuple(alpha.shape) != (K, H, W) or (counts is not None and tuple(counts.shape) != (K,)):
+        raise ValueError(f"sil_forward: alpha must be [{K},{H},{W}] and counts [{K}]")
+    if ws.numel() < sil_layout(K, V, F, H, W, capacity)["bytes"]:
+        raise ValueError(f"sil_forward: a workspace of {ws.numel()} bytes is too small")
+    fx, fy, cx, cy = (float(x) for x in intrinsics)
+    with torch.cuda.device(dev):
+        _lib.check(_sil_lib().sg_sil_forward(K, V, F, int(H), int(W), fx, fy, cx, cy, float(sigma), int(capacity), _ptr(verts), _ptr(faces),
+                                             _ptr(ws), _ptr(alpha), _ptr(counts), _stream(dev)), "sg_sil_forward")
+
+
+def sil_backward(verts, faces, intrinsics, H, W, sigma, capacity, ws, dalpha, row_ptr, corner, dverts):
+    """``sg_sil_backward`` on torch's current stream, after ``sil_forward`` with the same arguments on the same ``ws``:
+    ``dalpha`` [K,H,W], ``row_ptr`` [V+1] / ``corner`` [3F] int32 -> ``dverts`` [K,V,3] is written."""
+    dev, K, V, F = _sil_dims(verts, faces, "sil_backward")
+    _mesh_arg(ws, "sil_backward: ws", torch.uint8, dev); _mesh_arg(dalpha, "sil_backward: dalpha", torch.float32, dev)
+    _mesh_arg(row_ptr, "sil_backward: row_ptr", torch.int32, dev); _mesh_arg(corner, "sil_backward: corner", torch.int32, dev)
+    _mesh_arg(dverts, "sil_backward: dverts", torch.float32, dev)
+    if tuple(dalpha.shape) != (K, H, W) or tuple(dverts.shape) != (K, V, 3) or tuple(row_ptr.shape) != (V + 1,) or corner.numel() > 3 * F:
+        raise ValueError(f"sil_backward: dalpha must be [{K},{H},{W}], dverts [{K},{V},3], row_ptr [{V + 1}], corner at most [{3 * F}]")
+    if ws.numel() < sil_layout(K, V, F, H, W, capacity)["bytes"]:
+        raise ValueError(f"sil_backward: a workspace of {ws.numel()} bytes is too small")
+    fx, fy, cx, cy = (float(x) for x in intrinsics)
+    with torch.cuda.device(dev):
+        _lib.check(_sil_lib().sg_sil_backward(K, V, F, int(H), int(W), fx, fy, cx, cy, float(sigma), int(capacity), _ptr(verts), _ptr(faces),
+                                              _ptr(ws), _ptr(dalpha), _ptr(row_ptr), _ptr(corner), _ptr(dverts), _stream(dev)),
+                   "sg_sil_backward")
+
+
+def sil_pose_update(lr, pose, grad, m, v, grad_mask, lo, hi, step, terms=None, table=None):
+    """``sg_sil_pose_update`` on torch's current stream: ``pose`` / ``grad`` / ``m`` / ``v`` [K,72] fp32, ``grad_mask`` / ``lo`` / ``hi``
+    [72], ``step`` [1] int32; ``terms`` [K,2] with ``table`` [iterations,K,2], or neither."""
+    dev = pose.device if torch.is_tensor(pose) else None
+    pose = _mesh_arg(pose, "sil_pose_update: pose", torch.float32, dev, (_lib.SIL_POSE,))
+    K = int(pose.shape[0])
+    for name, t in (("grad", grad), ("m", m), ("v", v)):
+        if tuple(_mesh_arg(t, "sil_pose_update: " + name, torch.float32, dev).shape) != (K, _lib.SIL_POSE):
+            raise ValueError(f"sil_pose_update: {name} must be [{K},{_lib.SIL_POSE}], got {tuple(t.shape)}")
+    for name, t in (("grad_mask", grad_mask), ("lo", lo), ("hi", hi)):
+        if tuple(_mesh_arg(t, "sil_pose_update: " + name, torch.float32, dev).shape) != (_lib.SIL_POSE,):
+            raise ValueError(f"sil_pose_update: {name} must be [{_lib.SIL_POSE}], got {tuple(t.shape)}")
+    if tuple(_mesh_arg(step, "sil_pose_update: step", torch.int32, dev).shape) != (1,):
+        raise ValueError("sil_pose_update: step must be [1]")
+    iters = 0
+    if (terms is None) != (table is None):
+        raise ValueError("sil_pose_update: terms and table come together")
+    if terms is not None:
+        _mesh_arg(terms, "sil_pose_update: terms", torch.float32, dev); _mesh_arg(table, "sil_pose_update: table", torch.float32, dev)
+        iters = int(table.shape[0])
+        if tuple(terms.shape) != (K, 2) or tuple(table.shape) != (iters, K, 2):
+            raise ValueError(f"sil_pose_update: terms must be [{K},2] and table [iterations,{K},2]")
+    with torch.cuda.device(dev):
+        _lib.check(_sil_lib().sg_sil_pose_update(K, float(lr), _ptr(pose), _ptr(grad), _ptr(m), _ptr(v), _ptr(grad_mask), _ptr(lo), _ptr(hi),
+                                                 _ptr(step), _ptr(terms), _ptr(table), iters, _stream(dev)), "sg_sil_pose_update")

@@ -1,13 +1,18 @@
-"""The reference's pose refinement, stated and executable on the host: the ``--opt`` step of its ``prepare_kits.sh``
-(preprocess/utils/ooptimize_smpl.py:260-364 and ooptimize_smplh.py), which refines a kit's SMPL poses against the Sapiens keypoints and,
-through pytorch3d's ``MeshRasterizer`` + ``SoftSilhouetteShader``, against the mask.
+"""The reference's pose refinement: the ``--opt`` step of its ``prepare_kits.sh`` (preprocess/utils/ooptimize_smpl.py:260-364 and
+ooptimize_smplh.py), which refines a kit's SMPL poses against the Sapiens keypoints and, through pytorch3d's ``MeshRasterizer`` +
+``SoftSilhouetteShader``, against the mask.  Stated and executable on the host, and run on the device.
 
     RefineSpec            the reference's tables: keypoint map, gradient mask, joint limits, lr, iterations; ``.smpl()`` / ``.smplh()``
     silhouette_host       a soft silhouette of a posed triangle mesh, differentiable, vectorised over pixels x faces
     refine_pose_host      the reference's loop in torch on the CPU, fp64-capable, one frame after the other
+    RefineEngine          the loop on the device, pre-allocated for K frames per launch, one iteration recorded as a HIP graph
+    refine_pose           the device loop over any number of frames -> (global_orient, body_pose, report)
+    refine_kit            a kit directory -> ``score_demo_video/poses_optimized.npz``, the file ``kit.load_kit`` prefers
+    write_refined_poses   that file's writer (host): the reference's keys, atomic, refuses to overwrite
 
-THERE IS NO DEVICE PATH YET.  This module is the definition a device path will be held to, and what anyone without pytorch3d reads;
-at a kit's size (512 x 896, 13 776 faces, 100 iterations a frame) it is a definition, not a tool: every (pixel, face) pair is evaluated.
+The host functions are the definition the device path is held to, and what anyone without pytorch3d reads; at a kit's size
+(512 x 896, 13 776 faces, 100 iterations a frame) they are a definition, not a tool: every (pixel, face) pair is evaluated.  The device
+path (``sings_amd/silhouette.py``, csrc/sg_silhouette.hip) files the faces into tiles and evaluates the pairs of a tile's list.
 
 Per frame, independently of the others:
 
@@ -328,3 +333,285 @@ def refine_pose_host(body, betas, global_orient, body_pose, transl, camera, mask
         out[f] = pose.detach()
     out = out.numpy()
     return out[:, :3], out[:, 3:], _report(first, last, used.sum(-1).numpy(), faces_max)
+
+
+# ---- the loop on the device ---------------------------------------------------------------------------------------------------------------
+def _gpu_body(body, device):
+    from .body_model import BodyModel
+    if isinstance(body, BodyModel):
+        return body
+    m = dict(body)
+    if "vertex_label" not in m:
+        m["vertex_label"] = np.zeros(np.asarray(m["v_template"]).shape[0], np.int64)
+    return BodyModel(device=device, **m)
+
+
+class RefineEngine:
+    """The loop for K frames at once, every buffer allocated here: ``RefineEngine(body, betas, camera, spec, extra_joint_vertex_ids,
+    frames_per_launch=8)``.  ``body``: a ``BodyModel`` (or the dict of its arrays, put on ``betas``' device); ``betas`` [B] fp32 on the GPU.
+
+    One iteration (``_iteration``), for K independent frames: ``joint_transforms_hip`` -> ``lbs_extra`` (pose correctives and
+    ``pose_mean`` as ``host_forward`` has them) -> ``verts @ R + transl`` -> the joint rows -> ``project_joints`` / ``keypoint_term`` in
+    their masked-sum form -> ``soft_silhouette`` / ``silhouette_term`` -> backward -> ONE update launch (gate, Adam, the step counter and
+    the row ``[it - 1]`` of the ``[iterations, K, 2]`` table of terms, all in device memory).  Nothing in it reads the device.
+
+    ``run_batch`` is the entry: it loads up to K frames (a shorter batch is padded with copies of its first frame), counts the (tile,
+    face) pairs of the starting poses once (a host read), makes the pair list hold twice that, runs the iterations and reads the
+    overflow words once; a batch that overflowed is run again from its starting poses with twice the most pairs any launch had.
+
+    With ``capture`` the first iteration of the first batch runs eagerly, the second is recorded as a HIP graph and every further
+    one, of this and of later batches, is a replay.  A captured engine is only replayed: ``iterate()`` raises."""
+
+    def __init__(self, body, betas, camera, spec, extra_joint_vertex_ids=(), frames_per_launch=8, iterations=None, capture=True,
+                 capacity=None):
+        from . import silhouette as _sil
+        if not torch.is_tensor(betas) or not betas.is_cuda:
+            raise RuntimeError("pose_refine.RefineEngine: betas must be a GPU tensor (no CPU fallback; the host loop is refine_pose_host)")
+        self.device = betas.device
+        self.body = _gpu_body(body, self.device)
+        self.spec, self.K = spec, int(frames_per_launch)
+        if not 1 <= self.K <= _sil._lib.SIL_MAX_FRAMES:
+            raise ValueError(f"pose_refine.RefineEngine: frames_per_launch = {self.K} outside 1..{_sil._lib.SIL_MAX_FRAMES}")
+        self.iterations = spec.iterations if iterations is None else int(iterations)
+        self.capture, self.graph = bool(capture), None
+        self.intr, R, self.H, self.W = _camera_parts(camera)
+        J, V = self.body.num_joints, self.body.num_verts
+        self.extra = tuple(int(i) for i in extra_joint_vertex_ids)
+        if J + len(self.extra) != spec.n_joint_rows:
+            raise ValueError(f"pose_refine: {J} joints + {len(self.extra)} picked vertices are not the spec's {spec.n_joint_rows} joint rows")
+        if 3 * J < POSE:
+            raise ValueError(f"pose_refine: a body of {J} joints has no {POSE}-entry pose")
+        dev, K, f32 = self.device, self.K, torch.float32
+        with torch.cuda.device(dev), torch.no_grad():
+            b = betas.detach().to(f32).reshape(-1)
+            self.v_shaped = self.body.shaped(b)["v_shaped"][0].contiguous()
+            self.joints_rest = self.body.joints_rest(b).contiguous()
+            self.R = torch.as_tensor(R, dtype=f32, device=dev)
+            self.extra_t = torch.as_tensor(self.extra, dtype=torch.long, device=dev)
+            self.gm, self.lo, self.hi = _spec_tensors(spec, f32, dev)
+            z = lambda *shape, dt=f32: torch.zeros(shape, dtype=dt, device=dev)
+            self.pose, self.m, self.v, self.step = z(K, POSE), z(K, POSE), z(K, POSE), z(1, dt=torch.int32)
+            self.transl, self.mask = z(K, 3), z(K, self.H, self.W)
+            self.target, self.used = z(K, spec.n_joint_rows, 2), z(K, spec.n_joint_rows, dt=torch.bool)
+            self.terms, self.table = z(K, 2), z(max(1, self.iterations), K, 2)
+            self.pad = z(K, 3 * J - POSE) if 3 * J > POSE else None
+        self._sil = _sil
+        self.forced_capacity = None if capacity is None else int(capacity)
+        self.work = self.count_work = None
+        self.start_pairs = self.peak_pairs = self.reruns = 0
+
+    # -- one iteration
+    def _forward(self, pose):
+        from .body import joint_transforms_hip
+        from .lbs import lbs_extra
+        body = self.body
+        full = pose if self.pad is None else torch.cat([pose, self.pad], 1)
+        if body.pose_mean is not None:
+            full = full + body.pose_mean
+        A = joint_transforms_hip(full, self.joints_rest, body.parents)
+        verts = lbs_extra(A, self.v_shaped[None], body.posedirs, body.lbs_weights, full, disable_posedirs=body.posedirs is None)[0]
+        # (products and sums written out: element-wise launches only, nothing of a BLAS library inside the recorded iteration)
+        joints = (A[:, :, :3, :3] * self.joints_rest[None, :, None, :]).sum(-1) + A[:, :, :3, 3]
+        rows = torch.cat([joints, verts.index_select(1, self.extra_t)], 1) if self.extra else joints
+        to_cam = lambda p: (p[..., :, None] * self.R).sum(-2) + self.transl[:, None]
+        return to_cam(verts), to_cam(rows)
+
+    def _terms(self, pose, counts=False, work=None):
+        verts_cam, rows = self._forward(pose)
+        kp, _ = keypoint_term(project_joints(rows, self.intr, self.H, self.W), self.target, self.used)
+        out = self._sil.soft_silhouette(verts_cam.contiguous(), self.body.faces, self.intr, self.H, self.W, self.spec.sigma,
+                                        return_counts=counts, workspace=self.work if work is None else work, check=False)
+        alpha, cnt = out if counts else (out, None)
+        return kp, silhouette_term(alpha, self.mask), cnt
+
+    def gradient(self):
+        """The two terms and dL/dpose of the loaded frames at the current pose, without an update -> (terms [K,2], dkeypoint [K,72],
+        dsilhouette [K,72]) (for tests; eager)."""
+        self._need_work()
+        pose = self.pose.detach().clone().requires_grad_(True)
+        kp, sil, _ = self._terms(pose)
+        g_kp, = torch.autograd.grad(kp.sum(), pose, retain_graph=True)
+        g_sil, = torch.autograd.grad(sil.sum(), pose)
+        return torch.stack([kp, sil], 1).detach(), g_kp, g_sil
+
+    def _iteration(self):
+        pose = self.pose.detach().requires_grad_(True)
+        kp, sil, _ = self._terms(pose)
+        grad, = torch.autograd.grad((kp + sil).sum(), pose)
+        self.terms.copy_(torch.stack([kp.detach(), sil.detach()], 1))
+        from ._marshal import sil_pose_update
+        sil_pose_update(self.spec.lr, self.pose, grad.contiguous(), self.m, self.v, self.gm, self.lo, self.hi, self.step, self.terms,
+                        self.table)
+
+    def iterate(self):
+        """One eager iteration on the loaded frames.  Raises on an engine that has been captured: its buffers belong to the graph."""
+        if self.graph is not None:
+            raise RuntimeError("pose_refine.RefineEngine: this engine has been captured; it is only replayed (run_batch)")
+        self._need_work()
+        self._iteration()
+
+    def _record(self):
+        torch.cuda.synchronize(self.device)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._iteration()
+        self.graph = graph
+
+    # -- a batch
+    def load(self, pose, transl, masks, target, used):
+        """Up to K frames into the engine's buffers (tensors on any device); the moments, the step counter and the table start anew."""
+        n = int(pose.shape[0])
+        if not 1 <= n <= self.K:
+            raise ValueError(f"pose_refine.RefineEngine: a batch of {n} frames for K = {self.K}")
+        idx = torch.cat([torch.arange(n), torch.zeros(self.K - n, dtype=torch.long)])
+        with torch.no_grad():
+            for dst, src in ((self.pose, pose), (self.transl, transl), (self.mask, masks), (self.target, target), (self.used, used)):
+                dst.copy_(torch.as_tensor(src)[idx].to(dst.dtype))
+            for t in (self.m, self.v, self.step, self.table, self.terms):
+                t.zero_()
+        self.n_loaded = n
+
+    def _need_work(self, capacity=None):
+        V, F = self.body.num_verts, int(self.body.faces.shape[0])
+        if self.work is None or (capacity is not None and capacity > self.work.capacity):
+            cap = self._sil.default_capacity(self.K, F) if capacity is None else capacity
+            self.work = self._sil.SilhouetteWorkspace(self.K, V, self.body.faces, self.H, self.W, cap, self.device)
+            self.graph = None                                        # (a graph holds the addresses and the capacity of its workspace)
+
+    def count(self):
+        """One counting forward at the current pose, synchronous -> (pairs of all K frames, max faces per pixel [K] numpy).  It has a
+        workspace of its own: the one the iterations run in, which a graph may hold, is never launched into from here."""
+        V, F = self.body.num_verts, int(self.body.faces.shape[0])
+        capacity = self._sil.default_capacity(self.K, F) if self.count_work is None else self.count_work.capacity
+        while True:
+            if self.count_work is None or self.count_work.capacity < capacity:
+                self.count_work = self._sil.SilhouetteWorkspace(self.K, V, self.body.faces, self.H, self.W, capacity, self.device)
+            with torch.no_grad():
+                _, _, cnt = self._terms(self.pose, counts=True, work=self.count_work)
+            over, total, _ = self.count_work.info()
+            if not over:
+                return total, cnt.cpu().numpy().astype(np.int64)
+            capacity = total
+
+    def run_batch(self, pose, transl, masks, target, used):
+        """-> (pose [n,72] fp32 numpy, table [iterations,n,2] numpy, max faces per pixel at the starting poses [n])."""
+        self.load(pose, transl, masks, target, used)
+        with torch.cuda.device(self.device):
+            self.start_pairs, faces_max = self.count()
+            capacity = max(1, 2 * self.start_pairs) if self.forced_capacity is None else self.forced_capacity
+            self.reruns = 0
+            while True:
+                self._need_work(capacity)
+                self.load(pose, transl, masks, target, used)
+                self.work.reset_peak()
+                left = self.iterations
+                if self.capture and self.graph is None and left > 0:
+                    self._iteration()                                # the first iteration runs eagerly
+                    left -= 1
+                    if left > 0:
+                        self._record()
+                for _ in range(left):
+                    if self.capture:
+                        self.graph.replay()
+                    else:
+                        self._iteration()
+                over, self.peak_pairs = self.work.peak()
+                if not over:
+                    break
+                self.reruns += 1
+                if self.reruns > 8:
+                    raise RuntimeError(f"pose_refine.RefineEngine: the pair list overflowed {self.reruns} times (last: {self.peak_pairs} pairs)")
+                capacity = 2 * self.peak_pairs
+            n = self.n_loaded
+            return self.pose[:n].cpu().numpy(), self.table[:, :n].cpu().numpy(), faces_max[:n]
+
+
+def refine_pose(body, betas, global_orient, body_pose, transl, camera, masks, keypoints, scores, spec, extra_joint_vertex_ids=(),
+                frames_per_launch=8, capture=True, iterations=None, engine=None, trace=None):
+    """The loop on the device: ``betas`` [B] and the per-frame inputs as GPU tensors (host tensors raise), -> (global_orient [F,3],
+    body_pose [F,69], report) as fp32 numpy arrays.  The report has ``refine_pose_host``'s keys; ``max_faces_per_pixel`` comes from one
+    counting forward at the starting poses.  ``trace``: a list that receives every batch's [iterations, n, 2] table of terms."""
+    for name, t in (("betas", betas), ("global_orient", global_orient), ("body_pose", body_pose), ("transl", transl), ("masks", masks),
+                    ("keypoints", keypoints), ("scores", scores)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError(f"pose_refine.refine_pose: {name} must be a GPU tensor (no CPU fallback; the host loop is refine_pose_host)")
+    F = _check_inputs(global_orient, body_pose, transl, keypoints, scores, masks.shape[0])
+    if engine is None:
+        engine = RefineEngine(body, betas, camera, spec, extra_joint_vertex_ids, min(int(frames_per_launch), F), iterations, capture)
+    target, used = keypoint_targets(keypoints.float(), scores.float(), spec)
+    start = torch.cat([global_orient, body_pose], 1).float()
+    iters, K = engine.iterations, engine.K
+    out = np.zeros((F, POSE), np.float32)
+    first, last, faces_max = np.zeros((F, 2)), np.zeros((F, 2)), np.zeros(F, np.int64)
+    for at in range(0, F, K):
+        sl = slice(at, min(at + K, F))
+        out[sl], table, faces_max[sl] = engine.run_batch(start[sl], transl[sl], masks[sl], target[sl], used[sl])
+        if iters > 0:
+            first[sl], last[sl] = table[0], table[iters - 1]
+        if trace is not None:
+            trace.append(table)
+    return out[:, :3], out[:, 3:], _report(first, last, used.sum(-1).cpu().numpy(), faces_max)
+
+
+# ---- a kit ------------------------------------------------------------------------------------------------------------------------------
+REFINED_FILE = "poses_optimized.npz"
+
+
+def write_refined_poses(path, betas, global_orient, body_pose, transl, overwrite=False):
+    """``np.savez_compressed`` of the reference's keys (ooptimize_smpl.py:401-411): ``betas`` [B], ``global_orient`` [F,3], ``body_pose``
+    [F,69], ``transl`` [F,3], fp32.  Atomic: written beside ``path`` and renamed.  ``FileExistsError`` unless ``overwrite``."""
+    import os
+    import tempfile
+    path = str(path)
+    arrays = {"betas": np.asarray(betas, np.float32).reshape(-1), "global_orient": np.asarray(global_orient, np.float32),
+              "body_pose": np.asarray(body_pose, np.float32), "transl": np.asarray(transl, np.float32)}
+    F = arrays["global_orient"].shape[0] if arrays["global_orient"].ndim == 2 else -1
+    if arrays["global_orient"].shape != (F, 3) or arrays["body_pose"].shape != (F, 69) or arrays["transl"].shape != (F, 3) or F < 1:
+        raise ValueError(f"write_refined_poses: global_orient {arrays['global_orient'].shape}, body_pose {arrays['body_pose'].shape}, "
+                         f"transl {arrays['transl'].shape} must be [F,3], [F,69], [F,3]")
+    if not all(np.isfinite(a).all() for a in arrays.values()):
+        raise ValueError("write_refined_poses: an array is not finite")
+    if os.path.exists(path) and not overwrite:
+        raise FileExistsError(f"write_refined_poses: {path} exists (overwrite=True replaces it)")
+    folder = os.path.dirname(path) or "."
+    os.makedirs(folder, exist_ok=True)
+    fd, tmp = tempfile.mkstemp(suffix=".npz", prefix=".poses_", dir=folder)
+    try:
+        with os.fdopen(fd, "wb") as f:
+            np.savez_compressed(f, **arrays)
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        raise
+    return path
+
+
+def refine_kit(root, body, extra_joint_vertex_ids, spec=None, split="train+val", out=None, overwrite=False, frames_per_launch=8,
+               capture=True):
+    """What replaces ``prepare_kits.sh ... --opt``: ``load_kit(root, split)``, ``load_keypoints``, the masks from the store's fourth
+    channel as byte / 255 -> ``refine_pose`` -> ``<root>/score_demo_video/poses_optimized.npz`` (or ``out``).  The starting poses are
+    ``poses.npz``'s when a refined file is being replaced.  -> (path, report)."""
+    import os
+    from . import kit as _kit
+    spec = RefineSpec.smpl() if spec is None else spec
+    path = os.path.join(str(root), "score_demo_video", REFINED_FILE) if out is None else str(out)
+    if os.path.exists(path) and not overwrite:
+        raise FileExistsError(f"refine_kit: {path} exists (overwrite=True replaces it)")
+    k = _kit.load_kit(root, split)
+    dev = k.store.device
+    smpl = k.smpl
+    raw = os.path.join(str(root), "score_demo_video", "poses.npz")
+    if os.path.exists(os.path.join(str(root), "score_demo_video", REFINED_FILE)) and os.path.exists(raw):
+        p = _kit.load_smpl_param(raw)
+        drop = 0 if split == "train+val" else _kit.DROP_FIRST
+        idx = np.asarray(k.indices, np.int64) + drop
+        smpl = {"betas": torch.from_numpy(p["betas"]).to(dev),
+                **{key: torch.from_numpy(np.ascontiguousarray(p[key][idx])).to(dev) for key in ("global_orient", "body_pose", "transl")}}
+    kp, sc = _kit.load_keypoints(root, [i + (0 if split == "train+val" else _kit.DROP_FIRST) for i in k.indices])
+    masks = k.store.data[..., 3].float() / 255
+    go, bp, report = refine_pose(body, smpl["betas"].reshape(-1), smpl["global_orient"], smpl["body_pose"], smpl["transl"], k.camera, masks,
+                                 torch.from_numpy(kp).to(dev), torch.from_numpy(sc).to(dev), spec, extra_joint_vertex_ids,
+                                 frames_per_launch, capture)
+    write_refined_poses(path, smpl["betas"].cpu().numpy(), go, bp, smpl["transl"].cpu().numpy(), overwrite)
+    return path, report
